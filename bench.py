@@ -10,7 +10,10 @@ tokens, positive and negative document 256 tokens each, full length), i.e. three
 forward passes + SPLADELossV33 + backward, and on every `--accum`-th step the gradient
 all-reduce (N>1), clip, AdamW and LR-schedule update -- the work of
 ref:src/train/cli/train_v33_ddp.py:316-374.  Inputs are resident in HBM before the timed region.
-Prints ONE JSON line (rank 0): metric triplets/s (whole job), roofline and cpu_baseline objects.
+Prints ONE JSON line (rank 0): metric triplets/s (whole job) and ms_per_step.  A plain run sets up, warms up, times
+`--steps` micro-steps, writes the outputs of the last one (`--dump-outputs DIR`) and prints that line; `--full` adds
+the per-kernel-class roofline, the reference's literal loop, the trained-sparsity regime, BASELINE configs 4 / 5, the
+communicator record (N > 1) and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -172,6 +175,27 @@ def pmc_traffic(cls: str):
     return (tot / n if n else None), prov
 
 
+def dump_outputs(out_dir: str, loss, loss_dict: dict, model, per_param: int = 8192) -> None:
+    """What the timed path computed in its last micro-step, as float32 .npy files: the loss and every entry of its loss
+    dict (what ddp_trainer.micro_step returns), and a fixed, seeded sample of every parameter after that step (the
+    optimizer's output: up to `per_param` entries per tensor, in named_parameters order; ~4.5 MB for the 149 M model)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray(float(loss), dtype=np.float32))
+    for key, v in loss_dict.items():
+        np.save(os.path.join(out_dir, f"loss_dict_{key}.npy"), np.asarray(float(v), dtype=np.float32))
+    gen = torch.Generator().manual_seed(1234)
+    parts = []
+    with torch.no_grad():
+        for _, p in model.named_parameters():
+            flat = p.detach().reshape(-1)
+            if flat.numel() > per_param:
+                idx = torch.randint(flat.numel(), (per_param,), generator=gen).to(flat.device)
+                flat = flat[idx]
+            parts.append(flat.float().cpu())
+    np.save(os.path.join(out_dir, "params_sample.npy"), torch.cat(parts).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -195,7 +219,18 @@ def main():
                          "4 (cross-GPU in-batch negatives) beside the headline configuration")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="time the CPU oracle sample and exit (no GPU)")
     ap.add_argument("--cpu-cores", default=None, help="threads of the CPU sample: a number, or 'all' (physical cores)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: per-kernel-class roofline, the extra "
+                         "legs (--no-* above switch them off one by one), the communicator record at N > 1, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed micro-step to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    # A plain run does only what its headline figure needs; every other measurement or check is behind --full.
+    if not args.full:
+        args.no_cpu_baseline = args.no_profile = args.no_item_sync_leg = True
+        args.no_sparse_regime_leg = args.no_config_legs = True
 
     if args.cpu_baseline_only:
         n = None
@@ -223,7 +258,7 @@ def main():
         if os.environ.get("SNX_BENCH_BACKEND", "nccl") == "nccl" and ndev < args.gpus:
             raise SystemExit(f"bench.py: --gpus {args.gpus} but {ndev} GPU(s) visible; one process per GPU over RCCL")
         with socket.socket() as sk:
-            sk.bind(("127.0.0.1", 0))
+            sk.bind(("", 0))        # wildcard, as the rendezvous store listens on all addresses
             port = sk.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
@@ -284,14 +319,14 @@ def main():
     batches = make_batches(n_batches, B, Sq, Sd, k, model.vocab_size, model.config.pad_token_id, 42 + rank, dev,
                            teacher=args.margin_mse > 0)
     xneg = args.cross_gpu_negatives
-    state = {"i": 0, "gs": 0, "sync": False, "last": 0.0}
+    state = {"i": 0, "gs": 0, "sync": False, "last": 0.0, "loss_dict": None}
 
     def one_step():
         b = batches[state["i"] % n_batches]
         if state["sync"]:
             os.environ["SNX_FUSED_PASSES"] = "0"
-        loss, _ = T.micro_step(wrapped, loss_fn, b, state["gs"], dev, args.accum, xneg,
-                               last_of_window=(state["i"] + 1) % args.accum == 0)
+        loss, state["loss_dict"] = T.micro_step(wrapped, loss_fn, b, state["gs"], dev, args.accum, xneg,
+                                                last_of_window=(state["i"] + 1) % args.accum == 0)
         state["i"] += 1
         if state["sync"]:
             state["last"] = loss.item()                    # ref:train_v33_ddp.py:444, one host sync per micro-step
@@ -319,6 +354,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     final_loss = float(loss)
+    if args.dump_outputs and rank == 0:                 # before any --full leg moves the parameters on
+        dump_outputs(args.dump_outputs, loss, state["loss_dict"], model)
 
     fl = flops_per_triplet(Sq, Sd, k)
     triplets_per_s = args.steps * B * world / dt
@@ -341,7 +378,7 @@ def main():
     }
 
     # ---- what the communicator itself saw (N > 1): a SCALE record must not rest on this file's own `world` variable ----
-    if use_pg:
+    if use_pg and args.full:
         ck = torch.tensor([float(rank), 1.0], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(ck, op=dist.ReduceOp.SUM)                  # through the same group the gradients use
         names = [None] * dist.get_world_size()

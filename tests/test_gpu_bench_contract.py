@@ -1,19 +1,46 @@
-"""bench.py's one-line JSON contract (the driver parses it): a short real run on the GPU."""
+"""bench.py's one-line JSON contract (the driver parses it): short real runs on the GPU, plain and with --full."""
 import json
 import math
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.gpu
+def test_plain_bench_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps micro-steps, prints the headline line without the --full records and
+    writes the last timed micro-step's outputs as float32 .npy files."""
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 6 and d["warmup"] == 2 and d["n_gpus"] == 1
+    assert d["unit"] == "triplets/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert d["value"] == pytest.approx(64 * 1000.0 / d["ms_per_step"], rel=1e-6) and 100.0 < d["value"] < 1e5
+    for key in ("roofline", "kernel_classes", "extra", "cpu_baseline", "comm"):
+        assert key not in d, key
+    files = sorted(os.listdir(out))
+    assert {"loss.npy", "params_sample.npy", "loss_dict_infonce.npy", "loss_dict_nonzero_d.npy"} <= set(files), files
+    assert sum(os.path.getsize(out / f) for f in files) < 64 << 20
+    for f in files:
+        a = np.load(out / f)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), f
+    assert float(np.load(out / "loss.npy")) == pytest.approx(d["config"]["final_loss"], rel=1e-6)
+    assert np.load(out / "params_sample.npy").size > 100_000
+
+
+@pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "4",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -53,7 +80,7 @@ def test_bench_under_torchrun_one_rank_over_rccl():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(ROOT, "bench.py"),
                         "--gpus", "1", "--steps", "8", "--warmup", "4", "--no-cpu-baseline", "--no-profile",
-                        "--cross-gpu-negatives"],     # config 4: all-gather of the positives + reduce-scatter backward
+                        "--cross-gpu-negatives", "--full"],     # config 4: all-gather of the positives + reduce-scatter backward
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -78,7 +105,7 @@ def test_bench_launch_line_with_two_ranks_rehearsed_on_one_gpu():
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29537", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "4", "--warmup", "4", "--no-cpu-baseline"],
+                        "--gpus", "2", "--steps", "4", "--warmup", "4", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]

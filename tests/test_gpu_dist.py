@@ -28,7 +28,7 @@ def dev():
 @pytest.fixture(scope="module")
 def nccl_world1(dev):
     s = socket.socket()
-    s.bind(("127.0.0.1", 0))
+    s.bind(("", 0))       # every address: the TCPStore given this port listens on all of them
     port = s.getsockname()[1]
     s.close()
     torch.cuda.set_device(dev)
@@ -335,7 +335,7 @@ def test_two_ranks_share_one_gpu(dev, tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     pkg = os.path.join(root, "opensearch-neural-pre-train_amd")
     s = socket.socket()
-    s.bind(("127.0.0.1", 0))
+    s.bind(("", 0))       # every address: the TCPStore given this port listens on all of them
     port = s.getsockname()[1]
     s.close()
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([root, pkg, os.environ.get("PYTHONPATH", "")]),
@@ -419,7 +419,7 @@ def test_reference_train_epoch_replayed_on_one_gpu(dev, tmp_path, world, wrapper
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     pkg = os.path.join(root, "opensearch-neural-pre-train_amd")
     s = socket.socket()
-    s.bind(("127.0.0.1", 0))
+    s.bind(("", 0))       # every address: the TCPStore given this port listens on all of them
     port = s.getsockname()[1]
     s.close()
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([root, pkg, os.environ.get("PYTHONPATH", "")]),

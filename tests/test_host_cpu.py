@@ -269,7 +269,7 @@ def test_get_top_k_tokens_tie_order():
 # ---------------------------------------------------------------------------------- multi-process (gloo)
 def _free_port():
     s = socket.socket()
-    s.bind(("127.0.0.1", 0))
+    s.bind(("", 0))       # every address: the TCPStore given this port listens on all of them
     p = s.getsockname()[1]
     s.close()
     return p

@@ -1,26 +1,32 @@
-"""The drop-in boundary against the reference itself (build container only; skipped where /root/reference is absent, e.g.
-on the GPU box -- nothing of the reference travels).
+"""The drop-in boundary against the reference itself, checked against a stored record of the reference's interface
+(tests/golden/g11_reference_boundary.json, written by `python tools/make_golden.py g11` where the reference checkout is
+present; nothing of the reference is read at test time).
 
 SURVEY 8(b): the reference has no FFI on this path; its boundary is the Python import surface of
-ref:src/train/cli/train_v33_ddp.py:35-50.  The reference files are read as TEXT and compared through `ast` -- no
-reference code is imported or executed in the test process: every `from src.... import name` of the
-reference CLI must resolve to an attribute of this repo's module of the same dotted name, the eight trainer functions the
-CLI inlines (ref:train_v33_ddp.py:105-448; their home here is src.train.core.ddp_trainer, as north_star names it) must
-have the reference's parameter lists, this repo's CLI must accept the reference's flags with the same type / default /
-action, and the V33*Config dataclasses must have the reference's fields and defaults (ref:src/train/config/v33.py:21-132)."""
+ref:src/train/cli/train_v33_ddp.py:35-50.  The fixture was taken from the reference files read as TEXT through `ast` -- no
+reference code was imported or executed, and the extractors below are the ones that wrote it: every
+`from src.... import name` of the reference CLI must resolve to an attribute of this repo's module of the same dotted name,
+the eight trainer functions the CLI inlines (ref:train_v33_ddp.py:105-448; their home here is src.train.core.ddp_trainer,
+as north_star names it) must have the reference's parameter lists, this repo's CLI must accept the reference's flags with
+the same type / default / action, and the V33*Config dataclasses must have the reference's fields and defaults
+(ref:src/train/config/v33.py:21-132)."""
 import ast
 import dataclasses
 import importlib
 import inspect
+import json
 import os
 
-import pytest
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIXTURE = os.path.join(ROOT, "tests", "golden", "g11_reference_boundary.json")
+TRAINER_FNS = ("setup_distributed", "cleanup_distributed", "is_main_process", "create_dataloader_ddp", "save_checkpoint",
+               "load_checkpoint", "find_latest_checkpoint", "train_epoch")
+CONFIG_CLASSES = ("V33Config", "V33DataConfig", "V33LossConfig", "V33ModelConfig", "V33TrainingConfig")
 
-REF = "/root/reference"
-CLI = os.path.join(REF, "src/train/cli/train_v33_ddp.py")
-CFG = os.path.join(REF, "src/train/config/v33.py")
 
-pytestmark = pytest.mark.skipif(not os.path.exists(CLI), reason="reference checkout not present (build container only)")
+def _fixture():
+    with open(FIXTURE, encoding="utf-8") as fh:
+        return json.load(fh)
 
 
 def _tree(path):
@@ -73,21 +79,28 @@ def _flags(tree):
     return out
 
 
+def _cli_imports(tree):
+    """(required, optional) [(module, name)] of every `from src.x.y import a, b` of a CLI module: module level, and inside
+    its try/except for optional ones."""
+    wanted, optional = [], []
+    for node in ast.walk(tree):
+        if isinstance(node, ast.ImportFrom) and node.module and node.module.split(".")[0] == "src" and node.level == 0:
+            in_try = any(isinstance(p, ast.Try) and node in ast.walk(p) for p in tree.body)
+            (optional if in_try else wanted).extend((node.module, a.name) for a in node.names)
+    return wanted, optional
+
+
 def test_reference_cli_imports_resolve_here_and_signatures_match():
     import src                                               # this repo's mirror package (tests/conftest.py put it on sys.path)
     here = os.path.dirname(os.path.dirname(os.path.abspath(src.__file__)))
-    assert "opensearch-neural-pre-train_amd" in here and not here.startswith(REF)
-    ref = _tree(CLI)
-    # every `from src.x.y import a, b` of the reference CLI (module level, and inside its try/except for optional ones)
-    wanted, optional = [], []
-    for node in ast.walk(ref):
-        if isinstance(node, ast.ImportFrom) and node.module and node.module.split(".")[0] == "src" and node.level == 0:
-            in_try = any(isinstance(p, ast.Try) and node in ast.walk(p) for p in ref.body)
-            (optional if in_try else wanted).extend((node.module, a.name) for a in node.names)
+    assert "opensearch-neural-pre-train_amd" in here and here.startswith(ROOT)
+    ref = _fixture()
+    wanted = [tuple(x) for x in ref["cli_imports"]]
+    optional = [tuple(x) for x in ref["cli_optional_imports"]]
     assert ("src.model.splade_modern", "SPLADEModernBERT") in wanted and ("src.model.losses", "SPLADELossV33") in wanted
     for mod, name in wanted:
         m = importlib.import_module(mod)
-        assert not os.path.abspath(m.__file__).startswith(REF), mod
+        assert os.path.abspath(m.__file__).startswith(ROOT), mod
         assert hasattr(m, name), f"{mod}.{name} (imported by the reference CLI) is missing here"
     for mod, name in optional:                               # ref:train_v33_ddp.py:46-49: may stay absent
         try:
@@ -97,14 +110,15 @@ def test_reference_cli_imports_resolve_here_and_signatures_match():
         assert hasattr(m, name), f"{mod} exists here but lacks {name}"
     # the trainer functions: same names, same parameter lists (names, kinds, defaults)
     from src.train.core import ddp_trainer as T
-    ref_fns = _functions(ref)
-    for n in ("setup_distributed", "cleanup_distributed", "is_main_process", "create_dataloader_ddp", "save_checkpoint",
-              "load_checkpoint", "find_latest_checkpoint", "train_epoch"):
-        assert _sig_live(getattr(T, n)) == _sig_from_ast(ref_fns[n]), (n, _sig_live(getattr(T, n)), _sig_from_ast(ref_fns[n]))
+    ref_sigs = ref["trainer_signatures"]
+    assert sorted(ref_sigs) == sorted(TRAINER_FNS)
+    for n in TRAINER_FNS:
+        live = [list(x) for x in _sig_live(getattr(T, n))]
+        assert live == ref_sigs[n], (n, live, ref_sigs[n])
     # and this repo's own CLI declares the reference's flags (same type, default, action)
     from src.train.cli import train_v33_ddp as our_cli
     ours = _flags(_tree(inspect.getsourcefile(our_cli)))
-    theirs = _flags(ref)
+    theirs = ref["cli_flags"]
     assert len(theirs) == 12
     missing = {k: v for k, v in theirs.items() if ours.get(k) != v}
     assert not missing, missing
@@ -144,14 +158,14 @@ def _ref_dataclasses(tree):
 
 
 def test_config_dataclasses_equal_the_references():
-    ref = _ref_dataclasses(_tree(CFG))
+    ref = _fixture()["config_dataclasses"]
     from src.train.config import v33 as ours
-    for n in ("V33Config", "V33DataConfig", "V33LossConfig", "V33ModelConfig", "V33TrainingConfig"):
+    for n in CONFIG_CLASSES:
         fa = ref[n]
         fb = [(f.name, _default(f)) for f in dataclasses.fields(getattr(ours, n))]
         assert [x[0] for x in fa] == [x[0] for x in fb], n
         for (name, da), (_, db) in zip(fa, fb):
-            if isinstance(da, tuple) and da and da[0] == "<instance>":
+            if isinstance(da, list) and len(da) == 2 and da[0] == "<instance>":     # JSON keeps the marker as a list
                 assert dataclasses.is_dataclass(db) and type(db).__name__ == da[1], (n, name, da, db)
                 continue
             assert da == db and type(da) is type(db), (n, name, da, db)
@@ -163,3 +177,15 @@ def _default(f):
     if f.default_factory is not dataclasses.MISSING:
         return f.default_factory()
     return "<required>"
+
+
+def reference_record(cli_path: str, cfg_path: str) -> dict:
+    """The fixture these tests read, extracted from the reference's CLI and config modules (tools/make_golden.py g11)."""
+    cli = _tree(cli_path)
+    wanted, optional = _cli_imports(cli)
+    fns = _functions(cli)
+    classes = _ref_dataclasses(_tree(cfg_path))
+    return {"cli_imports": wanted, "cli_optional_imports": optional,
+            "trainer_signatures": {n: _sig_from_ast(fns[n]) for n in TRAINER_FNS},
+            "cli_flags": _flags(cli),
+            "config_dataclasses": {n: classes[n] for n in CONFIG_CLASSES}}

@@ -16,8 +16,8 @@ python3 tools/pmc_traffic.py "$F" "$W" $O/pmc_traffic.json > $O/pmc_traffic.txt 
 # the bench lines come AFTER the counter passes: bench.py reports `traffic` from profiles/${R}_pmc_traffic.json only when
 # that file was measured on the kernel sources it is running (sha256 inside)
 cp $O/pmc_traffic.json profiles/${R}_pmc_traffic.json
-echo "[prof] bench n1"; python3 bench.py > $O/bench_n1.json 2> $O/bench_n1.err || exit 1
-echo "[prof] bench cfg5"; python3 bench.py --d-len 512 --negatives 4 --margin-mse 0.5 --steps 16 --warmup 4 --no-cpu-baseline --no-sparse-regime-leg > $O/bench_cfg5_n1.json 2> $O/bench_cfg5.err || exit 1
+echo "[prof] bench n1"; python3 bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err || exit 1
+echo "[prof] bench cfg5"; python3 bench.py --d-len 512 --negatives 4 --margin-mse 0.5 --steps 16 --warmup 4 --no-cpu-baseline --no-sparse-regime-leg --full > $O/bench_cfg5_n1.json 2> $O/bench_cfg5.err || exit 1
 # shader-engine counters (MFMA utilisation, where the waves' cycles go): one pass, the program directly behind `--`
 echo "[prof] pmc sq"; rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU GRBM_GUI_ACTIVE --kernel-trace -d $O/pmc_sq -o s -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-profile --no-item-sync-leg --no-sparse-regime-leg --no-config-legs > $O/pmc_sq.log 2>&1 || exit 1
 S=$(find $O/pmc_sq -name "s_results.db" | head -1)

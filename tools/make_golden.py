@@ -19,7 +19,8 @@ Fixtures: g1 tiny fwd/bwd (+g6 edge rows), g2 tiny train_epoc
 2-proc gloo DDP), g3 full-size fwd/bwd summaries, g4 loss-only vectors, g5 collator layout,
 g6 inference post-processing, g7 BASELINE config 5 (d512, k=4, MarginMSE) at full size, g8 the g3 batch
 with an unsaturated InfoNCE, g9 the loss's KL-distillation branch, g10 BASELINE config 1 as written (64 micro-steps of the
-149 M model through the reference's train_epoch).
+149 M model through the reference's train_epoch), g11 the reference's import surface, trainer signatures, CLI flags and
+config defaults (tests/test_reference_boundary.py).
 """
 from __future__ import annotations
 
@@ -613,6 +614,19 @@ def g10():
               open(os.path.join(OUT, "g10_config1_train_epoch.json"), "w"), indent=1)
     print("g10 global_step", gs, "avg", avg, "first losses", [r[0] for r in rec[:4]], "wall", wall)
     dist.destroy_process_group()
+
+
+def g11():
+    """The reference's interface as tests/test_reference_boundary.py checks it: the CLI's `src.*` imports, the trainer
+    functions' parameter lists, the CLI flags and the V33*Config fields with their defaults.  The reference files are read as
+    text through `ast` by the test module's own extractors; nothing of the reference is imported."""
+    from tests.test_reference_boundary import reference_record
+    cli = os.path.join(REF, "src/train/cli/train_v33_ddp.py")
+    cfg = os.path.join(REF, "src/train/config/v33.py")
+    rec = reference_record(cli, cfg)
+    rec["source"] = {os.path.relpath(f, REF): hashlib.sha256(open(f, "rb").read()).hexdigest() for f in (cli, cfg)}
+    json.dump(rec, open(os.path.join(OUT, "g11_reference_boundary.json"), "w"), indent=1)
+    print("g11", len(rec["cli_imports"]), "imports", len(rec["cli_flags"]), "flags")
 
 
 if __name__ == "__main__":
