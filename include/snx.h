@@ -76,11 +76,16 @@ size_t snx_model_bwd_workspace_bytes(const snx_model_desc* d, int32_t T, int32_t
 /* byte offset, inside a save_for_bwd arena, of the packed arg-max keys u32 [nseq, vocab]
  * (bf16 bits of relu(logit) << 16 | 0xFFFF - row): lets a caller inspect the max-pool routing. */
 size_t snx_model_keys_offset(const snx_model_desc* d, int32_t T, int32_t nseq);
+/* byte offset, inside a save_for_bwd arena, of the per-token maximum keys u32 [T] (bf16 bits of relu(logit) << 16 |
+ * 0xFFFF - v*, v* = first vocabulary column of the token's maximum; 0xFFFF for masked tokens and tokens whose maximum
+ * is 0): the token_weights routing, written by every forward that saves for backward (which needs vocab <= 65535). */
+size_t snx_model_token_keys_offset(const snx_model_desc* d, int32_t T, int32_t nseq);
 
 /* SPLADEModernBERT.forward (ref:src/model/splade_modern.py:50-88):
  *   ids,mask [T] int64; pos [T] int32 (position of each row inside its sequence);
  *   rope_* [max_pos][32][2] fp32 (cos,sin) tables for theta_global / theta_local (hf:136-163);
- *   -> sparse [nseq, vocab] fp32, token_weights [T] fp32; `saved` = arena (see above). */
+ *   -> sparse [nseq, vocab] fp32, token_weights [T] fp32; `saved` = arena (see above).  With SNX_FWD_SAVE_FOR_BACKWARD
+ * the arena also keeps every token's arg-max column (snx_model_token_keys_offset): both outputs are differentiable. */
 int snx_model_forward(const snx_model_desc* d, const void* const* params /*[host]*/, const void* wcache,
                       const int64_t* ids, const int64_t* mask, const int32_t* cu_seqlens, const int32_t* pos,
                       const float* rope_global, const float* rope_local, void* saved, float* sparse,
@@ -106,7 +111,8 @@ int snx_model_forward_range(const snx_model_desc* d, const void* const* params /
 
 /* Backward of the above (the autograd graph of ref:src/model/splade_modern.py:69-86 and of the HF
  * encoder): g_sparse [nseq, vocab] fp32 = dL/d sparse_repr; every grads[i] (fp32, same shape as
- * params[i]) is ACCUMULATED into (+=).  token_weights is treated as non-differentiable. */
+ * params[i]) is ACCUMULATED into (+=).  These entry points take no gradient for token_weights (it is zero); the _tw
+ * variants below take one. */
 int snx_model_backward(const snx_model_desc* d, const void* const* params /*[host]*/, void* const* grads /*[host]*/,
                        const void* wcache, const int64_t* ids, const int64_t* mask, const int32_t* cu_seqlens,
                        const int32_t* pos, const float* rope_global, const float* rope_local, const void* saved,
@@ -139,6 +145,17 @@ int snx_model_backward_units_range(const snx_model_desc* d, const void* const* p
                                    const float* g_sparse, void* scratch, const int32_t* groups /*[host] or NULL*/,
                                    int32_t T_plan, int32_t nseq_plan, int32_t T, int32_t nseq, int32_t max_seqlen,
                                    int32_t unit_begin, int32_t unit_end, hipStream_t notify, hipStream_t stream);
+/* ... with g_token_weights [T] fp32 = dL/d token_weights in the arena's row order (NULL: exactly the entry point above):
+ *   d logit[t, v*(t)] += g_token_weights[t] mask[t] / (1 + x),  x = relu(logit[t, v*(t)]) > 0,
+ * added to the max-pool gradient of the same logit before its one bf16 rounding; every gradient deterministic. */
+int snx_model_backward_units_range_tw(const snx_model_desc* d, const void* const* params /*[host]*/,
+                                      void* const* grads /*[host]*/, const void* wcache, const int64_t* ids,
+                                      const int64_t* mask, const int32_t* cu_seqlens, const int32_t* pos,
+                                      const float* rope_global, const float* rope_local, const void* saved,
+                                      const float* g_sparse, const float* g_token_weights /*[T] or NULL*/, void* scratch,
+                                      const int32_t* groups /*[host] or NULL*/, int32_t T_plan, int32_t nseq_plan,
+                                      int32_t T, int32_t nseq, int32_t max_seqlen, int32_t unit_begin, int32_t unit_end,
+                                      hipStream_t notify, hipStream_t stream);
 
 /* ---- fp32 execution (csrc/f32_path.hip): what the reference computes OUTSIDE torch.autocast -- a bare
  * SPLADEModernBERT.forward (ref:src/model/splade_modern.py:50-88), its inference encoder (ref:benchmark/encoders.py:
@@ -156,6 +173,11 @@ int snx_model_backward_f32(const snx_model_desc* d, const void* const* params /*
                            const int64_t* ids, const int64_t* mask, const int32_t* cu_seqlens, const int32_t* pos,
                            const float* rope_global, const float* rope_local, const void* saved, const float* g_sparse,
                            void* scratch, int32_t T, int32_t nseq, hipStream_t stream);
+/* ... with g_token_weights [T] fp32 or NULL (= snx_model_backward_f32). */
+int snx_model_backward_f32_tw(const snx_model_desc* d, const void* const* params /*[host]*/, void* const* grads /*[host]*/,
+                              const int64_t* ids, const int64_t* mask, const int32_t* cu_seqlens, const int32_t* pos,
+                              const float* rope_global, const float* rope_local, const void* saved, const float* g_sparse,
+                              const float* g_token_weights, void* scratch, int32_t T, int32_t nseq, hipStream_t stream);
 /* fp32 GEMM on v_mfma_f32_32x32x2_f32 with strided operands: C[m,n] (+)= (R[m,n]) + sum_k A[m a_row + k a_k] B[n b_row + k b_k]
  * (nn.Linear in fp32: forward, dX and dW are the same kernel with different strides). */
 int snx_gemm_f32(const float* A, int64_t a_row, int64_t a_k, const float* B, int64_t b_row, int64_t b_k, float* C, int64_t ldc,
@@ -355,12 +377,25 @@ int snx_decoder_splade_fwd_ex(const void* Hd, const void* W, const float* bias, 
 int snx_decoder_splade_fwd(const void* Hd, const void* W, const float* bias, const int32_t* cu_seqlens,
                            const int64_t* mask, float* sparse, uint32_t* keys, float* token_weights, void* scratch,
                            int32_t T, int32_t nseq, int32_t max_seqlen, int32_t V, int32_t K, hipStream_t stream);
+/* snx_decoder_splade_fwd_ex that also records token_keys [T] u32 (see snx_model_token_keys_offset; written by the
+ * finalising call; V <= 65535).  token_keys = NULL is snx_decoder_splade_fwd_ex. */
+int snx_decoder_splade_fwd_rec(const void* Hd, const void* W, const float* bias, const int32_t* cu_seqlens,
+                               const int64_t* mask, float* sparse, uint32_t* keys, float* token_weights,
+                               uint32_t* token_keys, void* scratch, int32_t T, int32_t nseq, int32_t max_seqlen, int32_t V,
+                               int32_t K, int32_t finalize, hipStream_t stream);
 /* arg-max-routed backward: dHd [T,H] bf16 (overwritten), gradE [V,H] += , gradb [V] += ;
  * scratch: snx_splade_bwd_scratch_bytes() bytes (per-row bucket lists). */
 size_t snx_splade_bwd_scratch_bytes(int32_t nseq, int32_t max_seqlen, int32_t V);
 int snx_splade_bwd(const float* g, const uint32_t* keys, const void* Hd, const void* W, const int32_t* cu_seqlens,
                    void* dHd, float* gradE, float* gradb, void* scratch, int32_t T, int32_t nseq,
                    int32_t max_seqlen, int32_t V, int32_t H, hipStream_t stream);
+/* ... plus the token_weights direction: g_tw [T] fp32 (NULL: snx_splade_bwd), token_keys from
+ * snx_decoder_splade_fwd_rec, tw_scratch: snx_splade_tw_scratch_bytes(T, V) bytes. */
+size_t snx_splade_tw_scratch_bytes(int32_t T, int32_t V);
+int snx_splade_bwd_tw(const float* g, const uint32_t* keys, const float* g_tw, const uint32_t* token_keys, const void* Hd,
+                      const void* W, const int32_t* cu_seqlens, void* dHd, float* gradE, float* gradb, void* scratch,
+                      void* tw_scratch, int32_t T, int32_t nseq, int32_t max_seqlen, int32_t V, int32_t H,
+                      hipStream_t stream);
 
 /* ---- fused optimizer step (ref:src/train/cli/train_v33_ddp.py:367-374: clip_grad_norm_ + AdamW) ----
  * All four arrays are flat fp32 [n] (16-byte aligned).  hp [host] = {lr, beta1, beta2, eps, weight_decay,

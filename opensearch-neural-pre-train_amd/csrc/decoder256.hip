@@ -3,6 +3,7 @@
 //
 //   key[b, v]   = max over the valid rows s of sequence b of  bf16bits(relu(Hd[b,s,:] . W[v,:] + bias[v])) << 16 | 0xFFFF - s
 //   sparse[b,v] = log1p(value(key));   rowpart[2 nt + wn, t] = max over the 96 columns of half tile (nt, wn) of the value bits
+//   (REC, training forwards: of the column-tagged keys value bits << 16 | 0xFFFF - v, u32; see decoder_splade_kernel)
 //
 // The 128x128 kernel (one workgroup per (sequence, vocab tile), two per CU) runs at 0.27 of the MFMA peak: K = 768
 // gives every 128-row chunk a pipeline start-up of its own, and the operand tiles cross the L2 -> LDS path at 65
@@ -137,7 +138,7 @@ struct DecArgs {
   const i32x4* subtab;               // sub-tiles (pre-pass 2)
   const int32_t* hdr;                // hdr[0] = number of sub-tiles
   uint32_t* keys;                    // [nseq, V], zeroed
-  unsigned short* rowpart;           // [2 * ceil(V / 192), T]: one row per 96-column half tile
+  void* rowpart;                     // [2 * ceil(V / 192), T]: one row per 96-column half tile (u16; REC: u32 keys)
   int T, V, K, ntn;                  // ntn = ceil(V / 192)
 };
 
@@ -210,6 +211,7 @@ extern "C" int snx_dec256_trace_set(void* buf) {
 }
 #endif
 
+template <bool REC>
 __global__ __launch_bounds__(256) void decoder256_kernel(DecArgs g) {
 #ifdef SNX_GEMM_TRACE
   const unsigned long long tr_c0 = __builtin_amdgcn_s_memtime(), tr_r0 = __builtin_amdgcn_s_memrealtime();
@@ -396,6 +398,10 @@ __global__ __launch_bounds__(256) void decoder256_kernel(DecArgs g) {
       float bcol[NJ];
 #pragma unroll
       for (int j = 0; j < NJ; ++j) bcol[j] = rbf(pre_bias[j]);
+      // REC: column tags of the row keys (columns past V carry a negative value: their tag never matters)
+      uint32_t ctag[NJ];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) ctag[j] = (0xFFFFu - (uint32_t)(col0 + 32 * j)) & 0xFFFFu;
       // token rows of the 4 x 32 rows this lane stores row maxima for (lanes 16-31 / 48-63, lane & 15 = q <-> row
       // 8 (q >> 2) + 4 (lane >> 5) + (q & 3) of every sub-tile): requested before the last two half-steps
       int tok[4];
@@ -447,7 +453,7 @@ __global__ __launch_bounds__(256) void decoder256_kernel(DecArgs g) {
 #pragma unroll
         for (int v = 0; v < 16; v += 2) {             // rows v and v + 1 of this lane: one bf16 pair per column tile
           const uint32_t tag0 = tagbase - (uint32_t)(8 * (v >> 2) + (v & 3)), tag1 = tag0 - 1u;
-          int32_t k0[NJ], k1[NJ];
+          int32_t k0[NJ], k1[NJ], c0[NJ], c1[NJ];
 #pragma unroll
           for (int j = 0; j < NJ; ++j) {
             const f32x2 sum = (f32x2){acc[i][j][v], acc[i][j][v + 1]} + (f32x2){bcol[j], bcol[j]};
@@ -456,14 +462,22 @@ __global__ __launch_bounds__(256) void decoder256_kernel(DecArgs g) {
             k0[j] = (int32_t)((w << 16) | tag0);      // key = value bits << 16 | 0xFFFF - list position
             k1[j] = (int32_t)((w & 0xFFFF0000u) | tag1);
             best[j] = max(best[j], max(k0[j], k1[j]));   // tag0 > tag1: the earlier row wins a tie
+            if (REC) {                                // row keys: the same values tagged by column (lower v wins a tie)
+              c0[j] = (int32_t)((w << 16) | ctag[j]);
+              c1[j] = (int32_t)((w & 0xFFFF0000u) | ctag[j]);
+            }
           }
-          // a row's keys share their tag, so the row maximum of the keys is (max value bits) << 16 | tag
-          const int32_t r0 = half_max(max(max(max(k0[0], k0[1]), k0[2]), 0)), r1 = half_max(max(max(max(k1[0], k1[1]), k1[2]), 0));
+          // without REC: a row's keys share their tag, so the row maximum of the keys is (max value bits) << 16 | tag
+          const int32_t r0 = REC ? half_max(max(max(max(c0[0], c0[1]), c0[2]), 0)) : half_max(max(max(max(k0[0], k0[1]), k0[2]), 0));
+          const int32_t r1 = REC ? half_max(max(max(max(c1[0], c1[1]), c1[2]), 0)) : half_max(max(max(max(k1[0], k1[1]), k1[2]), 0));
           mine = (lane & 15) == v ? r0 : mine;
           mine = (lane & 15) == v + 1 ? r1 : mine;
           if ((v & 6) == 6) __builtin_amdgcn_sched_barrier(0);   // bound the window: four rows' worth of temporaries
         }
-        if (tok[i] >= 0) g.rowpart[(long)t96 * g.T + tok[i]] = (unsigned short)(mine >> 16);
+        if (tok[i] >= 0) {
+          if (REC) ((uint32_t*)g.rowpart)[(long)t96 * g.T + tok[i]] = (uint32_t)mine;
+          else ((unsigned short*)g.rowpart)[(long)t96 * g.T + tok[i]] = (unsigned short)(mine >> 16);
+        }
       }
       flush(cur_seq);
     }
@@ -509,7 +523,7 @@ size_t snx_dec256_table_bytes(int32_t T) { return (size_t)T * 4 + (size_t)T * 4 
 
 int snx_launch_decoder256(const void* Hd, const void* W, const float* bias, const int32_t* cu_seqlens,
                           const int64_t* mask, float* sparse, uint32_t* keys, void* scratch, size_t rowpart_bytes,
-                          int32_t T, int32_t nseq, int32_t V, int32_t K, hipStream_t st) {
+                          int32_t T, int32_t nseq, int32_t V, int32_t K, bool rec, hipStream_t st) {
   if ((K % 64) || T <= 0 || nseq <= 0 || V <= 0 || (long)T * K * 2 >= (1L << 32) || (long)V * K * 2 >= (1L << 32))
     return SNX_E_SHAPE;
   if (NJ != 3) return SNX_E_SHAPE;                    // the DMA / read schedule of the K loop is written for NJ = 3
@@ -524,18 +538,20 @@ int snx_launch_decoder256(const void* Hd, const void* W, const float* bias, cons
   SNX_CHECK_LAUNCH();
   hipError_t e = hipMemsetAsync(keys, 0, (size_t)nseq * V * 4, st);
   if (e != hipSuccess) return (int)e;
-  static bool attr[64] = {};
+  static bool attr[2][64] = {};
   int devid = 0;
   if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return SNX_E_ARG;
-  if (!attr[devid]) {
-    e = hipFuncSetAttribute((const void*)decoder256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RING * SLOT);
+  if (!attr[rec][devid]) {
+    e = hipFuncSetAttribute(rec ? (const void*)decoder256_kernel<true> : (const void*)decoder256_kernel<false>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, RING * SLOT);
     if (e != hipSuccess) return (int)e;
-    attr[devid] = true;
+    attr[rec][devid] = true;
   }
   DecArgs g;
   g.Hd = (const bf16_t*)Hd; g.W = (const bf16_t*)W; g.bias = bias; g.list = list; g.subtab = subtab; g.hdr = hdr;
-  g.keys = keys; g.rowpart = (unsigned short*)scratch; g.T = T; g.V = V; g.K = K; g.ntn = cdiv(V, TV);
-  hipLaunchKernelGGL(decoder256_kernel, dim3(NWG), dim3(256), RING * SLOT, st, g);
+  g.keys = keys; g.rowpart = scratch; g.T = T; g.V = V; g.K = K; g.ntn = cdiv(V, TV);
+  if (rec) hipLaunchKernelGGL(decoder256_kernel<true>, dim3(NWG), dim3(256), RING * SLOT, st, g);
+  else hipLaunchKernelGGL(decoder256_kernel<false>, dim3(NWG), dim3(256), RING * SLOT, st, g);
   SNX_CHECK_LAUNCH();
   const long total = (long)nseq * V;
   hipLaunchKernelGGL(dec256_finalize_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, keys, sparse, cu_seqlens, list, V,

@@ -48,7 +48,7 @@ struct TailArgs {                    // EPI 2: rows = tokens, columns = vocabula
   const int32_t* seqid;              // [T] sequence of every token
   const int32_t* pos;                // [T] position inside its sequence
   unsigned long long* keys;          // [nseq, V] value bits << 32 | 0xFFFFFFFF - pos, zero-initialised
-  uint32_t* twbits;                  // [T] bits of max_v value, zero-initialised
+  unsigned long long* twkeys;        // [T] bits of max_v value << 32 | 0xFFFFFFFF - v (first v of the maximum), zeroed
   int V;
 };
 
@@ -124,11 +124,14 @@ __device__ __forceinline__ void gemm_f32_epilogue(const GemmArgs& g, const TailA
         const unsigned long long key = ((unsigned long long)__float_as_uint(w) << 32) | (0xFFFFFFFFu - (uint32_t)ta.pos[row]);
         best = key > best ? key : best;
       }
-      // token maximum over this wave's 32 columns (the two halves of the wave hold different rows)
-      float mx = cok ? w : 0.f;
+      // token maximum over this wave's 32 columns (the two halves of the wave hold different rows), tagged by column
+      unsigned long long mx = cok ? ((unsigned long long)__float_as_uint(w) << 32) | (0xFFFFFFFFu - (uint32_t)col) : 0ull;
 #pragma unroll
-      for (int o = 16; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-      if (rok && (lane & 31) == 0) atomicMax(ta.twbits + row, __float_as_uint(mx));
+      for (int o = 16; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(mx, o, 64);
+        mx = other > mx ? other : mx;
+      }
+      if (rok && (lane & 31) == 0) atomicMax(ta.twkeys + row, mx);
     }
     if (cur >= 0 && cok) atomicMax(ta.keys + (long)cur * ta.V + col, best);
   }
@@ -321,10 +324,15 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_128_kernel(GemmArgs g, TailAr
           best0 = k0 > best0 ? k0 : best0;
           best1 = k1 > best1 ? k1 : best1;
         }
-        float mx = fmaxf(ok0 ? w0 : 0.f, ok1 ? w1 : 0.f);
+        const unsigned long long m0 = ok0 ? ((unsigned long long)__float_as_uint(w0) << 32) | (0xFFFFFFFFu - (uint32_t)col0) : 0ull;
+        const unsigned long long m1 = ok1 ? ((unsigned long long)__float_as_uint(w1) << 32) | (0xFFFFFFFFu - (uint32_t)col1) : 0ull;
+        unsigned long long mx = m0 > m1 ? m0 : m1;
 #pragma unroll
-        for (int o = 16; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        if (rok && c == 0) atomicMax(ta.twbits + row, __float_as_uint(mx));
+        for (int o = 16; o > 0; o >>= 1) {
+          const unsigned long long other = __shfl_xor(mx, o, 64);
+          mx = other > mx ? other : mx;
+        }
+        if (rok && c == 0) atomicMax(ta.twkeys + row, mx);
       }
     if (cur >= 0) {
       if (ok0) atomicMax(ta.keys + (long)cur * ta.V + col0, best0);
@@ -591,11 +599,11 @@ __global__ void seqid_kernel(const int32_t* __restrict__ cu, int32_t* __restrict
   seqid[t] = lo;
 }
 
-__global__ void tail_finalize_kernel(const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ twbits,
+__global__ void tail_finalize_kernel(const unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ twkeys,
                                      float* __restrict__ sparse, float* __restrict__ tw, long nv, int T) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < nv) sparse[i] = __uint_as_float((uint32_t)(keys[i] >> 32));
-  if (i < T) tw[i] = __uint_as_float(twbits[i]);
+  if (i < T) tw[i] = __uint_as_float((uint32_t)(twkeys[i] >> 32));
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -874,6 +882,28 @@ __global__ __launch_bounds__(256) void tail_f32_bwd_kernel(const float* __restri
   if (lane == 0) atomicAdd(gradb + v, c);
 }
 
+// routed backward of token_weights[t] = y = max_v log1p(relu(logit[t, v])) mask[t] (the first v of the maximum, twkeys):
+//   c = g_tw[t] / (1 + relu(x)) = g_tw exp(-y);  dHd[t] += c E[v];  gradE[v] += c Hd[t];  gradb[v] += c.   One wave per token.
+__global__ __launch_bounds__(256) void tail_f32_tw_bwd_kernel(const float* __restrict__ g_tw, const unsigned long long* __restrict__ twkeys,
+                                                              const float* __restrict__ Hd, const float* __restrict__ E,
+                                                              float* __restrict__ dHd, float* __restrict__ gradE,
+                                                              float* __restrict__ gradb, int T, int H) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= T) return;
+  const unsigned long long key = twkeys[t];
+  const float y = __uint_as_float((uint32_t)(key >> 32));
+  const float gv = g_tw[t];
+  if (!(y > 0.f) || gv == 0.f) return;
+  const int v = (int)(0xFFFFFFFFu - (uint32_t)key);
+  const float c = gv * expf(-y);
+  for (int d = lane; d < H; d += 64) {
+    atomicAdd(dHd + (long)t * H + d, c * E[(long)v * H + d]);
+    atomicAdd(gradE + (long)v * H + d, c * Hd[(long)t * H + d]);
+  }
+  if (lane == 0) atomicAdd(gradb + v, c);
+}
+
 __global__ void add_f32_kernel(float* __restrict__ dst, const float* __restrict__ src, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dst[i] += src[i];
@@ -902,7 +932,7 @@ struct PIdx {                        // canonical parameter order (model.hip)
 
 struct Plan {
   size_t h[129], x_attn[64], qkv[64], attn[64], lse[64], x_mlp[64], u[64], y[64];
-  size_t xf, dd, hd, keys, twbits, seqid, total;
+  size_t xf, dd, hd, keys, twkeys, seqid, total;
 };
 
 bool f32_desc_ok(const snx_model_desc* d) {
@@ -933,7 +963,7 @@ void plan(const snx_model_desc* d, size_t T, size_t nseq, bool save, Plan& s) {
   }
   s.xf = take(T * H * 4); s.dd = take(T * H * 4); s.hd = take(T * H * 4);
   s.keys = take(nseq * V * 8);
-  s.twbits = take(T * 4);
+  s.twkeys = take(T * 8);
   s.seqid = take(T * 4);
   s.total = off;
 }
@@ -1037,14 +1067,14 @@ extern "C" int snx_model_forward_f32(const snx_model_desc* d, const void* const*
   LAUNCH_ROWS(ln_f32_kernel<2>, T, B(s.dd), nullptr, F(p.head_norm()), B(s.hd), T, H, d->ln_eps);
   // tied decoder + SPLADE tail
   if (hipMemsetAsync(sv + s.keys, 0, (size_t)nseq * V * 8, st) != hipSuccess) return SNX_E_ARG;
-  if (hipMemsetAsync(sv + s.twbits, 0, (size_t)T * 4, st) != hipSuccess) return SNX_E_ARG;
+  if (hipMemsetAsync(sv + s.twkeys, 0, (size_t)T * 8, st) != hipSuccess) return SNX_E_ARG;
   {
     GemmArgs g{B(s.hd), H, 1, F(p.tok_emb()), H, 1, nullptr, 0, nullptr, 0, T, V, H, 0, 0};
-    TailArgs ta{F(p.dec_bias()), mask, seqid, pos, (unsigned long long*)(sv + s.keys), (uint32_t*)(sv + s.twbits), V};
+    TailArgs ta{F(p.dec_bias()), mask, seqid, pos, (unsigned long long*)(sv + s.keys), (unsigned long long*)(sv + s.twkeys), V};
     RC(launch_gemm<2>(g, ta, st));
   }
   const long nv = (long)nseq * V;
-  LAUNCH1D(tail_finalize_kernel, nv > T ? nv : T, (const unsigned long long*)(sv + s.keys), (const uint32_t*)(sv + s.twbits), sparse,
+  LAUNCH1D(tail_finalize_kernel, nv > T ? nv : T, (const unsigned long long*)(sv + s.keys), (const unsigned long long*)(sv + s.twkeys), sparse,
            token_weights, nv, T);
   return SNX_OK;
 }
@@ -1053,6 +1083,15 @@ extern "C" int snx_model_backward_f32(const snx_model_desc* d, const void* const
                                       const int64_t* ids, const int64_t* mask, const int32_t* cu_seqlens, const int32_t* pos,
                                       const float* rope_global, const float* rope_local, const void* saved,
                                       const float* g_sparse, void* scratch, int32_t T, int32_t nseq, hipStream_t st) {
+  return snx_model_backward_f32_tw(d, params, grads, ids, mask, cu_seqlens, pos, rope_global, rope_local, saved, g_sparse,
+                                   nullptr, scratch, T, nseq, st);
+}
+
+extern "C" int snx_model_backward_f32_tw(const snx_model_desc* d, const void* const* params, void* const* grads,
+                                         const int64_t* ids, const int64_t* mask, const int32_t* cu_seqlens, const int32_t* pos,
+                                         const float* rope_global, const float* rope_local, const void* saved,
+                                         const float* g_sparse, const float* g_token_weights, void* scratch, int32_t T,
+                                         int32_t nseq, hipStream_t st) {
   if (!f32_desc_ok(d)) return SNX_E_SHAPE;
   if (!params || !grads || !ids || !mask || !cu_seqlens || !pos || !rope_global || !rope_local || !saved || !g_sparse ||
       !scratch || T <= 0 || nseq <= 0)
@@ -1082,6 +1121,12 @@ extern "C" int snx_model_backward_f32(const snx_model_desc* d, const void* const
     const long nv = (long)nseq * V;
     hipLaunchKernelGGL(tail_f32_bwd_kernel, dim3(cdiv(nv, 4)), dim3(256), 0, st, g_sparse, (const unsigned long long*)(sv + s.keys),
                        S(s.hd), F(p.tok_emb()), cu_seqlens, Cc, G(p.tok_emb()), G(p.dec_bias()), nv, V, H);
+    SNX_CHECK_LAUNCH();
+  }
+  if (g_token_weights) {
+    hipLaunchKernelGGL(tail_f32_tw_bwd_kernel, dim3(cdiv(T, 4)), dim3(256), 0, st, g_token_weights,
+                       (const unsigned long long*)(sv + s.twkeys), S(s.hd), F(p.tok_emb()), Cc, G(p.tok_emb()),
+                       G(p.dec_bias()), T, H);
     SNX_CHECK_LAUNCH();
   }
   // hd = LN(gelu(dd)) w: A = d(dd)

@@ -79,6 +79,7 @@ struct SavedPlan {
   size_t keys;                   // u32 [nseq,V]
   size_t rowpart;                // forward-only scratch of the SPLADE head
   size_t rope_rows[2];           // fp32 [T,32,2]: every token's (cos, sin) row for theta_global / theta_local
+  size_t tkeys;                  // u32 [T]: every token's maximum over the vocabulary, value bits << 16 | 0xFFFF - v
   size_t total;
 };
 
@@ -109,6 +110,7 @@ bool plan_saved(const snx_model_desc* d, long T, long nseq, bool save, SavedPlan
   s.rowpart = take(snx_splade_head_scratch_bytes((int)T, (int)V));
   s.rope_rows[0] = take(T * 256);
   s.rope_rows[1] = take(T * 256);
+  s.tkeys = take(T * 4);
   s.total = off;
   return true;
 }
@@ -125,6 +127,7 @@ struct BwdPlan {
   size_t b;         // bf16 [T,H]   scratch (d head.dense out; d attention out)
   size_t delta;     // fp32 [heads,T]
   size_t splade;    // bucket lists of the routed SPLADE backward
+  size_t splade_tw; // token_weights direction of it (coefficients, counting sort by column)
   // workspaces of the ORDERED weight-gradient reductions ("det_reduce"): partial slabs of the layer's grouped dW launch
   // (side stream), of the head's dW launch (launch stream: may overlap the side stream's), partial dw rows of the
   // LayerNorm backward launches + the embedding gradient's token lists and dx rows (launch stream, one at a time)
@@ -145,6 +148,7 @@ void plan_bwd(const snx_model_desc* d, long T, long nseq, long max_seqlen, BwdPl
   p.b = take(T * H * 2);
   p.delta = take((size_t)d->heads * T * 4);
   p.splade = take(snx_splade_bwd_scratch_bytes((int)nseq, (int)max_seqlen, d->vocab));
+  p.splade_tw = take(snx_splade_tw_scratch_bytes((int)T, d->vocab));
   {
     const int Hh = d->hidden, Ii = d->inter;
     const snx_tn_problem layer[4] = {{nullptr, nullptr, nullptr, 3 * Hh, Hh, 0, 0}, {nullptr, nullptr, nullptr, 2 * Ii, Hh, 1, 0},
@@ -334,6 +338,12 @@ extern "C" size_t snx_model_keys_offset(const snx_model_desc* d, int32_t T, int3
   return s.keys;
 }
 
+extern "C" size_t snx_model_token_keys_offset(const snx_model_desc* d, int32_t T, int32_t nseq) {
+  SavedPlan s;
+  if (!desc_ok(d) || T <= 0 || nseq <= 0 || !plan_saved(d, T, nseq, true, s)) return (size_t)-1;
+  return s.tkeys;
+}
+
 extern "C" size_t snx_model_bwd_workspace_bytes(const snx_model_desc* d, int32_t T, int32_t nseq, int32_t max_seqlen) {
   if (!desc_ok(d) || T <= 0 || nseq <= 0 || max_seqlen <= 0) return 0;
   BwdPlan p;
@@ -412,6 +422,7 @@ extern "C" int snx_model_forward_range(const snx_model_desc* d, const void* cons
   } sv{view, s, (size_t)H, (size_t)I};
   uint32_t* keys = (uint32_t*)((char*)saved + s.keys) + (size_t)seq0 * V;
   char* rowpart = (char*)saved + s.rowpart;
+  uint32_t* tkeys = save ? (uint32_t*)((char*)saved + s.tkeys) + row0 : nullptr;   // training forwards record v*(t)
 
   const double TH = (double)T * H;
   { PROF(PC_EMBED, TH * 10); RC(snx_embed_ln_fwd(ids, F(p.tok_emb()), F(p.emb_norm()), hbuf(0), sv.x_attn(0), T, H, d->ln_eps, st)); }
@@ -465,9 +476,9 @@ extern "C" int snx_model_forward_range(const snx_model_desc* d, const void* cons
     for (int i = 0; i < g[0]; ++i) {
       const int sb = g[1 + 3 * i], ns = g[2 + 3 * i], ml = g[3 + 3 * i];
       if (sb < 0 || ns <= 0 || sb + ns > nseq || ml <= 0 || ml > max_seqlen) return SNX_E_ARG;
-      RC(snx_decoder_splade_fwd_ex(sv.hd(), wc + c.emb, F(p.dec_bias()), cu_seqlens + sb, mask,
-                                   sparse + (size_t)sb * V, keys + (size_t)sb * V, token_weights,
-                                   rowpart, T, ns, ml, V, H, i + 1 == g[0], st));
+      RC(snx_decoder_splade_fwd_rec(sv.hd(), wc + c.emb, F(p.dec_bias()), cu_seqlens + sb, mask,
+                                    sparse + (size_t)sb * V, keys + (size_t)sb * V, token_weights, tkeys,
+                                    rowpart, T, ns, ml, V, H, i + 1 == g[0], st));
     }
   }
   return SNX_OK;
@@ -499,6 +510,21 @@ extern "C" int snx_model_backward_units_range(const snx_model_desc* d, const voi
                                               void* scratch, const int32_t* groups, int32_t T_plan, int32_t nseq_plan,
                                               int32_t T, int32_t nseq, int32_t max_seqlen, int32_t unit_begin,
                                               int32_t unit_end, hipStream_t notify, hipStream_t st) {
+  return snx_model_backward_units_range_tw(d, params, grads, wcache, ids, mask, cu_seqlens, pos, rope_global, rope_local,
+                                           saved, g_sparse, nullptr, scratch, groups, T_plan, nseq_plan, T, nseq, max_seqlen,
+                                           unit_begin, unit_end, notify, st);
+}
+
+// ... and the gradient of token_weights as well: g_token_weights [T] fp32 (row order of the arena, read by unit 0), or
+// NULL (exactly snx_model_backward_units_range)
+extern "C" int snx_model_backward_units_range_tw(const snx_model_desc* d, const void* const* params, void* const* grads,
+                                                 const void* wcache, const int64_t* ids, const int64_t* mask,
+                                                 const int32_t* cu_seqlens, const int32_t* pos, const float* rope_global,
+                                                 const float* rope_local, const void* saved, const float* g_sparse,
+                                                 const float* g_token_weights, void* scratch, const int32_t* groups,
+                                                 int32_t T_plan, int32_t nseq_plan, int32_t T, int32_t nseq,
+                                                 int32_t max_seqlen, int32_t unit_begin, int32_t unit_end,
+                                                 hipStream_t notify, hipStream_t st) {
   if (!desc_ok(d)) return SNX_E_SHAPE;
   if (!params || !grads || !wcache || !ids || !mask || !cu_seqlens || !pos || !rope_global || !rope_local || !saved ||
       !g_sparse || !scratch || T <= 0 || nseq <= 0 || max_seqlen <= 0 || T > T_plan || nseq > nseq_plan)
@@ -558,8 +584,9 @@ extern "C" int snx_model_backward_units_range(const snx_model_desc* d, const voi
       // (round 6, measured and dropped: the weight half -- dE / db -- on the idle side stream beside the activation half:
       // 45.23 against 45.01 ms per micro-step on one box, ABAB; two gathers that share the CUs' wave slots contend more
       // than they hide)
-      RC(snx_splade_bwd(g_sparse, (const uint32_t*)(sv + s.keys), sv + s.hd, wc + c.emb, cu_seqlens, A, G(p.tok_emb()),
-                        G(p.dec_bias()), sc + b.splade, T, nseq, max_seqlen, V, H, st)); }
+      RC(snx_splade_bwd_tw(g_sparse, (const uint32_t*)(sv + s.keys), g_token_weights, (const uint32_t*)(sv + s.tkeys),
+                           sv + s.hd, wc + c.emb, cu_seqlens, A, G(p.tok_emb()), G(p.dec_bias()), sc + b.splade,
+                           sc + b.splade_tw, T, nseq, max_seqlen, V, H, st)); }
     { PROF(PC_LN_BWD, TH * 6); RC(snx_gelu_ln_bwd_x(A, sv + s.dd, F(p.head_norm()), Bb, G(p.head_norm()), T, H, d->ln_eps, LNWS(0), st)); }
     { PROF(PC_GEMM_TN, 2.0 * TH * H);
       RC(snx_gemm_tn_accum(Bb, sv + s.xf, G(p.head_dense()), T, H, H, sc + b.tnws_main, b.tnws_main_bytes, st)); }

@@ -13,6 +13,7 @@
 // (unsigned max = largest value, ties -> smallest s: torch's first-index argmax).  The key is
 // saved per (b, v): the backward pass routes the gradient to exactly that row (row a7 of §8).
 #include <cstdlib>
+#include <type_traits>
 
 #include "gemm_core.h"
 #include "config.h"
@@ -22,11 +23,15 @@
 #define SNX_DEC_GROUP 8
 #endif
 
-template <int BM>
+// REC (training forwards, SNX_FWD_SAVE_FOR_BACKWARD): the row maxima are column-tagged keys
+//   rowkey = bf16_bits(relu(logit)) << 16 | (0xFFFF - v)      (u32 per (tile, token); unsigned max = largest value,
+// ties -> lowest v) instead of bare value bits (u16), so that token_weights_kernel can keep each token's arg-max column
+// for the backward of token_weights.  REC = false compiles to the inference kernel of before.
+template <int BM, bool REC>
 __global__ __launch_bounds__(256, 2) void decoder_splade_kernel(
     const bf16_t* __restrict__ Hd, const bf16_t* __restrict__ W, const float* __restrict__ bias,
     const int32_t* __restrict__ cu_seqlens, const int64_t* __restrict__ mask, float* __restrict__ sparse,
-    uint32_t* __restrict__ keys, unsigned short* __restrict__ rowpart, int T, int V, int K, int n_tiles,
+    uint32_t* __restrict__ keys, void* __restrict__ rowpart, int T, int V, int K, int n_tiles,
     int total_tiles, int nseq) {
   constexpr int BN = 128;
   using Core = GemmCore<BM, BN, 2, 2>;
@@ -55,11 +60,13 @@ __global__ __launch_bounds__(256, 2) void decoder_splade_kernel(
 
   float bcol[Core::NI];
   bool colok[Core::NI];
+  uint32_t ctag[Core::NI];                            // REC: column tag of the row keys
 #pragma unroll
   for (int j = 0; j < Core::NI; ++j) {
     const int col = n0 + Core::acc_col(j);
     colok[j] = col < V;
     bcol[j] = colok[j] ? rbf(bias[col]) : 0.f;
+    ctag[j] = (0xFFFFu - (uint32_t)col) & 0xFFFFu;
   }
   uint32_t best[Core::NI];
 #pragma unroll
@@ -88,7 +95,12 @@ __global__ __launch_bounds__(256, 2) void decoder_splade_kernel(
           const uint32_t bits = (valid && colok[j]) ? bf16_bits(v) : 0u;
           const uint32_t key = (bits << 16) | rtag;
           best[j] = (valid && key > best[j]) ? key : best[j];
-          rb = bits > rb ? bits : rb;
+          if (REC) {
+            const uint32_t ck = (bits << 16) | ctag[j];
+            rb = ck > rb ? ck : rb;
+          } else {
+            rb = bits > rb ? bits : rb;
+          }
         }
         rb = max(rb, (uint32_t)__shfl_xor((int)rb, 1, 64));
         rb = max(rb, (uint32_t)__shfl_xor((int)rb, 2, 64));
@@ -102,7 +114,8 @@ __global__ __launch_bounds__(256, 2) void decoder_splade_kernel(
       const int srow = c0 + rr;
       if (srow < slen) {
         const uint32_t a = sRow[rr], b = sRow[BM + rr];
-        rowpart[(long)nt * T + s0 + srow] = (unsigned short)(a > b ? a : b);
+        if (REC) ((uint32_t*)rowpart)[(long)nt * T + s0 + srow] = a > b ? a : b;
+        else ((unsigned short*)rowpart)[(long)nt * T + s0 + srow] = (unsigned short)(a > b ? a : b);
       }
     }
   }
@@ -127,8 +140,14 @@ __global__ __launch_bounds__(256, 2) void decoder_splade_kernel(
 }
 
 // token_weights[t] = mask[t] ? log1p(max over vocab tiles of rowpart[nt][t]) : 0
-__global__ void token_weights_kernel(const unsigned short* __restrict__ rowpart, const int64_t* __restrict__ mask,
-                                     float* __restrict__ tw, int T, int n_tiles) {
+// REC: rowpart holds the column-tagged u32 keys; the maximum key is also kept as tkeys[t] (the token's arg-max column for
+// the backward; 0xFFFF = value 0 at column 0 for masked tokens and tokens whose every logit is <= 0, whatever the tile
+// order left in the tag), and tw has the same bits as without REC.
+template <bool REC>
+__global__ void token_weights_kernel(const void* __restrict__ rowpart_, const int64_t* __restrict__ mask,
+                                     float* __restrict__ tw, uint32_t* __restrict__ tkeys, int T, int n_tiles) {
+  using E = typename std::conditional<REC, uint32_t, unsigned short>::type;
+  const E* __restrict__ rowpart = (const E*)rowpart_;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= T) return;
   // 8 independent loads in flight per thread: one dependent load per tile made this pass latency-bound (130 us for
@@ -146,7 +165,14 @@ __global__ void token_weights_kernel(const unsigned short* __restrict__ rowpart,
     const uint32_t v = rowpart[(long)nt * T + t];
     m = v > m ? v : m;
   }
-  tw[t] = mask[t] != 0 ? log1pf(bits_to_f32(m)) : 0.f;
+  const bool live = mask[t] != 0;
+  if (REC) {
+    const uint32_t bits = m >> 16;
+    tw[t] = live ? log1pf(bits_to_f32(bits)) : 0.f;
+    tkeys[t] = (live && bits) ? m : 0xFFFFu;
+  } else {
+    tw[t] = live ? log1pf(bits_to_f32(m)) : 0.f;
+  }
 }
 
 // 256x256 persistent form (decoder256.hip)
@@ -154,7 +180,7 @@ size_t snx_dec256_table_bytes(int32_t T);
 int snx_dec256_rowtiles(int32_t V);                   // rows of the row-maximum array it writes (96-column half tiles)
 int snx_launch_decoder256(const void* Hd, const void* W, const float* bias, const int32_t* cu_seqlens,
                           const int64_t* mask, float* sparse, uint32_t* keys, void* scratch, size_t rowpart_bytes,
-                          int32_t T, int32_t nseq, int32_t V, int32_t K, hipStream_t st);
+                          int32_t T, int32_t nseq, int32_t V, int32_t K, bool rec, hipStream_t st);
 
 // SNX_DEC256=0 keeps the 128x128 kernel; the 256x192 form wants enough rows to fill its tiles.  (model.hip asks: the
 // 256x192 form takes all sequence groups of a pass in ONE call, the 128x128 kernel one call per group.)
@@ -162,62 +188,81 @@ bool snx_dec256_takes(int32_t T) {
   return g_snx_cfg.dec256 && T >= g_snx_cfg.dec256_min_t;
 }
 
-// row maxima [tiles, T] ushort (tiles = ceil(V / 128) for the 128x128 kernel, 2 ceil(V / 192) for the 256x192 form)
-// + the pre-pass tables of the latter
-extern "C" size_t snx_splade_head_scratch_bytes(int32_t T, int32_t V) {
+// row maxima [tiles, T] (u16 value bits; u32 column-tagged keys when the forward records the token arg-max: sized for
+// the latter) (tiles = ceil(V / 128) for the 128x128 kernel, 2 ceil(V / 192) for the 256x192 form) + the pre-pass
+// tables of the latter
+static size_t rowpart_bytes(int32_t T, int32_t V) {
   const size_t tiles = (size_t)(cdiv(V, 128) > snx_dec256_rowtiles(V) ? cdiv(V, 128) : snx_dec256_rowtiles(V));
-  return ((tiles * T * 2 + 255) & ~(size_t)255) + snx_dec256_table_bytes(T);
+  return (tiles * T * 4 + 255) & ~(size_t)255;
+}
+
+extern "C" size_t snx_splade_head_scratch_bytes(int32_t T, int32_t V) {
+  return rowpart_bytes(T, V) + snx_dec256_table_bytes(T);
 }
 
 // `finalize` = 0 skips the token_weights pass (used when several sequence groups of one token
-// buffer are processed by separate calls; the last call finalises all T rows).
-extern "C" int snx_decoder_splade_fwd_ex(const void* Hd, const void* W, const float* bias,
-                                         const int32_t* cu_seqlens, const int64_t* mask, float* sparse,
-                                         uint32_t* keys, float* token_weights, void* scratch, int32_t T,
-                                         int32_t nseq, int32_t max_seqlen, int32_t V, int32_t K, int32_t finalize,
-                                         hipStream_t st) {
+// buffer are processed by separate calls; the last call finalises all T rows).  token_keys != NULL: record every
+// token's arg-max column (token_weights_kernel<true>); the finalising call writes token_keys[0, T).
+extern "C" int snx_decoder_splade_fwd_rec(const void* Hd, const void* W, const float* bias,
+                                          const int32_t* cu_seqlens, const int64_t* mask, float* sparse,
+                                          uint32_t* keys, float* token_weights, uint32_t* token_keys, void* scratch,
+                                          int32_t T, int32_t nseq, int32_t max_seqlen, int32_t V, int32_t K,
+                                          int32_t finalize, hipStream_t st) {
   if (!Hd || !W || !bias || !cu_seqlens || !mask || !sparse || !keys || !token_weights || !scratch) return SNX_E_ARG;
   if (T <= 0 || nseq <= 0 || V <= 0 || K <= 0 || (K % 64) || max_seqlen > 65535) return SNX_E_SHAPE;
+  const bool rec = token_keys != nullptr;
+  if (rec && V > 65535) return SNX_E_SHAPE;           // the column tag is 16 bits
   const int n_tiles = cdiv(V, 128);
+  auto finish = [&](int tiles) -> int {
+    if (!finalize) return SNX_OK;
+    if (rec)
+      hipLaunchKernelGGL(token_weights_kernel<true>, dim3(cdiv(T, 256)), dim3(256), 0, st, (const void*)scratch, mask,
+                         token_weights, token_keys, T, tiles);
+    else
+      hipLaunchKernelGGL(token_weights_kernel<false>, dim3(cdiv(T, 256)), dim3(256), 0, st, (const void*)scratch, mask,
+                         token_weights, (uint32_t*)nullptr, T, tiles);
+    SNX_CHECK_LAUNCH();
+    return SNX_OK;
+  };
   if (snx_dec256_takes(T)) {
     const int rowtiles = snx_dec256_rowtiles(V);
-    const size_t tiles = (size_t)(n_tiles > rowtiles ? n_tiles : rowtiles);
-    const int rc = snx_launch_decoder256(Hd, W, bias, cu_seqlens, mask, sparse, keys, scratch, tiles * T * 2, T, nseq,
-                                         V, K, st);
+    const int rc = snx_launch_decoder256(Hd, W, bias, cu_seqlens, mask, sparse, keys, scratch, rowpart_bytes(T, V), T,
+                                         nseq, V, K, rec, st);
     if (rc != SNX_E_SHAPE) {
       if (rc != SNX_OK) return rc;
-      if (finalize) {
-        hipLaunchKernelGGL(token_weights_kernel, dim3(cdiv(T, 256)), dim3(256), 0, st, (const unsigned short*)scratch,
-                           mask, token_weights, T, rowtiles);
-        SNX_CHECK_LAUNCH();
-      }
-      return SNX_OK;
+      return finish(rowtiles);
     }
   }
   const long total_l = 8L * cdiv(cdiv(nseq, SNX_DEC_GROUP), 8) * SNX_DEC_GROUP * n_tiles;
   if (total_l > 0x7fffffffL) return SNX_E_SHAPE;
   const int total = (int)total_l;
-  unsigned short* rowpart = (unsigned short*)scratch;
+  void* rowpart = scratch;
+#define SNX_DEC128(BMV, RECV)                                                                                          \
+  do {                                                                                                                 \
+    using Core = GemmCore<BMV, 128, 2, 2>;                                                                             \
+    const size_t lds = Core::LDS_BYTES + (2 * 128 + 2 * BMV) * 4;                                                      \
+    hipLaunchKernelGGL((decoder_splade_kernel<BMV, RECV>), dim3(total), dim3(256), lds, st, (const bf16_t*)Hd,         \
+                       (const bf16_t*)W, bias, cu_seqlens, mask, sparse, keys, rowpart, T, V, K, n_tiles, total, nseq); \
+  } while (0)
   if (max_seqlen <= 64) {
-    using Core = GemmCore<64, 128, 2, 2>;
-    const size_t lds = Core::LDS_BYTES + (2 * 128 + 2 * 64) * 4;
-    hipLaunchKernelGGL(decoder_splade_kernel<64>, dim3(total), dim3(256), lds, st, (const bf16_t*)Hd,
-                       (const bf16_t*)W, bias, cu_seqlens, mask, sparse, keys, rowpart, T, V, K, n_tiles, total,
-                       nseq);
+    if (rec) SNX_DEC128(64, true);
+    else SNX_DEC128(64, false);
   } else {
-    using Core = GemmCore<128, 128, 2, 2>;
-    const size_t lds = Core::LDS_BYTES + (2 * 128 + 2 * 128) * 4;
-    hipLaunchKernelGGL(decoder_splade_kernel<128>, dim3(total), dim3(256), lds, st, (const bf16_t*)Hd,
-                       (const bf16_t*)W, bias, cu_seqlens, mask, sparse, keys, rowpart, T, V, K, n_tiles, total,
-                       nseq);
+    if (rec) SNX_DEC128(128, true);
+    else SNX_DEC128(128, false);
   }
+#undef SNX_DEC128
   SNX_CHECK_LAUNCH();
-  if (finalize) {
-    hipLaunchKernelGGL(token_weights_kernel, dim3(cdiv(T, 256)), dim3(256), 0, st, rowpart, mask, token_weights, T,
-                       n_tiles);
-    SNX_CHECK_LAUNCH();
-  }
-  return SNX_OK;
+  return finish(n_tiles);
+}
+
+extern "C" int snx_decoder_splade_fwd_ex(const void* Hd, const void* W, const float* bias,
+                                         const int32_t* cu_seqlens, const int64_t* mask, float* sparse,
+                                         uint32_t* keys, float* token_weights, void* scratch, int32_t T,
+                                         int32_t nseq, int32_t max_seqlen, int32_t V, int32_t K, int32_t finalize,
+                                         hipStream_t st) {
+  return snx_decoder_splade_fwd_rec(Hd, W, bias, cu_seqlens, mask, sparse, keys, token_weights, nullptr, scratch, T,
+                                    nseq, max_seqlen, V, K, finalize, st);
 }
 
 extern "C" int snx_decoder_splade_fwd(const void* Hd, const void* W, const float* bias, const int32_t* cu_seqlens,
@@ -475,13 +520,34 @@ __global__ __launch_bounds__(1024) void splade_bucket_kernel(const float* __rest
   for (int r = threadIdx.x; r <= rows; r += blockDim.x) row_off[(long)seq * (max_rows + 1) + r] = off[r];
 }
 
+// The token_weights direction's entry of token row t (snx_splade_bwd_tw): one more (v*(t), c_t) term of the row's fp32
+// sum, after its bucket entries and before the single rounding to bf16.  Wave-uniform (t is).
+template <int NV>
+__device__ __forceinline__ void tw_entry(f32x4 (&acc)[NV], const int32_t* __restrict__ tok_v,
+                                         const float* __restrict__ tok_c, const bf16_t* __restrict__ W, int t, int H,
+                                         int lane) {
+  const float c = tok_c[t];
+  if (c == 0.f) return;
+  const bf16_t* wrow = W + (long)tok_v[t] * H;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const bf16x4 w = *(const bf16x4*)(wrow + (i * 64 + lane) * 4);
+    acc[i][0] += c * bf2f(w[0]);
+    acc[i][1] += c * bf2f(w[1]);
+    acc[i][2] += c * bf2f(w[2]);
+    acc[i][3] += c * bf2f(w[3]);
+  }
+}
+
 template <int NV>
 __global__ __launch_bounds__(256) void splade_bwd_dh_rows_kernel(const int32_t* __restrict__ list_v,
                                                                  const float* __restrict__ list_c,
                                                                  const int32_t* __restrict__ row_off,
                                                                  const bf16_t* __restrict__ W,
                                                                  const int32_t* __restrict__ cu_seqlens,
-                                                                 bf16_t* __restrict__ dHd, int V, int H, int max_rows) {
+                                                                 bf16_t* __restrict__ dHd, int V, int H, int max_rows,
+                                                                 const int32_t* __restrict__ tok_v,
+                                                                 const float* __restrict__ tok_c) {
   const int seq = blockIdx.y;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -523,6 +589,7 @@ __global__ __launch_bounds__(256) void splade_bwd_dh_rows_kernel(const int32_t* 
       }
     }
   }
+  if (tok_c) tw_entry<NV>(acc, tok_v, tok_c, W, s0 + row, H, lane);
   bf16_t* out = dHd + (long)(s0 + row) * H;
 #pragma unroll
   for (int i = 0; i < NV; ++i)
@@ -580,7 +647,9 @@ __global__ __launch_bounds__(256) void splade_bwd_dh_panels_kernel(const int32_t
                                                                    const bf16_t* __restrict__ W,
                                                                    const int32_t* __restrict__ cu_seqlens,
                                                                    bf16_t* __restrict__ dHd, int V, int H, int max_rows,
-                                                                   int nseq, int npanel, int* __restrict__ counter) {
+                                                                   int nseq, int npanel, int* __restrict__ counter,
+                                                                   const int32_t* __restrict__ tok_v,
+                                                                   const float* __restrict__ tok_c) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nitems = items[nseq];
@@ -670,6 +739,7 @@ __global__ __launch_bounds__(256) void splade_bwd_dh_panels_kernel(const int32_t
     for (int j = 0; j < RW; ++j) {
       const int row = row0 + j;
       if (row < slen) {
+        if (tok_c) tw_entry<NV>(acc[j], tok_v, tok_c, W, s0 + row, H, lane);
         bf16_t* out = dHd + (long)(s0 + row) * H;
 #pragma unroll
         for (int i = 0; i < NV; ++i)
@@ -680,15 +750,216 @@ __global__ __launch_bounds__(256) void splade_bwd_dh_panels_kernel(const int32_t
   }
 }
 
+// ==========================================================================================
+// Backward of token_weights[t] = m_t log1p(x(t, v*(t))), v*(t) = first column of the token's maximum (tkeys, recorded by
+// token_weights_kernel<true>):
+//   c_t        = rbf((g_s + g_tw[t]) / (1 + x)) - rbf(g_s / (1 + x))       (x > 0; else 0)
+//   dHd[t]    += c_t W[v*]         (tw_entry: inside the gather's fp32 sum, rounded to bf16 once with the rest)
+//   dE[v], db[v] += sum over the tokens t with v*(t) = v of c_t Hd[t], c_t
+// g_s = g[seq(t), v*] when the sparse key of (seq(t), v*) routes to this very row (a one-token sequence always does), else
+// 0: the two upstream gradients of one logit then add BEFORE the bf16 rounding, as autograd adds them in fp32 before it
+// casts the logit's gradient; the difference of two bf16 values is exact in fp32, so the row's sum sees the combined
+// coefficient.  dE / db go through a counting sort of the active tokens by v* (stable: token order inside a column) and
+// one accumulation pass: no float atomics, the same bits in every run.
+// ==========================================================================================
+constexpr int TWC = 1024;                              // tokens per chunk of the counting sort (one workgroup)
+
+__global__ __launch_bounds__(TWC) void splade_tw_coef_kernel(const float* __restrict__ g, const uint32_t* __restrict__ keys,
+                                                            const float* __restrict__ g_tw, const uint32_t* __restrict__ tkeys,
+                                                            const int32_t* __restrict__ cu, int32_t* __restrict__ tok_v,
+                                                            float* __restrict__ tok_c, int32_t* __restrict__ tab, int T,
+                                                            int nseq, int V) {
+  const int t = blockIdx.x * TWC + threadIdx.x;
+  if (t >= T) return;
+  const uint32_t tk = tkeys[t];
+  const float x = bits_to_f32(tk >> 16);
+  const float gt = g_tw[t];
+  int v = -1;
+  float c = 0.f;
+  if (x > 0.f && gt != 0.f && t < cu[nseq]) {
+    v = 0xFFFF - (int)(tk & 0xFFFFu);
+    int lo = 0, hi = nseq - 1;                         // sequence of t: last s with cu[s] <= t
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (cu[mid] <= t) lo = mid;
+      else hi = mid - 1;
+    }
+    const long e = (long)lo * V + v;
+    const uint32_t sk = keys[e];
+    const bool same = (sk >> 16) == (tk >> 16) && (int)(0xFFFFu - (sk & 0xFFFFu)) == t - cu[lo];
+    const float gs = same ? g[e] : 0.f;
+    c = rbf((gs + gt) / (1.0f + x)) - rbf(gs / (1.0f + x));
+    if (c != 0.f) atomicAdd(&tab[(long)blockIdx.x * V + v], 1);   // integer counts: order-free
+    else v = -1;
+  }
+  tok_v[t] = v;
+  tok_c[t] = c;
+}
+
+// per column: exclusive prefix of the chunk counts over the chunks (in place), total -> tot[v]
+__global__ void splade_tw_colscan_kernel(int32_t* __restrict__ tab, int32_t* __restrict__ tot, int nchunk, int V) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  int run = 0;
+  for (int k = 0; k < nchunk; ++k) {
+    const int c = tab[(long)k * V + v];
+    tab[(long)k * V + v] = run;
+    run += c;
+  }
+  tot[v] = run;
+}
+
+// off[v] = exclusive prefix of tot over the columns, off[V] = number of active tokens (one workgroup)
+__global__ __launch_bounds__(1024) void splade_tw_vscan_kernel(const int32_t* __restrict__ tot, int32_t* __restrict__ off, int V) {
+  __shared__ int part[1024];
+  const int t = threadIdx.x;
+  const int per = (V + 1023) / 1024;
+  const int b = min(V, t * per), e = min(V, b + per);
+  int mine = 0;
+  for (int v = b; v < e; ++v) mine += tot[v];
+  part[t] = mine;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {                 // inclusive scan (Hillis-Steele)
+    const int add = t >= o ? part[t - o] : 0;
+    __syncthreads();
+    part[t] += add;
+    __syncthreads();
+  }
+  int run = part[t] - mine;
+  for (int v = b; v < e; ++v) {
+    off[v] = run;
+    run += tot[v];
+  }
+  if (t == 1023) off[V] = part[1023];
+}
+
+// slot of every active token: column start + tokens of the earlier chunks in that column + earlier tokens of this chunk
+// in that column (counted in LDS: stable, no atomics)
+__global__ __launch_bounds__(TWC) void splade_tw_fill_kernel(const int32_t* __restrict__ tok_v, const int32_t* __restrict__ tab,
+                                                            const int32_t* __restrict__ off, int32_t* __restrict__ list_t,
+                                                            int T, int V) {
+  __shared__ int sv[TWC];
+  const int i = threadIdx.x, t = blockIdx.x * TWC + i;
+  const int v = t < T ? tok_v[t] : -1;
+  sv[i] = v;
+  __syncthreads();
+  if (v < 0) return;
+  int r = 0;
+  for (int j = 0; j < i; ++j) r += sv[j] == v;
+  list_t[off[v] + tab[(long)blockIdx.x * V + v] + r] = t;
+}
+
+// dE[v] += sum_k c_{t_k} Hd[t_k], db[v] += sum_k c_{t_k} over column v's tokens in token order: one wave per column
+template <int NV>
+__global__ __launch_bounds__(256) void splade_tw_dw_kernel(const int32_t* __restrict__ list_t, const int32_t* __restrict__ off,
+                                                          const float* __restrict__ tok_c, const bf16_t* __restrict__ Hd,
+                                                          float* __restrict__ gradE, float* __restrict__ gradb, int V, int H) {
+  const int lane = threadIdx.x & 63;
+  const int v = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (v >= V) return;
+  const int beg = off[v], end = off[v + 1];
+  if (beg == end) return;
+  f32x4 acc[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float csum = 0.f;
+  for (int e0 = beg; e0 < end; e0 += 64) {
+    const int e = e0 + lane;
+    const int tl = e < end ? list_t[e] : 0;
+    const float cl = e < end ? tok_c[tl] : 0.f;
+    const int n = min(64, end - e0);
+    for (int u0 = 0; u0 < n; u0 += GB) {
+      float cb[GB];
+      bf16x4 hv[GB][NV];
+#pragma unroll
+      for (int u = 0; u < GB; ++u) {
+        const int src = u0 + u;                        // wave-uniform
+        cb[u] = src < n ? __shfl(cl, src, 64) : 0.f;
+        const bf16_t* hrow = Hd + (long)__shfl(tl, src < n ? src : 0, 64) * H;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) hv[u][i] = *(const bf16x4*)(hrow + (i * 64 + lane) * 4);
+      }
+#pragma unroll
+      for (int u = 0; u < GB; ++u) {
+        csum += cb[u];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+          acc[i][0] += cb[u] * bf2f(hv[u][i][0]);
+          acc[i][1] += cb[u] * bf2f(hv[u][i][1]);
+          acc[i][2] += cb[u] * bf2f(hv[u][i][2]);
+          acc[i][3] += cb[u] * bf2f(hv[u][i][3]);
+        }
+      }
+    }
+  }
+  if (lane == 0) gradb[v] += csum;
+  float* dst = gradE + (long)v * H;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    f32x4* p = (f32x4*)(dst + (i * 64 + lane) * 4);
+    *p = *p + acc[i];
+  }
+}
+
+static size_t tw_chunks(int32_t T) { return (size_t)cdiv(T, TWC); }
+
+// tok_v [T] | tok_c [T] | list_t [T] | off [V + 1] | tot [V] | tab [chunks, V]
+extern "C" size_t snx_splade_tw_scratch_bytes(int32_t T, int32_t V) {
+  if (T <= 0 || V <= 0) return 0;
+  return (size_t)T * 12 + 256 + ((size_t)2 * V + 1) * 4 + 256 + tw_chunks(T) * V * 4 + 256;
+}
+
 extern "C" size_t snx_splade_bwd_scratch_bytes(int32_t nseq, int32_t max_seqlen, int32_t V) {
   return (size_t)nseq * V * 8 + (size_t)nseq * (max_seqlen + 1) * 4 + 256 + ((size_t)nseq + 2) * 4 + 256;
 }
 
-extern "C" int snx_splade_bwd(const float* g, const uint32_t* keys, const void* Hd, const void* W,
-                              const int32_t* cu_seqlens, void* dHd, float* gradE, float* gradb, void* scratch,
-                              int32_t T, int32_t nseq, int32_t max_seqlen, int32_t V, int32_t H, hipStream_t st) {
+// g_tw == NULL: the sparse direction alone (nothing of the token direction is launched).  Else g_tw [T] (row order),
+// tkeys [T] (token_weights_kernel<true>) and tw_scratch (snx_splade_tw_scratch_bytes) are needed.
+extern "C" int snx_splade_bwd_tw(const float* g, const uint32_t* keys, const float* g_tw, const uint32_t* tkeys,
+                                 const void* Hd, const void* W, const int32_t* cu_seqlens, void* dHd, float* gradE,
+                                 float* gradb, void* scratch, void* tw_scratch, int32_t T, int32_t nseq,
+                                 int32_t max_seqlen, int32_t V, int32_t H, hipStream_t st) {
   if (!g || !keys || !Hd || !W || !cu_seqlens || !dHd || !gradE || !gradb || !scratch) return SNX_E_ARG;
+  if (g_tw && (!tkeys || !tw_scratch)) return SNX_E_ARG;
   if (T <= 0 || nseq <= 0 || V <= 0 || max_seqlen <= 0 || H <= 0 || (H % 256) || H > 1024) return SNX_E_SHAPE;
+  if (g_tw && V > 65535) return SNX_E_SHAPE;
+  // token direction, first half: coefficients (read by the dHd gather below) and the counting sort by column
+  int32_t* tok_v = nullptr;
+  float* tok_c = nullptr;
+  int32_t *list_t = nullptr, *tw_off = nullptr;
+  if (g_tw) {
+    char* tsc = (char*)tw_scratch;
+    tok_v = (int32_t*)tsc;
+    tok_c = (float*)(tsc + (size_t)T * 4);
+    list_t = (int32_t*)(tsc + (size_t)T * 8);
+    tw_off = (int32_t*)(tsc + (((size_t)T * 12 + 255) & ~(size_t)255));
+    int32_t* tot = tw_off + V + 1;
+    int32_t* tab = (int32_t*)(((uintptr_t)(tot + V) + 255) & ~(uintptr_t)255);
+    const int nchunk = (int)tw_chunks(T);
+    hipError_t e = hipMemsetAsync(tab, 0, (size_t)nchunk * V * 4, st);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(splade_tw_coef_kernel, dim3(nchunk), dim3(TWC), 0, st, g, keys, g_tw, tkeys, cu_seqlens, tok_v, tok_c,
+                       tab, T, nseq, V);
+    SNX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(splade_tw_colscan_kernel, dim3(cdiv(V, 256)), dim3(256), 0, st, tab, tot, nchunk, V);
+    SNX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(splade_tw_vscan_kernel, dim3(1), dim3(1024), 0, st, (const int32_t*)tot, tw_off, V);
+    SNX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(splade_tw_fill_kernel, dim3(nchunk), dim3(TWC), 0, st, (const int32_t*)tok_v, (const int32_t*)tab,
+                       (const int32_t*)tw_off, list_t, T, V);
+    SNX_CHECK_LAUNCH();
+  }
+  // token direction, second half (after the sparse direction's dE / db): dE, db in token order per column
+  auto launch_tw_dw = [&]() {
+    if (!g_tw) return;
+    const dim3 grid(cdiv(V, 4));
+    switch (H / 256) {
+      case 1: hipLaunchKernelGGL(splade_tw_dw_kernel<1>, grid, dim3(256), 0, st, list_t, tw_off, tok_c, (const bf16_t*)Hd, gradE, gradb, V, H); break;
+      case 2: hipLaunchKernelGGL(splade_tw_dw_kernel<2>, grid, dim3(256), 0, st, list_t, tw_off, tok_c, (const bf16_t*)Hd, gradE, gradb, V, H); break;
+      case 3: hipLaunchKernelGGL(splade_tw_dw_kernel<3>, grid, dim3(256), 0, st, list_t, tw_off, tok_c, (const bf16_t*)Hd, gradE, gradb, V, H); break;
+      default: hipLaunchKernelGGL(splade_tw_dw_kernel<4>, grid, dim3(256), 0, st, list_t, tw_off, tok_c, (const bf16_t*)Hd, gradE, gradb, V, H); break;
+    }
+  };
   const int blocks = cdiv(V, 32);               // 4 waves x 8 vocab rows per workgroup
   // "splade_dw_last" = 1 (round 6): the weight half (dE, db) AFTER the activation half.  The dHd gather below is bound by
   // how fast W_E rows (77 MB) come out of the Infinity Cache, where the decoder forward has just left them; run first, the
@@ -747,10 +1018,10 @@ extern "C" int snx_splade_bwd(const float* g, const uint32_t* keys, const void* 
   do {                                                                                                                      \
     if (ntl)                                                                                                                \
       hipLaunchKernelGGL((splade_bwd_dh_panels_kernel<NVV, true>), pgrid, dim3(256), 0, st, list_v, list_c, row_off, items,  \
-                         (const bf16_t*)W, cu_seqlens, (bf16_t*)dHd, V, H, max_seqlen, nseq, panels, items + nseq + 1);      \
+                         (const bf16_t*)W, cu_seqlens, (bf16_t*)dHd, V, H, max_seqlen, nseq, panels, items + nseq + 1, tok_v, tok_c); \
     else                                                                                                                    \
       hipLaunchKernelGGL((splade_bwd_dh_panels_kernel<NVV, false>), pgrid, dim3(256), 0, st, list_v, list_c, row_off, items, \
-                         (const bf16_t*)W, cu_seqlens, (bf16_t*)dHd, V, H, max_seqlen, nseq, panels, items + nseq + 1);      \
+                         (const bf16_t*)W, cu_seqlens, (bf16_t*)dHd, V, H, max_seqlen, nseq, panels, items + nseq + 1, tok_v, tok_c); \
   } while (0)
     switch (H / 256) {
       case 1: SNX_DH_PANELS(1); break;
@@ -764,19 +1035,30 @@ extern "C" int snx_splade_bwd(const float* g, const uint32_t* keys, const void* 
       launch_dw();
       SNX_CHECK_LAUNCH();
     }
+    launch_tw_dw();
+    SNX_CHECK_LAUNCH();
     return SNX_OK;
   }
   const dim3 grid(cdiv(max_seqlen, 4), nseq);
   switch (H / 256) {
-    case 1: hipLaunchKernelGGL(splade_bwd_dh_rows_kernel<1>, grid, dim3(256), 0, st, list_v, list_c, row_off, (const bf16_t*)W, cu_seqlens, (bf16_t*)dHd, V, H, max_seqlen); break;
-    case 2: hipLaunchKernelGGL(splade_bwd_dh_rows_kernel<2>, grid, dim3(256), 0, st, list_v, list_c, row_off, (const bf16_t*)W, cu_seqlens, (bf16_t*)dHd, V, H, max_seqlen); break;
-    case 3: hipLaunchKernelGGL(splade_bwd_dh_rows_kernel<3>, grid, dim3(256), 0, st, list_v, list_c, row_off, (const bf16_t*)W, cu_seqlens, (bf16_t*)dHd, V, H, max_seqlen); break;
-    default: hipLaunchKernelGGL(splade_bwd_dh_rows_kernel<4>, grid, dim3(256), 0, st, list_v, list_c, row_off, (const bf16_t*)W, cu_seqlens, (bf16_t*)dHd, V, H, max_seqlen); break;
+    case 1: hipLaunchKernelGGL(splade_bwd_dh_rows_kernel<1>, grid, dim3(256), 0, st, list_v, list_c, row_off, (const bf16_t*)W, cu_seqlens, (bf16_t*)dHd, V, H, max_seqlen, tok_v, tok_c); break;
+    case 2: hipLaunchKernelGGL(splade_bwd_dh_rows_kernel<2>, grid, dim3(256), 0, st, list_v, list_c, row_off, (const bf16_t*)W, cu_seqlens, (bf16_t*)dHd, V, H, max_seqlen, tok_v, tok_c); break;
+    case 3: hipLaunchKernelGGL(splade_bwd_dh_rows_kernel<3>, grid, dim3(256), 0, st, list_v, list_c, row_off, (const bf16_t*)W, cu_seqlens, (bf16_t*)dHd, V, H, max_seqlen, tok_v, tok_c); break;
+    default: hipLaunchKernelGGL(splade_bwd_dh_rows_kernel<4>, grid, dim3(256), 0, st, list_v, list_c, row_off, (const bf16_t*)W, cu_seqlens, (bf16_t*)dHd, V, H, max_seqlen, tok_v, tok_c); break;
   }
   SNX_CHECK_LAUNCH();
   if (dw_last) {
     launch_dw();
     SNX_CHECK_LAUNCH();
   }
+  launch_tw_dw();
+  SNX_CHECK_LAUNCH();
   return SNX_OK;
+}
+
+extern "C" int snx_splade_bwd(const float* g, const uint32_t* keys, const void* Hd, const void* W,
+                              const int32_t* cu_seqlens, void* dHd, float* gradE, float* gradb, void* scratch,
+                              int32_t T, int32_t nseq, int32_t max_seqlen, int32_t V, int32_t H, hipStream_t st) {
+  return snx_splade_bwd_tw(g, keys, nullptr, nullptr, Hd, W, cu_seqlens, dHd, gradE, gradb, scratch, nullptr, T, nseq,
+                           max_seqlen, V, H, st);
 }

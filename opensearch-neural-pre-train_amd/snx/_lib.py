@@ -62,6 +62,9 @@ SIGNATURES = {
     "snx_decoder_splade_fwd": (I32, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P]),
     "snx_decoder_splade_fwd_ex": (I32, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, P]),
     "snx_splade_bwd": (I32, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P]),
+    "snx_decoder_splade_fwd_rec": (I32, [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, P]),
+    "snx_splade_tw_scratch_bytes": (SZ, [I32, I32]),
+    "snx_splade_bwd_tw": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P]),
     "snx_loss_workspace_bytes": (SZ, [I32, I32, I32, I32]),
     "snx_loss_fwd": (I32, [P, P, P, P, P, P, P, P, P, P, P]),
     "snx_loss_bwd": (I32, [P, P, P, P, P, P, P, I32, P, P, P, P]),
@@ -69,11 +72,14 @@ SIGNATURES = {
     "snx_model_bwd_workspace_bytes": (SZ, [P, I32, I32, I32]),
     "snx_splade_bwd_scratch_bytes": (SZ, [I32, I32, I32]),
     "snx_model_keys_offset": (SZ, [P, I32, I32]),
+    "snx_model_token_keys_offset": (SZ, [P, I32, I32]),
     "snx_weight_cache_bytes": (SZ, [P]),
     "snx_weight_cache_refresh": (I32, [P, P, P, P]),
     "snx_model_forward": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, P]),
     "snx_model_forward_range": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, P]),
     "snx_model_backward_units_range": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, P, P]),
+    "snx_model_backward_units_range_tw": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32,
+                                                P, P]),
     "snx_model_backward": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, P]),
     "snx_model_backward_units": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P, P]),
     "snx_sparse_topk": (I32, [P, P, P, P, P, P, I32, I32, I32, I32, P]),
@@ -81,6 +87,7 @@ SIGNATURES = {
     "snx_model_bwd_workspace_bytes_f32": (SZ, [P, I32]),
     "snx_model_forward_f32": (I32, [P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, P]),
     "snx_model_backward_f32": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, I32, I32, P]),
+    "snx_model_backward_f32_tw": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, I32, I32, P]),
     "snx_gemm_f32": (I32, [P, I64, I64, P, I64, I64, P, I64, P, I64, I32, I32, I32, I32, P]),
     "snx_param_count": (I32, [P]),
     "snx_adamw_scratch_bytes": (SZ, []),

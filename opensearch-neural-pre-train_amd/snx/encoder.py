@@ -359,7 +359,8 @@ class EncoderRuntime:
             tw_full = torch.zeros((T_pad,), dtype=torch.float32, device=dev)
             tw_full[scatter] = tw
             tw = tw_full
-        aux = (ids, mask, cu, pos, rg, rl, T, nseq, smax, groups, fp32)
+        # aux[11]: the padded position of every native row (None: padded = native layout), for the gradient of tw
+        aux = (ids, mask, cu, pos, rg, rl, T, nseq, smax, groups, fp32, scatter)
         return sparse, tw, saved, aux
 
     def routing_rows(self, saved: torch.Tensor, aux) -> torch.Tensor:
@@ -372,15 +373,30 @@ class EncoderRuntime:
         keys = saved[off:off + B * self.geom.vocab_size * 4].view(torch.int32).view(B, -1).to(torch.int64) & 0xFFFFFFFF
         return 0xFFFF - (keys & 0xFFFF)
 
-    def backward_impl(self, saved: torch.Tensor, aux, g_sparse: torch.Tensor, sync_token=None, plan=None):
+    def token_routing(self, saved: torch.Tensor, aux) -> torch.Tensor:
+        """Arg-max vocabulary column per native token row chosen by the token maximum ([T] int64; rows whose
+        token weight is 0 -- masked, or every logit <= 0 -- read 0 and carry no gradient)."""
+        T, B = aux[6], aux[7]
+        if aux[10]:
+            raise NotImplementedError("token_routing: bf16 path only (the fp32 path keeps 64-bit keys)")
+        off = fn("snx_model_token_keys_offset")(C.byref(self._desc), T, B)
+        keys = saved[off:off + T * 4].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        return 0xFFFF - (keys & 0xFFFF)
+
+    def backward_impl(self, saved: torch.Tensor, aux, g_sparse: torch.Tensor, sync_token=None, plan=None, g_tw=None):
         """``plan`` = (T_plan, nseq_plan): `saved` was laid out for that many rows / sequences (a micro-step arena that
-        holds fewer passes than planned); default: the arena of exactly these T rows."""
-        ids, mask, cu, pos, rg, rl, T, B, S, groups, fp32 = aux  # B = total sequences, S = longest
+        holds fewer passes than planned); default: the arena of exactly these T rows.  ``g_tw``: dL/d token_weights
+        [T] in the native row order, or None (no gradient through token_weights: nothing of it is launched)."""
+        ids, mask, cu, pos, rg, rl, T, B, S, groups, fp32 = aux[:11]  # B = total sequences, S = longest
         Tp, Bp = plan if plan is not None else (T, B)
         dev = self._device()
         if g_sparse.shape != (B, self.geom.vocab_size):
             raise ValueError("bad gradient shape")
         g = g_sparse.to(torch.float32).contiguous()
+        if g_tw is not None:
+            if g_tw.numel() != T:
+                raise ValueError("bad token_weights gradient shape")
+            g_tw = g_tw.to(torch.float32).contiguous().view(-1)
         if self.direct_grads:
             grads = [p.grad for p in self.params]
             ret = None
@@ -398,20 +414,21 @@ class EncoderRuntime:
                 nbytes = fn("snx_model_bwd_workspace_bytes_f32")(C.byref(self._desc), T)
                 scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
                 args32 = (C.byref(self._desc), self._param_ptrs(), self._grad_ptrs(grads), _p(ids), _p(mask), _p(cu), _p(pos),
-                          _p(rg), _p(rl), _p(saved), _p(g), _p(scratch), T, B)
+                          _p(rg), _p(rl), _p(saved), _p(g), _p(g_tw), _p(scratch), T, B)
             else:
                 nbytes = fn("snx_model_bwd_workspace_bytes")(C.byref(self._desc), Tp, Bp, S)
                 scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
                 args = (C.byref(self._desc), self._param_ptrs(), self._grad_ptrs(grads), _p(self._weights()), _p(ids),
-                        _p(mask), _p(cu), _p(pos), _p(rg), _p(rl), _p(saved), _p(g), _p(scratch), groups, Tp, Bp, T, B, S)
+                        _p(mask), _p(cu), _p(pos), _p(rg), _p(rl), _p(saved), _p(g), _p(g_tw), _p(scratch), groups, Tp, Bp,
+                        T, B, S)
                 n_units = self.geom.num_hidden_layers + 2
 
             def run_all():
                 if fp32:
-                    check(fn("snx_model_backward_f32")(*args32, _stream()), "snx_model_backward_f32")
+                    check(fn("snx_model_backward_f32_tw")(*args32, _stream()), "snx_model_backward_f32_tw")
                 else:
-                    check(fn("snx_model_backward_units_range")(*args, 0, n_units, None, _stream()),
-                          "snx_model_backward_units_range")
+                    check(fn("snx_model_backward_units_range_tw")(*args, 0, n_units, None, _stream()),
+                          "snx_model_backward_units_range_tw")
 
             def run_units(ub, ue):
                 if fp32:                        # one native call; the exchange stream then waits for the launch stream
@@ -420,8 +437,8 @@ class EncoderRuntime:
                     sync.stream.wait_stream(torch.cuda.current_stream(dev))
                     return
                 # the native call makes the exchange stream wait for the launch stream and the weight-gradient stream
-                check(fn("snx_model_backward_units_range")(*args, ub, ue, C.c_void_p(sync.stream.cuda_stream), _stream()),
-                      "snx_model_backward_units_range")
+                check(fn("snx_model_backward_units_range_tw")(*args, ub, ue, C.c_void_p(sync.stream.cuda_stream),
+                                                                 _stream()), "snx_model_backward_units_range_tw")
 
             if sync is None:
                 run_all()
@@ -597,6 +614,7 @@ class StepArena:
             self.mask = torch.empty((self.T,), dtype=torch.int64, device=dev)
         self.placed = self.reported = 0
         self.grads: list = []
+        self.tw_grads: list = []                             # dL/d token_weights of every placed pass (None: none)
         self.nodes: list = []                                # weak references to the autograd nodes of the placed passes
         self.got: list = []                                  # which of them have reported
         self.wkey = None                                     # parameter versions the first placed pass computed with
@@ -650,6 +668,7 @@ class StepArena:
         self.row0.append(r0 + T)
         self.seq0.append(s0 + B)
         self.grads.append(None)
+        self.tw_grads.append(None)
         self.nodes.append(None)
         self.got.append(False)
         self.placed += 1
@@ -663,8 +682,16 @@ class StepArena:
         keys = self.saved[off:off + B * V * 4].view(torch.int32).view(B, -1).to(torch.int64) & 0xFFFFFFFF
         return 0xFFFF - (keys & 0xFFFF)
 
-    def report(self, k: int, g: Optional[torch.Tensor], token):
-        """Backward of node k: hand in dL/d sparse_k.  Returns the parameter gradients from the LAST node to report
+    def token_routing(self, k: int) -> torch.Tensor:
+        """Arg-max vocabulary column per token row of pass k (as EncoderRuntime.token_routing)."""
+        rt = self.rt
+        B, S = self.shapes[k]
+        off = fn("snx_model_token_keys_offset")(C.byref(rt._desc), self.T, self.nseq) + self.row0[k] * 4
+        keys = self.saved[off:off + B * S * 4].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        return 0xFFFF - (keys & 0xFFFF)
+
+    def report(self, k: int, g: Optional[torch.Tensor], token, g_tw: Optional[torch.Tensor] = None):
+        """Backward of node k: hand in dL/d sparse_k (and dL/d token_weights_k, or None).  Returns the parameter gradients from the LAST node to report
         (None in the flat-gradient mode, where the native backward accumulates in place)."""
         rt = self.rt
         if not self.reporting:
@@ -677,6 +704,7 @@ class StepArena:
                 rt.step_arena_backward_begins()
             torch.autograd.Variable._execution_engine.queue_callback(self._engine_done)
         self.grads[k] = g
+        self.tw_grads[k] = g_tw
         self.got[k] = True
         self.reported += 1
         sync = rt.grad_sync if (rt.direct_grads and rt.grad_sync is not None) else None
@@ -699,14 +727,21 @@ class StepArena:
         parts = [g.to(torch.float32) if g is not None else torch.zeros((b, V), dtype=torch.float32, device=self.dev)
                  for g, (b, _) in zip(self.grads, shapes)]
         g_all = _gather_rows(parts, [b for b, _ in shapes], V, self.dev)
+        g_tw = None
+        if any(t is not None for t in self.tw_grads):      # passes without one (unused, zero-filled, dead) carry zeros
+            g_tw = torch.zeros((T,), dtype=torch.float32, device=self.dev)
+            for t, r0, r1 in zip(self.tw_grads, self.row0[:-1], self.row0[1:]):
+                if t is not None:
+                    g_tw[r0:r1] = t.reshape(-1)
         cu, pos, groups = rt._layout(shapes, self.dev)
         smax = max(s for _, s in shapes)
         hd = rt.geom.hidden_size // rt.geom.num_attention_heads
         rg, rl = rt._rope_tables(max(smax, 64), self.dev, hd)
-        aux = (self.ids[:T], self.mask[:T], cu, pos, rg, rl, T, nseq, smax, groups if n > 1 else None, False)
-        grads = rt.backward_impl(self.saved, aux, g_all, token, plan=(self.T, self.nseq))
+        aux = (self.ids[:T], self.mask[:T], cu, pos, rg, rl, T, nseq, smax, groups if n > 1 else None, False, None)
+        grads = rt.backward_impl(self.saved, aux, g_all, token, plan=(self.T, self.nseq), g_tw=g_tw)
         self.saved = None
         self.grads = []
+        self.tw_grads = []
         return grads
 
     def _engine_done(self):
@@ -762,6 +797,8 @@ class _SpladeEncodeFn(torch.autograd.Function):
     def forward(ctx, rt: EncoderRuntime, n_pairs: int, lengths, *args):
         pairs = [(args[2 * i], args[2 * i + 1]) for i in range(n_pairs)]
         ctx.n_in = 2 * n_pairs + 1
+        # an unused token_weights output must arrive as None (no token-direction launch), not as materialised zeros
+        ctx.set_materialize_grads(False)
         ctx.rt, ctx.arena, ctx.counted = rt, None, False
         if n_pairs == 1 and lengths is None:
             placed = rt.step_arena_place(pairs[0][0], pairs[0][1])
@@ -769,7 +806,6 @@ class _SpladeEncodeFn(torch.autograd.Function):
                 sparse, tw, ctx.arena, ctx.k = placed
                 ctx.arena.attach(ctx.k, ctx)
                 ctx.sync_token = rt.grad_sync.on_forward() if (rt.direct_grads and rt.grad_sync is not None) else None
-                ctx.mark_non_differentiable(tw)
                 ctx.rows, ctx.vocab = [sparse.shape[0]], sparse.shape[1]
                 return sparse, tw
             ctx.counted = rt.step_arena_observe(pairs[0][0])
@@ -779,7 +815,6 @@ class _SpladeEncodeFn(torch.autograd.Function):
         ctx.sync_token = rt.grad_sync.on_forward() if (rt.direct_grads and rt.grad_sync is not None) else None
         if rt.keep_last_ctx:
             rt.last_ctx = (saved, aux)      # parity tests: routing of the latest forward
-        ctx.mark_non_differentiable(tw)
         ctx.rows = [ids.shape[0] for ids, _ in pairs]
         ctx.vocab = sparse.shape[1]
         outs, r0 = [], 0
@@ -792,12 +827,21 @@ class _SpladeEncodeFn(torch.autograd.Function):
     def backward(ctx, *gs):
         rt = ctx.rt
         head = (None, None) + tuple(None for _ in range(ctx.n_in))
+        # sparse outputs without a gradient: zeros, as autograd materialised them before token_weights had a backward
+        g_tw = gs[-1]
+        gs = tuple(torch.zeros((b, ctx.vocab), dtype=torch.float32, device=g_tw.device if g_tw is not None else rt._device())
+                   if g is None else g for g, b in zip(gs[:-1], ctx.rows))
         if ctx.arena is not None:
-            grads = ctx.arena.report(ctx.k, gs[0], ctx.sync_token)
+            grads = ctx.arena.report(ctx.k, gs[0], ctx.sync_token, g_tw)
             ctx.arena = None
             return head + (tuple(None for _ in rt.params) if grads is None else tuple(grads))
-        g_sparse = _gather_rows(gs[:-1], ctx.rows, ctx.vocab, ctx.saved_arena.device)
-        grads = rt.backward_impl(ctx.saved_arena, ctx.aux, g_sparse, ctx.sync_token)
+        g_sparse = _gather_rows(gs, ctx.rows, ctx.vocab, ctx.saved_arena.device)
+        scatter = ctx.aux[11]
+        if g_tw is not None:
+            g_tw = g_tw.reshape(-1)
+            if scatter is not None:                       # padded layout -> native rows (the index that padded tw)
+                g_tw = g_tw[scatter]
+        grads = rt.backward_impl(ctx.saved_arena, ctx.aux, g_sparse, ctx.sync_token, g_tw=g_tw)
         if ctx.counted:
             rt.step_arena_backward_begins()
         ctx.saved_arena = None

@@ -389,6 +389,52 @@ def decoder_splade_fwd(hd: torch.Tensor, w_bf16: torch.Tensor, bias: torch.Tenso
     return sparse, keys, tw
 
 
+def decoder_splade_fwd_tw(hd: torch.Tensor, w_bf16: torch.Tensor, bias: torch.Tensor, cu: torch.Tensor,
+                          mask: torch.Tensor, max_seqlen: int, validate: bool = True):
+    """decoder_splade_fwd that also records the token maximum's column (what a training forward keeps)
+    -> sparse_repr [nseq, V], keys [nseq, V] int32, token_weights [T], token_keys [T] int32
+    (bf16 bits of the token's maximum << 16 | 0xFFFF - its first column; 0xFFFF where token_weights is 0)."""
+    _chk(hd, BF16, "hd"); T, K = hd.shape
+    _chk(w_bf16, BF16, "w"); V = w_bf16.shape[0]
+    if w_bf16.shape[1] != K:
+        raise ValueError("decoder_splade_fwd_tw: K mismatch")
+    _chk(bias, torch.float32, "bias", (V,)); _chk(mask, torch.int64, "mask")
+    if mask.numel() != T:
+        raise ValueError("mask must have T elements")
+    if validate:
+        _check_seqs(cu, T, max_seqlen)
+    nseq = cu.numel() - 1
+    sparse = torch.empty((nseq, V), dtype=torch.float32, device=hd.device)
+    keys = torch.empty((nseq, V), dtype=torch.int32, device=hd.device)
+    tw = torch.empty((T,), dtype=torch.float32, device=hd.device)
+    tkeys = torch.empty((T,), dtype=torch.int32, device=hd.device)
+    scratch = torch.empty((fn("snx_splade_head_scratch_bytes")(T, V),), dtype=torch.uint8, device=hd.device)
+    check(fn("snx_decoder_splade_fwd_rec")(_p(hd), _p(w_bf16), _p(bias), _p(cu), _p(mask), _p(sparse), _p(keys), _p(tw),
+                                           _p(tkeys), _p(scratch), T, nseq, max_seqlen, V, K, 1, _stream()),
+          "snx_decoder_splade_fwd_rec")
+    return sparse, keys, tw, tkeys
+
+
+def splade_bwd_tw(g: torch.Tensor, keys: torch.Tensor, g_tw: Optional[torch.Tensor], tkeys: torch.Tensor, hd: torch.Tensor,
+                  w_bf16: torch.Tensor, cu: torch.Tensor, max_seqlen: int):
+    """Routed backward of the fused head for both outputs (g = dL/d sparse_repr [nseq, V], g_tw = dL/d token_weights
+    [T] or None) -> dHd [T, H] bf16, gradE [V, H] fp32, gradb [V] fp32 (fresh zeros accumulated into)."""
+    T, H = hd.shape
+    V = w_bf16.shape[0]
+    nseq = cu.numel() - 1
+    _chk(g, torch.float32, "g", (nseq, V)); _chk(keys, torch.int32, "keys", (nseq, V)); _chk(tkeys, torch.int32, "tkeys", (T,))
+    if g_tw is not None:
+        _chk(g_tw, torch.float32, "g_tw", (T,))
+    dhd = torch.empty((T, H), dtype=BF16, device=hd.device)
+    gradE = torch.zeros((V, H), dtype=torch.float32, device=hd.device)
+    gradb = torch.zeros((V,), dtype=torch.float32, device=hd.device)
+    scratch = torch.empty((fn("snx_splade_bwd_scratch_bytes")(nseq, max_seqlen, V),), dtype=torch.uint8, device=hd.device)
+    tws = torch.empty((fn("snx_splade_tw_scratch_bytes")(T, V),), dtype=torch.uint8, device=hd.device)
+    check(fn("snx_splade_bwd_tw")(_p(g), _p(keys), _p(g_tw), _p(tkeys), _p(hd), _p(w_bf16), _p(cu), _p(dhd), _p(gradE),
+                                  _p(gradb), _p(scratch), _p(tws), T, nseq, max_seqlen, V, H, _stream()), "snx_splade_bwd_tw")
+    return dhd, gradE, gradb
+
+
 # ----------------------------------------------------------------------------- inference post-processing
 def sparse_topk(rep: torch.Tensor, allowed: torch.Tensor, k: Optional[int] = None):
     """Per row of rep [B,V] fp32: survivors (rep > 0 and allowed[v]); more than k of them -> the k largest, weight

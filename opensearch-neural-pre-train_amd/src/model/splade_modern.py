@@ -13,8 +13,6 @@ Differences from the reference, all forced by the offline environment or documen
     ``config.json`` (weights are loaded from ``model.safetensors`` / ``model.pt`` when present),
     and the default hub name resolves to the built-in A.X-Encoder-base geometry with RANDOM
     initial weights (transformers modeling_modernbert.py:353-390 recipe) plus a warning;
-  * ``token_weights`` is returned but is not differentiable (the reference trainer discards it,
-    ref:src/train/cli/train_v33_ddp.py:339-343);
   * ``get_top_k_tokens`` breaks ties lowest-index-first (torch.topk leaves the order open).
 """
 from __future__ import annotations
