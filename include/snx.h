@@ -191,6 +191,29 @@ int snx_gemm_f32(const float* A, int64_t a_row, int64_t a_k, const float* B, int
 int snx_sparse_topk(const float* rep, const uint8_t* allowed, float* out_val, int32_t* out_idx, int32_t* out_cnt,
                     int32_t* out_sorted, int32_t B, int32_t V, int32_t k, int32_t cap, hipStream_t stream);
 
+/* ---- exact sparse retrieval for the mid-training evaluator (ref:benchmark/searchers.py:155-188: the OpenSearch
+ * neural-sparse search the reference benchmark runs; ref:benchmark/metrics.py:52-99: the hit ranks its metrics read) ----
+ * Docs and queries are CSR rows: ptr [n+1] int64, term [nnz] int32 strictly ascending within a row, w [nnz] fp32 > 0.
+ * Score definition (part of the ABI, bit-reproducible): s(q,d) = fp32 acc starting at +0, acc = fmaf(q_w, d_w, acc)
+ * over the shared terms in ascending term id.
+ * Index: term_ptr [V+1] int64, post_doc [nnz] int32, post_w [nnz] fp32 -- term-major, every posting list in doc-id
+ * order, byte-identical from run to run; workspace: snx_sparse_index_workspace_bytes(nd, V) bytes.
+ * Search: per query the top k (1 <= k <= 1024) docs with score > 0 -> out_doc / out_score [nq,k], score descending,
+ * ties lowest doc id first; unused slots doc -1, score 0.  target [nq] (or NULL): out_tscore [nq] = s(q, target)
+ * (bit-equal to the ranked value), out_rank [nq] = 1 + #{d: s_d > s_t} + #{d < t: s_d == s_t}, 0 when s_t == 0 or the
+ * target is out of range.  chunk_docs: docs per LDS-resident score chunk (0: default; <= 32768); it changes no bit.
+ * workspace: snx_sparse_search_workspace_bytes(nq, nd, k, chunk_docs) bytes. */
+size_t snx_sparse_index_workspace_bytes(int32_t nd, int32_t V);
+int snx_sparse_index_build(const int64_t* doc_ptr, const int32_t* doc_term, const float* doc_w, int32_t nd, int32_t V,
+                           int64_t nnz, int64_t* term_ptr, int32_t* post_doc, float* post_w, void* workspace,
+                           size_t ws_bytes, hipStream_t stream);
+size_t snx_sparse_search_workspace_bytes(int32_t nq, int32_t nd, int32_t k, int32_t chunk_docs);
+int snx_sparse_search(const int64_t* q_ptr, const int32_t* q_term, const float* q_w, int32_t nq, const int64_t* term_ptr,
+                      const int32_t* post_doc, const float* post_w, const int64_t* doc_ptr, const int32_t* doc_term,
+                      const float* doc_w, int32_t nd, int32_t V, const int32_t* target, int32_t k, int32_t chunk_docs,
+                      int32_t* out_doc, float* out_score, int32_t* out_rank, float* out_tscore, void* workspace,
+                      size_t ws_bytes, hipStream_t stream);
+
 /* ---- SPLADELossV33 (ref:src/model/losses.py:183-297) ------------------------------------- */
 /* dims [host] = {B, Bp, k, V, label_off, bf16_mm}: q [B,V], p [Bp,V] (Bp > B: all-gathered
  * positives for cross-GPU in-batch negatives, own rows start at label_off), n [B*k,V]; bf16_mm=1

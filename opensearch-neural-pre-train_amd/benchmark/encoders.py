@@ -24,6 +24,24 @@ from snx import ops
 logger = logging.getLogger(__name__)
 
 
+def special_token_ids(tokenizer) -> set:
+    """The ids the reference drops as special tokens (ref:encoders.py:327-328)."""
+    ids = (getattr(tokenizer, n, None) for n in ("cls_token_id", "sep_token_id", "pad_token_id", "unk_token_id",
+                                                  "bos_token_id", "eos_token_id"))
+    return {tid for tid in ids if tid is not None}
+
+
+def allowed_token_mask(token_lookup, special_ids, V: int) -> torch.Tensor:
+    """uint8 [V] (CPU): 1 where the reference keeps a positive weight (ref:encoders.py:327-331) -- not a special id,
+    token text non-empty and not starting with "[" or "<"."""
+    m = torch.zeros(V, dtype=torch.uint8)
+    for i in range(min(V, len(token_lookup))):
+        tok = token_lookup[i]
+        if i not in special_ids and tok and not tok.startswith(("[", "<")):
+            m[i] = 1
+    return m
+
+
 class NeuralSparseEncoderV33:
     """V33 sparse encoder using SPLADEModernBERT (A.X-Encoder-base geometry, 50K vocab)."""
 
@@ -46,9 +64,7 @@ class NeuralSparseEncoderV33:
         self.model = model.to(device)
         self.model.eval()
         self.vocab_size = self.tokenizer.vocab_size
-        ids = (getattr(self.tokenizer, n, None) for n in ("cls_token_id", "sep_token_id", "pad_token_id",
-                                                         "unk_token_id", "bos_token_id", "eos_token_id"))
-        self.special_token_ids = {tid for tid in ids if tid is not None}
+        self.special_token_ids = special_token_ids(self.tokenizer)
         self._token_lookup = list(self.tokenizer.convert_ids_to_tokens(list(range(self.vocab_size))))
         self._allowed = None
         logger.info(f"V33 neural sparse model loaded, vocab_size: {self.vocab_size}")
@@ -56,12 +72,7 @@ class NeuralSparseEncoderV33:
     # ---- device-side filter table: ref:encoders.py:327-331 per vocabulary id ----
     def _allowed_mask(self, V: int, device) -> torch.Tensor:
         if self._allowed is None or self._allowed.numel() != V or self._allowed.device != device:
-            m = torch.zeros(V, dtype=torch.uint8)
-            for i in range(min(V, len(self._token_lookup))):
-                tok = self._token_lookup[i]
-                if i not in self.special_token_ids and tok and not tok.startswith(("[", "<")):
-                    m[i] = 1
-            self._allowed = m.to(device)
+            self._allowed = allowed_token_mask(self._token_lookup, self.special_token_ids, V).to(device)
         return self._allowed
 
     def _create_collate_fn(self, max_length: Optional[int] = None):

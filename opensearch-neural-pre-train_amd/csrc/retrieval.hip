@@ -1,0 +1,501 @@
+// Exact sparse retrieval for the mid-training evaluator (src/train/eval): the work the reference hands to an
+// OpenSearch cluster (ref:benchmark/searchers.py:155-188, NeuralSparseSearcher) and scores with
+// ref:benchmark/metrics.py:52-99.
+//
+// Index build (doc CSR -> term-major inverted index, every posting list in doc-id order), deterministic by construction:
+//   docs are cut into nblk contiguous blocks; ix_count counts each (block, term) pair into C[nblk][V] (integer atomics:
+//   the totals do not depend on arrival order); ix_colscan turns every column of C into an exclusive prefix over the
+//   blocks and leaves the term totals in term_ptr; ix_scan makes term_ptr exclusive; ix_scatter walks the docs of a
+//   block IN ORDER (one barrier per doc; a doc holds each term at most once, so no two lanes share a cursor within a
+//   doc) and places doc d of term t at term_ptr[t] + C[b][t]++.  The result is the stable counting sort of the doc CSR
+//   by term: byte-identical from run to run, no per-term sort needed.
+//
+// Search (term-at-a-time, exact): one workgroup per (query, chunk of `chunk` docs).  The chunk's fp32 scores live in LDS;
+// for each query term, in ascending id order, the posting segment inside the chunk is found by binary search and
+// s[d] = fmaf(q_w, d_w, s[d]) is applied to it, with a barrier between terms (a doc appears at most once per posting
+// list, so no float atomics).  Every score is therefore fmaf over the shared terms in ascending term id starting from
+// +0, the ABI's definition, whatever the chunking.  Then a radix select on the score bit patterns (scores >= 0, so the
+// bits order like the floats; the trick of topk.hip) picks the chunk's top k under (score desc, doc asc), compacted in
+// doc order, and an integer count gives the chunk's share of the target rank.  sr_merge reduces the chunks of a query
+// the same way (its candidates are in doc order too) and sorts the <= k winners.  Chunk size changes no bit.
+#include "common.h"
+#include "snx.h"
+
+namespace {
+
+constexpr int IX_THREADS = 256;
+constexpr int IX_MAX_BLOCKS = 1024;
+constexpr long IX_TABLE_BUDGET = 1L << 24;     // entries of the [nblk, V] cursor table (int64): <= 128 MiB
+constexpr int SCAN_THREADS = 1024;
+
+constexpr int SR_THREADS = 512;
+constexpr int SR_WAVES = SR_THREADS / 64;
+constexpr int SR_TG = SR_THREADS / 2;          // query terms whose chunk bounds are searched at once
+constexpr int SR_KMAX = 1024;
+constexpr int SR_CHUNK_DEFAULT = 16384;        // 64 KiB of scores: two workgroups per CU
+constexpr int SR_CHUNK_MAX = 32768;            // 128 KiB of scores + ~14 KiB static LDS (160 KiB per workgroup)
+constexpr int TS_THREADS = 64;
+
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// ------------------------------------------------------------------------------------------------ index build
+inline int ix_blocks(int32_t nd, int32_t V) {
+  if (nd <= 0) return 0;
+  long nb = IX_TABLE_BUDGET / (V > 0 ? V : 1);
+  if (nb > IX_MAX_BLOCKS) nb = IX_MAX_BLOCKS;
+  if (nb < 1) nb = 1;
+  if (nb > nd) nb = nd;
+  const long dpb = (nd + nb - 1) / nb;
+  return (int)((nd + dpb - 1) / dpb);
+}
+
+__global__ __launch_bounds__(IX_THREADS) void ix_count_kernel(const int64_t* __restrict__ doc_ptr,
+                                                              const int32_t* __restrict__ doc_term, int32_t nd,
+                                                              int32_t V, int64_t nnz, int32_t dpb,
+                                                              unsigned long long* __restrict__ C) {
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int d0 = b * dpb, d1 = min(nd, d0 + dpb);
+  unsigned long long* row = C + (long)b * V;
+  for (int d = d0 + wave; d < d1; d += IX_THREADS / 64) {
+    const int64_t p0 = doc_ptr[d], p1 = min(doc_ptr[d + 1], nnz);
+    for (int64_t j = p0 + lane; j < p1; j += 64) {
+      const int t = doc_term[j];
+      if ((unsigned)t < (unsigned)V) atomicAdd(&row[t], 1ull);
+    }
+  }
+}
+
+// per term: C[b][t] <- sum_{b' < b} C[b'][t]; term_ptr[t] <- sum_b C[b][t]
+__global__ __launch_bounds__(IX_THREADS) void ix_colscan_kernel(unsigned long long* __restrict__ C, int nblk, int32_t V,
+                                                                int64_t* __restrict__ term_ptr) {
+  const int t = blockIdx.x * IX_THREADS + threadIdx.x;
+  if (t >= V) return;
+  unsigned long long acc = 0;
+  for (int b = 0; b < nblk; ++b) {
+    const unsigned long long c = C[(long)b * V + t];
+    C[(long)b * V + t] = acc;
+    acc += c;
+  }
+  term_ptr[t] = (int64_t)acc;
+}
+
+// term_ptr[0..V) counts -> exclusive offsets, term_ptr[V] = total (one workgroup; each thread owns a contiguous run)
+__global__ __launch_bounds__(SCAN_THREADS) void ix_scan_kernel(int64_t* __restrict__ term_ptr, int32_t V) {
+  __shared__ int64_t part[2][SCAN_THREADS];
+  const int tid = threadIdx.x;
+  const int per = (V + SCAN_THREADS - 1) / SCAN_THREADS;
+  const int i0 = min(V, tid * per), i1 = min(V, i0 + per);
+  int64_t s = 0;
+  for (int i = i0; i < i1; ++i) s += term_ptr[i];
+  part[0][tid] = s;
+  __syncthreads();
+  int cur = 0;
+  for (int off = 1; off < SCAN_THREADS; off <<= 1) {        // inclusive Hillis-Steele scan over the thread sums
+    const int64_t v = part[cur][tid] + (tid >= off ? part[cur][tid - off] : 0);
+    part[cur ^ 1][tid] = v;
+    cur ^= 1;
+    __syncthreads();
+  }
+  int64_t run = part[cur][tid] - s;
+  for (int i = i0; i < i1; ++i) {
+    const int64_t c = term_ptr[i];
+    term_ptr[i] = run;
+    run += c;
+  }
+  if (tid == SCAN_THREADS - 1) term_ptr[V] = part[cur][tid];
+}
+
+__global__ __launch_bounds__(IX_THREADS) void ix_scatter_kernel(const int64_t* __restrict__ doc_ptr,
+                                                                const int32_t* __restrict__ doc_term,
+                                                                const float* __restrict__ doc_w, int32_t nd, int32_t V,
+                                                                int64_t nnz, int32_t dpb, unsigned long long* C,
+                                                                const int64_t* __restrict__ term_ptr,
+                                                                int32_t* __restrict__ post_doc,
+                                                                float* __restrict__ post_w) {
+  const int b = blockIdx.x;
+  const int d0 = b * dpb, d1 = min(nd, d0 + dpb);
+  unsigned long long* row = C + (long)b * V;
+  for (int d = d0; d < d1; ++d) {                            // docs in order: the stable part of the counting sort
+    const int64_t p0 = doc_ptr[d], p1 = min(doc_ptr[d + 1], nnz);
+    for (int64_t j = p0 + threadIdx.x; j < p1; j += IX_THREADS) {
+      const int t = doc_term[j];
+      if ((unsigned)t >= (unsigned)V) continue;
+      const unsigned long long slot = row[t];
+      row[t] = slot + 1;
+      const int64_t pos = term_ptr[t] + (int64_t)slot;
+      post_doc[pos] = d;
+      post_w[pos] = doc_w[j];
+    }
+    __syncthreads();                                         // the next doc's cursor reads see this doc's increments
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ search
+__device__ __forceinline__ int64_t lower_bound_doc(const int32_t* __restrict__ a, int64_t lo, int64_t hi, int32_t x) {
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (a[mid] < x) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ uint32_t score_key(float s) { return s > 0.f ? __builtin_bit_cast(uint32_t, s) : 0u; }
+
+struct SelectSmem {
+  uint32_t hist[2048];
+  int wcnt[2][SR_WAVES];
+  int sh[4];                      // 0: count, 1: bin, 2: remaining
+  int run[2];                     // ordered take: eq seen, taken so far
+};
+
+__device__ __forceinline__ int block_sum_int(int v, SelectSmem& S) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if (tid == 0) S.sh[0] = 0;
+  __syncthreads();
+  if ((tid & 63) == 0 && v) atomicAdd(&S.sh[0], v);
+  __syncthreads();
+  const int r = S.sh[0];
+  __syncthreads();
+  return r;
+}
+
+// Radix select over key(i), i in [0, n), key 0 = no candidate.  -> thr, need_eq, nsel (block-uniform): the top k are
+// every key > thr and the first need_eq (lowest i) keys == thr; when at most k keys are non-zero, thr = 0 and all are.
+template <typename KeyF>
+__device__ void radix_select(KeyF key, long n, int k, SelectSmem& S, uint32_t& thr, int& need_eq, int& nsel) {
+  const int tid = threadIdx.x;
+  int local = 0;
+  for (long i = tid; i < n; i += SR_THREADS) local += key(i) != 0u;
+  const int npos = block_sum_int(local, S);
+  if (npos <= k) { thr = 0u; need_eq = 0; nsel = npos; return; }
+  uint32_t prefix = 0u, known = 0u;
+  int remaining = k;
+  const int shifts[3] = {21, 10, 0}, widths[3] = {11, 11, 10};
+  for (int p = 0; p < 3; ++p) {
+    const int shift = shifts[p];
+    const uint32_t bm = (1u << widths[p]) - 1u;
+    for (int i = tid; i < 2048; i += SR_THREADS) S.hist[i] = 0u;
+    __syncthreads();
+    for (long i = tid; i < n; i += SR_THREADS) {
+      const uint32_t kk = key(i);
+      if (kk != 0u && (kk & known) == prefix) atomicAdd(&S.hist[(kk >> shift) & bm], 1u);
+    }
+    __syncthreads();
+    if (tid == 0) {                                          // walk the bins from the top
+      int rem = remaining, b = (int)bm;
+      for (; b > 0; --b) {
+        const int c = (int)S.hist[b];
+        if (c >= rem) break;
+        rem -= c;
+      }
+      S.sh[1] = b;
+      S.sh[2] = rem;
+    }
+    __syncthreads();
+    prefix |= (uint32_t)S.sh[1] << shift;
+    known |= bm << shift;
+    remaining = S.sh[2];
+    __syncthreads();
+  }
+  thr = prefix;
+  need_eq = remaining;
+  nsel = k;
+}
+
+// The selection of radix_select in index order: emit(i, pos) with pos = 0, 1, ... following i.
+template <typename KeyF, typename EmitF>
+__device__ void ordered_take(KeyF key, long n, uint32_t thr, int need_eq, SelectSmem& S, EmitF emit) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  if (tid == 0) { S.run[0] = 0; S.run[1] = 0; }
+  __syncthreads();
+  for (long base = 0; base < n; base += SR_THREADS) {
+    const long i = base + tid;
+    const uint32_t kk = i < n ? key(i) : 0u;
+    const bool gt = kk > thr;
+    const bool eq = thr != 0u && kk == thr;
+    const unsigned long long mg = __ballot(gt), me = __ballot(eq);
+    if (lane == 0) { S.wcnt[0][wave] = __popcll(mg); S.wcnt[1][wave] = __popcll(me); }
+    __syncthreads();
+    int E = S.run[0], T = S.run[1];
+    for (int w = 0; w < wave; ++w) {
+      T += S.wcnt[0][w] + min(max(need_eq - E, 0), S.wcnt[1][w]);
+      E += S.wcnt[1][w];
+    }
+    const int eq_below = __popcll(me & below);
+    const bool take = gt || (eq && E + eq_below < need_eq);
+    if (take) emit(i, T + __popcll(mg & below) + min(max(need_eq - E, 0), eq_below));
+    __syncthreads();
+    if (tid == 0) {
+      int e = S.run[0], t = S.run[1];
+      for (int w = 0; w < SR_WAVES; ++w) {
+        t += S.wcnt[0][w] + min(max(need_eq - e, 0), S.wcnt[1][w]);
+        e += S.wcnt[1][w];
+      }
+      S.run[0] = e;
+      S.run[1] = t;
+    }
+    __syncthreads();
+  }
+}
+
+// s(q, target[q]) by a merge of the two id-sorted CSR rows: lanes find the query's terms in the doc row, lane 0 applies
+// fmaf in ascending term id -- the order of the LDS accumulation, so the value is bit-equal to the ranked one.
+__global__ __launch_bounds__(TS_THREADS) void sr_target_kernel(const int64_t* __restrict__ q_ptr,
+                                                               const int32_t* __restrict__ q_term,
+                                                               const float* __restrict__ q_w,
+                                                               const int64_t* __restrict__ doc_ptr,
+                                                               const int32_t* __restrict__ doc_term,
+                                                               const float* __restrict__ doc_w, int32_t nd,
+                                                               const int32_t* __restrict__ target,
+                                                               float* __restrict__ out_tscore) {
+  __shared__ float qv[TS_THREADS], dv[TS_THREADS];
+  __shared__ int hit[TS_THREADS];
+  const int q = blockIdx.x, lane = threadIdx.x;
+  const int t = target[q];
+  float acc = 0.f;
+  if ((unsigned)t < (unsigned)nd) {
+    const int64_t a = doc_ptr[t], b = doc_ptr[t + 1];
+    const int64_t qa = q_ptr[q], qb = q_ptr[q + 1];
+    for (int64_t g = qa; g < qb; g += TS_THREADS) {
+      const int64_t j = g + lane;
+      hit[lane] = 0;
+      if (j < qb) {
+        const int32_t term = q_term[j];
+        const int64_t p = lower_bound_doc(doc_term, a, b, term);
+        if (p < b && doc_term[p] == term) { hit[lane] = 1; qv[lane] = q_w[j]; dv[lane] = doc_w[p]; }
+      }
+      __syncthreads();
+      if (lane == 0) {
+        const int m = (int)min((int64_t)TS_THREADS, qb - g);
+        for (int i = 0; i < m; ++i)
+          if (hit[i]) acc = fmaf(qv[i], dv[i], acc);
+      }
+      __syncthreads();
+    }
+  }
+  if (lane == 0) out_tscore[q] = acc;
+}
+
+__global__ __launch_bounds__(SR_THREADS) void sr_chunk_kernel(const int64_t* __restrict__ q_ptr,
+                                                              const int32_t* __restrict__ q_term,
+                                                              const float* __restrict__ q_w,
+                                                              const int64_t* __restrict__ term_ptr,
+                                                              const int32_t* __restrict__ post_doc,
+                                                              const float* __restrict__ post_w, int32_t nd, int32_t V,
+                                                              int32_t chunk, int32_t nch, int32_t k,
+                                                              const int32_t* __restrict__ target,
+                                                              const float* __restrict__ tscore,
+                                                              unsigned long long* __restrict__ cand,
+                                                              int32_t* __restrict__ ccount,
+                                                              int32_t* __restrict__ rcount) {
+  extern __shared__ float sc[];                            // [chunk] scores of this chunk's docs
+  __shared__ SelectSmem S;
+  __shared__ int64_t seg0[SR_TG], seg1[SR_TG];
+  __shared__ float segw[SR_TG];
+  const int tid = threadIdx.x;
+  const long qc = blockIdx.x;
+  const int q = (int)(qc / nch), c = (int)(qc - (long)q * nch);
+  const int c0 = c * chunk;
+  const int n = max(0, min(chunk, nd - c0));
+  for (int i = tid; i < n; i += SR_THREADS) sc[i] = 0.f;
+  const int64_t qa = q_ptr[q], qb = q_ptr[q + 1];
+  for (int64_t g = qa; g < qb; g += SR_TG) {
+    const int ng = (int)min((int64_t)SR_TG, qb - g);
+    const int j = tid < SR_TG ? tid : tid - SR_TG;
+    if (j < ng) {                                          // both bounds of every term of the group at once
+      const int32_t term = q_term[g + j];
+      int64_t lo = 0, hi = 0;
+      if ((unsigned)term < (unsigned)V) { lo = term_ptr[term]; hi = term_ptr[term + 1]; }
+      if (tid < SR_TG) {
+        seg0[j] = lower_bound_doc(post_doc, lo, hi, c0);
+        segw[j] = q_w[g + j];
+      } else {
+        seg1[j] = lower_bound_doc(post_doc, lo, hi, c0 + n);
+      }
+    }
+    __syncthreads();                                       // (also orders the zero fill before the first term)
+    for (int jj = 0; jj < ng; ++jj) {                      // ascending term id: the ABI's accumulation order
+      const int64_t e = seg1[jj];
+      const float w = segw[jj];
+      for (int64_t i = seg0[jj] + tid; i < e; i += SR_THREADS) {
+        const int d = post_doc[i] - c0;
+        if ((unsigned)d < (unsigned)n) sc[d] = fmaf(w, post_w[i], sc[d]);
+      }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+  if (target) {                                            // 1 + #{s_d > s_t} + #{d < t: s_d == s_t}, summed by sr_merge
+    const float ts = tscore[q];
+    const int tt = target[q];
+    int local = 0;
+    if (ts > 0.f)
+      for (int i = tid; i < n; i += SR_THREADS) {
+        const float s = sc[i];
+        local += (s > ts) || (s == ts && c0 + i < tt);
+      }
+    const int r = block_sum_int(local, S);
+    if (tid == 0) rcount[qc] = r;
+  }
+  auto key = [&](long i) -> uint32_t { return score_key(sc[i]); };
+  uint32_t thr;
+  int need_eq, nsel;
+  radix_select(key, n, k, S, thr, need_eq, nsel);
+  unsigned long long* out = cand + qc * k;
+  ordered_take(key, n, thr, need_eq, S, [&](long i, int pos) {
+    out[pos] = ((unsigned long long)score_key(sc[i]) << 32) | (uint32_t)(c0 + (int)i);
+  });
+  if (tid == 0) ccount[qc] = nsel;
+}
+
+__global__ __launch_bounds__(SR_THREADS) void sr_merge_kernel(const unsigned long long* __restrict__ cand,
+                                                              const int32_t* __restrict__ ccount,
+                                                              const int32_t* __restrict__ rcount, int32_t nd,
+                                                              int32_t nch, int32_t k,
+                                                              const int32_t* __restrict__ target,
+                                                              const float* __restrict__ tscore,
+                                                              int32_t* __restrict__ out_doc,
+                                                              float* __restrict__ out_score,
+                                                              int32_t* __restrict__ out_rank) {
+  __shared__ SelectSmem S;
+  __shared__ unsigned long long sbuf[SR_KMAX];              // (score bits << 32 | ~doc): descending = the ABI's order
+  const int tid = threadIdx.x, q = blockIdx.x;
+  const long base = (long)q * nch;
+  if (target) {
+    int local = 0;
+    for (int c = tid; c < nch; c += SR_THREADS) local += rcount[base + c];
+    const int r = block_sum_int(local, S);
+    const int tt = target[q];
+    if (tid == 0) out_rank[q] = ((unsigned)tt < (unsigned)nd && tscore[q] > 0.f) ? 1 + r : 0;
+  }
+  const unsigned long long* qcand = cand + base * k;
+  const int32_t* qcnt = ccount + base;
+  auto key = [&](long f) -> uint32_t {                      // flat index c * k + i: doc order among the valid entries
+    const int c = (int)(f / k), i = (int)(f - (long)c * k);
+    return i < qcnt[c] ? (uint32_t)(qcand[f] >> 32) : 0u;
+  };
+  const long n = (long)nch * k;
+  uint32_t thr;
+  int need_eq, nsel;
+  radix_select(key, n, k, S, thr, need_eq, nsel);
+  int P = 1;
+  while (P < nsel) P <<= 1;
+  for (int i = tid; i < P; i += SR_THREADS) sbuf[i] = 0ull;
+  __syncthreads();
+  ordered_take(key, n, thr, need_eq, S, [&](long f, int pos) {
+    const unsigned long long e = qcand[f];
+    sbuf[pos] = (e & 0xFFFFFFFF00000000ull) | (0xFFFFFFFFull - (e & 0xFFFFFFFFull));
+  });
+  for (int size = 2; size <= P; size <<= 1)                 // bitonic sort, descending
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = tid; t < (P >> 1); t += SR_THREADS) {
+        const int lo = 2 * t - (t & (stride - 1));
+        const int hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const unsigned long long a = sbuf[lo], b = sbuf[hi];
+        if ((a < b) == desc) { sbuf[lo] = b; sbuf[hi] = a; }
+      }
+      __syncthreads();
+    }
+  int32_t* od = out_doc + (long)q * k;
+  float* os = out_score + (long)q * k;
+  for (int i = tid; i < k; i += SR_THREADS) {
+    if (i < nsel) {
+      const unsigned long long e = sbuf[i];
+      os[i] = __builtin_bit_cast(float, (uint32_t)(e >> 32));
+      od[i] = (int32_t)(0xFFFFFFFFu - (uint32_t)(e & 0xFFFFFFFFull));
+    } else {
+      os[i] = 0.f;
+      od[i] = -1;
+    }
+  }
+}
+
+inline int sr_chunk(int32_t chunk_docs) { return chunk_docs > 0 ? chunk_docs : SR_CHUNK_DEFAULT; }
+inline int sr_nch(int32_t nd, int chunk) { return nd > 0 ? (int)((nd + (long)chunk - 1) / chunk) : 1; }
+
+}  // namespace
+
+extern "C" size_t snx_sparse_index_workspace_bytes(int32_t nd, int32_t V) {
+  if (nd < 0 || V <= 0) return 0;
+  return (size_t)ix_blocks(nd, V) * (size_t)V * sizeof(unsigned long long);
+}
+
+extern "C" int snx_sparse_index_build(const int64_t* doc_ptr, const int32_t* doc_term, const float* doc_w, int32_t nd,
+                                      int32_t V, int64_t nnz, int64_t* term_ptr, int32_t* post_doc, float* post_w,
+                                      void* workspace, size_t ws_bytes, hipStream_t st) {
+  if (!doc_ptr || !term_ptr) return SNX_E_ARG;
+  if (nd < 0 || V <= 0 || nnz < 0) return SNX_E_SHAPE;
+  if (nnz > 0 && (!doc_term || !doc_w || !post_doc || !post_w)) return SNX_E_ARG;
+  const int nblk = ix_blocks(nd, V);
+  const size_t need = (size_t)nblk * (size_t)V * sizeof(unsigned long long);
+  if (need && (!workspace || ws_bytes < need)) return SNX_E_ARG;
+  if (nblk == 0 || nnz == 0) {                              // no postings: all-zero offsets
+    if (hipMemsetAsync(term_ptr, 0, (size_t)(V + 1) * sizeof(int64_t), st) != hipSuccess) return SNX_E_ARG;
+    return SNX_OK;
+  }
+  const int dpb = (int)((nd + (long)nblk - 1) / nblk);
+  unsigned long long* C = (unsigned long long*)workspace;
+  const hipError_t e = hipMemsetAsync(C, 0, need, st);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(ix_count_kernel, dim3(nblk), dim3(IX_THREADS), 0, st, doc_ptr, doc_term, nd, V, nnz, dpb, C);
+  SNX_CHECK_LAUNCH();
+  hipLaunchKernelGGL(ix_colscan_kernel, dim3(cdiv(V, IX_THREADS)), dim3(IX_THREADS), 0, st, C, nblk, V, term_ptr);
+  SNX_CHECK_LAUNCH();
+  hipLaunchKernelGGL(ix_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, term_ptr, V);
+  SNX_CHECK_LAUNCH();
+  hipLaunchKernelGGL(ix_scatter_kernel, dim3(nblk), dim3(IX_THREADS), 0, st, doc_ptr, doc_term, doc_w, nd, V, nnz, dpb,
+                     C, (const int64_t*)term_ptr, post_doc, post_w);
+  SNX_CHECK_LAUNCH();
+  return SNX_OK;
+}
+
+extern "C" size_t snx_sparse_search_workspace_bytes(int32_t nq, int32_t nd, int32_t k, int32_t chunk_docs) {
+  if (nq <= 0 || nd < 0 || k <= 0 || chunk_docs < 0) return 0;
+  const size_t blocks = (size_t)nq * (size_t)sr_nch(nd, sr_chunk(chunk_docs));
+  return align256(blocks * (size_t)k * 8) + 2 * align256(blocks * 4);
+}
+
+extern "C" int snx_sparse_search(const int64_t* q_ptr, const int32_t* q_term, const float* q_w, int32_t nq,
+                                 const int64_t* term_ptr, const int32_t* post_doc, const float* post_w,
+                                 const int64_t* doc_ptr, const int32_t* doc_term, const float* doc_w, int32_t nd,
+                                 int32_t V, const int32_t* target, int32_t k, int32_t chunk_docs, int32_t* out_doc,
+                                 float* out_score, int32_t* out_rank, float* out_tscore, void* workspace,
+                                 size_t ws_bytes, hipStream_t st) {
+  if (!q_ptr || !term_ptr || !doc_ptr || !out_doc || !out_score) return SNX_E_ARG;
+  if (target && (!out_rank || !out_tscore)) return SNX_E_ARG;
+  if (nq < 0 || nd < 0 || V <= 0 || k < 1 || k > SR_KMAX || chunk_docs < 0 || chunk_docs > SR_CHUNK_MAX)
+    return SNX_E_SHAPE;
+  if (nq == 0) return SNX_OK;
+  const int chunk = sr_chunk(chunk_docs);
+  const int nch = sr_nch(nd, chunk);
+  const long blocks = (long)nq * nch;
+  if (blocks > (1L << 31) / SR_THREADS) return SNX_E_SHAPE;       // one launch of the chunk grid
+  const size_t need = snx_sparse_search_workspace_bytes(nq, nd, k, chunk_docs);
+  if (!workspace || ws_bytes < need) return SNX_E_ARG;
+  char* w = (char*)workspace;
+  unsigned long long* cand = (unsigned long long*)w;
+  int32_t* ccount = (int32_t*)(w + align256((size_t)blocks * k * 8));
+  int32_t* rcount = (int32_t*)((char*)ccount + align256((size_t)blocks * 4));
+  if (target) {
+    hipLaunchKernelGGL(sr_target_kernel, dim3(nq), dim3(TS_THREADS), 0, st, q_ptr, q_term, q_w, doc_ptr, doc_term,
+                       doc_w, nd, target, out_tscore);
+    SNX_CHECK_LAUNCH();
+  }
+  const size_t lds = (size_t)chunk * sizeof(float);
+  if (lds > 48 * 1024) {
+    static LdsOptIn optin;
+    if (const int rc = optin.ensure((const void*)sr_chunk_kernel, SR_CHUNK_MAX * (int)sizeof(float))) return rc;
+  }
+  hipLaunchKernelGGL(sr_chunk_kernel, dim3((unsigned)blocks), dim3(SR_THREADS), lds, st, q_ptr, q_term, q_w, term_ptr,
+                     post_doc, post_w, nd, V, chunk, nch, k, target, (const float*)out_tscore, cand, ccount, rcount);
+  SNX_CHECK_LAUNCH();
+  hipLaunchKernelGGL(sr_merge_kernel, dim3(nq), dim3(SR_THREADS), 0, st, (const unsigned long long*)cand,
+                     (const int32_t*)ccount, (const int32_t*)rcount, nd, nch, k, target, (const float*)out_tscore,
+                     out_doc, out_score, out_rank);
+  SNX_CHECK_LAUNCH();
+  return SNX_OK;
+}

@@ -92,6 +92,10 @@ SIGNATURES = {
     "snx_param_count": (I32, [P]),
     "snx_adamw_scratch_bytes": (SZ, []),
     "snx_adamw_clip_step": (I32, [P, P, P, P, I64, P, I64, I64, I64, P, P, P]),
+    "snx_sparse_index_workspace_bytes": (SZ, [I32, I32]),
+    "snx_sparse_index_build": (I32, [P, P, P, I32, I32, I64, P, P, P, P, SZ, P]),
+    "snx_sparse_search_workspace_bytes": (SZ, [I32, I32, I32, I32]),
+    "snx_sparse_search": (I32, [P, P, P, I32, P, P, P, P, P, P, I32, I32, P, I32, I32, P, P, P, P, P, SZ, P]),
     "snx_version": (I32, []),
     "snx_prof_enable": (I32, [I32]),
     "snx_prof_num_classes": (I32, []),

@@ -32,6 +32,8 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     "gemm_tn256.hip": ("gemm_tn256_kernel",),
     "decoder256.hip": ("decoder256_kernel",),
     "gemm_nt256.hip": ("gemm_nt256_kernel",),
+    # no asm here: held to the zero-scratch rule (the LDS score chunk and the select state must stay out of memory)
+    "retrieval.hip": ("ix_scan_kernel", "sr_target_kernel", "sr_chunk_kernel", "sr_merge_kernel"),
 }
 
 # Kernels held to the global-load / vmcnt rule: nothing may touch a load's destination before a vmcnt wait that retires it.

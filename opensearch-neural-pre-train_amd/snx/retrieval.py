@@ -1,0 +1,161 @@
+"""Exact sparse retrieval on the GPU (csrc/retrieval.hip, include/snx.h "exact sparse retrieval").
+
+``SparseIndex`` is the inverted index of the mid-training evaluator: the reference hands indexing and search to an
+OpenSearch cluster (ref:benchmark/indexer.py, ref:benchmark/searchers.py:155-188); here the doc vectors are packed on the
+device batch by batch from the ``[B, cap]`` output of ``ops.sparse_topk`` (no ``[nd, V]`` buffer ever exists), a
+term-major index is built by a deterministic counting sort, and every query is scored exactly against every doc:
+
+    s(q, d) = fmaf over the shared terms in ascending term id, fp32, starting at +0  (the plain dot product)
+
+then ranked score descending, ties lowest doc id first.  Results are bit-reproducible and independent of
+``chunk_docs``."""
+from __future__ import annotations
+
+from typing import List, Optional, Tuple
+
+import torch
+
+from ._lib import check, fn
+from .ops import _chk, _p, _stream
+
+K_MAX = 1024
+CHUNK_MAX = 32768
+_SEARCH_WS_BUDGET = 256 << 20          # bytes of search workspace per launch: larger query sets go in slices
+
+
+def pack_rows(vals: torch.Tensor, ids: torch.Tensor, cnt: torch.Tensor, V: int, name: str = "rows"):
+    """[B, cap] (values, ids, counts) rows, in any order within a row -> (counts int64 [B], terms int32 [nnz] ascending
+    within each row, weights fp32 [nnz]) on the device.  Rows must hold distinct ids in [0, V) with weights > 0."""
+    _chk(vals, torch.float32, f"{name}.vals")
+    if vals.dim() != 2:
+        raise ValueError(f"{name}: vals must be [B, cap]")
+    B, cap = vals.shape
+    _chk(ids, torch.int32, f"{name}.ids", (B, cap))
+    _chk(cnt, torch.int32, f"{name}.cnt", (B,))
+    if ids.device != vals.device or cnt.device != vals.device:
+        raise ValueError(f"{name}: vals, ids and cnt must be on one device")
+    c = cnt.long()
+    live = torch.arange(cap, device=vals.device)[None, :] < c[:, None]
+    key = torch.where(live, ids.long(), torch.full_like(ids, V, dtype=torch.long))
+    skey, order = torch.sort(key, dim=1, stable=True)
+    w = torch.gather(vals, 1, order)
+    ok = (c >= 0).all() & (c <= cap).all()
+    if B and cap:
+        ok &= ((skey >= 0) & (skey < V) | ~live).all() & ((w > 0) & torch.isfinite(w) | ~live).all()
+        ok &= ((skey[:, 1:] > skey[:, :-1]) | ~live[:, 1:]).all()
+    if not bool(ok):
+        raise ValueError(f"{name}: every row needs 0 <= cnt <= cap and cnt distinct ids in [0, {V}) with finite weights > 0")
+    return c, skey[live].to(torch.int32), w[live].contiguous()
+
+
+class SparseIndex:
+    """Inverted index over sparse doc vectors, searched exactly on the GPU.
+
+        index = SparseIndex(V, device)
+        index.add(vals, ids, cnt)          # per batch: the [B, cap] output of ops.sparse_topk
+        index.build()
+        scores, docs, rank, tscore = index.search(q_vals, q_ids, q_cnt, k, targets=None)
+
+    Doc ids are the order of addition.  ``search`` returns top-k scores / doc ids [nq, k] (unused slots: 0 / -1) and,
+    given ``targets`` [nq], the target's 1-based rank under the same tie order (0 = score 0, a miss) and its score."""
+
+    def __init__(self, V: int, device):
+        if int(V) <= 0:
+            raise ValueError("SparseIndex: V must be positive")
+        self.V = int(V)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._cnt: List[torch.Tensor] = []
+        self._term: List[torch.Tensor] = []
+        self._w: List[torch.Tensor] = []
+        self.num_docs = 0
+        self.doc_ptr = self.doc_term = self.doc_w = None
+        self.term_ptr = self.post_doc = self.post_w = None
+
+    @property
+    def built(self) -> bool:
+        return self.term_ptr is not None
+
+    @property
+    def nnz(self) -> int:
+        return sum(int(t.numel()) for t in self._term)
+
+    def add(self, vals: torch.Tensor, ids: torch.Tensor, cnt: torch.Tensor) -> None:
+        if vals.device != self.device:
+            raise ValueError(f"SparseIndex.add: tensors must be on {self.device}")
+        c, t, w = pack_rows(vals, ids, cnt, self.V, "docs")
+        if self.num_docs + c.numel() >= 2 ** 31:
+            raise ValueError("SparseIndex: doc ids are int32")
+        self._cnt.append(c)
+        self._term.append(t)
+        self._w.append(w)
+        self.num_docs += int(c.numel())
+        self.term_ptr = None                                  # a new batch invalidates a built index
+
+    def build(self) -> "SparseIndex":
+        dev, nd, V = self.device, self.num_docs, self.V
+        cnt = torch.cat(self._cnt) if self._cnt else torch.zeros(0, dtype=torch.long, device=dev)
+        self.doc_term = torch.cat(self._term) if self._term else torch.zeros(0, dtype=torch.int32, device=dev)
+        self.doc_w = torch.cat(self._w) if self._w else torch.zeros(0, dtype=torch.float32, device=dev)
+        self.doc_ptr = torch.zeros(nd + 1, dtype=torch.long, device=dev)
+        torch.cumsum(cnt, 0, out=self.doc_ptr[1:])
+        nnz = int(self.doc_term.numel())
+        # the packed batches now live in the CSR: drop the per-batch copies, keep one list entry for further add()s
+        self._cnt, self._term, self._w = [cnt], [self.doc_term], [self.doc_w]
+        term_ptr = torch.empty(V + 1, dtype=torch.long, device=dev)
+        post_doc = torch.empty(nnz, dtype=torch.int32, device=dev)
+        post_w = torch.empty(nnz, dtype=torch.float32, device=dev)
+        ws_bytes = int(fn("snx_sparse_index_workspace_bytes")(nd, V))
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            check(fn("snx_sparse_index_build")(_p(self.doc_ptr), _p(self.doc_term), _p(self.doc_w), nd, V, nnz,
+                                                _p(term_ptr), _p(post_doc), _p(post_w), _p(ws), ws_bytes, _stream()),
+                  "snx_sparse_index_build")
+        self.term_ptr, self.post_doc, self.post_w = term_ptr, post_doc, post_w
+        return self
+
+    def search(self, q_vals: torch.Tensor, q_ids: torch.Tensor, q_cnt: torch.Tensor, k: int,
+               targets: Optional[torch.Tensor] = None, chunk_docs: int = 0
+               ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """Queries as [nq, cap] rows (e.g. ops.sparse_topk with k=64: weight order; sorted by id here) ->
+        (scores [nq, k] fp32, docs [nq, k] int32, target_rank [nq] int32 | None, target_score [nq] fp32 | None)."""
+        if not self.built:
+            raise RuntimeError("SparseIndex.search: call build() first")
+        k, chunk_docs = int(k), int(chunk_docs)
+        if not 1 <= k <= K_MAX:
+            raise ValueError(f"SparseIndex.search: k must be in [1, {K_MAX}]")
+        if not 0 <= chunk_docs <= CHUNK_MAX:
+            raise ValueError(f"SparseIndex.search: chunk_docs must be in [0, {CHUNK_MAX}] (0: default)")
+        if q_vals.device != self.device:
+            raise ValueError(f"SparseIndex.search: tensors must be on {self.device}")
+        qc, q_term, q_w = pack_rows(q_vals, q_ids, q_cnt, self.V, "queries")
+        nq, dev, nd = int(qc.numel()), self.device, self.num_docs
+        q_ptr = torch.zeros(nq + 1, dtype=torch.long, device=dev)
+        torch.cumsum(qc, 0, out=q_ptr[1:])
+        tgt = None
+        if targets is not None:
+            if not isinstance(targets, torch.Tensor) or targets.device != dev or targets.dim() != 1 or \
+                    targets.numel() != nq or targets.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"SparseIndex.search: targets must be an int tensor [{nq}] on {dev}")
+            if nq and not bool(((targets >= 0) & (targets < nd)).all()):
+                raise ValueError(f"SparseIndex.search: targets must be doc ids in [0, {nd})")
+            tgt = targets.to(torch.int32).contiguous()
+        scores = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        docs = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        rank = torch.empty(nq, dtype=torch.int32, device=dev) if tgt is not None else None
+        tscore = torch.empty(nq, dtype=torch.float32, device=dev) if tgt is not None else None
+        per_q = max(1, int(fn("snx_sparse_search_workspace_bytes")(1, nd, k, chunk_docs)))
+        step = max(1, min(nq, _SEARCH_WS_BUDGET // per_q))
+        with torch.cuda.device(dev):
+            for s in range(0, nq, step):
+                m = min(step, nq - s)
+                ws_bytes = int(fn("snx_sparse_search_workspace_bytes")(m, nd, k, chunk_docs))
+                ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+                check(fn("snx_sparse_search")(
+                    _p(q_ptr[s:]), _p(q_term), _p(q_w), m, _p(self.term_ptr), _p(self.post_doc), _p(self.post_w),
+                    _p(self.doc_ptr), _p(self.doc_term), _p(self.doc_w), nd, self.V,
+                    _p(None if tgt is None else tgt[s:]), k, chunk_docs, _p(docs[s:]), _p(scores[s:]),
+                    _p(None if rank is None else rank[s:]), _p(None if tscore is None else tscore[s:]), _p(ws), ws_bytes,
+                    _stream()), "snx_sparse_search")
+        return scores, docs, rank, tscore

@@ -29,6 +29,7 @@ from src.train.config.v33 import V33Config, V33DataConfig, V33LossConfig, V33Mod
 from src.train.core import ddp_trainer as T
 from src.train.data import load_training_data
 from src.train.data.collator import create_tokenizer
+from src.train.eval import MidTrainingEvaluator
 from src.train.utils import TensorBoardLogger, setup_logging
 
 logger = logging.getLogger(__name__)
@@ -95,6 +96,15 @@ def main() -> None:
     torch.manual_seed(config.training.seed + dist.get_rank())
     tokenizer = create_tokenizer(args.tokenizer or config.model.name)
     train_ds = load_training_data(config.data.train_files)
+    val_ds = None
+    if config.data.val_files:                      # ref:train_v33_ddp.py:515-519; a missing file does not stop training
+        try:
+            val_ds = load_training_data(config.data.val_files)
+            if T.is_main_process():
+                logger.info(f"Val samples: {len(val_ds):,}")
+        except FileNotFoundError as e:
+            if T.is_main_process():
+                logger.warning(f"Validation data not loaded ({e}): no mid-training evaluation")
     train_dl = T.create_dataloader_ddp(train_ds, tokenizer, config, is_train=True)
     model = SPLADEModernBERT(model_name=config.model.name, dropout=config.model.dropout).to(device)
     if T.is_main_process():
@@ -123,6 +133,16 @@ def main() -> None:
             st = T.load_checkpoint(T.unwrap(model), optimizer, scheduler, ckpt)
             start_epoch, global_step, best_metric = st["epoch"] + 1, st["global_step"], st.get("best_metric")
     tb = TensorBoardLogger(log_dir=str(out / "tensorboard"), experiment_name="v33_modernbert") if T.is_main_process() else None
+    evaluator = None
+    if T.is_main_process() and val_ds is not None:  # ref:train_v33_ddp.py:629-644
+        try:
+            evaluator = MidTrainingEvaluator(tokenizer=tokenizer, val_file=config.data.val_files[0], max_queries=200,
+                                             max_docs=1000, device=str(device),
+                                             query_max_length=config.data.query_max_length,
+                                             doc_max_length=config.data.doc_max_length)
+            logger.info("Mid-training evaluator initialized")
+        except Exception as e:
+            logger.warning(f"Could not init evaluator: {e}")
     t_start = time.time()
     for epoch in range(start_epoch, config.training.num_epochs + 1):
         t0 = time.time()
@@ -133,6 +153,16 @@ def main() -> None:
             nz_q, nz_d = loss_fn.get_avg_nonzero()
             logger.info(f"Epoch {epoch}/{config.training.num_epochs} | avg_loss={avg_loss:.4f} | nz_q={nz_q:.0f} | "
                         f"nz_d={nz_d:.0f} | time={(time.time() - t0) / 60:.1f}min")
+        if T.is_main_process() and evaluator and epoch % 5 == 0:     # ref:train_v33_ddp.py:679-697
+            try:
+                metrics = evaluator.evaluate(T.unwrap(model))
+                logger.info(f"Eval epoch {epoch}: R@1={metrics.get('recall@1', 0):.4f}, "
+                            f"R@5={metrics.get('recall@5', 0):.4f}")
+                if tb:
+                    for k, v in metrics.items():
+                        tb.log_scalar(f"eval/{k}", v, global_step)
+            except Exception as e:
+                logger.warning(f"Eval failed: {e}")
         if epoch % config.training.save_every_n_epochs == 0 or epoch == config.training.num_epochs:
             dist.barrier()
             T.save_checkpoint(model=model, optimizer=optimizer, scheduler=scheduler, epoch=epoch,

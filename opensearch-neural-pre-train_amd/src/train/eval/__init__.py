@@ -1,0 +1,165 @@
+"""Mid-training retrieval evaluation: ``MidTrainingEvaluator``.
+
+The reference CLI imports this class (ref:src/train/cli/train_v33_ddp.py:46-49, built at :629-644, run every 5 epochs at
+:679-697) from a module that is absent from the reference tree.  Here it is built on the native path: the model's own
+forward encodes a small fixed corpus taken from the validation triplets, ``ops.sparse_topk`` applies the inference
+encoder's vocabulary filter on the device, and ``snx.retrieval.SparseIndex`` scores every query against every doc
+exactly on the GPU.  The metrics are those of ref:benchmark/metrics.py:52-99 over single-target hit ranks.
+
+Scoring is the plain dot product of the sparse vectors -- SPLADE's own score and that of OpenSearch's ``neural_sparse``
+query -- not the saturation function of the ``rank_feature`` query the reference benchmark's searcher sends
+(ref:benchmark/searchers.py:155-188).  Ties rank the lower doc id first."""
+from __future__ import annotations
+
+import logging
+from dataclasses import dataclass
+from itertools import islice
+from typing import Dict, Iterable, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+logger = logging.getLogger(__name__)
+
+RETRIEVAL_SIZE = 10          # ref:benchmark/config.py:44
+QUERY_TOP_K = 64             # NeuralSparseSearcher's query encoding, ref:benchmark/searchers.py:161
+METRIC_KEYS = ("recall@1", "recall@5", "recall@10", "mrr@10", "ndcg@10")
+
+
+@dataclass
+class EvalCorpus:
+    queries: List[str]
+    docs: List[str]
+    targets: List[int]          # doc id of each query's positive
+    forced: int                 # positives kept although the corpus already held max_docs docs
+
+
+def _negatives(rec: dict) -> List[str]:
+    negs = rec.get("negatives")
+    if isinstance(negs, list):
+        return [n for n in negs if isinstance(n, str)]
+    neg = rec.get("negative")
+    return [neg] if isinstance(neg, str) else []
+
+
+def build_eval_corpus(records: Iterable[dict], max_queries: int, max_docs: int) -> EvalCorpus:
+    """The first ``max_queries`` records are the queries.  Docs: their positives, then their negatives, then positives and
+    negatives of later records, up to ``max_docs``; deduplicated by exact text (first occurrence keeps the id).  Every
+    chosen query's positive is in the corpus even past ``max_docs``; it is the query's one relevant doc."""
+    it = iter(records)
+    chosen = list(islice(it, max(0, int(max_queries))))
+    docs: List[str] = []
+    ids: Dict[str, int] = {}
+
+    def add(text: str, force: bool = False) -> Optional[int]:
+        if text in ids:
+            return ids[text]
+        if not force and len(docs) >= max_docs:
+            return None
+        ids[text] = len(docs)
+        docs.append(text)
+        return ids[text]
+
+    targets, forced = [], 0
+    for rec in chosen:
+        if rec["positive"] not in ids and len(docs) >= max_docs:
+            forced += 1
+        targets.append(add(rec["positive"], force=True))
+    for rec in chosen:
+        for n in _negatives(rec):
+            add(n)
+    for rec in it:
+        if len(docs) >= max_docs:
+            break
+        add(rec["positive"])
+        for n in _negatives(rec):
+            add(n)
+    return EvalCorpus([rec["query"] for rec in chosen], docs, targets, forced)
+
+
+def metrics_from_ranks(ranks: Sequence[int], k: int = RETRIEVAL_SIZE) -> Dict[str, float]:
+    """Full 1-based target ranks (0 = score 0, a miss) -> recall@1/5/10, mrr@10, ndcg@10 with the formulas of
+    ref:benchmark/metrics.py:52-99 over the top-``k`` retrieval (a target ranked below ``k`` is not retrieved)."""
+    hit = [int(r) if 1 <= int(r) <= k else None for r in ranks]
+    n = len(hit)
+    out = {f"recall@{c}": (sum(1 for h in hit if h is not None and h <= c) / n if n else 0.0) for c in (1, 5, 10)}
+    rr = [1.0 / h if h is not None else 0.0 for h in hit]
+    out["mrr@10"] = float(np.mean(rr)) if rr else 0.0
+    idcg = 1.0
+    nd = [(1.0 / np.log2(h + 1)) / idcg if h is not None and h <= 10 else 0.0 for h in hit]
+    out["ndcg@10"] = float(np.mean(nd)) if nd else 0.0
+    return out
+
+
+class MidTrainingEvaluator:
+    """Retrieval quality of the model being trained, on a fixed corpus built from ``val_file`` (a triplet JSONL read by
+    ``load_training_data``, or ``synthetic:N[:k]``).  ``evaluate(model)`` -> recall@1/5/10, mrr@10, ndcg@10,
+    num_queries, num_docs, avg_nnz_q, avg_nnz_d.  Queries keep their top 64 terms, docs every term that survives the
+    inference encoder's filter (ref:benchmark/indexer.py:59); retrieval size 10."""
+
+    def __init__(self, tokenizer, val_file: str, max_queries: int = 200, max_docs: int = 1000, device: str = "cuda",
+                 query_max_length: int = 64, doc_max_length: int = 256, batch_size: int = 64):
+        from benchmark.encoders import special_token_ids
+        from src.train.data import load_training_data
+        self.tokenizer = tokenizer
+        self.device = torch.device(device)
+        self.query_max_length, self.doc_max_length = int(query_max_length), int(doc_max_length)
+        self.batch_size = max(1, int(batch_size))
+        ds = load_training_data([val_file])
+        self.corpus = build_eval_corpus((ds[i] for i in range(len(ds))), max_queries, max_docs)
+        if self.corpus.forced:
+            logger.info(f"eval corpus: {self.corpus.forced} query positive(s) kept past max_docs={max_docs} "
+                        f"({len(self.corpus.docs)} docs)")
+        self._token_lookup = list(tokenizer.convert_ids_to_tokens(list(range(tokenizer.vocab_size))))
+        self._special = special_token_ids(tokenizer)
+        self._allowed: Optional[torch.Tensor] = None
+        self.last_ranks: Optional[List[int]] = None
+        logger.info(f"eval corpus: {len(self.corpus.queries)} queries, {len(self.corpus.docs)} docs from {val_file}")
+
+    def _allowed_mask(self, V: int) -> torch.Tensor:
+        from benchmark.encoders import allowed_token_mask
+        if self._allowed is None or self._allowed.numel() != V:
+            self._allowed = allowed_token_mask(self._token_lookup, self._special, V).to(self.device)
+        return self._allowed
+
+    def _encode(self, model, texts: List[str], max_length: int, top_k: Optional[int]):
+        """Batches of (vals, ids, cnt) from ops.sparse_topk over the model's sparse_repr."""
+        from snx import ops
+        for s in range(0, len(texts), self.batch_size):
+            enc = self.tokenizer(texts[s:s + self.batch_size], padding=True, truncation=True, max_length=max_length,
+                                 return_tensors="pt")
+            rep, _ = model(enc["input_ids"].to(self.device), enc["attention_mask"].to(self.device))
+            rep = rep.float().contiguous()
+            vals, ids, cnt, _ = ops.sparse_topk(rep, self._allowed_mask(rep.shape[1]),
+                                                None if top_k is None else min(top_k, rep.shape[1]))
+            yield vals, ids, cnt
+
+    def evaluate(self, model) -> Dict[str, float]:
+        from snx.retrieval import SparseIndex
+        c = self.corpus
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                index = None
+                for vals, ids, cnt in self._encode(model, c.docs, self.doc_max_length, None):
+                    if index is None:
+                        index = SparseIndex(vals.shape[1], self.device)
+                    index.add(vals, ids, cnt)
+                qb = list(self._encode(model, c.queries, self.query_max_length, QUERY_TOP_K))
+                ranks: List[int] = []
+                avg_q = 0.0
+                if qb and index is not None:
+                    index.build()
+                    q_vals, q_ids, q_cnt = (torch.cat([b[i] for b in qb]) for i in range(3))
+                    targets = torch.tensor(c.targets, dtype=torch.int32, device=self.device)
+                    _, _, rank, _ = index.search(q_vals, q_ids, q_cnt, RETRIEVAL_SIZE, targets=targets)
+                    ranks = rank.cpu().tolist()
+                    avg_q = float(q_cnt.double().mean())
+                avg_d = index.nnz / index.num_docs if index is not None and index.num_docs else 0.0
+        finally:
+            model.train(was_training)
+        self.last_ranks = ranks
+        out = metrics_from_ranks(ranks)
+        out.update(num_queries=float(len(c.queries)), num_docs=float(len(c.docs)), avg_nnz_q=avg_q, avg_nnz_d=avg_d)
+        return out

@@ -1,0 +1,127 @@
+#!/usr/bin/env python3
+"""Index build time and search throughput of the native sparse retrieval (snx.retrieval.SparseIndex,
+csrc/retrieval.hip) on synthetic Zipf-skewed data.
+
+    python tools/gpu_retrieval_bench.py [--sizes 1000x200,100000x10000,1000000x10000] [--out result.json]
+
+Docs draw 128 terms (with replacement, duplicates dropped: ~99 distinct) from a Zipf(1.0) law over V = 50000 with
+weights uniform in [0.1, 3); queries draw 64 the same way (~53 distinct).  Retrieval size 10 with a target per query
+(the evaluator's call).  Comparison row: torch.sparse CSR (docs) @ dense query block + torch.topk over query chunks,
+where the torch build supports it."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "opensearch-neural-pre-train_amd"))
+
+import torch  # noqa: E402
+
+V = 50000
+
+
+def zipf_rows(n, m, gen, dev, probs):
+    """[n, m] (vals, ids, cnt) rows of distinct Zipf-drawn ids, sentinel-padded after the live entries."""
+    ids = torch.multinomial(probs, n * m, replacement=True, generator=gen).view(n, m).to(dev)
+    ids, _ = torch.sort(ids, dim=1)
+    dup = torch.zeros_like(ids, dtype=torch.bool)
+    dup[:, 1:] = ids[:, 1:] == ids[:, :-1]
+    ids = torch.where(dup, torch.full_like(ids, V), ids)
+    ids, _ = torch.sort(ids, dim=1)
+    cnt = (ids < V).sum(1).to(torch.int32)
+    ids = torch.where(ids < V, ids, torch.zeros_like(ids)).to(torch.int32)
+    vals = (torch.rand(n, m, generator=gen) * 2.9 + 0.1).to(dev)
+    return vals.contiguous(), ids.contiguous(), cnt
+
+
+def sync_time(f):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    r = f()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t, r
+
+
+def run_case(nd, nq, dev, torch_cmp=True):
+    from snx.retrieval import SparseIndex
+    gen = torch.Generator().manual_seed(nd + nq)
+    probs = 1.0 / torch.arange(1, V + 1, dtype=torch.float64)
+    probs /= probs.sum()
+    batches = [zipf_rows(min(100_000, nd - s), 128, gen, dev, probs) for s in range(0, nd, 100_000)]
+    q = zipf_rows(nq, 64, gen, dev, probs)
+    targets = torch.randint(0, nd, (nq,), generator=gen).to(dev)
+
+    def build():
+        idx = SparseIndex(V, dev)
+        for b in batches:
+            idx.add(*b)
+        return idx.build()
+
+    build()                                                    # warm-up (library load, allocator)
+    t_build, idx = sync_time(build)
+    t_core, _ = sync_time(idx.build)                           # the native build alone (CSR already packed)
+    idx.search(q[0][:64], q[1][:64], q[2][:64], 10, targets=targets[:64])
+    times = []
+    for _ in range(3):
+        t, res = sync_time(lambda: idx.search(*q, 10, targets=targets))
+        times.append(t)
+    t_search = min(times)
+    row = {"docs": nd, "queries": nq, "nnz_docs": idx.nnz, "avg_nnz_doc": idx.nnz / nd,
+           "avg_nnz_query": float(q[2].float().mean()), "build_s_incl_packing": t_build, "build_s_native": t_core,
+           "search_s": t_search, "queries_per_s": nq / t_search}
+    if torch_cmp:
+        row["torch_sparse"] = torch_sparse_row(idx, q, nd, nq, dev)
+    return row
+
+
+def torch_sparse_row(idx, q, nd, nq, dev, budget_s=20.0):
+    """CSR docs [nd, V] @ dense query block [V, c] -> [nd, c] scores -> torch.topk(10) per query."""
+    try:
+        D = torch.sparse_csr_tensor(idx.doc_ptr, idx.doc_term.long(), idx.doc_w, size=(nd, V))
+        c = max(1, min(nq, (512 << 20) // (4 * nd)))         # the [nd, c] fp32 block <= 512 MiB
+        from snx.retrieval import pack_rows
+        qc, qt, qw = pack_rows(*q, V)
+        qptr = torch.zeros(nq + 1, dtype=torch.long, device=dev)
+        torch.cumsum(qc, 0, out=qptr[1:])
+        Q = torch.sparse_csr_tensor(qptr, qt.long(), qw, size=(nq, V)).to_dense()
+        done, t0 = 0, None
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        while done < nq:
+            blk = Q[done:done + c].t().contiguous()
+            s = D @ blk
+            torch.topk(s.t(), 10, dim=1)
+            done += blk.shape[1]
+            torch.cuda.synchronize()
+            if time.perf_counter() - t0 > budget_s:
+                break
+        t = time.perf_counter() - t0
+        return {"ok": True, "queries_timed": done, "search_s": t, "queries_per_s": done / t, "query_block": c}
+    except Exception as e:                                       # noqa: BLE001 -- reported, not hidden
+        return {"ok": False, "error": f"{type(e).__name__}: {e}"[:300]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="1000x200,100000x10000,1000000x10000")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--no-torch", action="store_true")
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    rows = []
+    for s in args.sizes.split(","):
+        nd, nq = (int(x) for x in s.split("x"))
+        row = run_case(nd, nq, dev, torch_cmp=not args.no_torch)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    res = {"device": torch.cuda.get_device_name(0), "rows": rows}
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
