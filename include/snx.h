@@ -214,6 +214,25 @@ int snx_sparse_search(const int64_t* q_ptr, const int32_t* q_term, const float* 
                       int32_t* out_doc, float* out_score, int32_t* out_rank, float* out_tscore, void* workspace,
                       size_t ws_bytes, hipStream_t stream);
 
+/* ---- hard-negative mining over the same index (src/train/mining) ----
+ * Pair scores: out[i] = s(pair_q[i], pair_d[i]) for npairs (query row, doc row) pairs over the query and doc CSR,
+ * bit-equal to the value the searches rank; a pair with an index out of range scores 0.
+ * Band search: per query q an exclusion row ex_doc[ex_ptr[q] .. ex_ptr[q+1]) (doc ids ascending and distinct; ex_ptr
+ * NULL: none) and ceiling[q] fp32 (NULL or +inf: none).  Doc d is ADMISSIBLE for q when s(q,d) > 0, d is not in the
+ * row, and s(q,d) < ceiling[q] (strict, fp32; a NaN ceiling admits nothing).  The admissible docs are ranked score
+ * descending, ties lowest doc id first (the search's order); ranks lo .. hi-1 (0-based, 0 <= lo < hi <= 1024) go to
+ * out_doc / out_score [nq, hi-lo], unused slots doc -1, score 0; out_found [nq] = filled slots.  chunk_docs as for
+ * the search: it changes no bit.  workspace: snx_sparse_search_band_workspace_bytes(nq, nd, hi, chunk_docs) bytes. */
+int snx_sparse_pair_scores(const int64_t* q_ptr, const int32_t* q_term, const float* q_w, int32_t nq,
+                           const int64_t* doc_ptr, const int32_t* doc_term, const float* doc_w, int32_t nd,
+                           const int32_t* pair_q, const int32_t* pair_d, int64_t npairs, float* out, hipStream_t stream);
+size_t snx_sparse_search_band_workspace_bytes(int32_t nq, int32_t nd, int32_t hi, int32_t chunk_docs);
+int snx_sparse_search_band(const int64_t* q_ptr, const int32_t* q_term, const float* q_w, int32_t nq,
+                           const int64_t* term_ptr, const int32_t* post_doc, const float* post_w, int32_t nd, int32_t V,
+                           const int64_t* ex_ptr, const int32_t* ex_doc, const float* ceiling, int32_t lo, int32_t hi,
+                           int32_t chunk_docs, int32_t* out_doc, float* out_score, int32_t* out_found, void* workspace,
+                           size_t ws_bytes, hipStream_t stream);
+
 /* ---- SPLADELossV33 (ref:src/model/losses.py:183-297) ------------------------------------- */
 /* dims [host] = {B, Bp, k, V, label_off, bf16_mm}: q [B,V], p [Bp,V] (Bp > B: all-gathered
  * positives for cross-GPU in-batch negatives, own rows start at label_off), n [B*k,V]; bf16_mm=1

@@ -414,6 +414,183 @@ __global__ __launch_bounds__(SR_THREADS) void sr_merge_kernel(const unsigned lon
   }
 }
 
+// s(q, d) of a list of (query, doc) pairs: sr_target_kernel with one pair per workgroup instead of one target per query.
+// A pair whose query or doc index is out of range scores 0.
+__global__ __launch_bounds__(TS_THREADS) void sr_pair_kernel(const int64_t* __restrict__ q_ptr,
+                                                             const int32_t* __restrict__ q_term,
+                                                             const float* __restrict__ q_w, int32_t nq,
+                                                             const int64_t* __restrict__ doc_ptr,
+                                                             const int32_t* __restrict__ doc_term,
+                                                             const float* __restrict__ doc_w, int32_t nd,
+                                                             const int32_t* __restrict__ pair_q,
+                                                             const int32_t* __restrict__ pair_d,
+                                                             float* __restrict__ out) {
+  __shared__ float qv[TS_THREADS], dv[TS_THREADS];
+  __shared__ int hit[TS_THREADS];
+  const long p = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int q = pair_q[p], t = pair_d[p];
+  float acc = 0.f;
+  if ((unsigned)q < (unsigned)nq && (unsigned)t < (unsigned)nd) {
+    const int64_t a = doc_ptr[t], b = doc_ptr[t + 1];
+    const int64_t qa = q_ptr[q], qb = q_ptr[q + 1];
+    for (int64_t g = qa; g < qb; g += TS_THREADS) {
+      const int64_t j = g + lane;
+      hit[lane] = 0;
+      if (j < qb) {
+        const int32_t term = q_term[j];
+        const int64_t pos = lower_bound_doc(doc_term, a, b, term);
+        if (pos < b && doc_term[pos] == term) { hit[lane] = 1; qv[lane] = q_w[j]; dv[lane] = doc_w[pos]; }
+      }
+      __syncthreads();
+      if (lane == 0) {
+        const int m = (int)min((int64_t)TS_THREADS, qb - g);
+        for (int i = 0; i < m; ++i)
+          if (hit[i]) acc = fmaf(qv[i], dv[i], acc);
+      }
+      __syncthreads();
+    }
+  }
+  if (lane == 0) out[p] = acc;
+}
+
+// Band search, chunk stage: the LDS accumulation of sr_chunk_kernel, then the query's excluded docs inside the chunk (a
+// binary search of the ascending exclusion row for the chunk's doc range) are zeroed, and a score that is not below the
+// query's ceiling gets key 0.  Key 0 is "no candidate" to radix_select, so the chunk keeps its top `hi` ADMISSIBLE docs.
+__global__ __launch_bounds__(SR_THREADS) void sb_chunk_kernel(const int64_t* __restrict__ q_ptr,
+                                                              const int32_t* __restrict__ q_term,
+                                                              const float* __restrict__ q_w,
+                                                              const int64_t* __restrict__ term_ptr,
+                                                              const int32_t* __restrict__ post_doc,
+                                                              const float* __restrict__ post_w, int32_t nd, int32_t V,
+                                                              int32_t chunk, int32_t nch, int32_t hi,
+                                                              const int64_t* __restrict__ ex_ptr,
+                                                              const int32_t* __restrict__ ex_doc,
+                                                              const float* __restrict__ ceiling,
+                                                              unsigned long long* __restrict__ cand,
+                                                              int32_t* __restrict__ ccount) {
+  extern __shared__ float sc[];
+  __shared__ SelectSmem S;
+  __shared__ int64_t seg0[SR_TG], seg1[SR_TG];
+  __shared__ float segw[SR_TG];
+  const int tid = threadIdx.x;
+  const long qc = blockIdx.x;
+  const int q = (int)(qc / nch), c = (int)(qc - (long)q * nch);
+  const int c0 = c * chunk;
+  const int n = max(0, min(chunk, nd - c0));
+  for (int i = tid; i < n; i += SR_THREADS) sc[i] = 0.f;
+  const int64_t qa = q_ptr[q], qb = q_ptr[q + 1];
+  for (int64_t g = qa; g < qb; g += SR_TG) {
+    const int ng = (int)min((int64_t)SR_TG, qb - g);
+    const int j = tid < SR_TG ? tid : tid - SR_TG;
+    if (j < ng) {
+      const int32_t term = q_term[g + j];
+      int64_t lo = 0, hi2 = 0;
+      if ((unsigned)term < (unsigned)V) { lo = term_ptr[term]; hi2 = term_ptr[term + 1]; }
+      if (tid < SR_TG) {
+        seg0[j] = lower_bound_doc(post_doc, lo, hi2, c0);
+        segw[j] = q_w[g + j];
+      } else {
+        seg1[j] = lower_bound_doc(post_doc, lo, hi2, c0 + n);
+      }
+    }
+    __syncthreads();
+    for (int jj = 0; jj < ng; ++jj) {                      // ascending term id: the ABI's accumulation order
+      const int64_t e = seg1[jj];
+      const float w = segw[jj];
+      for (int64_t i = seg0[jj] + tid; i < e; i += SR_THREADS) {
+        const int d = post_doc[i] - c0;
+        if ((unsigned)d < (unsigned)n) sc[d] = fmaf(w, post_w[i], sc[d]);
+      }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+  if (ex_ptr) {                                            // the row's docs in [c0, c0 + n): one binary search per bound
+    if (tid < 2) {
+      const int64_t a = ex_ptr[q], b = ex_ptr[q + 1];
+      seg0[tid] = lower_bound_doc(ex_doc, a, b, tid == 0 ? c0 : c0 + n);
+    }
+    __syncthreads();
+    const int64_t e0 = seg0[0], e1 = seg0[1];
+    for (int64_t i = e0 + tid; i < e1; i += SR_THREADS) {
+      const int d = ex_doc[i] - c0;
+      if ((unsigned)d < (unsigned)n) sc[d] = 0.f;
+    }
+    __syncthreads();
+  }
+  const float ceil_q = ceiling ? ceiling[q] : __builtin_huge_valf();
+  auto key = [&](long i) -> uint32_t {
+    const float s = sc[i];
+    return s < ceil_q ? score_key(s) : 0u;                 // a NaN ceiling admits nothing
+  };
+  uint32_t thr;
+  int need_eq, nsel;
+  radix_select(key, n, hi, S, thr, need_eq, nsel);
+  unsigned long long* out = cand + qc * hi;
+  ordered_take(key, n, thr, need_eq, S, [&](long i, int pos) {
+    out[pos] = ((unsigned long long)score_key(sc[i]) << 32) | (uint32_t)(c0 + (int)i);
+  });
+  if (tid == 0) ccount[qc] = nsel;
+}
+
+// Band search, merge stage: sr_merge_kernel's selection of the top `hi` over the chunks' candidates and its bitonic
+// sort, then ranks lo .. hi-1 are written.
+__global__ __launch_bounds__(SR_THREADS) void sb_merge_kernel(const unsigned long long* __restrict__ cand,
+                                                              const int32_t* __restrict__ ccount, int32_t nch,
+                                                              int32_t lo, int32_t hi, int32_t* __restrict__ out_doc,
+                                                              float* __restrict__ out_score,
+                                                              int32_t* __restrict__ out_found) {
+  __shared__ SelectSmem S;
+  __shared__ unsigned long long sbuf[SR_KMAX];
+  const int tid = threadIdx.x, q = blockIdx.x;
+  const long base = (long)q * nch;
+  const unsigned long long* qcand = cand + base * hi;
+  const int32_t* qcnt = ccount + base;
+  auto key = [&](long f) -> uint32_t {
+    const int c = (int)(f / hi), i = (int)(f - (long)c * hi);
+    return i < qcnt[c] ? (uint32_t)(qcand[f] >> 32) : 0u;
+  };
+  const long n = (long)nch * hi;
+  uint32_t thr;
+  int need_eq, nsel;
+  radix_select(key, n, hi, S, thr, need_eq, nsel);
+  int P = 1;
+  while (P < nsel) P <<= 1;
+  for (int i = tid; i < P; i += SR_THREADS) sbuf[i] = 0ull;
+  __syncthreads();
+  ordered_take(key, n, thr, need_eq, S, [&](long f, int pos) {
+    const unsigned long long e = qcand[f];
+    sbuf[pos] = (e & 0xFFFFFFFF00000000ull) | (0xFFFFFFFFull - (e & 0xFFFFFFFFull));
+  });
+  for (int size = 2; size <= P; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = tid; t < (P >> 1); t += SR_THREADS) {
+        const int a0 = 2 * t - (t & (stride - 1));
+        const int a1 = a0 + stride;
+        const bool desc = (a0 & size) == 0;
+        const unsigned long long a = sbuf[a0], b = sbuf[a1];
+        if ((a < b) == desc) { sbuf[a0] = b; sbuf[a1] = a; }
+      }
+      __syncthreads();
+    }
+  const int w = hi - lo;
+  int32_t* od = out_doc + (long)q * w;
+  float* os = out_score + (long)q * w;
+  for (int j = tid; j < w; j += SR_THREADS) {
+    const int r = lo + j;
+    if (r < nsel) {
+      const unsigned long long e = sbuf[r];
+      os[j] = __builtin_bit_cast(float, (uint32_t)(e >> 32));
+      od[j] = (int32_t)(0xFFFFFFFFu - (uint32_t)(e & 0xFFFFFFFFull));
+    } else {
+      os[j] = 0.f;
+      od[j] = -1;
+    }
+  }
+  if (tid == 0) out_found[q] = max(0, nsel - lo);
+}
+
 inline int sr_chunk(int32_t chunk_docs) { return chunk_docs > 0 ? chunk_docs : SR_CHUNK_DEFAULT; }
 inline int sr_nch(int32_t nd, int chunk) { return nd > 0 ? (int)((nd + (long)chunk - 1) / chunk) : 1; }
 
@@ -496,6 +673,62 @@ extern "C" int snx_sparse_search(const int64_t* q_ptr, const int32_t* q_term, co
   hipLaunchKernelGGL(sr_merge_kernel, dim3(nq), dim3(SR_THREADS), 0, st, (const unsigned long long*)cand,
                      (const int32_t*)ccount, (const int32_t*)rcount, nd, nch, k, target, (const float*)out_tscore,
                      out_doc, out_score, out_rank);
+  SNX_CHECK_LAUNCH();
+  return SNX_OK;
+}
+
+
+extern "C" int snx_sparse_pair_scores(const int64_t* q_ptr, const int32_t* q_term, const float* q_w, int32_t nq,
+                                      const int64_t* doc_ptr, const int32_t* doc_term, const float* doc_w, int32_t nd,
+                                      const int32_t* pair_q, const int32_t* pair_d, int64_t npairs, float* out,
+                                      hipStream_t st) {
+  if (!q_ptr || !doc_ptr) return SNX_E_ARG;
+  if (nq < 0 || nd < 0 || npairs < 0 || npairs > 0x7FFFFFFFL) return SNX_E_SHAPE;
+  if (npairs == 0) return SNX_OK;
+  if (!pair_q || !pair_d || !out) return SNX_E_ARG;
+  hipLaunchKernelGGL(sr_pair_kernel, dim3((unsigned)npairs), dim3(TS_THREADS), 0, st, q_ptr, q_term, q_w, nq, doc_ptr,
+                     doc_term, doc_w, nd, pair_q, pair_d, out);
+  SNX_CHECK_LAUNCH();
+  return SNX_OK;
+}
+
+extern "C" size_t snx_sparse_search_band_workspace_bytes(int32_t nq, int32_t nd, int32_t hi, int32_t chunk_docs) {
+  if (nq <= 0 || nd < 0 || hi <= 0 || chunk_docs < 0) return 0;
+  const size_t blocks = (size_t)nq * (size_t)sr_nch(nd, sr_chunk(chunk_docs));
+  return align256(blocks * (size_t)hi * 8) + align256(blocks * 4);
+}
+
+extern "C" int snx_sparse_search_band(const int64_t* q_ptr, const int32_t* q_term, const float* q_w, int32_t nq,
+                                      const int64_t* term_ptr, const int32_t* post_doc, const float* post_w,
+                                      int32_t nd, int32_t V, const int64_t* ex_ptr, const int32_t* ex_doc,
+                                      const float* ceiling, int32_t lo, int32_t hi, int32_t chunk_docs,
+                                      int32_t* out_doc, float* out_score, int32_t* out_found, void* workspace,
+                                      size_t ws_bytes, hipStream_t st) {
+  if (!q_ptr || !term_ptr || !out_doc || !out_score || !out_found) return SNX_E_ARG;
+  if (ex_ptr && !ex_doc) return SNX_E_ARG;
+  if (nq < 0 || nd < 0 || V <= 0 || lo < 0 || hi <= lo || hi > SR_KMAX || chunk_docs < 0 ||
+      chunk_docs > SR_CHUNK_MAX)
+    return SNX_E_SHAPE;
+  if (nq == 0) return SNX_OK;
+  const int chunk = sr_chunk(chunk_docs);
+  const int nch = sr_nch(nd, chunk);
+  const long blocks = (long)nq * nch;
+  if (blocks > (1L << 31) / SR_THREADS) return SNX_E_SHAPE;
+  const size_t need = snx_sparse_search_band_workspace_bytes(nq, nd, hi, chunk_docs);
+  if (!workspace || ws_bytes < need) return SNX_E_ARG;
+  char* w = (char*)workspace;
+  unsigned long long* cand = (unsigned long long*)w;
+  int32_t* ccount = (int32_t*)(w + align256((size_t)blocks * hi * 8));
+  const size_t lds = (size_t)chunk * sizeof(float);
+  if (lds > 48 * 1024) {
+    static LdsOptIn optin;
+    if (const int rc = optin.ensure((const void*)sb_chunk_kernel, SR_CHUNK_MAX * (int)sizeof(float))) return rc;
+  }
+  hipLaunchKernelGGL(sb_chunk_kernel, dim3((unsigned)blocks), dim3(SR_THREADS), lds, st, q_ptr, q_term, q_w, term_ptr,
+                     post_doc, post_w, nd, V, chunk, nch, hi, ex_ptr, ex_doc, ceiling, cand, ccount);
+  SNX_CHECK_LAUNCH();
+  hipLaunchKernelGGL(sb_merge_kernel, dim3(nq), dim3(SR_THREADS), 0, st, (const unsigned long long*)cand,
+                     (const int32_t*)ccount, nch, lo, hi, out_doc, out_score, out_found);
   SNX_CHECK_LAUNCH();
   return SNX_OK;
 }

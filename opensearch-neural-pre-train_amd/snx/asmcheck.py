@@ -33,7 +33,8 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     "decoder256.hip": ("decoder256_kernel",),
     "gemm_nt256.hip": ("gemm_nt256_kernel",),
     # no asm here: held to the zero-scratch rule (the LDS score chunk and the select state must stay out of memory)
-    "retrieval.hip": ("ix_scan_kernel", "sr_target_kernel", "sr_chunk_kernel", "sr_merge_kernel"),
+    "retrieval.hip": ("ix_scan_kernel", "sr_target_kernel", "sr_chunk_kernel", "sr_merge_kernel",
+                      "sr_pair_kernel", "sb_chunk_kernel", "sb_merge_kernel"),
 }
 
 # Kernels held to the global-load / vmcnt rule: nothing may touch a load's destination before a vmcnt wait that retires it.

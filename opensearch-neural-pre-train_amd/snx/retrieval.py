@@ -8,7 +8,9 @@ term-major index is built by a deterministic counting sort, and every query is s
     s(q, d) = fmaf over the shared terms in ascending term id, fp32, starting at +0  (the plain dot product)
 
 then ranked score descending, ties lowest doc id first.  Results are bit-reproducible and independent of
-``chunk_docs``."""
+``chunk_docs``.  ``search_band`` and ``pair_scores`` serve the hard-negative miner (src.train.mining): a rank band of the
+ADMISSIBLE docs (score > 0, not in the query's exclusion row, score < the query's ceiling) and s(q, d) of given pairs,
+bit-equal to the ranked values."""
 from __future__ import annotations
 
 from typing import List, Optional, Tuple
@@ -48,6 +50,35 @@ def pack_rows(vals: torch.Tensor, ids: torch.Tensor, cnt: torch.Tensor, V: int, 
     return c, skey[live].to(torch.int32), w[live].contiguous()
 
 
+def exclusion_csr(exclude, nq: int, nd: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exclusion rows -> (ptr int64 [nq+1], docs int32) on ``device``, every row sorted ascending and deduplicated.
+    ``exclude``: a list of ``nq`` per-query doc-id lists, or a CSR pair, the tuple (ptr [nq+1], docs) of int tensors whose
+    ptr starts at 0, does not decrease and ends at len(docs).  Every id must lie in [0, nd)."""
+    if isinstance(exclude, tuple) and len(exclude) == 2 and all(isinstance(x, torch.Tensor) for x in exclude):
+        ptr, docs = exclude
+        if ptr.dim() != 1 or docs.dim() != 1 or ptr.numel() != nq + 1 or ptr.is_floating_point() or \
+                docs.is_floating_point():
+            raise ValueError(f"exclusion rows: a CSR pair needs int tensors ptr [{nq + 1}] and docs [n]")
+        ptr, docs = ptr.to(docs.device, torch.long), docs.long()        # normalised where the pair lives
+        if int(ptr[0]) != 0 or int(ptr[-1]) != docs.numel() or bool((ptr[1:] < ptr[:-1]).any()):
+            raise ValueError("exclusion rows: ptr must start at 0, not decrease and end at len(docs)")
+        row = torch.repeat_interleave(torch.arange(nq, dtype=torch.long, device=docs.device), ptr[1:] - ptr[:-1])
+    else:
+        rows = list(exclude)
+        if len(rows) != nq:
+            raise ValueError(f"exclusion rows: {len(rows)} rows for {nq} queries")
+        lens = [len(r) for r in rows]
+        docs = torch.tensor([int(d) for r in rows for d in r], dtype=torch.long)
+        row = torch.repeat_interleave(torch.arange(nq, dtype=torch.long), torch.tensor(lens, dtype=torch.long))
+    if docs.numel() and not bool(((docs >= 0) & (docs < nd)).all()):
+        raise ValueError(f"exclusion rows: doc ids must lie in [0, {nd})")
+    key = torch.unique(row * max(nd, 1) + docs)             # sorted: by row, then doc; duplicates merged
+    r, d = key // max(nd, 1), key % max(nd, 1)
+    ptr = torch.zeros(nq + 1, dtype=torch.long, device=key.device)
+    torch.cumsum(torch.bincount(r, minlength=nq), 0, out=ptr[1:])
+    return ptr.to(device), d.to(torch.int32).to(device)
+
+
 class SparseIndex:
     """Inverted index over sparse doc vectors, searched exactly on the GPU.
 
@@ -55,6 +86,8 @@ class SparseIndex:
         index.add(vals, ids, cnt)          # per batch: the [B, cap] output of ops.sparse_topk
         index.build()
         scores, docs, rank, tscore = index.search(q_vals, q_ids, q_cnt, k, targets=None)
+        scores, docs, found = index.search_band(q_vals, q_ids, q_cnt, lo, hi, exclude=None, ceiling=None)
+        s = index.pair_scores(q_vals, q_ids, q_cnt, pairs)
 
     Doc ids are the order of addition.  ``search`` returns top-k scores / doc ids [nq, k] (unused slots: 0 / -1) and,
     given ``targets`` [nq], the target's 1-based rank under the same tie order (0 = score 0, a miss) and its score."""
@@ -92,6 +125,31 @@ class SparseIndex:
         self._w.append(w)
         self.num_docs += int(c.numel())
         self.term_ptr = None                                  # a new batch invalidates a built index
+
+    def add_csr(self, cnt: torch.Tensor, terms: torch.Tensor, weights: torch.Tensor) -> None:
+        """Docs already packed as pack_rows returns them: counts int64 [B], terms int32 ascending within each row,
+        weights fp32 > 0."""
+        if not (cnt.device == terms.device == weights.device == self.device):
+            raise ValueError(f"SparseIndex.add_csr: tensors must be on {self.device}")
+        if cnt.dtype != torch.long or terms.dtype != torch.int32 or weights.dtype != torch.float32 or cnt.dim() != 1 or \
+                terms.dim() != 1 or weights.shape != terms.shape:
+            raise ValueError("SparseIndex.add_csr: counts int64 [B], terms int32 [nnz], weights fp32 [nnz]")
+        if (cnt < 0).any() or int(cnt.sum()) != terms.numel():
+            raise ValueError("SparseIndex.add_csr: counts must be >= 0 and sum to nnz")
+        if terms.numel():
+            row = torch.repeat_interleave(torch.arange(cnt.numel(), device=self.device), cnt)
+            ok = ((terms >= 0) & (terms < self.V)).all() & ((weights > 0) & torch.isfinite(weights)).all()
+            ok &= ((terms[1:] > terms[:-1]) | (row[1:] != row[:-1])).all()
+            if not bool(ok):
+                raise ValueError(f"SparseIndex.add_csr: rows need ascending distinct ids in [0, {self.V}) and "
+                                 "finite weights > 0")
+        if self.num_docs + cnt.numel() >= 2 ** 31:
+            raise ValueError("SparseIndex: doc ids are int32")
+        self._cnt.append(cnt.contiguous())
+        self._term.append(terms.contiguous())
+        self._w.append(weights.contiguous())
+        self.num_docs += int(cnt.numel())
+        self.term_ptr = None
 
     def build(self) -> "SparseIndex":
         dev, nd, V = self.device, self.num_docs, self.V
@@ -159,3 +217,78 @@ class SparseIndex:
                     _p(None if rank is None else rank[s:]), _p(None if tscore is None else tscore[s:]), _p(ws), ws_bytes,
                     _stream()), "snx_sparse_search")
         return scores, docs, rank, tscore
+
+    def _queries(self, q_vals, q_ids, q_cnt, who: str):
+        if not self.built:
+            raise RuntimeError(f"SparseIndex.{who}: call build() first")
+        if q_vals.device != self.device:
+            raise ValueError(f"SparseIndex.{who}: tensors must be on {self.device}")
+        qc, q_term, q_w = pack_rows(q_vals, q_ids, q_cnt, self.V, "queries")
+        q_ptr = torch.zeros(qc.numel() + 1, dtype=torch.long, device=self.device)
+        torch.cumsum(qc, 0, out=q_ptr[1:])
+        return int(qc.numel()), q_ptr, q_term, q_w
+
+    def pair_scores(self, q_vals: torch.Tensor, q_ids: torch.Tensor, q_cnt: torch.Tensor,
+                    pairs: torch.Tensor) -> torch.Tensor:
+        """``pairs`` int [n, 2] of (query row, doc id) -> s(q, d) fp32 [n], bit-equal to the scores the searches rank."""
+        nq, q_ptr, q_term, q_w = self._queries(q_vals, q_ids, q_cnt, "pair_scores")
+        nd, dev = self.num_docs, self.device
+        if not isinstance(pairs, torch.Tensor) or pairs.device != dev or pairs.dim() != 2 or pairs.shape[1] != 2 or \
+                pairs.is_floating_point():
+            raise ValueError(f"SparseIndex.pair_scores: pairs must be an int tensor [n, 2] on {dev}")
+        n = int(pairs.shape[0])
+        if n and not bool(((pairs[:, 0] >= 0) & (pairs[:, 0] < nq) & (pairs[:, 1] >= 0) & (pairs[:, 1] < nd)).all()):
+            raise ValueError(f"SparseIndex.pair_scores: pairs must be (query in [0, {nq}), doc in [0, {nd}))")
+        pq = pairs[:, 0].to(torch.int32).contiguous()
+        pd = pairs[:, 1].to(torch.int32).contiguous()
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            check(fn("snx_sparse_pair_scores")(_p(q_ptr), _p(q_term), _p(q_w), nq, _p(self.doc_ptr), _p(self.doc_term),
+                                                _p(self.doc_w), nd, _p(pq), _p(pd), n, _p(out), _stream()),
+                  "snx_sparse_pair_scores")
+        return out
+
+    def search_band(self, q_vals: torch.Tensor, q_ids: torch.Tensor, q_cnt: torch.Tensor, lo: int, hi: int,
+                    exclude=None, ceiling: Optional[torch.Tensor] = None, chunk_docs: int = 0
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Ranks ``lo .. hi-1`` (0-based) of each query's ADMISSIBLE docs -- score > 0, not in ``exclude[q]``, score <
+        ``ceiling[q]`` (fp32, strict; +inf: none) -- under (score desc, doc asc) -> (scores [nq, hi-lo] fp32, docs
+        [nq, hi-lo] int32, found [nq] int32); unused slots 0 / -1.  ``exclude``: None, per-query doc-id lists, or a CSR
+        pair (see exclusion_csr); ``ceiling``: None or fp32 [nq] on the index's device."""
+        lo, hi, chunk_docs = int(lo), int(hi), int(chunk_docs)
+        if not 0 <= lo < hi <= K_MAX:
+            raise ValueError(f"SparseIndex.search_band: need 0 <= lo < hi <= {K_MAX}")
+        if not 0 <= chunk_docs <= CHUNK_MAX:
+            raise ValueError(f"SparseIndex.search_band: chunk_docs must be in [0, {CHUNK_MAX}] (0: default)")
+        nq, q_ptr, q_term, q_w = self._queries(q_vals, q_ids, q_cnt, "search_band")
+        dev, nd = self.device, self.num_docs
+        ex_ptr = ex_doc = None
+        if exclude is not None:
+            ex_ptr, ex_doc = exclusion_csr(exclude, nq, nd, dev)
+            if ex_doc.numel() == 0:
+                ex_ptr = ex_doc = None
+        ceil = None
+        if ceiling is not None:
+            if not isinstance(ceiling, torch.Tensor) or ceiling.device != dev or ceiling.dtype != torch.float32 or \
+                    ceiling.dim() != 1 or ceiling.numel() != nq:
+                raise ValueError(f"SparseIndex.search_band: ceiling must be fp32 [{nq}] on {dev}")
+            if nq and bool(torch.isnan(ceiling).any()):
+                raise ValueError("SparseIndex.search_band: ceiling must not be NaN (+inf: no ceiling)")
+            ceil = ceiling.contiguous()
+        w = hi - lo
+        scores = torch.empty((nq, w), dtype=torch.float32, device=dev)
+        docs = torch.empty((nq, w), dtype=torch.int32, device=dev)
+        found = torch.empty(nq, dtype=torch.int32, device=dev)
+        per_q = max(1, int(fn("snx_sparse_search_band_workspace_bytes")(1, nd, hi, chunk_docs)))
+        step = max(1, min(nq, _SEARCH_WS_BUDGET // per_q))
+        with torch.cuda.device(dev):
+            for s in range(0, nq, step):
+                m = min(step, nq - s)
+                ws_bytes = int(fn("snx_sparse_search_band_workspace_bytes")(m, nd, hi, chunk_docs))
+                ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+                check(fn("snx_sparse_search_band")(
+                    _p(q_ptr[s:]), _p(q_term), _p(q_w), m, _p(self.term_ptr), _p(self.post_doc), _p(self.post_w), nd,
+                    self.V, _p(None if ex_ptr is None else ex_ptr[s:]), _p(ex_doc), _p(None if ceil is None else ceil[s:]),
+                    lo, hi, chunk_docs, _p(docs[s:]), _p(scores[s:]), _p(found[s:]), _p(ws), ws_bytes, _stream()),
+                    "snx_sparse_search_band")
+        return scores, docs, found

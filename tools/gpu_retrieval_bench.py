@@ -3,11 +3,17 @@
 csrc/retrieval.hip) on synthetic Zipf-skewed data.
 
     python tools/gpu_retrieval_bench.py [--sizes 1000x200,100000x10000,1000000x10000] [--out result.json]
+    python tools/gpu_retrieval_bench.py --band [--sizes 1000000x10000] [--miner-records 4000]
 
 Docs draw 128 terms (with replacement, duplicates dropped: ~99 distinct) from a Zipf(1.0) law over V = 50000 with
 weights uniform in [0.1, 3); queries draw 64 the same way (~53 distinct).  Retrieval size 10 with a target per query
 (the evaluator's call).  Comparison row: torch.sparse CSR (docs) @ dense query block + torch.topk over query chunks,
-where the torch build supports it."""
+where the torch build supports it.
+
+--band: the miner's search (SparseIndex.search_band, ranks [10, 50)) against plain search at k = 50 on the same data,
+with 1% of the docs excluded per query, without and with a ceiling (half the query's 100th score); the exclusion rows'
+normalisation (exclusion_csr, on the device) is timed on its own.  Then one timed end-to-end miner run
+(src.train.mining.mine_negatives) on synthetic triplet shards with a random-init model, in docs/s and queries/s."""
 import argparse
 import json
 import os
@@ -103,14 +109,81 @@ def torch_sparse_row(idx, q, nd, nq, dev, budget_s=20.0):
         return {"ok": False, "error": f"{type(e).__name__}: {e}"[:300]}
 
 
+def band_case(nd, nq, dev, lo=10, hi=50):
+    from snx.retrieval import SparseIndex, exclusion_csr
+    gen = torch.Generator().manual_seed(nd + nq)
+    probs = 1.0 / torch.arange(1, V + 1, dtype=torch.float64)
+    probs /= probs.sum()
+    idx = SparseIndex(V, dev)
+    for s in range(0, nd, 100_000):
+        idx.add(*zipf_rows(min(100_000, nd - s), 128, gen, dev, probs))
+    idx.build()
+    q = zipf_rows(nq, 64, gen, dev, probs)
+    m = max(1, nd // 100)
+    ex_docs = torch.randint(0, nd, (nq * m,), generator=gen).to(dev)
+    ex_ptr = torch.arange(0, nq * m + 1, m, dtype=torch.long, device=dev)
+    t_norm, ex = sync_time(lambda: exclusion_csr((ex_ptr, ex_docs), nq, nd, dev))
+    top, _, _, _ = idx.search(*q, 100)
+    ceiling = (top[:, -1] * 0.5 + top[:, 0] * 0.5).contiguous()
+    idx.search(q[0][:64], q[1][:64], q[2][:64], hi)
+
+    def best(f):
+        return min(sync_time(f)[0] for _ in range(3))
+
+    t_search = best(lambda: idx.search(*q, hi))
+    t_band = best(lambda: idx.search_band(*q, lo, hi, exclude=ex))
+    t_band_ceil = best(lambda: idx.search_band(*q, lo, hi, exclude=ex, ceiling=ceiling))
+    t_band_none = best(lambda: idx.search_band(*q, lo, hi))
+    return {"docs": nd, "queries": nq, "band": [lo, hi], "excluded_per_query": m, "search_k_s": t_search,
+            "band_s": t_band, "band_ceiling_s": t_band_ceil, "band_no_exclusion_s": t_band_none,
+            "exclusion_normalise_s": t_norm, "band_over_search": t_band / t_search,
+            "band_ceiling_over_search": t_band_ceil / t_search}
+
+
+def miner_case(n_records, dev):
+    import tempfile
+    from src.model.splade_modern import SPLADEModernBERT
+    from src.train.data import SyntheticTripletDataset
+    from src.train.data.collator import create_tokenizer
+    from src.train.mining import mine_negatives
+    ds = SyntheticTripletDataset(n_records, num_negatives=3, seed=1)
+    with tempfile.TemporaryDirectory() as d:
+        for sh in range(2):
+            with open(os.path.join(d, f"train_{sh:02d}.jsonl"), "w") as f:
+                for i in range(sh, n_records, 2):
+                    f.write(json.dumps(ds[i]) + "\n")
+        torch.manual_seed(0)
+        model = SPLADEModernBERT(model_name="skt/A.X-Encoder-base").to(dev)
+        tok = create_tokenizer("hash:50000")
+        files = sorted(os.path.join(d, f) for f in os.listdir(d))
+        t, summ = sync_time(lambda: mine_negatives(model, tok, files, os.path.join(d, "out"), device=dev))
+    return {"records": summ["records"], "docs": summ["docs"], "queries": summ["queries"], "seconds": t,
+            "docs_per_s": summ["docs"] / t, "queries_per_s": summ["queries"] / t, "band_fill": summ["band_fill"]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000x200,100000x10000,1000000x10000")
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--band", action="store_true", help="search_band vs search, then an end-to-end miner run")
+    ap.add_argument("--miner-records", type=int, default=4000)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     rows = []
+    if args.band:
+        sizes = args.sizes if args.sizes != ap.get_default("sizes") else "1000000x10000"
+        for s in sizes.split(","):
+            nd, nq = (int(x) for x in s.split("x"))
+            rows.append(band_case(nd, nq, dev))
+            print(json.dumps(rows[-1]), flush=True)
+        if args.miner_records > 0:
+            rows.append({"miner": miner_case(args.miner_records, dev)})
+            print(json.dumps(rows[-1]), flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump({"device": torch.cuda.get_device_name(0), "rows": rows}, f, indent=1)
+        return
     for s in args.sizes.split(","):
         nd, nq = (int(x) for x in s.split("x"))
         row = run_case(nd, nq, dev, torch_cmp=not args.no_torch)
