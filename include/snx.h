@@ -233,6 +233,56 @@ int snx_sparse_search_band(const int64_t* q_ptr, const int32_t* q_term, const fl
                            int32_t chunk_docs, int32_t* out_doc, float* out_score, int32_t* out_found, void* workspace,
                            size_t ws_bytes, hipStream_t stream);
 
+/* ---- SEISMIC approximate search over the same index (Bruch et al., SIGIR 2024; the `sparse_vector` ANN method of
+ * ref:huggingface/v33/README.md, measured at ref:scripts/neural_sparse_search_aws.py:1314-1510).  A deterministic form
+ * of the published algorithm with OpenSearch's parameter names; it does not reproduce OpenSearch's numbers (no centroid
+ * sampling, fp32 summaries without quantization, one index per corpus).  s(a, b) is the score above, applied to
+ * query.doc, doc.doc and query.summary alike; "search order" = score descending, ties lowest doc id first.
+ * Build, for every term t (parameters n_postings >= 1, cluster_ratio r in (0, 1], summary_prune_ratio alpha in (0, 1]):
+ *   1. P_t = the first min(|L_t|, n_postings) postings of t by (weight desc, doc asc); prune_ptr [V+1] (host scan of
+ *      the kept counts), prune_doc / prune_w [npruned] hold each P_t in doc order;
+ *   2. c_t = min(|P_t|, max(1, ceil(r |P_t|))), computed by the caller in float64: cent_cnt [V] int32, cent_ptr [V+1];
+ *   3. centroid j = the doc at position floor(j |P_t| / c_t) of P_t in the order of 1. -> cent_doc [ncent];
+ *   4. each doc of P_t goes to the centroid of highest s(doc, centroid) (full doc vectors), ties lowest j ->
+ *      assign [npruned] (the centroid index, aligned with prune_doc), cent_size [ncent] (docs per centroid);
+ *   5. block j = the docs of centroid j in ascending doc id; empty blocks are dropped, the others keep (t, j) order.
+ *      snx_seismic_build_blocks writes them to blk_doc [npruned]: cursor [ncent] int64 holds each centroid's block start
+ *      (the caller's exclusive scan of cent_size) on entry and its block end on return;
+ *   6. per block (blk_ptr [nblocks+1] over blk_doc, empty blocks excluded): m_u = max weight of term u over its docs;
+ *      entries sorted by (m desc, u asc); total = fp32 left fold of the m's; the shortest prefix whose fp32 left-fold
+ *      sum is >= fp32(alpha) * total (fp32 multiply), at least one entry, stored in ascending term id.  Called twice:
+ *      sum_ptr NULL -> sum_cnt [nblocks] = kept entries; then with sum_ptr [nblocks+1] (the caller's scan) -> sum_term /
+ *      sum_w.  workspace: snx_seismic_build_workspace_bytes(V, nblocks) bytes.
+ * Search (k in [1, 1024], top_n >= 1, heap_factor > 0 fp32, +inf allowed; rows of at most max_q_nnz <= 1024 terms --
+ * a longer row is searched as an empty one): Q_cut = the top_n query entries by (weight desc, term asc); H = the top k,
+ * in search order, of the docs scored so far with s > 0.  The terms of Q_cut are visited in that order, each term's
+ * blocks (term_blk_ptr [V+1] over the blocks) in block order; with r = s(q, summary) (full q) a block is skipped iff
+ * |H| == k and heap_factor * r < s_k (fp32 multiply; a NaN product skips nothing), otherwise every doc of the block is
+ * scored with s(q, d) and offered to H (a doc already in H is not added again).  Output: H in search order -> out_doc /
+ * out_score [nq,k], unused slots doc -1, score 0; target [nq] (or NULL): out_rank = the target's 1-based position in
+ * the output (0: absent), out_tscore = s(q, target).  out_stats [nq,3] int64: blocks of the Q_cut lists, blocks scored,
+ * docs scored (sum of the scored blocks' sizes).  No workspace. */
+size_t snx_seismic_build_workspace_bytes(int32_t V, int64_t nblocks);
+int snx_seismic_build_clusters(const int64_t* term_ptr, const int32_t* post_doc, const float* post_w,
+                               const int64_t* doc_ptr, const int32_t* doc_term, const float* doc_w, int32_t nd,
+                               int32_t V, int32_t n_postings, const int64_t* prune_ptr, const int32_t* cent_cnt,
+                               const int64_t* cent_ptr, int64_t npruned, int64_t ncent, int32_t* prune_doc,
+                               float* prune_w, int32_t* cent_doc, int32_t* assign, int32_t* cent_size,
+                               hipStream_t stream);
+int snx_seismic_build_blocks(const int64_t* prune_ptr, const int32_t* prune_doc, const int32_t* assign,
+                             const int64_t* cent_ptr, int32_t V, int64_t npruned, int64_t* cursor, int32_t* blk_doc,
+                             hipStream_t stream);
+int snx_seismic_build_summaries(const int64_t* doc_ptr, const int32_t* doc_term, const float* doc_w, int32_t nd,
+                                int32_t V, const int64_t* blk_ptr, const int32_t* blk_doc, int64_t nblocks, float alpha,
+                                const int64_t* sum_ptr, int32_t* sum_cnt, int32_t* sum_term, float* sum_w,
+                                void* workspace, size_t ws_bytes, hipStream_t stream);
+int snx_seismic_search(const int64_t* q_ptr, const int32_t* q_term, const float* q_w, int32_t nq, int32_t max_q_nnz,
+                       const int64_t* term_blk_ptr, const int64_t* blk_ptr, const int32_t* blk_doc,
+                       const int64_t* sum_ptr, const int32_t* sum_term, const float* sum_w, const int64_t* doc_ptr,
+                       const int32_t* doc_term, const float* doc_w, int32_t nd, int32_t V, const int32_t* target,
+                       int32_t k, int32_t top_n, float heap_factor, int32_t* out_doc, float* out_score,
+                       int32_t* out_rank, float* out_tscore, int64_t* out_stats, hipStream_t stream);
+
 /* ---- SPLADELossV33 (ref:src/model/losses.py:183-297) ------------------------------------- */
 /* dims [host] = {B, Bp, k, V, label_off, bf16_mm}: q [B,V], p [Bp,V] (Bp > B: all-gathered
  * positives for cross-GPU in-batch negatives, own rows start at label_off), n [B*k,V]; bf16_mm=1

@@ -99,6 +99,12 @@ SIGNATURES = {
     "snx_sparse_pair_scores": (I32, [P, P, P, I32, P, P, P, I32, P, P, I64, P, P]),
     "snx_sparse_search_band_workspace_bytes": (SZ, [I32, I32, I32, I32]),
     "snx_sparse_search_band": (I32, [P, P, P, I32, P, P, P, I32, I32, P, P, P, I32, I32, I32, P, P, P, P, SZ, P]),
+    "snx_seismic_build_workspace_bytes": (SZ, [I32, I64]),
+    "snx_seismic_build_clusters": (I32, [P, P, P, P, P, P, I32, I32, I32, P, P, P, I64, I64, P, P, P, P, P, P]),
+    "snx_seismic_build_blocks": (I32, [P, P, P, P, I32, I64, P, P, P]),
+    "snx_seismic_build_summaries": (I32, [P, P, P, I32, I32, P, P, I64, F32, P, P, P, P, P, SZ, P]),
+    "snx_seismic_search": (I32, [P, P, P, I32, I32, P, P, P, P, P, P, P, P, P, I32, I32, P, I32, I32, F32, P, P, P, P, P,
+                                 P]),
     "snx_version": (I32, []),
     "snx_prof_enable": (I32, [I32]),
     "snx_prof_num_classes": (I32, []),

@@ -35,6 +35,9 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     # no asm here: held to the zero-scratch rule (the LDS score chunk and the select state must stay out of memory)
     "retrieval.hip": ("ix_scan_kernel", "sr_target_kernel", "sr_chunk_kernel", "sr_merge_kernel",
                       "sr_pair_kernel", "sb_chunk_kernel", "sb_merge_kernel"),
+    # the same rule for the SEISMIC build and search (query, top-k keys and sort buffers stay in LDS, not scratch)
+    "seismic.hip": ("sz_prune_kernel", "sz_centroid_kernel", "sz_assign_kernel", "sz_fill_kernel", "sz_summary_kernel",
+                    "sz_search_kernel"),
 }
 
 # Kernels held to the global-load / vmcnt rule: nothing may touch a load's destination before a vmcnt wait that retires it.

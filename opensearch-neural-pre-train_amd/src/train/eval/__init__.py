@@ -98,9 +98,11 @@ class MidTrainingEvaluator:
     inference encoder's filter (ref:benchmark/indexer.py:59); retrieval size 10."""
 
     def __init__(self, tokenizer, val_file: str, max_queries: int = 200, max_docs: int = 1000, device: str = "cuda",
-                 query_max_length: int = 64, doc_max_length: int = 256, batch_size: int = 64):
+                 query_max_length: int = 64, doc_max_length: int = 256, batch_size: int = 64,
+                 seismic: Optional[dict] = None):
         from benchmark.encoders import special_token_ids
         from src.train.data import load_training_data
+        self.seismic = seismic_params(seismic) if seismic is not None else None
         self.tokenizer = tokenizer
         self.device = torch.device(device)
         self.query_max_length, self.doc_max_length = int(query_max_length), int(doc_max_length)
@@ -134,7 +136,9 @@ class MidTrainingEvaluator:
                                                 None if top_k is None else min(top_k, rep.shape[1]))
             yield vals, ids, cnt
 
-    def evaluate(self, model) -> Dict[str, float]:
+    def encode(self, model):
+        """The corpus through ``model`` -> (SparseIndex over the docs, built when there are queries, or None; the query
+        rows (vals, ids, cnt) or None).  The model's training mode is restored."""
         from snx.retrieval import SparseIndex
         c = self.corpus
         was_training = model.training
@@ -147,19 +151,93 @@ class MidTrainingEvaluator:
                         index = SparseIndex(vals.shape[1], self.device)
                     index.add(vals, ids, cnt)
                 qb = list(self._encode(model, c.queries, self.query_max_length, QUERY_TOP_K))
-                ranks: List[int] = []
-                avg_q = 0.0
+                queries = None
                 if qb and index is not None:
                     index.build()
-                    q_vals, q_ids, q_cnt = (torch.cat([b[i] for b in qb]) for i in range(3))
-                    targets = torch.tensor(c.targets, dtype=torch.int32, device=self.device)
-                    _, _, rank, _ = index.search(q_vals, q_ids, q_cnt, RETRIEVAL_SIZE, targets=targets)
-                    ranks = rank.cpu().tolist()
-                    avg_q = float(q_cnt.double().mean())
-                avg_d = index.nnz / index.num_docs if index is not None and index.num_docs else 0.0
+                    queries = tuple(torch.cat([b[i] for b in qb]) for i in range(3))
         finally:
             model.train(was_training)
+        return index, queries
+
+    def evaluate(self, model) -> Dict[str, float]:
+        c = self.corpus
+        index, queries = self.encode(model)
+        ranks: List[int] = []
+        avg_q = 0.0
+        extra: Dict[str, float] = {}
+        if queries is not None:
+            targets = torch.tensor(c.targets, dtype=torch.int32, device=self.device)
+            _, docs, rank, _ = index.search(*queries, RETRIEVAL_SIZE, targets=targets)
+            ranks = rank.cpu().tolist()
+            avg_q = float(queries[2].double().mean())
+            if self.seismic is not None:
+                extra = seismic_eval(index, queries, targets, docs, self.seismic)[0]
+        elif self.seismic is not None:
+            extra = {f"seismic_{k}": 0.0 for k in METRIC_KEYS + ("overlap@5", "postings_frac")}
+        avg_d = index.nnz / index.num_docs if index is not None and index.num_docs else 0.0
         self.last_ranks = ranks
         out = metrics_from_ranks(ranks)
         out.update(num_queries=float(len(c.queries)), num_docs=float(len(c.docs)), avg_nnz_q=avg_q, avg_nnz_d=avg_d)
+        out.update(extra)
         return out
+
+
+SEISMIC_DEFAULTS = {"n_postings": 300, "cluster_ratio": 0.1, "summary_prune_ratio": 0.4, "top_n": 10,
+                    "heap_factor": 1.0}
+
+
+def seismic_params(p: dict) -> dict:
+    """The five SEISMIC parameters (snx.retrieval.SeismicIndex), missing ones at their defaults."""
+    bad = set(p) - set(SEISMIC_DEFAULTS)
+    if bad:
+        raise ValueError(f"seismic: unknown parameter(s) {sorted(bad)}; known: {list(SEISMIC_DEFAULTS)}")
+    return {**SEISMIC_DEFAULTS, **p}
+
+
+def overlap_at(ann_docs, exact_docs, k: int = 5) -> float:
+    """ref:scripts/neural_sparse_search_aws.py:1205-1215 (_recall_at_k), averaged over queries: |ANN top k & exact top
+    k| / |exact top k|, 0 for a query whose exact list is empty.  Rows are doc ids, -1 = unused slot."""
+    vals = []
+    for a, e in zip(np.asarray(ann_docs), np.asarray(exact_docs)):
+        es = {int(d) for d in e[:k] if d >= 0}
+        vals.append(len(es & {int(d) for d in a[:k] if d >= 0}) / len(es) if es else 0.0)
+    return float(np.mean(vals)) if vals else 0.0
+
+
+def cut_postings(index, queries, top_n: int) -> torch.Tensor:
+    """int64 [nq]: postings of the exact index under each query's top_n terms by (weight desc, term asc)."""
+    vals, ids, cnt = queries
+    live = torch.arange(vals.shape[1], device=vals.device)[None, :] < cnt.long()[:, None]
+    key = torch.where(live, ids.long(), torch.full_like(ids, index.V, dtype=torch.long))
+    o1 = torch.sort(key, dim=1, stable=True)[1]
+    w1 = torch.where(torch.gather(live, 1, o1), torch.gather(vals, 1, o1), torch.zeros_like(vals))
+    o2 = torch.sort(-w1, dim=1, stable=True)[1]
+    t = torch.gather(torch.gather(ids.long(), 1, o1), 1, o2)[:, :top_n]
+    ok = torch.gather(torch.gather(live, 1, o1), 1, o2)[:, :top_n]
+    lens = index.term_ptr[t.clamp(0, index.V - 1) + 1] - index.term_ptr[t.clamp(0, index.V - 1)]
+    return torch.where(ok, lens, torch.zeros_like(lens)).sum(1)
+
+
+def seismic_eval(index, queries, targets, exact_docs, params: dict, six=None):
+    """SEISMIC over the exact index's corpus -> (metrics, info).  metrics: seismic_recall@1/5/10, seismic_mrr@10,
+    seismic_ndcg@10 (the ANN ranks), seismic_overlap@5 (against ``exact_docs``), seismic_postings_frac (docs scored over
+    the exact postings of the Q_cut terms, summed over queries).  info: the SeismicIndex, build_s, search_s and the
+    counters' means.  ``six``: an index already built with ``params``' index settings."""
+    import time
+    from snx.retrieval import SeismicIndex
+    p = seismic_params(params)
+    if six is None:
+        six = SeismicIndex(index, p["n_postings"], p["cluster_ratio"], p["summary_prune_ratio"])
+    torch.cuda.synchronize(index.device)
+    t0 = time.perf_counter()
+    _, docs, rank, _, stats = six.search(*queries, RETRIEVAL_SIZE, top_n=p["top_n"], heap_factor=p["heap_factor"],
+                                         targets=targets)
+    torch.cuda.synchronize(index.device)
+    search_s = time.perf_counter() - t0
+    out = {f"seismic_{k}": v for k, v in metrics_from_ranks(rank.cpu().tolist()).items()}
+    out["seismic_overlap@5"] = overlap_at(docs.cpu().numpy(), exact_docs.cpu().numpy(), 5)
+    total = int(cut_postings(index, queries, p["top_n"]).sum())
+    out["seismic_postings_frac"] = float(stats["postings_scored"].sum()) / total if total else 0.0
+    info = {"index": six, "build_s": six.build_seconds, "search_s": search_s}
+    info.update({k: float(v.double().mean()) for k, v in stats.items()})
+    return out, info

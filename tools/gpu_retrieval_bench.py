@@ -4,6 +4,7 @@ csrc/retrieval.hip) on synthetic Zipf-skewed data.
 
     python tools/gpu_retrieval_bench.py [--sizes 1000x200,100000x10000,1000000x10000] [--out result.json]
     python tools/gpu_retrieval_bench.py --band [--sizes 1000000x10000] [--miner-records 4000]
+    python tools/gpu_retrieval_bench.py --seismic [--sizes 1000000x10000]
 
 Docs draw 128 terms (with replacement, duplicates dropped: ~99 distinct) from a Zipf(1.0) law over V = 50000 with
 weights uniform in [0.1, 3); queries draw 64 the same way (~53 distinct).  Retrieval size 10 with a target per query
@@ -13,7 +14,12 @@ where the torch build supports it.
 --band: the miner's search (SparseIndex.search_band, ranks [10, 50)) against plain search at k = 50 on the same data,
 with 1% of the docs excluded per query, without and with a ceiling (half the query's 100th score); the exclusion rows'
 normalisation (exclusion_csr, on the device) is timed on its own.  Then one timed end-to-end miner run
-(src.train.mining.mine_negatives) on synthetic triplet shards with a random-init model, in docs/s and queries/s."""
+(src.train.mining.mine_negatives) on synthetic triplet shards with a random-init model, in docs/s and queries/s.
+
+--seismic: SeismicIndex (csrc/seismic.hip) at the reference's index defaults (n_postings 300, cluster_ratio 0.1,
+summary_prune_ratio 0.4) on the same data: build seconds, then per heap_factor in {0.5, 1, 2} at top_n 10 and k = 10
+the queries/s against exact search, the mean overlap@10 with the exact top 10 and the fraction of the Q_cut terms'
+postings that were scored."""
 import argparse
 import json
 import os
@@ -140,6 +146,38 @@ def band_case(nd, nq, dev, lo=10, hi=50):
             "band_ceiling_over_search": t_band_ceil / t_search}
 
 
+def seismic_case(nd, nq, dev, k=10, top_n=10):
+    from snx.retrieval import SeismicIndex, SparseIndex
+    from src.train.eval import cut_postings, overlap_at
+    gen = torch.Generator().manual_seed(nd + nq)
+    probs = 1.0 / torch.arange(1, V + 1, dtype=torch.float64)
+    probs /= probs.sum()
+    idx = SparseIndex(V, dev)
+    for s in range(0, nd, 100_000):
+        idx.add(*zipf_rows(min(100_000, nd - s), 128, gen, dev, probs))
+    idx.build()
+    q = zipf_rows(nq, 64, gen, dev, probs)
+    idx.search(q[0][:64], q[1][:64], q[2][:64], k)
+
+    def best(f):
+        return min(sync_time(f)[0] for _ in range(3))
+
+    t_exact = best(lambda: idx.search(*q, k))
+    _, exact_docs, _, _ = idx.search(*q, k)
+    SeismicIndex(idx, 300, 0.1, 0.4)                           # warm-up (code objects, allocator)
+    t_build, six = sync_time(lambda: SeismicIndex(idx, 300, 0.1, 0.4))
+    cut = int(cut_postings(idx, q, top_n).sum())
+    row = {"docs": nd, "queries": nq, "k": k, "top_n": top_n, "build_s": t_build, "num_blocks": six.num_blocks,
+           "summary_nnz": six.summary_nnz, "exact_search_s": t_exact, "exact_queries_per_s": nq / t_exact, "legs": []}
+    for hf in (0.5, 1.0, 2.0):
+        t = best(lambda: six.search(*q, k, top_n=top_n, heap_factor=hf))
+        _, docs, _, _, stats = six.search(*q, k, top_n=top_n, heap_factor=hf)
+        row["legs"].append({"heap_factor": hf, "search_s": t, "queries_per_s": nq / t, "over_exact": t / t_exact,
+                            "overlap@10": overlap_at(docs.cpu().numpy(), exact_docs.cpu().numpy(), k),
+                            "postings_frac": float(stats["postings_scored"].sum()) / cut if cut else 0.0})
+    return row
+
+
 def miner_case(n_records, dev):
     import tempfile
     from src.model.splade_modern import SPLADEModernBERT
@@ -168,9 +206,20 @@ def main():
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--band", action="store_true", help="search_band vs search, then an end-to-end miner run")
     ap.add_argument("--miner-records", type=int, default=4000)
+    ap.add_argument("--seismic", action="store_true", help="SeismicIndex build and search against exact search")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     rows = []
+    if args.seismic:
+        sizes = args.sizes if args.sizes != ap.get_default("sizes") else "1000000x10000"
+        for s in sizes.split(","):
+            nd, nq = (int(x) for x in s.split("x"))
+            rows.append(seismic_case(nd, nq, dev))
+            print(json.dumps(rows[-1]), flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump({"device": torch.cuda.get_device_name(0), "rows": rows}, f, indent=1)
+        return
     if args.band:
         sizes = args.sizes if args.sizes != ap.get_default("sizes") else "1000000x10000"
         for s in sizes.split(","):
