@@ -283,6 +283,57 @@ int snx_seismic_search(const int64_t* q_ptr, const int32_t* q_term, const float*
                        int32_t k, int32_t top_n, float heap_factor, int32_t* out_doc, float* out_score,
                        int32_t* out_rank, float* out_tscore, int64_t* out_stats, hipStream_t stream);
 
+/* ---- pruning and two-phase search over the same index (csrc/two_phase.hip): the reference's other serving path, its
+ * `rank_features` index behind OpenSearch's neural_sparse_two_phase_processor (ref:benchmark/index_manager.py:197-238:
+ * prune_ratio 0.4, expansion_rate 5, max_window_size 10000; :147: it and SEISMIC exclude each other), and the ingest-time
+ * prune rules OpenSearch exposes as prune_type = max_ratio | abs_value | top_k | alpha_mass.  The thresholds below are
+ * this project's deterministic definitions under OpenSearch's names; OpenSearch's own float arithmetic is not claimed.
+ * Prune of one CSR row (ptr [n+1] int64, w [nnz] fp32 > 0; the terms ascend strictly within a row, so position order is
+ * term order and the terms themselves are not read); `value` is taken as fp32:
+ *   SNX_PRUNE_MAX_RATIO  r in [0, 1]       keep an entry iff w >= fp32(r) * w_max (fp32 multiply); a non-empty row always
+ *                                          keeps its maximum;
+ *   SNX_PRUNE_ABS_VALUE  a >= 0            keep iff w >= fp32(a); a row may become empty;
+ *   SNX_PRUNE_TOP_K      n >= 1, integral  keep the first n entries by (weight desc, term asc) (n above 2^30 counts as 2^30);
+ *   SNX_PRUNE_ALPHA_MASS alpha in (0, 1]   rule 6 of the SEISMIC section applied to the row: entries ordered by (weight
+ *                                          desc, term asc), total = the fp32 left fold of the weights in that order; keep
+ *                                          the shortest prefix whose fp32 left-fold sum is >= fp32(alpha) * total (fp32
+ *                                          multiply), at least one entry.
+ * Empty rows stay empty.  snx_sparse_prune_rows writes keep [nnz] uint8 (1: kept) and kept_cnt [n] int32; the caller
+ * compacts the rows.  max_row_nnz: the caller's bound on the row length (rows of V entries are fine); it sizes the
+ * workspace, snx_sparse_prune_workspace_bytes(prune_type, n, max_row_nnz) bytes -- 0 unless alpha_mass has to sort rows
+ * that do not fit in LDS, each workgroup then sorts in a slot of its own.  An alpha_mass row longer than the declared
+ * bound is not pruned: its keep flags are 0 and its kept_cnt is -1.  Unknown type or value outside its range: SNX_E_ARG.
+ * Rescore: cand_doc [nq, W] int32 (1 <= W <= 1024; -1 or any id outside [0, nd): unused slot), k in [1, W].  Every
+ * candidate is scored with the full s(q, d) of the exact index (the ascending-term fmaf chain: bit-equal to what
+ * snx_sparse_search and snx_sparse_pair_scores return); the candidates with s > 0 are ranked in search order (score
+ * descending, ties lowest doc id first), a doc id repeated within a row counts once, the top k go to out_doc /
+ * out_score [nq, k], unused slots doc -1, score 0.  target [nq] (or NULL): out_tscore = s(q, target), out_rank = the
+ * target's 1-based position in the output, 0 when absent (the SEISMIC search's conventions).  No workspace.
+ * Two-phase search is a composition, not an entry point:
+ *   Q_high = the kept entries of every query row under a prune (default SNX_PRUNE_MAX_RATIO 0.4);
+ *   W = min(floor(k * expansion_rate), max_window_size), computed by the caller in float64, k <= W <= 1024 (the
+ *       reference's settings at retrieval size 10: W = 50);
+ *   phase 1: C = the out_doc of snx_sparse_search over the Q_high rows with k = W;
+ *   phase 2: snx_sparse_rescore of C with the full query rows.
+ * Deviation from OpenSearch: Lucene's rescorer adds the low-token partial sum to the phase-1 score; here a window doc
+ * gets the exact single-chain s(q, d).  The two are the same number up to fp32 rounding, and this form keeps the rule
+ * that every returned score is the exact index's, bit for bit.  Consequences: the output is exactly the top k of C
+ * under the exact score; a prune that keeps everything (max_ratio 0) makes the result snx_sparse_search's bit for bit,
+ * for any W >= k (there out_rank is the position in the output, 0 below k); a doc that matches only dropped query terms
+ * is never found, whatever W -- a property of the method, not of this implementation. */
+#define SNX_PRUNE_MAX_RATIO 0
+#define SNX_PRUNE_ABS_VALUE 1
+#define SNX_PRUNE_TOP_K 2
+#define SNX_PRUNE_ALPHA_MASS 3
+size_t snx_sparse_prune_workspace_bytes(int32_t prune_type, int32_t n, int32_t max_row_nnz);
+int snx_sparse_prune_rows(const int64_t* ptr, const float* w, int32_t n, int64_t nnz, int32_t max_row_nnz,
+                          int32_t prune_type, float value, uint8_t* keep, int32_t* kept_cnt, void* workspace,
+                          size_t ws_bytes, hipStream_t stream);
+int snx_sparse_rescore(const int64_t* q_ptr, const int32_t* q_term, const float* q_w, int32_t nq,
+                       const int32_t* cand_doc, int32_t W, const int64_t* doc_ptr, const int32_t* doc_term,
+                       const float* doc_w, int32_t nd, const int32_t* target, int32_t k, int32_t* out_doc,
+                       float* out_score, int32_t* out_rank, float* out_tscore, hipStream_t stream);
+
 /* ---- SPLADELossV33 (ref:src/model/losses.py:183-297) ------------------------------------- */
 /* dims [host] = {B, Bp, k, V, label_off, bf16_mm}: q [B,V], p [Bp,V] (Bp > B: all-gathered
  * positives for cross-GPU in-batch negatives, own rows start at label_off), n [B*k,V]; bf16_mm=1

@@ -105,6 +105,9 @@ SIGNATURES = {
     "snx_seismic_build_summaries": (I32, [P, P, P, I32, I32, P, P, I64, F32, P, P, P, P, P, SZ, P]),
     "snx_seismic_search": (I32, [P, P, P, I32, I32, P, P, P, P, P, P, P, P, P, I32, I32, P, I32, I32, F32, P, P, P, P, P,
                                  P]),
+    "snx_sparse_prune_workspace_bytes": (SZ, [I32, I32, I32]),
+    "snx_sparse_prune_rows": (I32, [P, P, I32, I64, I32, I32, F32, P, P, P, SZ, P]),
+    "snx_sparse_rescore": (I32, [P, P, P, I32, P, I32, P, P, P, I32, P, I32, P, P, P, P, P]),
     "snx_version": (I32, []),
     "snx_prof_enable": (I32, [I32]),
     "snx_prof_num_classes": (I32, []),

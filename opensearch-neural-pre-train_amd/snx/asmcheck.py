@@ -38,6 +38,8 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     # the same rule for the SEISMIC build and search (query, top-k keys and sort buffers stay in LDS, not scratch)
     "seismic.hip": ("sz_prune_kernel", "sz_centroid_kernel", "sz_assign_kernel", "sz_fill_kernel", "sz_summary_kernel",
                     "sz_search_kernel"),
+    # and for pruning and the two-phase rescore (sort buffers, the staged query and the window keys stay in LDS)
+    "two_phase.hip": ("tp_prune_kernel", "tp_rescore_kernel"),
 }
 
 # Kernels held to the global-load / vmcnt rule: nothing may touch a load's destination before a vmcnt wait that retires it.

@@ -11,7 +11,9 @@ then ranked score descending, ties lowest doc id first.  Results are bit-reprodu
 ``chunk_docs``.  ``search_band`` and ``pair_scores`` serve the hard-negative miner (src.train.mining): a rank band of the
 ADMISSIBLE docs (score > 0, not in the query's exclusion row, score < the query's ceiling) and s(q, d) of given pairs,
 bit-equal to the ranked values.  ``SeismicIndex`` is the approximate SEISMIC search over a built ``SparseIndex``
-(csrc/seismic.hip, include/snx.h "SEISMIC")."""
+(csrc/seismic.hip, include/snx.h "SEISMIC").  ``prune_rows``, ``SparseIndex.pruned``, ``SparseIndex.rescore`` and
+``SparseIndex.search_two_phase`` are the prune rules and the two-phase search of the reference's ``rank_features``
+serving path (csrc/two_phase.hip, include/snx.h "pruning and two-phase search")."""
 from __future__ import annotations
 
 import time
@@ -51,6 +53,79 @@ def pack_rows(vals: torch.Tensor, ids: torch.Tensor, cnt: torch.Tensor, V: int, 
     if not bool(ok):
         raise ValueError(f"{name}: every row needs 0 <= cnt <= cap and cnt distinct ids in [0, {V}) with finite weights > 0")
     return c, skey[live].to(torch.int32), w[live].contiguous()
+
+
+PRUNE_TYPES = {"max_ratio": 0, "abs_value": 1, "top_k": 2, "alpha_mass": 3}       # SNX_PRUNE_* of include/snx.h
+WINDOW_MAX = 1024                      # rescore window cap
+
+
+def _prune_code(prune_type, value) -> Tuple[int, float]:
+    """(SNX_PRUNE_* code, the value as fp32) of a prune setting, validated as the C interface validates it."""
+    if prune_type not in PRUNE_TYPES:
+        raise ValueError(f"prune_type must be one of {list(PRUNE_TYPES)}, not {prune_type!r}")
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{prune_type}: the value must be a number")
+    with np.errstate(over="ignore"):
+        v = float(np.float32(value))
+    ok = {"max_ratio": 0.0 <= v <= 1.0, "abs_value": v >= 0.0, "alpha_mass": 0.0 < v <= 1.0,
+          "top_k": v >= 1.0 and v == float(value) and v == np.floor(v)}[prune_type]
+    if not ok:                                                # NaN fails every comparison
+        raise ValueError(f"{prune_type}: value {value!r} is outside its range (max_ratio [0, 1], abs_value >= 0, "
+                         "top_k an integer >= 1, alpha_mass (0, 1])")
+    return PRUNE_TYPES[prune_type], v
+
+
+def _keep_flags(cnt: torch.Tensor, weights: torch.Tensor, code: int, value: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """snx_sparse_prune_rows over CSR rows -> (keep bool [nnz], kept counts int64 [n])."""
+    dev, n, nnz = weights.device, int(cnt.numel()), int(weights.numel())
+    ptr = torch.zeros(n + 1, dtype=torch.long, device=dev)
+    torch.cumsum(cnt, 0, out=ptr[1:])
+    keep = torch.empty(nnz, dtype=torch.uint8, device=dev)
+    kept = torch.empty(n, dtype=torch.int32, device=dev)
+    longest = int(cnt.max()) if n else 0
+    ws_bytes = int(fn("snx_sparse_prune_workspace_bytes")(code, n, longest))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(fn("snx_sparse_prune_rows")(_p(ptr), _p(weights), n, nnz, longest, code, value, _p(keep), _p(kept),
+                                           _p(ws), ws_bytes, _stream()), "snx_sparse_prune_rows")
+    return keep.bool(), kept.long()
+
+
+def prune_rows(cnt: torch.Tensor, terms: torch.Tensor, weights: torch.Tensor, prune_type: str, value):
+    """Prune CSR rows (the triple of ``pack_rows``: counts int64 [n], terms int32 ascending within a row, weights fp32
+    > 0, on a GPU) by one of the rules of include/snx.h: ``max_ratio`` r in [0, 1] keeps w >= fp32(r) * w_max,
+    ``abs_value`` a >= 0 keeps w >= fp32(a), ``top_k`` n >= 1 keeps the n heaviest (ties: lowest term), ``alpha_mass``
+    alpha in (0, 1] keeps the shortest heaviest-first prefix holding the alpha share of the row's weight mass.
+    -> (kept, rest): two CSR triples of the same layout, rows in place (a row may be empty in either)."""
+    code, v = _prune_code(prune_type, value)
+    if not (isinstance(cnt, torch.Tensor) and isinstance(terms, torch.Tensor) and isinstance(weights, torch.Tensor)) or \
+            cnt.dtype != torch.long or terms.dtype != torch.int32 or weights.dtype != torch.float32 or cnt.dim() != 1 or \
+            terms.dim() != 1 or weights.shape != terms.shape:
+        raise ValueError("prune_rows: counts int64 [n], terms int32 [nnz], weights fp32 [nnz]")
+    if not (cnt.device == terms.device == weights.device) or cnt.device.type != "cuda":
+        raise ValueError("prune_rows: the rows must live on one GPU")
+    if cnt.numel() >= 2 ** 31 or bool((cnt < 0).any()) or int(cnt.sum()) != terms.numel() or \
+            (cnt.numel() and int(cnt.max()) >= 2 ** 31):
+        raise ValueError("prune_rows: counts must be >= 0 and sum to nnz")
+    cnt, terms, weights = cnt.contiguous(), terms.contiguous(), weights.contiguous()
+    keep, kept = _keep_flags(cnt, weights, code, v)
+    return (kept, terms[keep], weights[keep]), (cnt - kept, terms[~keep], weights[~keep])
+
+
+def two_phase_window(k: int, expansion_rate: float, max_window_size: int) -> int:
+    """W = min(floor(k * expansion_rate), max_window_size) in float64 (include/snx.h); k <= W <= 1024 or ValueError --
+    the window is never clamped silently."""
+    k = int(k)
+    if not 1 <= k <= K_MAX:
+        raise ValueError(f"two-phase search: k must be in [1, {K_MAX}]")
+    rate, cap = float(expansion_rate), float(max_window_size)
+    if not rate > 0 or not np.isfinite(rate) or not cap >= 1:
+        raise ValueError("two-phase search: expansion_rate must be finite and > 0, max_window_size >= 1")
+    W = int(min(np.floor(np.float64(k) * np.float64(rate)), np.floor(cap)))
+    if not k <= W <= WINDOW_MAX:
+        raise ValueError(f"two-phase search: the window min(floor({k} * {rate}), {max_window_size}) = {W} must lie in "
+                         f"[k, {WINDOW_MAX}]")
+    return W
 
 
 def exclusion_csr(exclude, nq: int, nd: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -190,24 +265,33 @@ class SparseIndex:
             raise ValueError(f"SparseIndex.search: chunk_docs must be in [0, {CHUNK_MAX}] (0: default)")
         if q_vals.device != self.device:
             raise ValueError(f"SparseIndex.search: tensors must be on {self.device}")
-        qc, q_term, q_w = pack_rows(q_vals, q_ids, q_cnt, self.V, "queries")
-        nq, dev, nd = int(qc.numel()), self.device, self.num_docs
-        q_ptr = torch.zeros(nq + 1, dtype=torch.long, device=dev)
-        torch.cumsum(qc, 0, out=q_ptr[1:])
-        tgt = None
-        if targets is not None:
-            if not isinstance(targets, torch.Tensor) or targets.device != dev or targets.dim() != 1 or \
-                    targets.numel() != nq or targets.dtype not in (torch.int32, torch.int64):
-                raise ValueError(f"SparseIndex.search: targets must be an int tensor [{nq}] on {dev}")
-            if nq and not bool(((targets >= 0) & (targets < nd)).all()):
-                raise ValueError(f"SparseIndex.search: targets must be doc ids in [0, {nd})")
-            tgt = targets.to(torch.int32).contiguous()
+        nq, q_ptr, q_term, q_w = self._queries(q_vals, q_ids, q_cnt, "search")
+        tgt = self._targets(targets, nq, "search")
+        return self._search_csr(q_ptr, q_term, q_w, nq, k, tgt, chunk_docs)
+
+    def _targets(self, targets, nq: int, who: str) -> Optional[torch.Tensor]:
+        if targets is None:
+            return None
+        dev, nd = self.device, self.num_docs
+        if not isinstance(targets, torch.Tensor) or targets.device != dev or targets.dim() != 1 or \
+                targets.numel() != nq or targets.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"SparseIndex.{who}: targets must be an int tensor [{nq}] on {dev}")
+        if nq and not bool(((targets >= 0) & (targets < nd)).all()):
+            raise ValueError(f"SparseIndex.{who}: targets must be doc ids in [0, {nd})")
+        return targets.to(torch.int32).contiguous()
+
+    def _search_csr(self, q_ptr, q_term, q_w, nq: int, k: int, tgt, chunk_docs: int, query_slice: int = 0):
+        """snx_sparse_search over query rows already in CSR form, in slices of the workspace budget (or of
+        ``query_slice`` queries); the slicing changes no bit."""
+        dev, nd = self.device, self.num_docs
         scores = torch.empty((nq, k), dtype=torch.float32, device=dev)
         docs = torch.empty((nq, k), dtype=torch.int32, device=dev)
         rank = torch.empty(nq, dtype=torch.int32, device=dev) if tgt is not None else None
         tscore = torch.empty(nq, dtype=torch.float32, device=dev) if tgt is not None else None
         per_q = max(1, int(fn("snx_sparse_search_workspace_bytes")(1, nd, k, chunk_docs)))
         step = max(1, min(nq, _SEARCH_WS_BUDGET // per_q))
+        if query_slice:
+            step = min(step, int(query_slice))
         with torch.cuda.device(dev):
             for s in range(0, nq, step):
                 m = min(step, nq - s)
@@ -295,6 +379,91 @@ class SparseIndex:
                     lo, hi, chunk_docs, _p(docs[s:]), _p(scores[s:]), _p(found[s:]), _p(ws), ws_bytes, _stream()),
                     "snx_sparse_search_band")
         return scores, docs, found
+
+    def pruned(self, prune_type: str, value) -> "SparseIndex":
+        """Ingest-time pruning: a new built index over this index's doc rows pruned by ``prune_rows``' rule, with the
+        same doc ids (a doc pruned to nothing stays as an empty row).  This index is left untouched."""
+        code, v = _prune_code(prune_type, value)
+        if not self.built:
+            raise RuntimeError("SparseIndex.pruned: call build() first")
+        cnt = self.doc_ptr[1:] - self.doc_ptr[:-1]
+        keep, kept = _keep_flags(cnt, self.doc_w, code, v)
+        out = SparseIndex(self.V, self.device)
+        out._cnt, out._term, out._w = [kept], [self.doc_term[keep]], [self.doc_w[keep]]
+        out.num_docs = self.num_docs
+        return out.build()
+
+    def rescore(self, q_vals: torch.Tensor, q_ids: torch.Tensor, q_cnt: torch.Tensor, cand_docs: torch.Tensor, k: int,
+                targets: Optional[torch.Tensor] = None, query_slice: int = 0
+                ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """``cand_docs`` int32 [nq, W] (1 <= W <= 1024; -1: unused slot): every candidate scored with the exact s(q, d),
+        the top ``k`` <= W of those with s > 0 in search order, a repeated doc counted once -> (scores [nq, k] fp32,
+        docs [nq, k] int32 (unused: 0 / -1), rank [nq] int32 | None (the target's 1-based position in the output, 0 =
+        absent), tscore [nq] fp32 | None).  ``query_slice``: queries per launch (0: all); it changes no bit."""
+        nq, q_ptr, q_term, q_w = self._queries(q_vals, q_ids, q_cnt, "rescore")
+        dev = self.device
+        if not isinstance(cand_docs, torch.Tensor) or cand_docs.device != dev or cand_docs.dtype != torch.int32 or \
+                cand_docs.dim() != 2 or cand_docs.shape[0] != nq:
+            raise ValueError(f"SparseIndex.rescore: cand_docs must be int32 [{nq}, W] on {dev}")
+        W, k = int(cand_docs.shape[1]), int(k)
+        if not 1 <= W <= WINDOW_MAX or not 1 <= k <= W:
+            raise ValueError(f"SparseIndex.rescore: need 1 <= k <= W <= {WINDOW_MAX}")
+        tgt = self._targets(targets, nq, "rescore")
+        return self._rescore_csr(q_ptr, q_term, q_w, nq, cand_docs.contiguous(), k, tgt, query_slice)
+
+    def _rescore_csr(self, q_ptr, q_term, q_w, nq: int, cand: torch.Tensor, k: int, tgt, query_slice: int = 0):
+        dev, W = self.device, int(cand.shape[1])
+        if isinstance(query_slice, bool) or int(query_slice) < 0:
+            raise ValueError("SparseIndex: query_slice must be >= 0 (0: default)")
+        scores = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        docs = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        rank = torch.empty(nq, dtype=torch.int32, device=dev) if tgt is not None else None
+        tscore = torch.empty(nq, dtype=torch.float32, device=dev) if tgt is not None else None
+        step = int(query_slice) or max(nq, 1)
+        with torch.cuda.device(dev):
+            for s in range(0, nq, step):
+                m = min(step, nq - s)
+                check(fn("snx_sparse_rescore")(
+                    _p(q_ptr[s:]), _p(q_term), _p(q_w), m, _p(cand[s:]), W, _p(self.doc_ptr), _p(self.doc_term),
+                    _p(self.doc_w), self.num_docs, _p(None if tgt is None else tgt[s:]), k, _p(docs[s:]),
+                    _p(scores[s:]), _p(None if rank is None else rank[s:]),
+                    _p(None if tscore is None else tscore[s:]), _stream()), "snx_sparse_rescore")
+        return scores, docs, rank, tscore
+
+    def search_two_phase(self, q_vals: torch.Tensor, q_ids: torch.Tensor, q_cnt: torch.Tensor, k: int,
+                         prune_type: str = "max_ratio", prune_value=0.4, expansion_rate: float = 5.0,
+                         max_window_size: int = 10000, targets: Optional[torch.Tensor] = None, chunk_docs: int = 0,
+                         query_slice: int = 0):
+        """Two-phase search (include/snx.h; OpenSearch's neural_sparse_two_phase_processor, defaults the reference's
+        ref:benchmark/index_manager.py:197-238): phase 1 is ``search`` with only the query entries kept by the prune
+        (Q_high) and k = W = min(floor(k * expansion_rate), max_window_size) -- ValueError unless k <= W <= 1024 --;
+        phase 2 rescores that window with the full query.  Every returned score is the exact s(q, d); a doc that matches
+        only dropped query terms is never found.  -> (scores [nq, k], docs [nq, k], rank | None (position in the output,
+        0 = absent), tscore | None, stats {"postings_high", "postings_all", "window_filled"} -> int64 [nq]: posting-list
+        lengths under the Q_high terms and under all query terms, and the docs phase 1 found).  ``chunk_docs`` and
+        ``query_slice`` change no bit."""
+        code, v = _prune_code(prune_type, prune_value)
+        W = two_phase_window(k, expansion_rate, max_window_size)
+        k, chunk_docs = int(k), int(chunk_docs)
+        if not 0 <= chunk_docs <= CHUNK_MAX:
+            raise ValueError(f"SparseIndex.search_two_phase: chunk_docs must be in [0, {CHUNK_MAX}] (0: default)")
+        if isinstance(query_slice, bool) or int(query_slice) < 0:
+            raise ValueError("SparseIndex.search_two_phase: query_slice must be >= 0 (0: default)")
+        nq, q_ptr, q_term, q_w = self._queries(q_vals, q_ids, q_cnt, "search_two_phase")
+        tgt = self._targets(targets, nq, "search_two_phase")
+        dev = self.device
+        qc = q_ptr[1:] - q_ptr[:-1]
+        keep, high_cnt = _keep_flags(qc, q_w, code, v)
+        h_ptr = torch.zeros(nq + 1, dtype=torch.long, device=dev)
+        torch.cumsum(high_cnt, 0, out=h_ptr[1:])
+        _, window, _, _ = self._search_csr(h_ptr, q_term[keep], q_w[keep], nq, W, None, chunk_docs, query_slice)
+        scores, docs, rank, tscore = self._rescore_csr(q_ptr, q_term, q_w, nq, window, k, tgt, query_slice)
+        lens = (self.term_ptr[1:] - self.term_ptr[:-1])[q_term.long()]
+        row = torch.repeat_interleave(torch.arange(nq, device=dev), qc)
+        zero = torch.zeros(nq, dtype=torch.long, device=dev)
+        stats = {"postings_high": zero.index_add(0, row[keep], lens[keep]), "postings_all": zero.index_add(0, row, lens),
+                 "window_filled": (window >= 0).sum(1)}
+        return scores, docs, rank, tscore, stats
 
 
 SEISMIC_Q_MAX = 1024                   # query nnz cap of the SEISMIC search (the query lives in LDS)

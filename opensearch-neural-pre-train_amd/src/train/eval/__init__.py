@@ -94,15 +94,18 @@ def metrics_from_ranks(ranks: Sequence[int], k: int = RETRIEVAL_SIZE) -> Dict[st
 class MidTrainingEvaluator:
     """Retrieval quality of the model being trained, on a fixed corpus built from ``val_file`` (a triplet JSONL read by
     ``load_training_data``, or ``synthetic:N[:k]``).  ``evaluate(model)`` -> recall@1/5/10, mrr@10, ndcg@10,
-    num_queries, num_docs, avg_nnz_q, avg_nnz_d.  Queries keep their top 64 terms, docs every term that survives the
-    inference encoder's filter (ref:benchmark/indexer.py:59); retrieval size 10."""
+    num_queries, num_docs, avg_nnz_q, avg_nnz_d; with ``seismic`` / ``two_phase`` (parameter dicts, see seismic_params /
+    two_phase_params) also the seismic_* / two_phase_* keys of seismic_eval / two_phase_eval.  Queries keep their top
+    64 terms, docs every term that survives the inference encoder's filter (ref:benchmark/indexer.py:59); retrieval
+    size 10."""
 
     def __init__(self, tokenizer, val_file: str, max_queries: int = 200, max_docs: int = 1000, device: str = "cuda",
                  query_max_length: int = 64, doc_max_length: int = 256, batch_size: int = 64,
-                 seismic: Optional[dict] = None):
+                 seismic: Optional[dict] = None, two_phase: Optional[dict] = None):
         from benchmark.encoders import special_token_ids
         from src.train.data import load_training_data
         self.seismic = seismic_params(seismic) if seismic is not None else None
+        self.two_phase = two_phase_params(two_phase) if two_phase is not None else None
         self.tokenizer = tokenizer
         self.device = torch.device(device)
         self.query_max_length, self.doc_max_length = int(query_max_length), int(doc_max_length)
@@ -172,8 +175,13 @@ class MidTrainingEvaluator:
             avg_q = float(queries[2].double().mean())
             if self.seismic is not None:
                 extra = seismic_eval(index, queries, targets, docs, self.seismic)[0]
-        elif self.seismic is not None:
-            extra = {f"seismic_{k}": 0.0 for k in METRIC_KEYS + ("overlap@5", "postings_frac")}
+            if self.two_phase is not None:
+                extra.update(two_phase_eval(index, queries, targets, docs, self.two_phase)[0])
+        else:
+            if self.seismic is not None:
+                extra = {f"seismic_{k}": 0.0 for k in METRIC_KEYS + ("overlap@5", "postings_frac")}
+            if self.two_phase is not None:
+                extra.update({f"two_phase_{k}": 0.0 for k in METRIC_KEYS + ("overlap@5", "postings_frac")})
         avg_d = index.nnz / index.num_docs if index is not None and index.num_docs else 0.0
         self.last_ranks = ranks
         out = metrics_from_ranks(ranks)
@@ -239,5 +247,44 @@ def seismic_eval(index, queries, targets, exact_docs, params: dict, six=None):
     total = int(cut_postings(index, queries, p["top_n"]).sum())
     out["seismic_postings_frac"] = float(stats["postings_scored"].sum()) / total if total else 0.0
     info = {"index": six, "build_s": six.build_seconds, "search_s": search_s}
+    info.update({k: float(v.double().mean()) for k, v in stats.items()})
+    return out, info
+
+
+# OpenSearch's neural_sparse_two_phase_processor as the reference configures it (ref:benchmark/index_manager.py:197-238)
+TWO_PHASE_DEFAULTS = {"prune_type": "max_ratio", "prune_value": 0.4, "expansion_rate": 5.0, "max_window_size": 10000}
+
+
+def two_phase_params(p: dict) -> dict:
+    """The four two-phase parameters (snx.retrieval.SparseIndex.search_two_phase), missing ones at their defaults."""
+    bad = set(p) - set(TWO_PHASE_DEFAULTS)
+    if bad:
+        raise ValueError(f"two_phase: unknown parameter(s) {sorted(bad)}; known: {list(TWO_PHASE_DEFAULTS)}")
+    return {**TWO_PHASE_DEFAULTS, **p}
+
+
+def two_phase_eval(index, queries, targets, exact_docs, params: dict, doc_prune=None):
+    """Two-phase search over the exact index's corpus -> (metrics, info).  metrics: two_phase_recall@1/5/10,
+    two_phase_mrr@10, two_phase_ndcg@10 (the two-phase ranks), two_phase_overlap@5 (against ``exact_docs``),
+    two_phase_postings_frac (posting-list lengths under the Q_high terms over those under all query terms, summed over
+    queries).  ``doc_prune`` = (prune_type, value): the search runs on ``index.pruned(...)`` (ingest-time pruning) and
+    doc_postings_frac = pruned nnz / nnz is added.  info: the index searched, search_s and the counters' means."""
+    import time
+    p = two_phase_params(params)
+    out = {}
+    searched = index
+    if doc_prune is not None:
+        searched = index.pruned(*doc_prune)
+        out["doc_postings_frac"] = searched.nnz / index.nnz if index.nnz else 0.0
+    torch.cuda.synchronize(index.device)
+    t0 = time.perf_counter()
+    _, docs, rank, _, stats = searched.search_two_phase(*queries, RETRIEVAL_SIZE, targets=targets, **p)
+    torch.cuda.synchronize(index.device)
+    search_s = time.perf_counter() - t0
+    out.update({f"two_phase_{k}": v for k, v in metrics_from_ranks(rank.cpu().tolist()).items()})
+    out["two_phase_overlap@5"] = overlap_at(docs.cpu().numpy(), exact_docs.cpu().numpy(), 5)
+    total = int(stats["postings_all"].sum())
+    out["two_phase_postings_frac"] = float(stats["postings_high"].sum()) / total if total else 0.0
+    info = {"index": searched, "search_s": search_s}
     info.update({k: float(v.double().mean()) for k, v in stats.items()})
     return out, info

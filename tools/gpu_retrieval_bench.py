@@ -5,6 +5,7 @@ csrc/retrieval.hip) on synthetic Zipf-skewed data.
     python tools/gpu_retrieval_bench.py [--sizes 1000x200,100000x10000,1000000x10000] [--out result.json]
     python tools/gpu_retrieval_bench.py --band [--sizes 1000000x10000] [--miner-records 4000]
     python tools/gpu_retrieval_bench.py --seismic [--sizes 1000000x10000]
+    python tools/gpu_retrieval_bench.py --two-phase [--sizes 100000x10000,1000000x10000]
 
 Docs draw 128 terms (with replacement, duplicates dropped: ~99 distinct) from a Zipf(1.0) law over V = 50000 with
 weights uniform in [0.1, 3); queries draw 64 the same way (~53 distinct).  Retrieval size 10 with a target per query
@@ -19,7 +20,12 @@ normalisation (exclusion_csr, on the device) is timed on its own.  Then one time
 --seismic: SeismicIndex (csrc/seismic.hip) at the reference's index defaults (n_postings 300, cluster_ratio 0.1,
 summary_prune_ratio 0.4) on the same data: build seconds, then per heap_factor in {0.5, 1, 2} at top_n 10 and k = 10
 the queries/s against exact search, the mean overlap@10 with the exact top 10 and the fraction of the Q_cut terms'
-postings that were scored."""
+postings that were scored.
+
+--two-phase: SparseIndex.search_two_phase (csrc/two_phase.hip) at the reference's setting (max_ratio 0.4, expansion_rate
+5, max_window_size 10000; k = 10, so a window of 50) against plain search on the same data, alternating, median of 5 after
+a warm-up: queries/s, the mean overlap@10 with the exact top 10 and the share of the query terms' postings under the kept
+terms; then the prune kernel alone over the whole doc CSR per prune type, and the build time of pruned("max_ratio", 0.1)."""
 import argparse
 import json
 import os
@@ -178,6 +184,46 @@ def seismic_case(nd, nq, dev, k=10, top_n=10):
     return row
 
 
+def two_phase_case(nd, nq, dev, k=10, reps=5):
+    from statistics import median
+    from snx.retrieval import PRUNE_TYPES, SparseIndex, _keep_flags
+    from src.train.eval import overlap_at
+    gen = torch.Generator().manual_seed(nd + nq)
+    probs = 1.0 / torch.arange(1, V + 1, dtype=torch.float64)
+    probs /= probs.sum()
+    idx = SparseIndex(V, dev)
+    for s in range(0, nd, 100_000):
+        idx.add(*zipf_rows(min(100_000, nd - s), 128, gen, dev, probs))
+    idx.build()
+    q = zipf_rows(nq, 64, gen, dev, probs)
+    idx.search(*q, k)                                          # warm-up of both paths at the timed shapes
+    idx.search_two_phase(*q, k)
+    t_exact, t_two = [], []
+    for _ in range(reps):                                      # alternating: both see the same machine state
+        t_exact.append(sync_time(lambda: idx.search(*q, k))[0])
+        t_two.append(sync_time(lambda: idx.search_two_phase(*q, k))[0])
+    _, exact_docs, _, _ = idx.search(*q, k)
+    _, docs, _, _, stats = idx.search_two_phase(*q, k)
+    te, tt = median(t_exact), median(t_two)
+    row = {"docs": nd, "queries": nq, "k": k, "prune": ["max_ratio", 0.4], "expansion_rate": 5.0, "window": 50,
+           "exact_search_s": te, "exact_search_s_all": t_exact, "two_phase_s": tt, "two_phase_s_all": t_two,
+           "exact_queries_per_s": nq / te, "two_phase_queries_per_s": nq / tt, "two_phase_over_exact": tt / te,
+           "overlap@10": overlap_at(docs.cpu().numpy(), exact_docs.cpu().numpy(), k),
+           "postings_frac": float(stats["postings_high"].sum()) / max(1, int(stats["postings_all"].sum())),
+           "window_filled_mean": float(stats["window_filled"].double().mean()), "prune_kernel": {}}
+    cnt = idx.doc_ptr[1:] - idx.doc_ptr[:-1]
+    for name, value in (("max_ratio", 0.1), ("abs_value", 0.5), ("top_k", 64.0), ("alpha_mass", 0.9)):
+        _keep_flags(cnt, idx.doc_w, PRUNE_TYPES[name], value)
+        ts = [sync_time(lambda: _keep_flags(cnt, idx.doc_w, PRUNE_TYPES[name], value))[0] for _ in range(reps)]
+        _, kept = _keep_flags(cnt, idx.doc_w, PRUNE_TYPES[name], value)
+        row["prune_kernel"][name] = {"value": value, "seconds": median(ts), "entries_per_s": idx.nnz / median(ts),
+                                     "kept_frac": int(kept.sum()) / idx.nnz}
+    idx.pruned("max_ratio", 0.1)
+    ts = [sync_time(lambda: idx.pruned("max_ratio", 0.1))[0] for _ in range(3)]
+    row["pruned_build_s"] = median(ts)
+    return row
+
+
 def miner_case(n_records, dev):
     import tempfile
     from src.model.splade_modern import SPLADEModernBERT
@@ -207,9 +253,20 @@ def main():
     ap.add_argument("--band", action="store_true", help="search_band vs search, then an end-to-end miner run")
     ap.add_argument("--miner-records", type=int, default=4000)
     ap.add_argument("--seismic", action="store_true", help="SeismicIndex build and search against exact search")
+    ap.add_argument("--two-phase", action="store_true", help="search_two_phase, the prune kernel and pruned() vs search")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     rows = []
+    if args.two_phase:
+        sizes = args.sizes if args.sizes != ap.get_default("sizes") else "100000x10000,1000000x10000"
+        for s in sizes.split(","):
+            nd, nq = (int(x) for x in s.split("x"))
+            rows.append(two_phase_case(nd, nq, dev))
+            print(json.dumps(rows[-1]), flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump({"device": torch.cuda.get_device_name(0), "rows": rows}, f, indent=1)
+        return
     if args.seismic:
         sizes = args.sizes if args.sizes != ap.get_default("sizes") else "1000000x10000"
         for s in sizes.split(","):
