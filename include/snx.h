@@ -334,6 +334,61 @@ int snx_sparse_rescore(const int64_t* q_ptr, const int32_t* q_term, const float*
                        const float* doc_w, int32_t nd, const int32_t* target, int32_t k, int32_t* out_doc,
                        float* out_score, int32_t* out_rank, float* out_tscore, hipStream_t stream);
 
+/* ---- BM25 baseline and rank fusion (csrc/hybrid.hip): the lexical baseline the reference quotes every number against
+ * (ref:huggingface/v33/README.md:189-233) and the fusion of ranked lists from several retrievers
+ * (ref:benchmark/score_fusion.py, ref:benchmark/hybrid_searcher.py:501-522, ref:scripts/run_7way_benchmark.py).
+ * Term counts: input_ids, attention_mask [n, S] int64 (what the tokenizer yields), allowed [V] uint8.  A position COUNTS
+ * when its mask is non-zero, 0 <= id < V and allowed[id] != 0.  Per row: out_term [n, S] int32 = the distinct counted ids
+ * strictly ascending, out_tf [n, S] int32 = their occurrence counts (unused slots: term -1, tf 0), out_cnt [n] = distinct
+ * ids, out_len [n] = counted positions = sum of tf.  Integer exact.  1 <= S <= snx_term_counts_max_len() = 8192 (the
+ * model's position limit; the row is sorted in LDS), beyond: SNX_E_SHAPE.
+ * Document frequencies: df [V] int32, df[t] += the number of entries of term [nnz] equal to t -- over CSR rows, whose
+ * terms are distinct within a row, the number of rows that contain t.  Integer atomics: exact, order-independent; it
+ * ADDS, so batches accumulate (the caller zeroes df once).  Entries outside [0, V) are skipped.
+ * BM25 weights, elementwise over a CSR (ptr [n+1] int64, term / tf [nnz] int32, dl [n] int32 = out_len), in float64 with
+ * every operation rounded on its own (no fma contraction):
+ *   norm_d = k1 * ((1.0 - b) + b * ((double)dl_d / avgdl))
+ *   w(t,d) = (float)( idf[t] * ((double)tf / ((double)tf + norm_d)) )
+ * idf [V] float64 is the caller's: numpy.log1p((N - df + 0.5) / (df + 0.5)) evaluated on the host (the `bm25` smoothing
+ * of ref:tools/idf-compute/src/main.rs:202, Lucene's form; libm logs are not bit-reproducible across implementations and
+ * the table has V entries); avgdl = the exact integer sum of dl over N, in float64, by the caller.  k1 >= 0 (default
+ * 1.2), b in [0, 1] (default 0.75), avgdl > 0 when there are entries; otherwise SNX_E_ARG.  The BM25 score of a query is
+ * s(q, d) of the exact index over these weights with query weights fp32(count): every guarantee of that section holds.
+ * Deviations from OpenSearch: like Lucene >= 8 the (k1 + 1) factor is dropped; Lucene quantises the document length to
+ * one byte, this form does not; the analyzer is the model's own tokenizer, not `nori`; lengths are taken after the
+ * caller's truncation (the evaluator's doc_max_length); OpenSearch's numbers are not claimed.
+ * Rank fusion: docs [L, nq, R] int32, scores [L, nq, R] fp32 (NULL allowed unless SNX_FUSE_LINEAR), 1 <= L <= 4, 1 <= R
+ * <= 1024.  List l of query q = the leading entries of docs[l, q, :] up to the first negative doc id; the rank of an entry
+ * is its position + 1.  Precondition: doc ids distinct within a list (search outputs are); a violation reads and writes
+ * nothing out of bounds, its result is otherwise unspecified.  max_rank = max(len_0 + 1, ..., len_{L-1} + 1, 100) per
+ * query; a doc absent from a list takes this rank.  All arithmetic is float64, every operation rounded on its own, in
+ * the reference's operand order -- fused scores equal ref:benchmark/score_fusion.py and the triple RRF of
+ * ref:benchmark/hybrid_searcher.py:501-522 bit for bit.  params [host] float64:
+ *   SNX_FUSE_RRF           {k}: left fold over the lists, in list order, of 1.0 / (k + rank_l);
+ *   SNX_FUSE_WEIGHTED_RRF  {k, w_0 .. w_{L-1}}: the same fold of w_l / (k + rank_l);
+ *   SNX_FUSE_LINEAR        {alpha}, L == 2: per list min-max over its own scores widened to double, (s - min) / (max -
+ *                          min), 1.0 for every entry when all scores are equal, 0.0 for an absent doc; fused = alpha * a
+ *                          + (1.0 - alpha) * b (two products, one sum), list 0 weighted by alpha.
+ * k >= 0 finite, w_l finite, alpha in [0, 1]; a violation, L out of range, an unknown method or linear with L != 2:
+ * SNX_E_ARG.  R or top_k (1 <= top_k <= 4096) out of range: SNX_E_SHAPE.  The union of the lists is ordered by fused
+ * score descending, ties lowest doc id first (the reference leaves ties to Python's set iteration; this rule is the
+ * project's, as everywhere); the first top_k go to out_doc [nq, top_k] int32 / out_score [nq, top_k] float64, unused
+ * slots doc -1, score 0; out_total [nq] = the size of the union (the reference's total_hits); target [nq] (or NULL):
+ * out_rank = the target's 1-based position in the whole fused order, 0 when it is in no list.  No workspace. */
+#define SNX_FUSE_RRF 0
+#define SNX_FUSE_WEIGHTED_RRF 1
+#define SNX_FUSE_LINEAR 2
+int32_t snx_term_counts_max_len(void);
+int snx_term_counts(const int64_t* input_ids, const int64_t* attention_mask, const uint8_t* allowed, int32_t n, int32_t S,
+                    int32_t V, int32_t* out_term, int32_t* out_tf, int32_t* out_cnt, int32_t* out_len,
+                    hipStream_t stream);
+int snx_bm25_doc_freq(const int32_t* term, int64_t nnz, int32_t V, int32_t* df, hipStream_t stream);
+int snx_bm25_weights(const int64_t* ptr, const int32_t* term, const int32_t* tf, const int32_t* dl, const double* idf,
+                     int32_t n, int64_t nnz, int32_t V, double avgdl, double k1, double b, float* w, hipStream_t stream);
+int snx_fuse_ranked(const int32_t* docs, const float* scores, int32_t L, int32_t nq, int32_t R, int32_t method,
+                    const double* params /*[host]*/, const int32_t* target, int32_t top_k, int32_t* out_doc,
+                    double* out_score, int32_t* out_total, int32_t* out_rank, hipStream_t stream);
+
 /* ---- SPLADELossV33 (ref:src/model/losses.py:183-297) ------------------------------------- */
 /* dims [host] = {B, Bp, k, V, label_off, bf16_mm}: q [B,V], p [Bp,V] (Bp > B: all-gathered
  * positives for cross-GPU in-batch negatives, own rows start at label_off), n [B*k,V]; bf16_mm=1

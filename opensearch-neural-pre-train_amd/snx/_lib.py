@@ -17,6 +17,7 @@ P = C.c_void_p
 I32 = C.c_int32
 I64 = C.c_int64
 F32 = C.c_float
+F64 = C.c_double
 SZ = C.c_size_t
 
 # name -> (restype, argtypes); mirrors include/snx.h one to one
@@ -108,6 +109,11 @@ SIGNATURES = {
     "snx_sparse_prune_workspace_bytes": (SZ, [I32, I32, I32]),
     "snx_sparse_prune_rows": (I32, [P, P, I32, I64, I32, I32, F32, P, P, P, SZ, P]),
     "snx_sparse_rescore": (I32, [P, P, P, I32, P, I32, P, P, P, I32, P, I32, P, P, P, P, P]),
+    "snx_term_counts_max_len": (I32, []),
+    "snx_term_counts": (I32, [P, P, P, I32, I32, I32, P, P, P, P, P]),
+    "snx_bm25_doc_freq": (I32, [P, I64, I32, P, P]),
+    "snx_bm25_weights": (I32, [P, P, P, P, P, I32, I64, I32, F64, F64, F64, P, P]),
+    "snx_fuse_ranked": (I32, [P, P, I32, I32, I32, I32, P, P, I32, P, P, P, P, P]),
     "snx_version": (I32, []),
     "snx_prof_enable": (I32, [I32]),
     "snx_prof_num_classes": (I32, []),

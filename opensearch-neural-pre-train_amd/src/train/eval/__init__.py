@@ -94,18 +94,22 @@ def metrics_from_ranks(ranks: Sequence[int], k: int = RETRIEVAL_SIZE) -> Dict[st
 class MidTrainingEvaluator:
     """Retrieval quality of the model being trained, on a fixed corpus built from ``val_file`` (a triplet JSONL read by
     ``load_training_data``, or ``synthetic:N[:k]``).  ``evaluate(model)`` -> recall@1/5/10, mrr@10, ndcg@10,
-    num_queries, num_docs, avg_nnz_q, avg_nnz_d; with ``seismic`` / ``two_phase`` (parameter dicts, see seismic_params /
-    two_phase_params) also the seismic_* / two_phase_* keys of seismic_eval / two_phase_eval.  Queries keep their top
+    num_queries, num_docs, avg_nnz_q, avg_nnz_d; with ``seismic`` / ``two_phase`` / ``hybrid`` (parameter dicts, see
+    seismic_params / two_phase_params / hybrid_params) also the seismic_* / two_phase_* keys of seismic_eval /
+    two_phase_eval and the bm25_* / hybrid_* / *_p keys of hybrid_eval (BM25 under the same tokenizer, BM25 + sparse
+    fusion, paired t-tests).  Queries keep their top
     64 terms, docs every term that survives the inference encoder's filter (ref:benchmark/indexer.py:59); retrieval
     size 10."""
 
     def __init__(self, tokenizer, val_file: str, max_queries: int = 200, max_docs: int = 1000, device: str = "cuda",
                  query_max_length: int = 64, doc_max_length: int = 256, batch_size: int = 64,
-                 seismic: Optional[dict] = None, two_phase: Optional[dict] = None):
+                 seismic: Optional[dict] = None, two_phase: Optional[dict] = None, hybrid: Optional[dict] = None):
         from benchmark.encoders import special_token_ids
         from src.train.data import load_training_data
         self.seismic = seismic_params(seismic) if seismic is not None else None
         self.two_phase = two_phase_params(two_phase) if two_phase is not None else None
+        self.hybrid = hybrid_params(hybrid) if hybrid is not None else None
+        self._bm25 = None                    # (Bm25Index, query rows): the corpus is fixed, built once per evaluator
         self.tokenizer = tokenizer
         self.device = torch.device(device)
         self.query_max_length, self.doc_max_length = int(query_max_length), int(doc_max_length)
@@ -177,11 +181,17 @@ class MidTrainingEvaluator:
                 extra = seismic_eval(index, queries, targets, docs, self.seismic)[0]
             if self.two_phase is not None:
                 extra.update(two_phase_eval(index, queries, targets, docs, self.two_phase)[0])
+            if self.hybrid is not None:
+                if self._bm25 is None:
+                    self._bm25 = bm25_index(self, index.V, self.hybrid)
+                extra.update(hybrid_eval(index, queries, targets, *self._bm25, self.hybrid)[0])
         else:
             if self.seismic is not None:
                 extra = {f"seismic_{k}": 0.0 for k in METRIC_KEYS + ("overlap@5", "postings_frac")}
             if self.two_phase is not None:
                 extra.update({f"two_phase_{k}": 0.0 for k in METRIC_KEYS + ("overlap@5", "postings_frac")})
+            if self.hybrid is not None:
+                extra.update({k: 0.0 for k in HYBRID_KEYS})
         avg_d = index.nnz / index.num_docs if index is not None and index.num_docs else 0.0
         self.last_ranks = ranks
         out = metrics_from_ranks(ranks)
@@ -288,3 +298,135 @@ def two_phase_eval(index, queries, targets, exact_docs, params: dict, doc_prune=
     info = {"index": searched, "search_s": search_s}
     info.update({k: float(v.double().mean()) for k, v in stats.items()})
     return out, info
+
+
+# ---- BM25 baseline, hybrid fusion and the significance test (ref:benchmark/hybrid_searcher.py, ref:benchmark/metrics.py)
+# fusion method, RRF constant, linear weight and per-retriever depth: ref:benchmark/hybrid_searcher.py:621-631; k1 / b:
+# OpenSearch's BM25 defaults
+HYBRID_DEFAULTS = {"method": "rrf", "k": 60, "alpha": 0.4, "retrieval_k": 100, "k1": 1.2, "b": 0.75}
+HYBRID_KEYS = tuple(f"bm25_{k}" for k in METRIC_KEYS) + tuple(f"hybrid_{k}" for k in METRIC_KEYS) + \
+    ("hybrid_total", "sparse_vs_bm25_p", "hybrid_vs_sparse_p")
+
+
+def hybrid_params(p: dict) -> dict:
+    """The six hybrid parameters (snx.retrieval.Bm25Index / fuse_ranked), missing ones at their defaults."""
+    bad = set(p) - set(HYBRID_DEFAULTS)
+    if bad:
+        raise ValueError(f"hybrid: unknown parameter(s) {sorted(bad)}; known: {list(HYBRID_DEFAULTS)}")
+    out = {**HYBRID_DEFAULTS, **p}
+    if out["method"] not in ("rrf", "weighted_rrf", "linear"):
+        raise ValueError(f"hybrid: unknown method {out['method']!r}")
+    if not 1 <= int(out["retrieval_k"]) <= 1024:
+        raise ValueError("hybrid: retrieval_k must be in [1, 1024]")
+    return out
+
+
+def fusion_kwargs(p: dict) -> dict:
+    """The parameters ``fuse_ranked`` takes for ``p['method']``."""
+    return {"alpha": p["alpha"]} if p["method"] == "linear" else {"k": p["k"]}
+
+
+def _betacf(a: float, b: float, x: float) -> float:
+    """Continued fraction of the incomplete beta function (modified Lentz), float64."""
+    tiny = 1e-300
+    qab, qap, qam = a + b, a + 1.0, a - 1.0
+    c, d = 1.0, 1.0 - qab * x / qap
+    d = 1.0 / (d if abs(d) > tiny else tiny)
+    h = d
+    for m in range(1, 10000):
+        m2 = 2 * m
+        aa = m * (b - m) * x / ((qam + m2) * (a + m2))
+        d = 1.0 + aa * d
+        d = 1.0 / (d if abs(d) > tiny else tiny)
+        c = 1.0 + aa / c
+        c = c if abs(c) > tiny else tiny
+        h *= d * c
+        aa = -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2))
+        d = 1.0 + aa * d
+        d = 1.0 / (d if abs(d) > tiny else tiny)
+        c = 1.0 + aa / c
+        c = c if abs(c) > tiny else tiny
+        delta = d * c
+        h *= delta
+        if abs(delta - 1.0) < 1e-16:
+            break
+    return h
+
+
+def betainc(a: float, b: float, x: float) -> float:
+    """Regularised incomplete beta function I_x(a, b), float64 (continued fraction on the side where it converges fast)."""
+    import math
+    if x <= 0.0:
+        return 0.0
+    if x >= 1.0:
+        return 1.0
+    front = math.exp(math.lgamma(a + b) - math.lgamma(a) - math.lgamma(b) + a * math.log(x) + b * math.log1p(-x))
+    if x < (a + 1.0) / (a + b + 2.0):
+        return front * _betacf(a, b, x) / a
+    return 1.0 - front * _betacf(b, a, 1.0 - x) / b
+
+
+def paired_t_test(ranks_a: Sequence[int], ranks_b: Sequence[int], k: int = RETRIEVAL_SIZE) -> Dict[str, float]:
+    """ref:benchmark/metrics.py:149-177 over target ranks: reciprocal hit ranks (a rank of 0 or above ``k`` is not
+    retrieved and counts 0.0), then the paired two-sided t-test -> statistic, p_value, significant (p < 0.05).  The
+    Student-t tail is I_{df / (df + t^2)}(df / 2, 1 / 2) with ``betainc`` above (no scipy).  Fewer than two pairs or all
+    differences equal to 0: nan, not significant -- what the reference returns."""
+    if len(ranks_a) != len(ranks_b):
+        raise ValueError("Result lists must have same length for paired test")
+    rr = [np.array([1.0 / int(r) if 1 <= int(r) <= k else 0.0 for r in ranks], np.float64) for ranks in (ranks_a, ranks_b)]
+    d = rr[0] - rr[1]
+    n = len(d)
+    t, p = float("nan"), float("nan")
+    if n >= 2:
+        mean = float(np.mean(d))
+        var = float(np.sum((d - np.mean(d)) ** 2) / (n - 1))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = float(np.float64(mean) / np.sqrt(np.float64(var) / n))
+        if np.isfinite(t):
+            df = float(n - 1)
+            p = betainc(0.5 * df, 0.5, df / (df + t * t))
+        elif not np.isnan(t):
+            p = 0.0
+    return {"statistic": t, "p_value": p, "significant": bool(p < 0.05)}
+
+
+def bm25_index(ev: "MidTrainingEvaluator", V: int, params: dict):
+    """The BM25 index over the evaluator's docs and the queries' rows (vals, ids, cnt), tokenized as the encoder sees them
+    (the evaluator's truncation and vocabulary filter).  Independent of the model."""
+    from snx.retrieval import Bm25Index
+    bm = Bm25Index(V, ev.device, k1=params["k1"], b=params["b"])
+    allowed = ev._allowed_mask(V)
+
+    def batches(texts, max_length):
+        for s in range(0, len(texts), ev.batch_size):
+            enc = ev.tokenizer(texts[s:s + ev.batch_size], padding=True, truncation=True, max_length=max_length,
+                               return_tensors="pt")
+            yield enc["input_ids"].to(ev.device), enc["attention_mask"].to(ev.device)
+    for ids, mask in batches(ev.corpus.docs, ev.doc_max_length):
+        bm.add_tokens(ids, mask, allowed)
+    bm.build()
+    rows = [bm.query_rows(ids, mask, allowed) for ids, mask in batches(ev.corpus.queries, ev.query_max_length)]
+    cap = max(r[0].shape[1] for r in rows)
+    pad = lambda x: torch.nn.functional.pad(x, (0, cap - x.shape[1]))            # noqa: E731
+    return bm, (torch.cat([pad(r[0]) for r in rows]), torch.cat([pad(r[1]) for r in rows]), torch.cat([r[2] for r in rows]))
+
+
+def hybrid_eval(index, queries, targets, bm, bm_queries, params: dict):
+    """BM25 and BM25 + sparse fusion over the exact index's corpus -> (metrics, info).  metrics: bm25_* and hybrid_* (the
+    five METRIC_KEYS each: BM25's ranks; the ranks after fusing the two retrievers' top ``retrieval_k`` lists, list 0 =
+    BM25, returning RETRIEVAL_SIZE), hybrid_total (mean union size), sparse_vs_bm25_p and hybrid_vs_sparse_p (paired
+    t-tests over reciprocal hit ranks).  info: the rank lists and the two searches' (docs, scores) lists."""
+    from snx.retrieval import fuse_ranked
+    p = hybrid_params(params)
+    rk = int(p["retrieval_k"])
+    b_s, b_d, b_rank, _ = bm.index.search(*bm_queries, rk, targets=targets)
+    s_s, s_d, s_rank, _ = index.search(*queries, rk, targets=targets)
+    _, _, h_rank, total = fuse_ranked([(b_d, b_s), (s_d, s_s)], p["method"], RETRIEVAL_SIZE, targets=targets,
+                                      **fusion_kwargs(p))
+    ranks = {"bm25": b_rank.cpu().tolist(), "sparse": s_rank.cpu().tolist(), "hybrid": h_rank.cpu().tolist()}
+    out = {f"bm25_{k}": v for k, v in metrics_from_ranks(ranks["bm25"]).items()}
+    out.update({f"hybrid_{k}": v for k, v in metrics_from_ranks(ranks["hybrid"]).items()})
+    out["hybrid_total"] = float(total.double().mean()) if total.numel() else 0.0
+    out["sparse_vs_bm25_p"] = paired_t_test(ranks["sparse"], ranks["bm25"])["p_value"]
+    out["hybrid_vs_sparse_p"] = paired_t_test(ranks["hybrid"], ranks["sparse"])["p_value"]
+    return out, {"ranks": ranks, "bm25": (b_d, b_s), "sparse": (s_d, s_s)}

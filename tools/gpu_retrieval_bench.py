@@ -6,6 +6,7 @@ csrc/retrieval.hip) on synthetic Zipf-skewed data.
     python tools/gpu_retrieval_bench.py --band [--sizes 1000000x10000] [--miner-records 4000]
     python tools/gpu_retrieval_bench.py --seismic [--sizes 1000000x10000]
     python tools/gpu_retrieval_bench.py --two-phase [--sizes 100000x10000,1000000x10000]
+    python tools/gpu_retrieval_bench.py --hybrid [--sizes 100000x10000,1000000x10000]
 
 Docs draw 128 terms (with replacement, duplicates dropped: ~99 distinct) from a Zipf(1.0) law over V = 50000 with
 weights uniform in [0.1, 3); queries draw 64 the same way (~53 distinct).  Retrieval size 10 with a target per query
@@ -25,7 +26,13 @@ postings that were scored.
 --two-phase: SparseIndex.search_two_phase (csrc/two_phase.hip) at the reference's setting (max_ratio 0.4, expansion_rate
 5, max_window_size 10000; k = 10, so a window of 50) against plain search on the same data, alternating, median of 5 after
 a warm-up: queries/s, the mean overlap@10 with the exact top 10 and the share of the query terms' postings under the kept
-terms; then the prune kernel alone over the whole doc CSR per prune type, and the build time of pruned("max_ratio", 0.1)."""
+terms; then the prune kernel alone over the whole doc CSR per prune type, and the build time of pruned("max_ratio", 0.1).
+
+--hybrid: the BM25 baseline and rank fusion (csrc/hybrid.hip).  Token rows of 128 (docs) and 16 (queries) positions are
+drawn with replacement from the same Zipf law, every id allowed: Bm25Index.add_tokens + build in docs/s (term counts, df,
+weights, the SparseIndex build), BM25 search_tokens at k = 100 in queries/s, then fuse_ranked (RRF, top 10 with targets)
+over L = 2 and 3 random lists of R = 100 and 1000 doc ids in queries/s, medians of 5 after a warm-up; as a comparison
+row the same rule as plain Python dicts on the host over the first 200 queries."""
 import argparse
 import json
 import os
@@ -224,6 +231,70 @@ def two_phase_case(nd, nq, dev, k=10, reps=5):
     return row
 
 
+def dict_rrf(docs, k=60.0, top_k=10):
+    """ref:benchmark/score_fusion.py's rule over one query's lists of doc ids, as Python dicts (ties: lowest id first)."""
+    ranks = [{d: i + 1 for i, d in enumerate(lst)} for lst in docs]
+    max_rank = max([len(lst) + 1 for lst in docs] + [100])
+    fused = {}
+    for d in set().union(*ranks):
+        acc = None
+        for r in ranks:
+            term = 1.0 / (k + r.get(d, max_rank))
+            acc = term if acc is None else acc + term
+        fused[d] = acc
+    return sorted(fused.items(), key=lambda x: (-x[1], x[0]))[:top_k]
+
+
+def hybrid_case(nd, nq, dev, reps=5, host_queries=200):
+    from statistics import median
+    from snx.retrieval import Bm25Index, fuse_ranked
+    gen = torch.Generator().manual_seed(nd + nq)
+    probs = 1.0 / torch.arange(1, V + 1, dtype=torch.float64)
+    probs /= probs.sum()
+    allowed = torch.ones(V, dtype=torch.uint8, device=dev)
+
+    def tokens(n, m):
+        ids = torch.multinomial(probs, n * m, replacement=True, generator=gen).view(n, m).to(dev)
+        return ids, torch.ones_like(ids)
+    batches = [tokens(min(100_000, nd - s), 128) for s in range(0, nd, 100_000)]
+    qi, qm = tokens(nq, 16)
+
+    def build():
+        bm = Bm25Index(V, dev)
+        for ids, mask in batches:
+            bm.add_tokens(ids, mask, allowed)
+        return bm.build()
+    build()                                                    # warm-up
+    ts = [sync_time(build)[0] for _ in range(3)]
+    bm = build()
+    bm.search_tokens(qi, qm, allowed, 100)
+    tq = [sync_time(lambda: bm.search_tokens(qi, qm, allowed, 100))[0] for _ in range(reps)]
+    row = {"docs": nd, "queries": nq, "doc_tokens": 128, "query_tokens": 16, "bm25_build_s": median(ts),
+           "bm25_build_docs_per_s": nd / median(ts), "bm25_nnz": bm.index.nnz, "avgdl": bm.avgdl,
+           "bm25_search_s": median(tq), "bm25_search_queries_per_s": nq / median(tq), "fuse": []}
+    targets = torch.randint(0, nd, (nq,), generator=gen).to(torch.int32).to(dev)
+    for R in (100, 1000):
+        pool = min(nd, 4 * R)                                  # lists drawn from a pool of 4 R docs: heavy overlap
+        lists = []
+        for _ in range(3):
+            d = torch.argsort(torch.rand(nq, pool, generator=gen), 1)[:, :R].to(torch.int32).to(dev)
+            sc = torch.sort(torch.rand(nq, R, generator=gen), 1, descending=True)[0].to(dev)
+            lists.append((d, sc))
+        for L in (2, 3):
+            fuse_ranked(lists[:L], "rrf", 10, targets=targets)
+            tf = [sync_time(lambda: fuse_ranked(lists[:L], "rrf", 10, targets=targets))[0] for _ in range(reps)]
+            _, gd, _, _ = fuse_ranked(lists[:L], "rrf", 10, targets=targets)
+            m = min(nq, host_queries)
+            host = [lst[0][:m].cpu().tolist() for lst in lists[:L]]
+            t0 = time.perf_counter()
+            hd = [[d for d, _ in dict_rrf([h[q] for h in host])] for q in range(m)]
+            th = time.perf_counter() - t0
+            row["fuse"].append({"R": R, "L": L, "seconds": median(tf), "queries_per_s": nq / median(tf),
+                                "python_dict_queries": m, "python_dict_queries_per_s": m / th,
+                                "same_docs_as_python": gd[:m].cpu().tolist() == hd})
+    return row
+
+
 def miner_case(n_records, dev):
     import tempfile
     from src.model.splade_modern import SPLADEModernBERT
@@ -254,9 +325,20 @@ def main():
     ap.add_argument("--miner-records", type=int, default=4000)
     ap.add_argument("--seismic", action="store_true", help="SeismicIndex build and search against exact search")
     ap.add_argument("--two-phase", action="store_true", help="search_two_phase, the prune kernel and pruned() vs search")
+    ap.add_argument("--hybrid", action="store_true", help="Bm25Index build and search, fuse_ranked vs Python dicts")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     rows = []
+    if args.hybrid:
+        sizes = args.sizes if args.sizes != ap.get_default("sizes") else "100000x10000,1000000x10000"
+        for s in sizes.split(","):
+            nd, nq = (int(x) for x in s.split("x"))
+            rows.append(hybrid_case(nd, nq, dev))
+            print(json.dumps(rows[-1]), flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump({"device": torch.cuda.get_device_name(0), "rows": rows}, f, indent=1)
+        return
     if args.two_phase:
         sizes = args.sizes if args.sizes != ap.get_default("sizes") else "100000x10000,1000000x10000"
         for s in sizes.split(","):
