@@ -389,6 +389,53 @@ int snx_fuse_ranked(const int32_t* docs, const float* scores, int32_t L, int32_t
                     const double* params /*[host]*/, const int32_t* target, int32_t top_k, int32_t* out_doc,
                     double* out_score, int32_t* out_total, int32_t* out_rank, hipStream_t stream);
 
+/* ---- relevance judgments (csrc/qrels.hip): scoring against qrels with several relevant docs per query, the protocol of
+ * the reference's headline numbers (ref:benchmark/hf_data_loader.py:21 query_relevant_docs; ref:benchmark/hf_runner.py:
+ * 191-215: a hit is the first retrieved doc that is in the query's relevant SET; ref:benchmark/metrics.py:180-215: the
+ * bootstrap interval).  A relevance row set is a CSR pair: rel_ptr [nq+1] int64, rel_doc [n] int32, every row ascending
+ * and distinct (a violation reads and writes nothing out of bounds, its result is otherwise unspecified).  Ids outside
+ * [0, nd) are skipped, never read through.
+ * First relevant: query CSR, doc CSR and term-major index as for snx_sparse_search, s(q,d) the score of the "exact sparse
+ * retrieval" section.  Per query the BEST RELEVANT DOC d* is the in-range row member with the highest s(q,d) > 0, ties
+ * lowest doc id.  out_doc [nq] = d* (-1: none), out_score [nq] = s(q,d*) (0 when none), bit-equal to what
+ * snx_sparse_search ranks; out_rank [nq] = 1 + #{d: s_d > s*} + #{d < d*: s_d == s*} over the WHOLE corpus, 0 when no
+ * relevant doc scores > 0 -- the minimum over the row of snx_sparse_search's single-target out_rank; out_nrel [nq] = row
+ * members in range.  One score accumulation per query whatever the row length; stream-ordered, no host synchronisation.
+ * chunk_docs as for the search (0: default; <= 32768): it changes no bit.
+ * workspace: snx_sparse_first_relevant_workspace_bytes(nq, nd, chunk_docs) bytes.
+ * Ranked relevance: docs [nq, R] int32, 1 <= R <= 4096, any ranked lists (search, rescore, SEISMIC, fusion outputs); a list
+ * ends at its first negative id, the position of an entry is its index + 1, an entry is RELEVANT when it lies in [0, nd)
+ * and in the query's row (binary search); a doc id repeated in a list counts at every position.  cutoffs [host] int32,
+ * 1 <= ncut <= 8 entries, strictly ascending, each in [1, R]; disc [R] float64 is the caller's device table, disc[p-1] the
+ * discount of position p: the Python layer fills it with 1.0 / numpy.log2(p + 1) -- the kernel computes no logarithm (libm
+ * is not bit-reproducible; snx_bm25_weights treats idf the same way).  out_first [nq] = position of the first relevant
+ * entry of the whole list, 0 if none; out_hits [nq, ncut] int32 = relevant entries at positions <= cutoffs[j];
+ * out_dcg [nq, ncut] float64 = the left fold from +0.0, in position order, of disc[p-1] over the relevant positions
+ * p <= cutoffs[j], every add rounded on its own.  One wave per list: the launch geometry changes no bit.  Cutoffs out of
+ * range or not ascending, ncut out of range: SNX_E_ARG; R out of range: SNX_E_SHAPE.  No workspace.
+ * Bootstrap means: values [n, M] float64 (1 <= M <= 16), idx [nboot, n] int32 (resample b draws rows idx[b, 0..n));
+ * out [nboot, M] float64, out[b,m] = (sum over i of values[idx[b,i], m]) / (double)n.  THE SUMMATION ORDER IS PART OF THE
+ * ABI: i = 0 .. n-1 is cut into segments of SNX_BOOTSTRAP_SEGMENT = 64 consecutive positions (the last may be shorter);
+ * inside a segment the terms are added in ascending i, a left fold starting from +0.0; the segment sums are then added in
+ * ascending segment order, again a left fold from +0.0; one IEEE division by (double)n ends it.  Every add is rounded on
+ * its own.  Bit-identical from run to run and independent of the launch shape.  Precondition: every index lies in [0, n).
+ * The kernel does not read through an index outside the range (the term is left out), but it cannot report it without a
+ * host synchronisation: the caller checks the indices where they are drawn (snx.retrieval.bootstrap_means does, and
+ * raises the SNX_E_ARG error).  n < 1, M out of range, nboot < 0: SNX_E_SHAPE.  No workspace. */
+#define SNX_BOOTSTRAP_SEGMENT 64
+size_t snx_sparse_first_relevant_workspace_bytes(int32_t nq, int32_t nd, int32_t chunk_docs);
+int snx_sparse_first_relevant(const int64_t* q_ptr, const int32_t* q_term, const float* q_w, int32_t nq,
+                              const int64_t* term_ptr, const int32_t* post_doc, const float* post_w,
+                              const int64_t* doc_ptr, const int32_t* doc_term, const float* doc_w, int32_t nd, int32_t V,
+                              const int64_t* rel_ptr, const int32_t* rel_doc, int32_t chunk_docs, int32_t* out_doc,
+                              float* out_score, int32_t* out_rank, int32_t* out_nrel, void* workspace, size_t ws_bytes,
+                              hipStream_t stream);
+int snx_ranked_relevance(const int32_t* docs, int32_t nq, int32_t R, int32_t nd, const int64_t* rel_ptr,
+                         const int32_t* rel_doc, const int32_t* cutoffs /*[host]*/, int32_t ncut, const double* disc,
+                         int32_t* out_first, int32_t* out_hits, double* out_dcg, hipStream_t stream);
+int snx_bootstrap_means(const double* values, int32_t n, int32_t M, const int32_t* idx, int32_t nboot, double* out,
+                        hipStream_t stream);
+
 /* ---- SPLADELossV33 (ref:src/model/losses.py:183-297) ------------------------------------- */
 /* dims [host] = {B, Bp, k, V, label_off, bf16_mm}: q [B,V], p [Bp,V] (Bp > B: all-gathered
  * positives for cross-GPU in-batch negatives, own rows start at label_off), n [B*k,V]; bf16_mm=1

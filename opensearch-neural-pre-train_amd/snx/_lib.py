@@ -114,6 +114,10 @@ SIGNATURES = {
     "snx_bm25_doc_freq": (I32, [P, I64, I32, P, P]),
     "snx_bm25_weights": (I32, [P, P, P, P, P, I32, I64, I32, F64, F64, F64, P, P]),
     "snx_fuse_ranked": (I32, [P, P, I32, I32, I32, I32, P, P, I32, P, P, P, P, P]),
+    "snx_sparse_first_relevant_workspace_bytes": (SZ, [I32, I32, I32]),
+    "snx_sparse_first_relevant": (I32, [P, P, P, I32, P, P, P, P, P, P, I32, I32, P, P, I32, P, P, P, P, P, SZ, P]),
+    "snx_ranked_relevance": (I32, [P, I32, I32, I32, P, P, P, I32, P, P, P, P, P]),
+    "snx_bootstrap_means": (I32, [P, I32, I32, P, I32, P, P]),
     "snx_version": (I32, []),
     "snx_prof_enable": (I32, [I32]),
     "snx_prof_num_classes": (I32, []),

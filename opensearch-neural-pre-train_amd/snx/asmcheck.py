@@ -40,6 +40,9 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
                     "sz_search_kernel"),
     # and for pruning and the two-phase rescore (sort buffers, the staged query and the window keys stay in LDS)
     "two_phase.hip": ("tp_prune_kernel", "tp_rescore_kernel"),
+    # and for the relevance-judgment kernels that keep state in LDS (the score chunk; the bootstrap's per-thread column
+    # sums, 16 float64 accumulators that must stay in registers); qr_ranked_kernel holds no LDS and is not listed
+    "qrels.hip": ("qr_best_kernel", "qr_count_kernel", "qr_boot_kernel"),
 }
 
 # Kernels held to the global-load / vmcnt rule: nothing may touch a load's destination before a vmcnt wait that retires it.

@@ -15,7 +15,9 @@ bit-equal to the ranked values.  ``SeismicIndex`` is the approximate SEISMIC sea
 ``SparseIndex.search_two_phase`` are the prune rules and the two-phase search of the reference's ``rank_features``
 serving path (csrc/two_phase.hip, include/snx.h "pruning and two-phase search").  ``term_counts``, ``Bm25Index`` and
 ``fuse_ranked`` are the lexical BM25 baseline under the model's tokenizer and the rank fusion of the reference's hybrid
-searchers (csrc/hybrid.hip, include/snx.h "BM25 baseline and rank fusion")."""
+searchers (csrc/hybrid.hip, include/snx.h "BM25 baseline and rank fusion").  ``relevance_csr``,
+``SparseIndex.first_relevant``, ``ranked_relevance`` and ``bootstrap_means`` score any of these searches against qrels with
+several relevant docs per query (csrc/qrels.hip, include/snx.h "relevance judgments")."""
 from __future__ import annotations
 
 import time
@@ -467,6 +469,37 @@ class SparseIndex:
                  "window_filled": (window >= 0).sum(1)}
         return scores, docs, rank, tscore, stats
 
+    def first_relevant(self, q_vals: torch.Tensor, q_ids: torch.Tensor, q_cnt: torch.Tensor, relevant, chunk_docs: int = 0
+                           ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The best relevant doc of every query and its rank in the WHOLE corpus (snx_sparse_first_relevant): ``relevant``
+        as ``relevance_csr`` takes it.  -> (doc int32 [nq]: the row member with the highest s(q, d) > 0, ties lowest id, -1 =
+        none; score fp32 [nq]: bit-equal to the ranked value; rank int32 [nq]: 1 + the docs in front of it under the
+        search's order, 0 = no relevant doc scores -- the minimum over the row of ``search(targets=d)``'s rank, at the cost of
+        one scoring pass; nrel int32 [nq]: row members in [0, num_docs)).  ``chunk_docs`` changes no bit."""
+        chunk_docs = int(chunk_docs)
+        if not 0 <= chunk_docs <= CHUNK_MAX:
+            raise ValueError(f"SparseIndex.first_relevant: chunk_docs must be in [0, {CHUNK_MAX}] (0: default)")
+        nq, q_ptr, q_term, q_w = self._queries(q_vals, q_ids, q_cnt, "first_relevant")
+        dev, nd = self.device, self.num_docs
+        rel_ptr, rel_doc = relevance_csr(relevant, nq, nd, dev)
+        doc = torch.empty(nq, dtype=torch.int32, device=dev)
+        score = torch.empty(nq, dtype=torch.float32, device=dev)
+        rank = torch.empty(nq, dtype=torch.int32, device=dev)
+        nrel = torch.empty(nq, dtype=torch.int32, device=dev)
+        chunk = chunk_docs or 16384
+        step = max(1, _FIRST_RELEVANT_BLOCKS // max(1, -(-nd // chunk)))
+        with torch.cuda.device(dev):
+            for s in range(0, nq, step):
+                m = min(step, nq - s)
+                ws_bytes = int(fn("snx_sparse_first_relevant_workspace_bytes")(m, nd, chunk_docs))
+                ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+                check(fn("snx_sparse_first_relevant")(
+                    _p(q_ptr[s:]), _p(q_term), _p(q_w), m, _p(self.term_ptr), _p(self.post_doc), _p(self.post_w),
+                    _p(self.doc_ptr), _p(self.doc_term), _p(self.doc_w), nd, self.V, _p(rel_ptr[s:]), _p(rel_doc),
+                    chunk_docs, _p(doc[s:]), _p(score[s:]), _p(rank[s:]), _p(nrel[s:]), _p(ws), ws_bytes, _stream()),
+                    "snx_sparse_first_relevant")
+        return doc, score, rank, nrel
+
 
 SEISMIC_Q_MAX = 1024                   # query nnz cap of the SEISMIC search (the query lives in LDS)
 _SEISMIC_QUERY_SLICE = 1 << 20         # queries per search launch (one workgroup each)
@@ -853,3 +886,145 @@ def fuse_ranked(lists, method: str, top_k: int, targets: Optional[torch.Tensor] 
                                     C.cast(host, C.c_void_p), _p(tgt), top_k, _p(out_d), _p(out_s), _p(total), _p(rank),
                                     _stream()), "snx_fuse_ranked")
     return out_s, out_d, rank, total
+
+
+# ------------------------------------------------------------------------------------------------ relevance judgments
+RANKED_R_MAX = 4096
+CUTOFFS_MAX = 8
+BOOTSTRAP_M_MAX = 16
+BOOTSTRAP_SEGMENT = 64                 # SNX_BOOTSTRAP_SEGMENT of include/snx.h: part of the summation order
+_FIRST_RELEVANT_BLOCKS = 1 << 21       # (query, chunk) workgroups per launch: larger query sets go in slices
+
+
+def relevance_csr(relevant, nq: int, nd: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Relevance rows (qrels) -> (ptr int64 [nq+1], docs int32) on ``device``, every row sorted ascending and
+    deduplicated.  ``relevant`` takes the two forms of ``exclusion_csr``: a list of ``nq`` per-query doc-id lists, or a
+    CSR pair, the tuple (ptr [nq+1], docs) of int tensors whose ptr starts at 0, does not decrease and ends at len(docs).
+    Unlike an exclusion row a relevance row may name ids outside [0, nd) (a judged doc that is not in the corpus): they
+    stay in the row and the kernels skip them (include/snx.h "relevance judgments").  Ids must fit in int32."""
+    nq, nd = int(nq), int(nd)
+    if nq < 0 or nd < 0:
+        raise ValueError("relevance rows: nq and nd must be >= 0")
+    if isinstance(relevant, tuple) and len(relevant) == 2 and all(isinstance(x, torch.Tensor) for x in relevant):
+        ptr, docs = relevant
+        if ptr.dim() != 1 or docs.dim() != 1 or ptr.numel() != nq + 1 or ptr.is_floating_point() or \
+                docs.is_floating_point():
+            raise ValueError(f"relevance rows: a CSR pair needs int tensors ptr [{nq + 1}] and docs [n]")
+        ptr, docs = ptr.to(docs.device, torch.long), docs.long()
+        if int(ptr[0]) != 0 or int(ptr[-1]) != docs.numel() or bool((ptr[1:] < ptr[:-1]).any()):
+            raise ValueError("relevance rows: ptr must start at 0, not decrease and end at len(docs)")
+        row = torch.repeat_interleave(torch.arange(nq, dtype=torch.long, device=docs.device), ptr[1:] - ptr[:-1])
+    else:
+        if isinstance(relevant, (str, bytes)) or not hasattr(relevant, "__iter__"):
+            raise ValueError("relevance rows: per-query doc-id lists or a CSR pair of tensors")
+        rows = [list(r) for r in relevant]
+        if len(rows) != nq:
+            raise ValueError(f"relevance rows: {len(rows)} rows for {nq} queries")
+        flat = [d for r in rows for d in r]
+        if any(isinstance(d, bool) or not isinstance(d, (int, np.integer)) for d in flat):
+            raise ValueError("relevance rows: doc ids must be ints")
+        docs = torch.tensor([int(d) for d in flat], dtype=torch.long)
+        row = torch.repeat_interleave(torch.arange(nq, dtype=torch.long),
+                                      torch.tensor([len(r) for r in rows], dtype=torch.long))
+    if docs.numel() and not bool(((docs >= -2 ** 31) & (docs < 2 ** 31)).all()):
+        raise ValueError("relevance rows: doc ids must fit in int32")
+    key = torch.unique(row * 2 ** 32 + (docs + 2 ** 31))      # sorted: by row, then doc; duplicates merged
+    r, d = key // 2 ** 32, key % 2 ** 32 - 2 ** 31
+    ptr = torch.zeros(nq + 1, dtype=torch.long, device=key.device)
+    torch.cumsum(torch.bincount(r, minlength=nq), 0, out=ptr[1:])
+    return ptr.to(device), d.to(torch.int32).to(device)
+
+
+def discount_table(R: int) -> np.ndarray:
+    """disc [R] float64 on the host: 1.0 / numpy.log2(p + 1), p = 1 .. R (include/snx.h: the kernel computes no log)."""
+    return 1.0 / np.log2(np.arange(1, int(R) + 1, dtype=np.float64) + 1.0)
+
+
+def ranked_relevance(docs: torch.Tensor, relevant, nd: int, cutoffs=(1, 5, 10)
+                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Ranked lists against relevance rows on the GPU (snx_ranked_relevance).  ``docs`` int32 [nq, R] (R <= 4096; a list
+    ends at its first negative id): the doc output of ``search``, ``search_two_phase``, ``SeismicIndex.search``,
+    ``Bm25Index.search_tokens`` or ``fuse_ranked``; ``relevant`` as ``relevance_csr`` takes it, ``nd`` the corpus size;
+    ``cutoffs``: 1 .. 8 strictly ascending ints in [1, R].  -> (first int32 [nq]: 1-based position of the first relevant
+    entry, 0 = none; hits int32 [nq, ncut]: relevant entries within each cutoff; dcg float64 [nq, ncut]: the left fold in
+    position order of ``discount_table(R)[p - 1]`` over the relevant positions within each cutoff)."""
+    if not isinstance(docs, torch.Tensor) or docs.dim() != 2 or docs.dtype != torch.int32 or docs.device.type != "cuda":
+        raise ValueError("ranked_relevance: docs must be int32 [nq, R] on a GPU")
+    dev, (nq, R) = docs.device, docs.shape
+    if not 1 <= R <= RANKED_R_MAX:
+        raise ValueError(f"ranked_relevance: lists of 1 .. {RANKED_R_MAX} entries")
+    cuts = [c for c in cutoffs]
+    if not 1 <= len(cuts) <= CUTOFFS_MAX or any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) for c in cuts):
+        raise ValueError(f"ranked_relevance: 1 .. {CUTOFFS_MAX} integer cutoffs")
+    cuts = [int(c) for c in cuts]
+    if cuts[0] < 1 or cuts[-1] > R or any(b <= a for a, b in zip(cuts, cuts[1:])):
+        raise ValueError(f"ranked_relevance: cutoffs must ascend strictly within [1, {R}]")
+    rel_ptr, rel_doc = relevance_csr(relevant, int(nq), nd, dev)
+    docs = docs.contiguous()
+    disc = torch.from_numpy(discount_table(R)).to(dev)
+    first = torch.empty(nq, dtype=torch.int32, device=dev)
+    hits = torch.empty((nq, len(cuts)), dtype=torch.int32, device=dev)
+    dcg = torch.empty((nq, len(cuts)), dtype=torch.float64, device=dev)
+    import ctypes as C
+    host = (C.c_int32 * len(cuts))(*cuts)
+    with torch.cuda.device(dev):
+        check(fn("snx_ranked_relevance")(_p(docs), int(nq), int(R), int(nd), _p(rel_ptr), _p(rel_doc),
+                                         C.cast(host, C.c_void_p), len(cuts), _p(disc), _p(first), _p(hits), _p(dcg),
+                                         _stream()), "snx_ranked_relevance")
+    return first, hits, dcg
+
+
+def bootstrap_indices(n: int, n_bootstrap: int = 1000, seed: int = 42) -> np.ndarray:
+    """Resample indices int32 [n_bootstrap, n], drawn on the host as the reference draws them
+    (ref:benchmark/metrics.py:198-204): ``numpy.random.RandomState(seed)``, then one ``randint(0, n, size=n)`` per
+    resample, in order -- the stream of ``numpy.random.seed(seed)`` followed by ``numpy.random.choice(n, size=n,
+    replace=True)`` per resample (tests/test_qrels_host.py holds the two equal over all draws)."""
+    n, n_bootstrap = int(n), int(n_bootstrap)
+    if n < 1 or n >= 2 ** 31 or n_bootstrap < 0:
+        raise ValueError("bootstrap_indices: need 1 <= n < 2^31 and n_bootstrap >= 0")
+    rs = np.random.RandomState(int(seed))
+    out = np.empty((n_bootstrap, n), dtype=np.int32)
+    for b in range(n_bootstrap):
+        out[b] = rs.randint(0, n, size=n)
+    return out
+
+
+def bootstrap_means(values, n_bootstrap: int = 1000, seed: int = 42, device=None, indices=None) -> torch.Tensor:
+    """Bootstrap means on the GPU (snx_bootstrap_means): ``values`` [n] or [n, M] (M <= 16; a tensor or an array, taken as
+    float64) -> float64 [n_bootstrap, M] on the device: out[b, m] = the mean of column m over resample b, summed in the
+    fixed order of include/snx.h (segments of 64 positions, left folds inside and across), bit-identical from run to
+    run.  The resamples are ``bootstrap_indices(n, n_bootstrap, seed)`` unless ``indices`` int [n_bootstrap, n] is
+    given; an index outside [0, n) is an argument error (checked here, where the indices are drawn: the C interface's
+    precondition).  ``device``: where to run (default: the values' GPU, else the current one)."""
+    if isinstance(values, torch.Tensor):
+        if device is None and values.device.type == "cuda":
+            device = values.device
+        v = values.detach().to(torch.float64).cpu().numpy()
+    else:
+        v = np.asarray(values, dtype=np.float64)
+    if v.ndim == 1:
+        v = v[:, None]
+    if v.ndim != 2 or v.shape[0] < 1 or not 1 <= v.shape[1] <= BOOTSTRAP_M_MAX:
+        raise ValueError(f"bootstrap_means: values must be [n] or [n, M] with n >= 1 and M <= {BOOTSTRAP_M_MAX}")
+    n, M = v.shape
+    if indices is None:
+        idx = bootstrap_indices(n, n_bootstrap, seed)
+    else:
+        idx = indices.cpu().numpy() if isinstance(indices, torch.Tensor) else np.asarray(indices)
+        if idx.ndim != 2 or idx.shape[1] != n or idx.dtype.kind not in "iu":
+            raise ValueError(f"bootstrap_means: indices must be an int array [n_bootstrap, {n}]")
+        if idx.size and (idx.min() < 0 or idx.max() >= n):
+            from ._lib import SnxError
+            raise SnxError(f"snx_bootstrap_means failed: SNX_E_ARG (a resample index lies outside [0, {n}))")
+        idx = idx.astype(np.int32)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise ValueError("bootstrap_means: runs on a GPU")
+    nb = int(idx.shape[0])
+    vals = torch.from_numpy(np.ascontiguousarray(v)).to(dev)
+    didx = torch.from_numpy(np.ascontiguousarray(idx)).to(dev)
+    out = torch.empty((nb, M), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(fn("snx_bootstrap_means")(_p(vals), int(n), int(M), _p(didx), nb, _p(out), _stream()),
+              "snx_bootstrap_means")
+    return out

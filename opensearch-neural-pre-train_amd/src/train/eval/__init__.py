@@ -8,7 +8,11 @@ exactly on the GPU.  The metrics are those of ref:benchmark/metrics.py:52-99 ove
 
 Scoring is the plain dot product of the sparse vectors -- SPLADE's own score and that of OpenSearch's ``neural_sparse``
 query -- not the saturation function of the ``rank_feature`` query the reference benchmark's searcher sends
-(ref:benchmark/searchers.py:155-188).  Ties rank the lower doc id first."""
+(ref:benchmark/searchers.py:155-188).  Ties rank the lower doc id first.
+
+``load_benchmark_dir``, ``qrels_metrics`` and ``bootstrap_confidence_interval`` score a benchmark directory with qrels
+(several relevant docs per query) the way the reference's benchmark runner does; the evaluator above keeps its
+single-positive protocol."""
 from __future__ import annotations
 
 import logging
@@ -430,3 +434,159 @@ def hybrid_eval(index, queries, targets, bm, bm_queries, params: dict):
     out["sparse_vs_bm25_p"] = paired_t_test(ranks["sparse"], ranks["bm25"])["p_value"]
     out["hybrid_vs_sparse_p"] = paired_t_test(ranks["hybrid"], ranks["sparse"])["p_value"]
     return out, {"ranks": ranks, "bm25": (b_d, b_s), "sparse": (s_d, s_s)}
+
+
+# ---- benchmarks with qrels: several relevant docs per query (ref:benchmark/hf_data_loader.py, ref:benchmark/hf_runner.py,
+# ref:benchmark/metrics.py:180-215; snx.retrieval "relevance judgments")
+QRELS_CUTOFFS = (1, 5, 10)
+REPORT_KEYS = {"recall@1": "recall_at_1", "recall@5": "recall_at_5", "recall@10": "recall_at_10", "mrr": "mrr",
+               "ndcg@10": "ndcg_at_10"}                      # the key names of ref:benchmark/metrics.py:36-49
+
+
+@dataclass
+class BenchmarkData:
+    query_ids: List[str]
+    queries: List[str]
+    doc_ids: List[str]
+    docs: List[str]
+    titles: List[str]
+    relevant: List[List[int]]   # per query: positions in ``docs`` of its relevant docs, ascending
+    judged: List[int]           # per query: qrels with score > 0, those naming a doc outside the corpus included
+
+
+def load_benchmark_dir(path: str, max_queries: Optional[int] = None) -> BenchmarkData:
+    """A BEIR/MTEB-style directory -- ``corpus.jsonl`` (``_id``, ``text``, optional ``title``), ``queries.jsonl`` (``_id``,
+    ``text``), ``qrels.jsonl`` (``query-id``, ``corpus-id``, ``score``) -- read by the rules of the reference's local
+    loader (ref:benchmark/hf_data_loader.py:401-459): a qrel counts when ``score > 0``; the queries are those with a
+    counting qrel, in order of first appearance in ``qrels.jsonl``; ``max_queries`` (None or 0: all) truncates that
+    order; a corpus ``_id`` seen twice keeps its first position and its last text.  A relevant id that is not in the
+    corpus is kept out of the query's row, but the query stays: it can then only miss."""
+    import json
+    import os
+    doc_pos: Dict[str, int] = {}
+    docs: List[str] = []
+    titles: List[str] = []
+    with open(os.path.join(path, "corpus.jsonl"), encoding="utf-8") as f:
+        for line in f:
+            if not line.strip():
+                continue
+            d = json.loads(line)
+            i = doc_pos.setdefault(d["_id"], len(docs))
+            if i == len(docs):
+                docs.append(d["text"])
+                titles.append(d.get("title", ""))
+            else:
+                docs[i], titles[i] = d["text"], d.get("title", "")
+    text_of: Dict[str, str] = {}
+    with open(os.path.join(path, "queries.jsonl"), encoding="utf-8") as f:
+        for line in f:
+            if line.strip():
+                q = json.loads(line)
+                text_of[q["_id"]] = q["text"]
+    rel: Dict[str, List[str]] = {}
+    with open(os.path.join(path, "qrels.jsonl"), encoding="utf-8") as f:
+        for line in f:
+            if line.strip():
+                r = json.loads(line)
+                if r["score"] > 0:
+                    rel.setdefault(r["query-id"], []).append(r["corpus-id"])
+    qids = list(rel)
+    if max_queries:
+        qids = qids[:max_queries]
+    unknown = [q for q in qids if q not in text_of]
+    if unknown:
+        raise ValueError(f"{path}: qrels.jsonl names {len(unknown)} query id(s) that queries.jsonl lacks, first {unknown[0]!r}")
+    rows = [sorted({doc_pos[d] for d in rel[q] if d in doc_pos}) for q in qids]
+    return BenchmarkData(qids, [text_of[q] for q in qids], list(doc_pos), docs, titles, rows, [len(rel[q]) for q in qids])
+
+
+class BenchmarkEvaluator(MidTrainingEvaluator):
+    """The evaluator's encoding path (``encode``, and ``bm25_index`` over it) for a ``BenchmarkData`` instead of a
+    validation file; ``relevant`` holds the qrels rows.  It does not score by itself: see src.train.cli.eval_benchmark."""
+
+    def __init__(self, tokenizer, data: BenchmarkData, device: str = "cuda", query_max_length: int = 64,
+                 doc_max_length: int = 256, batch_size: int = 64):
+        from benchmark.encoders import special_token_ids
+        self.seismic = self.two_phase = self.hybrid = self._bm25 = None
+        self.tokenizer = tokenizer
+        self.device = torch.device(device)
+        self.query_max_length, self.doc_max_length = int(query_max_length), int(doc_max_length)
+        self.batch_size = max(1, int(batch_size))
+        self.corpus = EvalCorpus(list(data.queries), list(data.docs), [], 0)
+        self.relevant = [list(r) for r in data.relevant]
+        self._token_lookup = list(tokenizer.convert_ids_to_tokens(list(range(tokenizer.vocab_size))))
+        self._special = special_token_ids(tokenizer)
+        self._allowed = None
+        self.last_ranks = None
+
+    def evaluate(self, model):
+        raise NotImplementedError("BenchmarkEvaluator encodes; src.train.cli.eval_benchmark scores against the qrels")
+
+
+def first_relevant_values(first_rank, k: int = RETRIEVAL_SIZE) -> np.ndarray:
+    """Per-query values float64 [nq, 5] under the first-relevant rule, columns recall@1, recall@5, recall@10, reciprocal
+    rank, ndcg@10 (ref:benchmark/metrics.py:52-99 per query): ``first_rank`` is the 1-based rank of the first relevant
+    doc, 0 = none; a rank beyond the list depth ``k`` is a miss."""
+    r = np.asarray(first_rank.cpu() if isinstance(first_rank, torch.Tensor) else first_rank, dtype=np.int64).reshape(-1)
+    hit = (r >= 1) & (r <= int(k))
+    safe = np.where(hit, r, 1)
+    out = np.zeros((r.size, 5), np.float64)
+    for j, c in enumerate((1, 5, 10)):
+        out[:, j] = hit & (r <= c)
+    out[:, 3] = np.where(hit, 1.0 / safe, 0.0)
+    out[:, 4] = np.where(hit & (r <= 10), 1.0 / np.log2(safe + 1), 0.0)
+    return out
+
+
+def qrels_metrics(first_rank, hits, dcg, nrel, cutoffs: Sequence[int] = QRELS_CUTOFFS, k: int = RETRIEVAL_SIZE
+                  ) -> Dict[str, float]:
+    """Metrics of ranked lists against qrels, from the outputs of ``snx.retrieval.ranked_relevance`` (``first_rank``
+    [nq], ``hits`` / ``dcg`` [nq, ncut] at ``cutoffs``) and the row sizes ``nrel`` [nq] (``first_relevant``'s fourth
+    output).  The reference's five numbers under its first-relevant rule (ref:benchmark/hf_runner.py:191-215 into
+    ref:benchmark/metrics.py): recall@1/5/10, mrr, ndcg@10, a rank beyond the list depth ``k`` being a miss.  And per
+    cutoff c the two standard multi-relevant numbers it lacks: recall_frac@c = mean of hits / nrel (0 for an empty row),
+    ndcg_multi@c = mean of dcg / idcg, idcg = the left-fold prefix sum of the same discount table over min(nrel, c)
+    positions.  Plus num_queries."""
+    from snx.retrieval import discount_table
+    cpu = lambda x: np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x)      # noqa: E731
+    cuts = [int(c) for c in cutoffs]
+    hits = cpu(hits).astype(np.float64).reshape(-1, len(cuts))
+    dcg = cpu(dcg).astype(np.float64).reshape(-1, len(cuts))
+    nrel = cpu(nrel).astype(np.int64).reshape(-1)
+    vals = first_relevant_values(first_rank, k)
+    nq = vals.shape[0]
+    if hits.shape[0] != nq or nrel.size != nq:
+        raise ValueError("qrels_metrics: first_rank, hits, dcg and nrel must describe the same queries")
+    mean = lambda x: float(np.mean(x)) if nq else 0.0                             # noqa: E731
+    out = {name: mean(vals[:, j]) for j, name in enumerate(REPORT_KEYS)}
+    ideal = np.concatenate([[0.0], np.cumsum(discount_table(max(cuts)))]) if cuts else np.zeros(1)
+    for j, c in enumerate(cuts):
+        out[f"recall_frac@{c}"] = mean(np.where(nrel > 0, hits[:, j] / np.maximum(nrel, 1), 0.0))
+        idcg = ideal[np.minimum(nrel, c)]
+        out[f"ndcg_multi@{c}"] = mean(np.where(idcg > 0, dcg[:, j] / np.where(idcg > 0, idcg, 1.0), 0.0))
+    out["num_queries"] = nq
+    return out
+
+
+def interval_from_means(per_query_values, means, confidence: float = 0.95) -> Dict[str, float]:
+    """The arithmetic of ref:benchmark/metrics.py:208-215 over resample means already formed: point_estimate = the mean
+    of the values, lower / upper = the (1 -+ confidence) / 2 percentiles of ``means`` (numpy's linear interpolation)."""
+    v = np.asarray(per_query_values, np.float64).reshape(-1)
+    m = np.asarray(means, np.float64).reshape(-1)
+    return {"point_estimate": float(np.mean(v)), "lower": float(np.percentile(m, (1 - confidence) / 2 * 100)),
+            "upper": float(np.percentile(m, (1 + confidence) / 2 * 100))}
+
+
+def bootstrap_confidence_interval(per_query_values, n_bootstrap: int = 1000, confidence: float = 0.95, seed: int = 42,
+                                  device=None):
+    """ref:benchmark/metrics.py:180-215 for a metric that is the mean of per-query values (all five of the reference's
+    are): the ``n_bootstrap`` resample means come from ``snx.retrieval.bootstrap_means`` on the GPU -- the reference's
+    own resamples for ``seed`` 42 -- and the percentiles are taken on the host.  ``per_query_values`` [n] -> {point_estimate,
+    lower, upper}; [n, M] (M <= 16, one launch) -> a list of M such dicts."""
+    from snx.retrieval import bootstrap_means
+    v = per_query_values.detach().cpu().numpy() if isinstance(per_query_values, torch.Tensor) else per_query_values
+    v = np.asarray(v, np.float64)
+    means = bootstrap_means(v, n_bootstrap=n_bootstrap, seed=seed, device=device).cpu().numpy()
+    if v.ndim == 1:
+        return interval_from_means(v, means[:, 0], confidence)
+    return [interval_from_means(v[:, m], means[:, m], confidence) for m in range(v.shape[1])]

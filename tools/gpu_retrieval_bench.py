@@ -7,6 +7,7 @@ csrc/retrieval.hip) on synthetic Zipf-skewed data.
     python tools/gpu_retrieval_bench.py --seismic [--sizes 1000000x10000]
     python tools/gpu_retrieval_bench.py --two-phase [--sizes 100000x10000,1000000x10000]
     python tools/gpu_retrieval_bench.py --hybrid [--sizes 100000x10000,1000000x10000]
+    python tools/gpu_retrieval_bench.py --qrels [--sizes 100000x2000,1000000x2000]
 
 Docs draw 128 terms (with replacement, duplicates dropped: ~99 distinct) from a Zipf(1.0) law over V = 50000 with
 weights uniform in [0.1, 3); queries draw 64 the same way (~53 distinct).  Retrieval size 10 with a target per query
@@ -32,7 +33,14 @@ terms; then the prune kernel alone over the whole doc CSR per prune type, and th
 drawn with replacement from the same Zipf law, every id allowed: Bm25Index.add_tokens + build in docs/s (term counts, df,
 weights, the SparseIndex build), BM25 search_tokens at k = 100 in queries/s, then fuse_ranked (RRF, top 10 with targets)
 over L = 2 and 3 random lists of R = 100 and 1000 doc ids in queries/s, medians of 5 after a warm-up; as a comparison
-row the same rule as plain Python dicts on the host over the first 200 queries."""
+row the same rule as plain Python dicts on the host over the first 200 queries.
+
+--qrels: scoring against qrels (csrc/qrels.hip) on the Zipf data of the first mode, every query with 1 .. 8 random
+relevant docs (mean 4.5), medians of 5 after a warm-up.  SparseIndex.first_relevant against the emulation it replaces: one
+search(k = 1, targets=...) per row position and the minimum of the ranks on the host.  ranked_relevance over the search's
+top 100 against the reference's Python set loop over the same lists on the host (transfer included, first 2000 queries).
+bootstrap_means (1000 resamples, 3 columns; the host-side index draws timed apart) against the reference-style numpy loop,
+one fancy-indexed mean per resample and column."""
 import argparse
 import json
 import os
@@ -295,6 +303,83 @@ def hybrid_case(nd, nq, dev, reps=5, host_queries=200):
     return row
 
 
+def qrels_case(nd, nq, dev, reps=5, host_queries=2000):
+    from statistics import median
+    import numpy as np
+    from snx.retrieval import SparseIndex, bootstrap_indices, bootstrap_means, ranked_relevance, relevance_csr
+    gen = torch.Generator().manual_seed(nd + nq)
+    probs = 1.0 / torch.arange(1, V + 1, dtype=torch.float64)
+    probs /= probs.sum()
+    idx = SparseIndex(V, dev)
+    for s in range(0, nd, 100_000):
+        idx.add(*zipf_rows(min(100_000, nd - s), 128, gen, dev, probs))
+    idx.build()
+    q = zipf_rows(nq, 64, gen, dev, probs)
+    rng = np.random.default_rng(nd + nq)
+    rows = [sorted(set(rng.integers(0, nd, int(rng.integers(1, 9))).tolist())) for _ in range(nq)]
+    rel = relevance_csr(rows, nq, nd, dev)
+    width = max(len(r) for r in rows)
+
+    def emulated():
+        best = torch.zeros(nq, dtype=torch.int32)
+        for j in range(width):
+            tgt = torch.tensor([r[j] if j < len(r) else 0 for r in rows], dtype=torch.int32, device=dev)
+            live = torch.tensor([j < len(r) for r in rows])
+            rk = idx.search(*q, 1, targets=tgt)[2].cpu()
+            use = live & (rk > 0) & ((best == 0) | (rk < best))
+            best = torch.where(use, rk, best)
+        return best
+    idx.first_relevant(*q, rel)
+    t_new = median(sync_time(lambda: idx.first_relevant(*q, rel))[0] for _ in range(reps))
+    t_old, best = sync_time(emulated)
+    rank = idx.first_relevant(*q, rel)[2]
+    row = {"docs": nd, "queries": nq, "mean_row": sum(len(r) for r in rows) / nq, "max_row": width,
+           "first_relevant_s": t_new, "per_doc_search_min_s": t_old, "speedup": t_old / t_new,
+           "same_ranks": bool(torch.equal(best, rank.cpu()))}
+    docs = idx.search(*q, 100)[1]
+    ranked_relevance(docs, rel, nd)
+    t_rr = median(sync_time(lambda: ranked_relevance(docs, rel, nd))[0] for _ in range(reps))
+    m = min(nq, host_queries)
+
+    def set_loop():                                            # ref:benchmark/hf_runner.py:198-203 per query
+        lists = docs[:m].cpu().tolist()
+        out = []
+        for qi in range(m):
+            relevant, hit = set(rows[qi]), 0
+            for r, d in enumerate(lists[qi], 1):
+                if d < 0:
+                    break
+                if d in relevant:
+                    hit = r
+                    break
+            out.append(hit)
+        return out
+    t_loop, first_host = sync_time(set_loop)
+    first = ranked_relevance(docs, rel, nd)[0]
+    row.update(ranked_relevance_s=t_rr, ranked_relevance_queries_per_s=nq / t_rr, python_set_loop_queries=m,
+               python_set_loop_queries_per_s=m / t_loop, same_first_as_python=first[:m].cpu().tolist() == first_host)
+    vals = np.stack([(rng.random(nq) < 0.4).astype(np.float64), rng.random(nq), rng.random(nq)], 1)
+    t0 = time.perf_counter()
+    bidx = bootstrap_indices(nq, 1000, 42)
+    t_draw = time.perf_counter() - t0
+    bootstrap_means(vals, indices=bidx, device=dev)
+    t_bm = median(sync_time(lambda: bootstrap_means(vals, indices=bidx, device=dev))[0] for _ in range(reps))
+
+    def numpy_loop():                                          # ref:benchmark/metrics.py:198-206 with array metrics
+        np.random.seed(42)
+        out = np.empty((1000, 3))
+        for b in range(1000):
+            ind = np.random.choice(nq, size=nq, replace=True)
+            for c in range(3):
+                out[b, c] = np.mean(vals[ind, c])
+        return out
+    t_np, host = sync_time(numpy_loop)
+    got = bootstrap_means(vals, indices=bidx, device=dev).cpu().numpy()
+    row.update(bootstrap_means_s=t_bm, bootstrap_index_draw_s=t_draw, numpy_loop_s=t_np,
+               bootstrap_max_abs_diff=float(np.abs(got - host).max()))
+    return row
+
+
 def miner_case(n_records, dev):
     import tempfile
     from src.model.splade_modern import SPLADEModernBERT
@@ -326,9 +411,20 @@ def main():
     ap.add_argument("--seismic", action="store_true", help="SeismicIndex build and search against exact search")
     ap.add_argument("--two-phase", action="store_true", help="search_two_phase, the prune kernel and pruned() vs search")
     ap.add_argument("--hybrid", action="store_true", help="Bm25Index build and search, fuse_ranked vs Python dicts")
+    ap.add_argument("--qrels", action="store_true", help="first_relevant, ranked_relevance, bootstrap_means vs host loops")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     rows = []
+    if args.qrels:
+        sizes = args.sizes if args.sizes != ap.get_default("sizes") else "100000x2000,1000000x2000"
+        for s in sizes.split(","):
+            nd, nq = (int(x) for x in s.split("x"))
+            rows.append(qrels_case(nd, nq, dev))
+            print(json.dumps(rows[-1]), flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump({"device": torch.cuda.get_device_name(0), "rows": rows}, f, indent=1)
+        return
     if args.hybrid:
         sizes = args.sizes if args.sizes != ap.get_default("sizes") else "100000x10000,1000000x10000"
         for s in sizes.split(","):
