@@ -20,7 +20,9 @@
 //                          target's position are read.  No float atomics: byte-identical from run to run.
 #include <math.h>
 
-#include "common.h"
+// pow2_at_least comes from sparse_common.h; the bitonic network (other comparators than the rank key's) and the float64
+// helpers are this file's own.
+#include "sparse_common.h"
 #include "snx.h"
 
 namespace {
@@ -32,12 +34,6 @@ constexpr int HY_LMAX = 4;                       // fusion: lists per query
 constexpr int HY_RMAX = 1024;                    // fusion: entries per list (the search's k cap)
 constexpr int HY_EMAX = HY_LMAX * HY_RMAX;       // fusion: entries per query
 constexpr int HY_INVALID = 0x7FFFFFFF;
-
-__host__ __device__ inline int pow2_at_least(int n) {
-  int p = 1;
-  while (p < n) p <<= 1;
-  return p;
-}
 
 // a * b and a + b in float64, each rounded once: hipcc contracts `a * b + c` (and the __d*_rn intrinsics, which are
 // plain operators to it) into v_fma_f64 where it sees fit; the contracts of this file are stated per operation.

@@ -3,13 +3,12 @@
 // relevant SET; ref:benchmark/metrics.py:180-215 resamples the per-query values 1000 times).  The reference walks Python
 // lists per query and rebuilds a list per resample; here the judgments are a CSR on the device next to the index.
 //
-//   qr_best_kernel      one workgroup per query, one thread per relevant doc of its row: s(q, d) by walking the query's
-//                       terms in ascending id and looking each up in the doc's CSR row (the fmaf chain of the exact
-//                       search, so the value is bit-equal to the ranked one), then a workgroup maximum of
-//                       (score bits << 32 | ~doc): highest score, ties lowest doc id.
+//   qr_best_kernel      one workgroup per query, one thread per relevant doc of its row: s(q, d) by row_dot_search (the
+//                       fmaf chain of the exact search, so the value is bit-equal to the ranked one), then a workgroup
+//                       maximum of the rank key: highest score, ties lowest doc id.
 //   qr_count_kernel     one workgroup per (query, chunk of docs): the LDS score accumulation of retrieval.hip's
-//                       sr_chunk_kernel followed by its integer count of the docs in front of the best relevant doc.  No
-//                       selection pass: one accumulation per query whatever the row length.
+//                       sr_chunk_kernel (same constants, sparse_common.h) and its integer count of the docs in front of
+//                       the best relevant doc.  No selection pass: one accumulation per query whatever the row length.
 //   qr_rank_kernel      adds the chunks' counts of a query (integers: the chunking changes no bit).
 //   qr_ranked_kernel    one wave per ranked list, 64 positions at a time: every lane tests its entry by binary search in
 //                       the sorted row, a ballot puts the hits in position order, and the wave walks the set bits: one
@@ -19,17 +18,12 @@
 //                       segment order.  The order is a function of n alone.
 #include <math.h>
 
-#include "common.h"
+#include "sparse_common.h"
 #include "snx.h"
 
 namespace {
 
 constexpr int QB_THREADS = 256;
-constexpr int QC_THREADS = 512;
-constexpr int QC_WAVES = QC_THREADS / 64;
-constexpr int QC_TG = QC_THREADS / 2;          // query terms whose chunk bounds are searched at once
-constexpr int QC_CHUNK_DEFAULT = 16384;        // the exact search's chunking (retrieval.hip)
-constexpr int QC_CHUNK_MAX = 32768;
 constexpr int QR_THREADS = 256;
 constexpr int QR_WAVES = QR_THREADS / 64;
 constexpr int QR_RMAX = 4096;
@@ -37,19 +31,6 @@ constexpr int QR_CUTS = 8;
 constexpr int BT_THREADS = 256;
 constexpr int BT_MMAX = 16;
 constexpr int BT_SEG = SNX_BOOTSTRAP_SEGMENT;
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline int qc_chunk(int32_t chunk_docs) { return chunk_docs > 0 ? chunk_docs : QC_CHUNK_DEFAULT; }
-inline int qc_nch(int32_t nd, int chunk) { return nd > 0 ? (int)((nd + (long)chunk - 1) / chunk) : 1; }
-
-template <typename T>
-__device__ __forceinline__ int64_t lower_bound(const T* __restrict__ a, int64_t lo, int64_t hi, T x) {
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < x) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 
 // ------------------------------------------------------------------------------------------------ first relevant
 __global__ __launch_bounds__(QB_THREADS) void qr_best_kernel(
@@ -69,17 +50,9 @@ __global__ __launch_bounds__(QB_THREADS) void qr_best_kernel(
     if ((unsigned)d >= (unsigned)nd) continue;               // skipped, never read through
     ++cnt;
     const int64_t a = doc_ptr[d], b = doc_ptr[d + 1];
-    int64_t from = a;
-    float acc = 0.f;
-    for (int64_t j = qa; j < qb && from < b; ++j) {          // ascending term id: the ABI's accumulation order
-      const int32_t term = q_term[j];
-      const int64_t p = lower_bound(doc_term, from, b, term);
-      if (p < b && doc_term[p] == term) acc = fmaf(q_w[j], doc_w[p], acc);
-      from = p;
-    }
+    const float acc = row_dot_search(q_term, q_w, qa, qb, doc_term, doc_w, a, b);
     if (acc > 0.f) {
-      const unsigned long long key =
-          ((unsigned long long)__builtin_bit_cast(uint32_t, acc) << 32) | (0xFFFFFFFFu - (uint32_t)d);
+      const unsigned long long key = rank_key(fbits(acc), (uint32_t)d);
       if (key > best) best = key;
     }
   }
@@ -98,8 +71,8 @@ __global__ __launch_bounds__(QB_THREADS) void qr_best_kernel(
     }
     out_nrel[q] = cnt;
     if (best != 0ull) {
-      out_doc[q] = (int32_t)(0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull));
-      out_score[q] = __builtin_bit_cast(float, (uint32_t)(best >> 32));
+      out_doc[q] = rank_id(best);
+      out_score[q] = bitsf(rank_bits(best));
     } else {
       out_doc[q] = -1;
       out_score[q] = 0.f;
@@ -107,15 +80,15 @@ __global__ __launch_bounds__(QB_THREADS) void qr_best_kernel(
   }
 }
 
-__global__ __launch_bounds__(QC_THREADS) void qr_count_kernel(
+__global__ __launch_bounds__(SR_THREADS) void qr_count_kernel(
     const int64_t* __restrict__ q_ptr, const int32_t* __restrict__ q_term, const float* __restrict__ q_w,
     const int64_t* __restrict__ term_ptr, const int32_t* __restrict__ post_doc, const float* __restrict__ post_w, int32_t nd,
     int32_t V, int32_t chunk, int32_t nch, const int32_t* __restrict__ best_doc, const float* __restrict__ best_score,
     int32_t* __restrict__ rcount) {
   extern __shared__ float sc[];                              // [chunk] scores of this chunk's docs
-  __shared__ int64_t seg0[QC_TG], seg1[QC_TG];
-  __shared__ float segw[QC_TG];
-  __shared__ int wsum[QC_WAVES];
+  __shared__ int64_t seg0[SR_TG], seg1[SR_TG];
+  __shared__ float segw[SR_TG];
+  __shared__ int wsum[SR_WAVES];
   const int tid = threadIdx.x;
   const long qc = blockIdx.x;
   const int q = (int)(qc / nch), c = (int)(qc - (long)q * nch);
@@ -127,27 +100,27 @@ __global__ __launch_bounds__(QC_THREADS) void qr_count_kernel(
   const int tt = best_doc[q];
   const int c0 = c * chunk;
   const int n = max(0, min(chunk, nd - c0));
-  for (int i = tid; i < n; i += QC_THREADS) sc[i] = 0.f;
+  for (int i = tid; i < n; i += SR_THREADS) sc[i] = 0.f;
   const int64_t qa = q_ptr[q], qb = q_ptr[q + 1];
-  for (int64_t g = qa; g < qb; g += QC_TG) {
-    const int ng = (int)min((int64_t)QC_TG, qb - g);
-    const int j = tid < QC_TG ? tid : tid - QC_TG;
+  for (int64_t g = qa; g < qb; g += SR_TG) {
+    const int ng = (int)min((int64_t)SR_TG, qb - g);
+    const int j = tid < SR_TG ? tid : tid - SR_TG;
     if (j < ng) {                                            // both bounds of every term of the group at once
       const int32_t term = q_term[g + j];
       int64_t lo = 0, hi = 0;
       if ((unsigned)term < (unsigned)V) { lo = term_ptr[term]; hi = term_ptr[term + 1]; }
-      if (tid < QC_TG) {
-        seg0[j] = lower_bound(post_doc, lo, hi, (int32_t)c0);
+      if (tid < SR_TG) {
+        seg0[j] = lower_bound(post_doc, lo, hi, c0);
         segw[j] = q_w[g + j];
       } else {
-        seg1[j] = lower_bound(post_doc, lo, hi, (int32_t)(c0 + n));
+        seg1[j] = lower_bound(post_doc, lo, hi, c0 + n);
       }
     }
     __syncthreads();                                         // (also orders the zero fill before the first term)
     for (int jj = 0; jj < ng; ++jj) {                        // ascending term id: the ABI's accumulation order
       const int64_t e = seg1[jj];
       const float w = segw[jj];
-      for (int64_t i = seg0[jj] + tid; i < e; i += QC_THREADS) {
+      for (int64_t i = seg0[jj] + tid; i < e; i += SR_THREADS) {
         const int d = post_doc[i] - c0;
         if ((unsigned)d < (unsigned)n) sc[d] = fmaf(w, post_w[i], sc[d]);
       }
@@ -156,7 +129,7 @@ __global__ __launch_bounds__(QC_THREADS) void qr_count_kernel(
   }
   __syncthreads();
   int local = 0;                                             // #{s_d > s*} + #{d < d*: s_d == s*} inside the chunk
-  for (int i = tid; i < n; i += QC_THREADS) {
+  for (int i = tid; i < n; i += SR_THREADS) {
     const float s = sc[i];
     local += (s > ts) || (s == ts && c0 + i < tt);
   }
@@ -166,7 +139,7 @@ __global__ __launch_bounds__(QC_THREADS) void qr_count_kernel(
   __syncthreads();
   if (tid == 0) {
     int r = 0;
-    for (int w = 0; w < QC_WAVES; ++w) r += wsum[w];
+    for (int w = 0; w < SR_WAVES; ++w) r += wsum[w];
     rcount[qc] = r;
   }
 }
@@ -287,7 +260,7 @@ LdsOptIn g_count_lds;
 
 extern "C" size_t snx_sparse_first_relevant_workspace_bytes(int32_t nq, int32_t nd, int32_t chunk_docs) {
   if (nq <= 0 || nd < 0 || chunk_docs < 0) return 0;
-  return align256((size_t)nq * (size_t)qc_nch(nd, qc_chunk(chunk_docs)) * 4);
+  return align256((size_t)nq * (size_t)sr_nch(nd, sr_chunk(chunk_docs)) * 4);
 }
 
 extern "C" int snx_sparse_first_relevant(const int64_t* q_ptr, const int32_t* q_term, const float* q_w, int32_t nq,
@@ -297,12 +270,12 @@ extern "C" int snx_sparse_first_relevant(const int64_t* q_ptr, const int32_t* q_
                                          int32_t* out_doc, float* out_score, int32_t* out_rank, int32_t* out_nrel,
                                          void* workspace, size_t ws_bytes, hipStream_t st) {
   if (!q_ptr || !term_ptr || !doc_ptr || !rel_ptr || !out_doc || !out_score || !out_rank || !out_nrel) return SNX_E_ARG;
-  if (nq < 0 || nd < 0 || V <= 0 || chunk_docs < 0 || chunk_docs > QC_CHUNK_MAX) return SNX_E_SHAPE;
+  if (nq < 0 || nd < 0 || V <= 0 || chunk_docs < 0 || chunk_docs > SR_CHUNK_MAX) return SNX_E_SHAPE;
   if (nq == 0) return SNX_OK;
-  const int chunk = qc_chunk(chunk_docs);
-  const int nch = qc_nch(nd, chunk);
+  const int chunk = sr_chunk(chunk_docs);
+  const int nch = sr_nch(nd, chunk);
   const long blocks = (long)nq * nch;
-  if (blocks > (1L << 31) / QC_THREADS) return SNX_E_SHAPE;       // one launch of the chunk grid
+  if (blocks > (1L << 31) / SR_THREADS) return SNX_E_SHAPE;       // one launch of the chunk grid
   const size_t need = snx_sparse_first_relevant_workspace_bytes(nq, nd, chunk_docs);
   if (!workspace || ws_bytes < need) return SNX_E_ARG;
   int32_t* rcount = (int32_t*)workspace;
@@ -311,9 +284,9 @@ extern "C" int snx_sparse_first_relevant(const int64_t* q_ptr, const int32_t* q_
   SNX_CHECK_LAUNCH();
   const size_t lds = (size_t)chunk * sizeof(float);
   if (lds > 48 * 1024) {
-    if (const int rc = g_count_lds.ensure((const void*)qr_count_kernel, QC_CHUNK_MAX * (int)sizeof(float))) return rc;
+    if (const int rc = g_count_lds.ensure((const void*)qr_count_kernel, SR_CHUNK_MAX * (int)sizeof(float))) return rc;
   }
-  hipLaunchKernelGGL(qr_count_kernel, dim3((unsigned)blocks), dim3(QC_THREADS), lds, st, q_ptr, q_term, q_w, term_ptr,
+  hipLaunchKernelGGL(qr_count_kernel, dim3((unsigned)blocks), dim3(SR_THREADS), lds, st, q_ptr, q_term, q_w, term_ptr,
                      post_doc, post_w, nd, V, chunk, nch, (const int32_t*)out_doc, (const float*)out_score, rcount);
   SNX_CHECK_LAUNCH();
   hipLaunchKernelGGL(qr_rank_kernel, dim3(cdiv(nq, 64)), dim3(64), 0, st, (const int32_t*)rcount, nq, nch,

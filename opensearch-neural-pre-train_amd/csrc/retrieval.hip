@@ -18,7 +18,12 @@
 // bits order like the floats; the trick of topk.hip) picks the chunk's top k under (score desc, doc asc), compacted in
 // doc order, and an integer count gives the chunk's share of the target rank.  sr_merge reduces the chunks of a query
 // the same way (its candidates are in doc order too) and sorts the <= k winners.  Chunk size changes no bit.
-#include "common.h"
+//
+// From sparse_common.h: the chunk constants, lower_bound, the radix select and ordered take, block_sum, the pair score
+// (row_dot_lanes) and the rank key.  The chunk accumulation (sr_chunk_kernel, sb_chunk_kernel; qr_count_kernel in
+// qrels.hip) and the merge front (sr_merge_kernel, sb_merge_kernel) stay written out in their kernels: as functions they
+// compile to other code, which would have to be timed against this one first.
+#include "sparse_common.h"
 #include "snx.h"
 
 namespace {
@@ -28,15 +33,7 @@ constexpr int IX_MAX_BLOCKS = 1024;
 constexpr long IX_TABLE_BUDGET = 1L << 24;     // entries of the [nblk, V] cursor table (int64): <= 128 MiB
 constexpr int SCAN_THREADS = 1024;
 
-constexpr int SR_THREADS = 512;
-constexpr int SR_WAVES = SR_THREADS / 64;
-constexpr int SR_TG = SR_THREADS / 2;          // query terms whose chunk bounds are searched at once
-constexpr int SR_KMAX = 1024;
-constexpr int SR_CHUNK_DEFAULT = 16384;        // 64 KiB of scores: two workgroups per CU
-constexpr int SR_CHUNK_MAX = 32768;            // 128 KiB of scores + ~14 KiB static LDS (160 KiB per workgroup)
 constexpr int TS_THREADS = 64;
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ------------------------------------------------------------------------------------------------ index build
 inline int ix_blocks(int32_t nd, int32_t V) {
@@ -131,118 +128,10 @@ __global__ __launch_bounds__(IX_THREADS) void ix_scatter_kernel(const int64_t* _
 }
 
 // ------------------------------------------------------------------------------------------------ search
-__device__ __forceinline__ int64_t lower_bound_doc(const int32_t* __restrict__ a, int64_t lo, int64_t hi, int32_t x) {
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < x) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
+__device__ __forceinline__ uint32_t score_key(float s) { return s > 0.f ? fbits(s) : 0u; }
 
-__device__ __forceinline__ uint32_t score_key(float s) { return s > 0.f ? __builtin_bit_cast(uint32_t, s) : 0u; }
-
-struct SelectSmem {
-  uint32_t hist[2048];
-  int wcnt[2][SR_WAVES];
-  int sh[4];                      // 0: count, 1: bin, 2: remaining
-  int run[2];                     // ordered take: eq seen, taken so far
-};
-
-__device__ __forceinline__ int block_sum_int(int v, SelectSmem& S) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if (tid == 0) S.sh[0] = 0;
-  __syncthreads();
-  if ((tid & 63) == 0 && v) atomicAdd(&S.sh[0], v);
-  __syncthreads();
-  const int r = S.sh[0];
-  __syncthreads();
-  return r;
-}
-
-// Radix select over key(i), i in [0, n), key 0 = no candidate.  -> thr, need_eq, nsel (block-uniform): the top k are
-// every key > thr and the first need_eq (lowest i) keys == thr; when at most k keys are non-zero, thr = 0 and all are.
-template <typename KeyF>
-__device__ void radix_select(KeyF key, long n, int k, SelectSmem& S, uint32_t& thr, int& need_eq, int& nsel) {
-  const int tid = threadIdx.x;
-  int local = 0;
-  for (long i = tid; i < n; i += SR_THREADS) local += key(i) != 0u;
-  const int npos = block_sum_int(local, S);
-  if (npos <= k) { thr = 0u; need_eq = 0; nsel = npos; return; }
-  uint32_t prefix = 0u, known = 0u;
-  int remaining = k;
-  const int shifts[3] = {21, 10, 0}, widths[3] = {11, 11, 10};
-  for (int p = 0; p < 3; ++p) {
-    const int shift = shifts[p];
-    const uint32_t bm = (1u << widths[p]) - 1u;
-    for (int i = tid; i < 2048; i += SR_THREADS) S.hist[i] = 0u;
-    __syncthreads();
-    for (long i = tid; i < n; i += SR_THREADS) {
-      const uint32_t kk = key(i);
-      if (kk != 0u && (kk & known) == prefix) atomicAdd(&S.hist[(kk >> shift) & bm], 1u);
-    }
-    __syncthreads();
-    if (tid == 0) {                                          // walk the bins from the top
-      int rem = remaining, b = (int)bm;
-      for (; b > 0; --b) {
-        const int c = (int)S.hist[b];
-        if (c >= rem) break;
-        rem -= c;
-      }
-      S.sh[1] = b;
-      S.sh[2] = rem;
-    }
-    __syncthreads();
-    prefix |= (uint32_t)S.sh[1] << shift;
-    known |= bm << shift;
-    remaining = S.sh[2];
-    __syncthreads();
-  }
-  thr = prefix;
-  need_eq = remaining;
-  nsel = k;
-}
-
-// The selection of radix_select in index order: emit(i, pos) with pos = 0, 1, ... following i.
-template <typename KeyF, typename EmitF>
-__device__ void ordered_take(KeyF key, long n, uint32_t thr, int need_eq, SelectSmem& S, EmitF emit) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  if (tid == 0) { S.run[0] = 0; S.run[1] = 0; }
-  __syncthreads();
-  for (long base = 0; base < n; base += SR_THREADS) {
-    const long i = base + tid;
-    const uint32_t kk = i < n ? key(i) : 0u;
-    const bool gt = kk > thr;
-    const bool eq = thr != 0u && kk == thr;
-    const unsigned long long mg = __ballot(gt), me = __ballot(eq);
-    if (lane == 0) { S.wcnt[0][wave] = __popcll(mg); S.wcnt[1][wave] = __popcll(me); }
-    __syncthreads();
-    int E = S.run[0], T = S.run[1];
-    for (int w = 0; w < wave; ++w) {
-      T += S.wcnt[0][w] + min(max(need_eq - E, 0), S.wcnt[1][w]);
-      E += S.wcnt[1][w];
-    }
-    const int eq_below = __popcll(me & below);
-    const bool take = gt || (eq && E + eq_below < need_eq);
-    if (take) emit(i, T + __popcll(mg & below) + min(max(need_eq - E, 0), eq_below));
-    __syncthreads();
-    if (tid == 0) {
-      int e = S.run[0], t = S.run[1];
-      for (int w = 0; w < SR_WAVES; ++w) {
-        t += S.wcnt[0][w] + min(max(need_eq - e, 0), S.wcnt[1][w]);
-        e += S.wcnt[1][w];
-      }
-      S.run[0] = e;
-      S.run[1] = t;
-    }
-    __syncthreads();
-  }
-}
-
-// s(q, target[q]) by a merge of the two id-sorted CSR rows: lanes find the query's terms in the doc row, lane 0 applies
-// fmaf in ascending term id -- the order of the LDS accumulation, so the value is bit-equal to the ranked one.
+// s(q, target[q]) by row_dot_lanes: fmaf in ascending term id, the order of the LDS accumulation, so the value is
+// bit-equal to the ranked one.
 __global__ __launch_bounds__(TS_THREADS) void sr_target_kernel(const int64_t* __restrict__ q_ptr,
                                                                const int32_t* __restrict__ q_term,
                                                                const float* __restrict__ q_w,
@@ -251,32 +140,11 @@ __global__ __launch_bounds__(TS_THREADS) void sr_target_kernel(const int64_t* __
                                                                const float* __restrict__ doc_w, int32_t nd,
                                                                const int32_t* __restrict__ target,
                                                                float* __restrict__ out_tscore) {
-  __shared__ float qv[TS_THREADS], dv[TS_THREADS];
-  __shared__ int hit[TS_THREADS];
-  const int q = blockIdx.x, lane = threadIdx.x;
-  const int t = target[q];
+  const int q = blockIdx.x, t = target[q];
   float acc = 0.f;
-  if ((unsigned)t < (unsigned)nd) {
-    const int64_t a = doc_ptr[t], b = doc_ptr[t + 1];
-    const int64_t qa = q_ptr[q], qb = q_ptr[q + 1];
-    for (int64_t g = qa; g < qb; g += TS_THREADS) {
-      const int64_t j = g + lane;
-      hit[lane] = 0;
-      if (j < qb) {
-        const int32_t term = q_term[j];
-        const int64_t p = lower_bound_doc(doc_term, a, b, term);
-        if (p < b && doc_term[p] == term) { hit[lane] = 1; qv[lane] = q_w[j]; dv[lane] = doc_w[p]; }
-      }
-      __syncthreads();
-      if (lane == 0) {
-        const int m = (int)min((int64_t)TS_THREADS, qb - g);
-        for (int i = 0; i < m; ++i)
-          if (hit[i]) acc = fmaf(qv[i], dv[i], acc);
-      }
-      __syncthreads();
-    }
-  }
-  if (lane == 0) out_tscore[q] = acc;
+  if ((unsigned)t < (unsigned)nd)
+    acc = row_dot_lanes<TS_THREADS>(q_term, q_w, q_ptr[q], q_ptr[q + 1], doc_term, doc_w, doc_ptr[t], doc_ptr[t + 1]);
+  if (threadIdx.x == 0) out_tscore[q] = acc;
 }
 
 __global__ __launch_bounds__(SR_THREADS) void sr_chunk_kernel(const int64_t* __restrict__ q_ptr,
@@ -310,10 +178,10 @@ __global__ __launch_bounds__(SR_THREADS) void sr_chunk_kernel(const int64_t* __r
       int64_t lo = 0, hi = 0;
       if ((unsigned)term < (unsigned)V) { lo = term_ptr[term]; hi = term_ptr[term + 1]; }
       if (tid < SR_TG) {
-        seg0[j] = lower_bound_doc(post_doc, lo, hi, c0);
+        seg0[j] = lower_bound(post_doc, lo, hi, c0);
         segw[j] = q_w[g + j];
       } else {
-        seg1[j] = lower_bound_doc(post_doc, lo, hi, c0 + n);
+        seg1[j] = lower_bound(post_doc, lo, hi, c0 + n);
       }
     }
     __syncthreads();                                       // (also orders the zero fill before the first term)
@@ -337,7 +205,7 @@ __global__ __launch_bounds__(SR_THREADS) void sr_chunk_kernel(const int64_t* __r
         const float s = sc[i];
         local += (s > ts) || (s == ts && c0 + i < tt);
       }
-    const int r = block_sum_int(local, S);
+    const int r = block_sum(local, S.sh[0]);
     if (tid == 0) rcount[qc] = r;
   }
   auto key = [&](long i) -> uint32_t { return score_key(sc[i]); };
@@ -367,7 +235,7 @@ __global__ __launch_bounds__(SR_THREADS) void sr_merge_kernel(const unsigned lon
   if (target) {
     int local = 0;
     for (int c = tid; c < nch; c += SR_THREADS) local += rcount[base + c];
-    const int r = block_sum_int(local, S);
+    const int r = block_sum(local, S.sh[0]);
     const int tt = target[q];
     if (tid == 0) out_rank[q] = ((unsigned)tt < (unsigned)nd && tscore[q] > 0.f) ? 1 + r : 0;
   }
@@ -381,15 +249,14 @@ __global__ __launch_bounds__(SR_THREADS) void sr_merge_kernel(const unsigned lon
   uint32_t thr;
   int need_eq, nsel;
   radix_select(key, n, k, S, thr, need_eq, nsel);
-  int P = 1;
-  while (P < nsel) P <<= 1;
+  const int P = pow2_at_least(nsel);
   for (int i = tid; i < P; i += SR_THREADS) sbuf[i] = 0ull;
   __syncthreads();
   ordered_take(key, n, thr, need_eq, S, [&](long f, int pos) {
     const unsigned long long e = qcand[f];
-    sbuf[pos] = (e & 0xFFFFFFFF00000000ull) | (0xFFFFFFFFull - (e & 0xFFFFFFFFull));
+    sbuf[pos] = rank_key((uint32_t)(e >> 32), (uint32_t)e);
   });
-  for (int size = 2; size <= P; size <<= 1)                 // bitonic sort, descending
+  for (int size = 2; size <= P; size <<= 1)                 // bitonic sort, descending; written out (see sparse_common.h, bitonic_desc)
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
       for (int t = tid; t < (P >> 1); t += SR_THREADS) {
         const int lo = 2 * t - (t & (stride - 1));
@@ -405,8 +272,8 @@ __global__ __launch_bounds__(SR_THREADS) void sr_merge_kernel(const unsigned lon
   for (int i = tid; i < k; i += SR_THREADS) {
     if (i < nsel) {
       const unsigned long long e = sbuf[i];
-      os[i] = __builtin_bit_cast(float, (uint32_t)(e >> 32));
-      od[i] = (int32_t)(0xFFFFFFFFu - (uint32_t)(e & 0xFFFFFFFFull));
+      os[i] = bitsf(rank_bits(e));
+      od[i] = rank_id(e);
     } else {
       os[i] = 0.f;
       od[i] = -1;
@@ -425,33 +292,12 @@ __global__ __launch_bounds__(TS_THREADS) void sr_pair_kernel(const int64_t* __re
                                                              const int32_t* __restrict__ pair_q,
                                                              const int32_t* __restrict__ pair_d,
                                                              float* __restrict__ out) {
-  __shared__ float qv[TS_THREADS], dv[TS_THREADS];
-  __shared__ int hit[TS_THREADS];
   const long p = blockIdx.x;
-  const int lane = threadIdx.x;
   const int q = pair_q[p], t = pair_d[p];
   float acc = 0.f;
-  if ((unsigned)q < (unsigned)nq && (unsigned)t < (unsigned)nd) {
-    const int64_t a = doc_ptr[t], b = doc_ptr[t + 1];
-    const int64_t qa = q_ptr[q], qb = q_ptr[q + 1];
-    for (int64_t g = qa; g < qb; g += TS_THREADS) {
-      const int64_t j = g + lane;
-      hit[lane] = 0;
-      if (j < qb) {
-        const int32_t term = q_term[j];
-        const int64_t pos = lower_bound_doc(doc_term, a, b, term);
-        if (pos < b && doc_term[pos] == term) { hit[lane] = 1; qv[lane] = q_w[j]; dv[lane] = doc_w[pos]; }
-      }
-      __syncthreads();
-      if (lane == 0) {
-        const int m = (int)min((int64_t)TS_THREADS, qb - g);
-        for (int i = 0; i < m; ++i)
-          if (hit[i]) acc = fmaf(qv[i], dv[i], acc);
-      }
-      __syncthreads();
-    }
-  }
-  if (lane == 0) out[p] = acc;
+  if ((unsigned)q < (unsigned)nq && (unsigned)t < (unsigned)nd)
+    acc = row_dot_lanes<TS_THREADS>(q_term, q_w, q_ptr[q], q_ptr[q + 1], doc_term, doc_w, doc_ptr[t], doc_ptr[t + 1]);
+  if (threadIdx.x == 0) out[p] = acc;
 }
 
 // Band search, chunk stage: the LDS accumulation of sr_chunk_kernel, then the query's excluded docs inside the chunk (a
@@ -488,10 +334,10 @@ __global__ __launch_bounds__(SR_THREADS) void sb_chunk_kernel(const int64_t* __r
       int64_t lo = 0, hi2 = 0;
       if ((unsigned)term < (unsigned)V) { lo = term_ptr[term]; hi2 = term_ptr[term + 1]; }
       if (tid < SR_TG) {
-        seg0[j] = lower_bound_doc(post_doc, lo, hi2, c0);
+        seg0[j] = lower_bound(post_doc, lo, hi2, c0);
         segw[j] = q_w[g + j];
       } else {
-        seg1[j] = lower_bound_doc(post_doc, lo, hi2, c0 + n);
+        seg1[j] = lower_bound(post_doc, lo, hi2, c0 + n);
       }
     }
     __syncthreads();
@@ -509,7 +355,7 @@ __global__ __launch_bounds__(SR_THREADS) void sb_chunk_kernel(const int64_t* __r
   if (ex_ptr) {                                            // the row's docs in [c0, c0 + n): one binary search per bound
     if (tid < 2) {
       const int64_t a = ex_ptr[q], b = ex_ptr[q + 1];
-      seg0[tid] = lower_bound_doc(ex_doc, a, b, tid == 0 ? c0 : c0 + n);
+      seg0[tid] = lower_bound(ex_doc, a, b, tid == 0 ? c0 : c0 + n);
     }
     __syncthreads();
     const int64_t e0 = seg0[0], e1 = seg0[1];
@@ -534,8 +380,8 @@ __global__ __launch_bounds__(SR_THREADS) void sb_chunk_kernel(const int64_t* __r
   if (tid == 0) ccount[qc] = nsel;
 }
 
-// Band search, merge stage: sr_merge_kernel's selection of the top `hi` over the chunks' candidates and its bitonic
-// sort, then ranks lo .. hi-1 are written.
+// Band search, merge stage: sr_merge_kernel's selection of the top `hi` over the chunks' candidates, then ranks
+// lo .. hi-1 are written.
 __global__ __launch_bounds__(SR_THREADS) void sb_merge_kernel(const unsigned long long* __restrict__ cand,
                                                               const int32_t* __restrict__ ccount, int32_t nch,
                                                               int32_t lo, int32_t hi, int32_t* __restrict__ out_doc,
@@ -555,15 +401,14 @@ __global__ __launch_bounds__(SR_THREADS) void sb_merge_kernel(const unsigned lon
   uint32_t thr;
   int need_eq, nsel;
   radix_select(key, n, hi, S, thr, need_eq, nsel);
-  int P = 1;
-  while (P < nsel) P <<= 1;
+  const int P = pow2_at_least(nsel);
   for (int i = tid; i < P; i += SR_THREADS) sbuf[i] = 0ull;
   __syncthreads();
   ordered_take(key, n, thr, need_eq, S, [&](long f, int pos) {
     const unsigned long long e = qcand[f];
-    sbuf[pos] = (e & 0xFFFFFFFF00000000ull) | (0xFFFFFFFFull - (e & 0xFFFFFFFFull));
+    sbuf[pos] = rank_key((uint32_t)(e >> 32), (uint32_t)e);
   });
-  for (int size = 2; size <= P; size <<= 1)
+  for (int size = 2; size <= P; size <<= 1)                 // the sort of sr_merge_kernel
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
       for (int t = tid; t < (P >> 1); t += SR_THREADS) {
         const int a0 = 2 * t - (t & (stride - 1));
@@ -581,8 +426,8 @@ __global__ __launch_bounds__(SR_THREADS) void sb_merge_kernel(const unsigned lon
     const int r = lo + j;
     if (r < nsel) {
       const unsigned long long e = sbuf[r];
-      os[j] = __builtin_bit_cast(float, (uint32_t)(e >> 32));
-      od[j] = (int32_t)(0xFFFFFFFFu - (uint32_t)(e & 0xFFFFFFFFull));
+      os[j] = bitsf(rank_bits(e));
+      od[j] = rank_id(e);
     } else {
       os[j] = 0.f;
       od[j] = -1;
@@ -590,9 +435,6 @@ __global__ __launch_bounds__(SR_THREADS) void sb_merge_kernel(const unsigned lon
   }
   if (tid == 0) out_found[q] = max(0, nsel - lo);
 }
-
-inline int sr_chunk(int32_t chunk_docs) { return chunk_docs > 0 ? chunk_docs : SR_CHUNK_DEFAULT; }
-inline int sr_nch(int32_t nd, int chunk) { return nd > 0 ? (int)((nd + (long)chunk - 1) / chunk) : 1; }
 
 }  // namespace
 

@@ -25,7 +25,8 @@
 // order against the running k-th score; a scored block's docs are scored one lane per doc (merge walk against the query,
 // fmaf chain) and merged into the sorted top k in LDS (64-bit keys score bits << 32 | ~doc, double-buffered, every key
 // placed by counting, so the result depends on the key set only).  No float atomics: byte-identical from run to run.
-#include "common.h"
+// row_dot, the rank key (score bits << 32 | ~doc) and bitonic_desc come from sparse_common.h.
+#include "sparse_common.h"
 #include "snx.h"
 
 namespace {
@@ -38,50 +39,6 @@ constexpr int SZ_SORT_LDS = 4096;                // summary unions up to this si
 constexpr int SZ_SLOTS = 256;                    // summary workgroups (workspace slots)
 constexpr int SZ_RTILE = 1024;                   // rank-by-counting tile
 constexpr int SZ_CTILE = 512;                    // centroid rows staged per step of the assignment
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-__host__ __device__ inline long pow2_at_least(long n) {
-  long p = 1;
-  while (p < n) p <<= 1;
-  return p;
-}
-
-// s(a, b) of the ABI: fmaf over the shared terms in ascending term id, from +0 (rows strictly ascending)
-__device__ __forceinline__ float row_dot(const int32_t* at, const float* aw, int64_t a0, int64_t a1,
-                                         const int32_t* bt, const float* bw, int64_t b0, int64_t b1) {
-  float acc = 0.f;
-  while (a0 < a1 && b0 < b1) {
-    const int32_t x = at[a0], y = bt[b0];
-    if (x == y) {
-      acc = fmaf(aw[a0], bw[b0], acc);
-      ++a0;
-      ++b0;
-    } else if (x < y) {
-      ++a0;
-    } else {
-      ++b0;
-    }
-  }
-  return acc;
-}
-
-__device__ __forceinline__ uint32_t fbits(float x) { return __builtin_bit_cast(uint32_t, x); }
-__device__ __forceinline__ float bitsf(uint32_t x) { return __builtin_bit_cast(float, x); }
-
-// descending bitonic sort of a[0..P), P a power of two, by the whole workgroup (a: LDS or the workgroup's own slot)
-__device__ void bitonic_desc(unsigned long long* a, long P) {
-  for (long size = 2; size <= P; size <<= 1)
-    for (long stride = size >> 1; stride > 0; stride >>= 1) {
-      for (long t = threadIdx.x; t < (P >> 1); t += SZ_THREADS) {
-        const long lo = 2 * t - (t & (stride - 1));
-        const long hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const unsigned long long x = a[lo], y = a[hi];
-        if ((x < y) == desc) { a[lo] = y; a[hi] = x; }
-      }
-      __syncthreads();
-    }
-}
 
 // ------------------------------------------------------------------------------------------------ build: pruning
 __global__ __launch_bounds__(SZ_THREADS) void sz_prune_kernel(const int64_t* __restrict__ term_ptr,
@@ -180,14 +137,12 @@ __global__ __launch_bounds__(SZ_THREADS) void sz_centroid_kernel(const int64_t* 
   if (p <= 0 || c <= 0) return;                              // uniform over the workgroup
   for (int64_t base = 0; base < p; base += SZ_THREADS) {
     const int64_t i = base + tid;
-    const unsigned long long ki =
-        i < p ? ((unsigned long long)fbits(prune_w[a + i]) << 32) | (0xFFFFFFFFull - (uint32_t)prune_doc[a + i]) : 0ull;
+    const unsigned long long ki = i < p ? rank_key(fbits(prune_w[a + i]), (uint32_t)prune_doc[a + i]) : 0ull;
     int64_t rank = 0;
     for (int64_t j0 = 0; j0 < p; j0 += SZ_RTILE) {
       const int n = (int)min((int64_t)SZ_RTILE, p - j0);
       for (int j = tid; j < n; j += SZ_THREADS)
-        tile[j] = ((unsigned long long)fbits(prune_w[a + j0 + j]) << 32) |
-                  (0xFFFFFFFFull - (uint32_t)prune_doc[a + j0 + j]);
+        tile[j] = rank_key(fbits(prune_w[a + j0 + j]), (uint32_t)prune_doc[a + j0 + j]);
       __syncthreads();
       for (int j = 0; j < n; ++j) rank += tile[j] > ki;
       __syncthreads();
@@ -313,27 +268,26 @@ __global__ __launch_bounds__(SZ_THREADS) void sz_summary_kernel(const int64_t* _
     }
     __syncthreads();
     const int n = nterm;
-    const long P = pow2_at_least(n);
+    const long P = pow2_at_least((long)n);
     unsigned long long* buf = P <= SZ_SORT_LDS ? sbuf : G;
     for (long i = tid; i < P; i += SZ_THREADS) {             // (m desc, u asc); the padding 0 sorts last
       unsigned long long kk = 0ull;
       if (i < n) {
         const int u = L[i];
-        kk = ((unsigned long long)__hip_atomic_load(&M[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) << 32) |
-             (0xFFFFFFFFull - (uint32_t)u);
+        kk = rank_key(__hip_atomic_load(&M[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), (uint32_t)u);
       }
       buf[i] = kk;
     }
     __syncthreads();
-    bitonic_desc(buf, P);
+    bitonic_desc<SZ_THREADS>(buf, P);
     if (tid == 0) {                                          // the fp32 left folds, in sorted order
       float total = 0.f;
-      for (int i = 0; i < n; ++i) total = total + bitsf((uint32_t)(buf[i] >> 32));
+      for (int i = 0; i < n; ++i) total = total + bitsf(rank_bits(buf[i]));
       const float goal = alpha * total;
       float acc = 0.f;
       int keep = 0;
       for (int i = 0; i < n; ++i) {
-        acc = acc + bitsf((uint32_t)(buf[i] >> 32));
+        acc = acc + bitsf(rank_bits(buf[i]));
         keep = i + 1;
         if (acc >= goal) break;
       }
@@ -348,7 +302,7 @@ __global__ __launch_bounds__(SZ_THREADS) void sz_summary_kernel(const int64_t* _
         buf[i] = i < keep ? ((kk & 0xFFFFFFFFull) << 32) | (kk >> 32) : 0ull;   // (~u) << 32 | m: desc = u asc
       }
       __syncthreads();
-      bitonic_desc(buf, pow2_at_least(keep));
+      bitonic_desc<SZ_THREADS>(buf, pow2_at_least((long)keep));
       const int64_t o = sum_ptr[b];
       for (int i = tid; i < keep; i += SZ_THREADS) {
         const unsigned long long kk = buf[i];
@@ -412,7 +366,7 @@ __global__ __launch_bounds__(SZ_THREADS) void sz_search_kernel(
       __syncthreads();
       for (int jb = 0; jb < nb; ++jb) {
         if (S.hcount == k) {
-          const float sk = bitsf((uint32_t)(S.H[cur][k - 1] >> 32));
+          const float sk = bitsf(rank_bits(S.H[cur][k - 1]));
           if (hf * S.rsum[jb] < sk) continue;                // a NaN product skips nothing
         }
         const int64_t e0 = blk_ptr[bb + jb], e1 = blk_ptr[bb + jb + 1];
@@ -424,7 +378,7 @@ __global__ __launch_bounds__(SZ_THREADS) void sz_search_kernel(
           if (e + tid < e1) {
             const int d = blk_doc[e + tid];
             const float s = row_dot(qt, qw, 0, nq, doc_term, doc_w, doc_ptr[d], doc_ptr[d + 1]);
-            unsigned long long key = s > 0.f ? ((unsigned long long)fbits(s) << 32) | (0xFFFFFFFFull - (uint32_t)d) : 0ull;
+            unsigned long long key = s > 0.f ? rank_key(fbits(s), (uint32_t)d) : 0ull;
             if (key && hc0 == k && key <= Hc[k - 1]) key = 0ull;
             if (key) {                                       // already in H (the same doc from an earlier block)?
               int lo = 0, hi = hc0;
@@ -477,8 +431,8 @@ __global__ __launch_bounds__(SZ_THREADS) void sz_search_kernel(
     int d = -1;
     if (i < hc) {
       const unsigned long long v = S.H[cur][i];
-      s = bitsf((uint32_t)(v >> 32));
-      d = (int)(0xFFFFFFFFu - (uint32_t)(v & 0xFFFFFFFFull));
+      s = bitsf(rank_bits(v));
+      d = rank_id(v);
       if (d == tt) S.found = i + 1;
     }
     out_score[(int64_t)q * k + i] = s;
@@ -499,7 +453,7 @@ __global__ __launch_bounds__(SZ_THREADS) void sz_search_kernel(
 
 inline size_t summary_list_off(int32_t V) { return align256((size_t)V * 4); }
 inline size_t summary_sort_off(int32_t V) { return 2 * align256((size_t)V * 4); }
-inline size_t summary_slot_bytes(int32_t V) { return summary_sort_off(V) + align256((size_t)pow2_at_least(V) * 8); }
+inline size_t summary_slot_bytes(int32_t V) { return summary_sort_off(V) + align256((size_t)pow2_at_least((long)V) * 8); }
 
 }  // namespace
 

@@ -20,7 +20,8 @@
 // rows (snx/retrieval.py SparseIndex.search_two_phase).  No float atomics: byte-identical from run to run.
 #include <math.h>
 
-#include "common.h"
+// row_dot, the rank key and bitonic_desc come from sparse_common.h.
+#include "sparse_common.h"
 #include "snx.h"
 
 namespace {
@@ -33,50 +34,6 @@ constexpr int TP_GRID = 2048;                    // prune workgroups otherwise
 constexpr int TP_QMAX = 1024;                    // query terms staged in LDS by the rescore
 constexpr int TP_WMAX = 1024;                    // rescore window cap
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-__host__ __device__ inline long pow2_at_least(long n) {
-  long p = 1;
-  while (p < n) p <<= 1;
-  return p;
-}
-
-__device__ __forceinline__ uint32_t fbits(float x) { return __builtin_bit_cast(uint32_t, x); }
-__device__ __forceinline__ float bitsf(uint32_t x) { return __builtin_bit_cast(float, x); }
-
-// s(a, b) of the ABI: fmaf over the shared terms in ascending term id, from +0 (rows strictly ascending)
-__device__ __forceinline__ float row_dot(const int32_t* at, const float* aw, int64_t a0, int64_t a1,
-                                         const int32_t* bt, const float* bw, int64_t b0, int64_t b1) {
-  float acc = 0.f;
-  while (a0 < a1 && b0 < b1) {
-    const int32_t x = at[a0], y = bt[b0];
-    if (x == y) {
-      acc = fmaf(aw[a0], bw[b0], acc);
-      ++a0;
-      ++b0;
-    } else if (x < y) {
-      ++a0;
-    } else {
-      ++b0;
-    }
-  }
-  return acc;
-}
-
-// descending bitonic sort of a[0..P), P a power of two, by the whole workgroup (a: LDS or the workgroup's own slot)
-__device__ void bitonic_desc(unsigned long long* a, long P) {
-  for (long size = 2; size <= P; size <<= 1)
-    for (long stride = size >> 1; stride > 0; stride >>= 1) {
-      for (long t = threadIdx.x; t < (P >> 1); t += TP_THREADS) {
-        const long lo = 2 * t - (t & (stride - 1));
-        const long hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const unsigned long long x = a[lo], y = a[hi];
-        if ((x < y) == desc) { a[lo] = y; a[hi] = x; }
-      }
-      __syncthreads();
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ prune
 struct PruneSmem {
   unsigned long long sbuf[TP_SORT_LDS];
@@ -87,7 +44,8 @@ struct PruneSmem {
   int nkeep;
 };
 
-__device__ __forceinline__ int block_sum(int v, int* wsum) {
+// sum over the workgroup through a per-wave array (two barriers; the select's block_sum keeps its LDS word)
+__device__ __forceinline__ int wave_array_sum(int v, int* wsum) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   __syncthreads();                                           // the previous readers of wsum are done
@@ -135,7 +93,7 @@ __global__ __launch_bounds__(TP_THREADS) void tp_prune_kernel(const int64_t* __r
         rk[i] = k ? 1 : 0;
         local += k;
       }
-      kept = block_sum(local, S.wsum);
+      kept = wave_array_sum(local, S.wsum);
     } else if (type == SNX_PRUNE_TOP_K) {
       if (L <= topn) {
         for (int64_t i = tid; i < L; i += TP_THREADS) rk[i] = 1;
@@ -187,24 +145,24 @@ __global__ __launch_bounds__(TP_THREADS) void tp_prune_kernel(const int64_t* __r
         kept = topn;
       }
     } else {                                                 // SNX_PRUNE_ALPHA_MASS
-      const long P = pow2_at_least(L);
+      const long P = pow2_at_least((long)L);
       unsigned long long* buf = P <= TP_SORT_LDS ? S.sbuf : G;
       if (P > TP_SORT_LDS && (!G || P > slot_cap)) {         // longer than the caller declared: not pruned
         for (int64_t i = tid; i < L; i += TP_THREADS) rk[i] = 0;
         kept = -1;
       } else {
         for (long i = tid; i < P; i += TP_THREADS)           // (weight desc, position asc); the padding 0 sorts last
-          buf[i] = i < L ? ((unsigned long long)fbits(rw[i]) << 32) | (0xFFFFFFFFull - (uint32_t)i) : 0ull;
+          buf[i] = i < L ? rank_key(fbits(rw[i]), (uint32_t)i) : 0ull;
         __syncthreads();
-        bitonic_desc(buf, P);
+        bitonic_desc<TP_THREADS>(buf, P);
         if (tid == 0) {                                      // the fp32 left folds, in sorted order
           float total = 0.f;
-          for (int64_t i = 0; i < L; ++i) total = total + bitsf((uint32_t)(buf[i] >> 32));
+          for (int64_t i = 0; i < L; ++i) total = total + bitsf(rank_bits(buf[i]));
           const float goal = value * total;
           float acc = 0.f;
           int k = 0;
           for (int64_t i = 0; i < L; ++i) {
-            acc = acc + bitsf((uint32_t)(buf[i] >> 32));
+            acc = acc + bitsf(rank_bits(buf[i]));
             k = (int)i + 1;
             if (acc >= goal) break;
           }
@@ -213,7 +171,7 @@ __global__ __launch_bounds__(TP_THREADS) void tp_prune_kernel(const int64_t* __r
         __syncthreads();
         kept = S.nkeep;
         for (int64_t i = tid; i < L; i += TP_THREADS)
-          rk[0xFFFFFFFFu - (uint32_t)(buf[i] & 0xFFFFFFFFull)] = i < kept ? 1 : 0;
+          rk[(uint32_t)rank_id(buf[i])] = i < kept ? 1 : 0;
         __syncthreads();                                     // buf and nkeep are rewritten by the next row
       }
     }
@@ -244,7 +202,7 @@ __global__ __launch_bounds__(TP_THREADS) void tp_rescore_kernel(
   const int nqt = staged ? (int)max(qb - qa, (int64_t)0) : 0;
   for (int i = tid; i < nqt; i += TP_THREADS) { S.qt[i] = q_term[qa + i]; S.qw[i] = q_w[qa + i]; }
   if (tid == 0) S.found = 0;
-  const int P = (int)pow2_at_least(W);
+  const int P = (int)pow2_at_least((long)W);
   __syncthreads();
   const int32_t* cand = cand_doc + (int64_t)q * W;
   for (int c = tid; c < P; c += TP_THREADS) {                // one lane per candidate
@@ -255,13 +213,13 @@ __global__ __launch_bounds__(TP_THREADS) void tp_rescore_kernel(
         const int64_t d0 = doc_ptr[d], d1 = doc_ptr[d + 1];
         const float s = staged ? row_dot(S.qt, S.qw, 0, nqt, doc_term, doc_w, d0, d1)
                                : row_dot(q_term, q_w, qa, qb, doc_term, doc_w, d0, d1);
-        if (s > 0.f) key = ((unsigned long long)fbits(s) << 32) | (0xFFFFFFFFull - (uint32_t)d);
+        if (s > 0.f) key = rank_key(fbits(s), (uint32_t)d);
       }
     }
     S.key[c] = key;
   }
   __syncthreads();
-  bitonic_desc(S.key, P);
+  bitonic_desc<TP_THREADS>(S.key, (long)P);
   const int tt = target ? target[q] : -1;
   int32_t* od = out_doc + (int64_t)q * k;
   float* os = out_score + (int64_t)q * k;
@@ -280,8 +238,8 @@ __global__ __launch_bounds__(TP_THREADS) void tp_rescore_kernel(
       nu += S.wsum[x];
     }
     if (uniq && pos < k) {
-      const int d = (int)(0xFFFFFFFFu - (uint32_t)(kk & 0xFFFFFFFFull));
-      os[pos] = bitsf((uint32_t)(kk >> 32));
+      const int d = rank_id(kk);
+      os[pos] = bitsf(rank_bits(kk));
       od[pos] = d;
       if (d == tt) S.found = pos + 1;
     }
@@ -313,7 +271,7 @@ inline bool prune_value_ok(int32_t type, float v) {
   }
 }
 
-inline size_t prune_slot_bytes(int32_t max_row_nnz) { return align256((size_t)pow2_at_least(max_row_nnz) * 8); }
+inline size_t prune_slot_bytes(int32_t max_row_nnz) { return align256((size_t)pow2_at_least((long)max_row_nnz) * 8); }
 
 }  // namespace
 
@@ -336,7 +294,7 @@ extern "C" int snx_sparse_prune_rows(const int64_t* ptr, const float* w, int32_t
   const int32_t topn = prune_type == SNX_PRUNE_TOP_K ? (value < 1073741824.f ? (int32_t)value : 1 << 30) : 0;
   hipLaunchKernelGGL(tp_prune_kernel, dim3(grid), dim3(TP_THREADS), 0, st, ptr, w, n, nnz, prune_type, value, topn,
                      keep, kept_cnt, need ? (char*)workspace : (char*)nullptr, need ? prune_slot_bytes(max_row_nnz) : 0,
-                     need ? pow2_at_least(max_row_nnz) : 0L);
+                     need ? pow2_at_least((long)max_row_nnz) : 0L);
   SNX_CHECK_LAUNCH();
   return SNX_OK;
 }

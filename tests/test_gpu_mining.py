@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_gpu_retrieval import _dense, _index, _rows, _to_device
+from tests.test_gpu_retrieval import _dense, _index, _long_query_corpus, _rows, _to_device
 
 pytestmark = pytest.mark.gpu
 
@@ -86,6 +86,27 @@ def test_band_exact_exclusions_ceilings_and_short_bands(dev):
     # a band longer than the admissible set
     sc, dc, fd = _band_case(dev, idx, S, queries, 0, 64, excl, None, 0)
     assert int(fd[5]) < 64 and (dc[5, int(fd[5]):] == -1).all()
+
+
+@pytest.mark.parametrize("hi", [1, 7])
+def test_band_exact_query_longer_than_one_staging_group(dev, hi):
+    docs, queries, V = _long_query_corpus()                 # 300 terms in query 0, query 1 empty
+    idx = _index(docs, V, dev)
+    S = _dense(queries, V) @ _dense(docs, V).T
+    excl = [[int(np.argmax(S[0]))], [], [3]]
+    _, _, fd = _band_case(dev, idx, S, queries, 0, hi, excl, None, 128)
+    assert fd[0] == hi and fd[1] == 0
+
+
+def test_pair_scores_exact_query_longer_than_one_lookup_step(dev):
+    docs, queries, V = _long_query_corpus()                 # 300 terms: five steps of 64 lanes, the last one partial
+    idx = _index(docs, V, dev)
+    S = _dense(queries, V) @ _dense(docs, V).T
+    qv, qi, qc = _to_device(queries, dev, np.random.default_rng(7))
+    pq, pd = np.divmod(np.arange(3 * len(docs)), len(docs))
+    pairs = torch.from_numpy(np.stack([pq, pd], 1).astype(np.int32)).to(dev)
+    ps = idx.pair_scores(qv, qi, qc, pairs)
+    assert np.array_equal(ps.cpu().numpy().astype(np.float64), S.reshape(-1))
 
 
 def test_band_exact_hi_1024_and_100k_docs(dev):

@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from tests import qrels_reference as Q
-from tests.test_gpu_retrieval import _to_device
+from tests.test_gpu_retrieval import _index, _long_query_corpus, _to_device
 from tests.test_qrels_host import GOLDEN_DIR, OURS, REPORT, golden_qrels, interval_bound
 
 pytestmark = pytest.mark.gpu
@@ -127,6 +127,18 @@ def test_first_relevant_equals_the_reference_and_the_single_target_minimum(dev, 
         idx.first_relevant(*q, relevant, chunk_docs=32769)
     with pytest.raises(ValueError):
         idx.first_relevant(*q, relevant[:-1])
+
+
+def test_first_relevant_with_a_query_longer_than_one_staging_group(dev):
+    docs, queries, V = _long_query_corpus()                 # 300 terms in query 0, query 1 empty
+    idx = _index(docs, V, dev)
+    S = Q.scores(queries, docs, V)
+    relevant = [[0, 5, 120, 299], [4], list(range(0, 300, 3))]                # doc 0 is empty
+    want = Q.first_relevant(S, relevant)
+    got = [x.cpu().numpy() for x in idx.first_relevant(*_to_device(queries, dev), relevant, chunk_docs=128)]
+    for name, g, w in zip(("doc", "score", "rank", "nrel"), got, want):
+        assert np.array_equal(_bits(g), _bits(w)), name
+    assert got[2][0] > 0 and got[2][1] == 0
 
 
 def test_first_rank_in_a_list_is_the_whole_corpus_rank_when_it_fits(dev, corpus):

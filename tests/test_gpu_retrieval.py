@@ -133,6 +133,26 @@ def test_exact_many_chunks_100k_docs(dev):
         _search_exact_case(dev, docs, queries, V, k, targets, chunk_docs=chunk)
 
 
+def _long_query_corpus():
+    """V = 1024, 300 docs, 3 queries: one of 300 terms (more than the 256 terms whose chunk bounds are staged at once and
+    more than the 64 a pair-score step looks up, so those loops run twice and more), one empty, one ordinary."""
+    rng = np.random.default_rng(23)
+    V = 1024
+    docs = _rows(rng, 300, V, 40, np.array([16, 32, 64]), common=7, empty_every=17)
+    queries = _rows(rng, 3, V, 12, np.array([16, 32, 64]))
+    t = np.sort(rng.choice(V, size=300, replace=False))
+    queries[0] = (t, rng.choice(np.array([16, 32, 64]), size=300).astype(np.float64) / 64.0)
+    queries[1] = (np.zeros(0, np.int64), np.zeros(0, np.float64))
+    return docs, queries, V
+
+
+@pytest.mark.parametrize("k", [1, 7])
+def test_exact_query_longer_than_one_staging_group(dev, k):
+    docs, queries, V = _long_query_corpus()
+    _, S, rr = _search_exact_case(dev, docs, queries, V, k, [5, 9, 0], chunk_docs=128)   # target 0: an empty doc
+    assert (S[0] > 0).sum() > 7 and rr[0] > 0 and rr[1] == 0 and rr[2] == 0
+
+
 # ------------------------------------------------------------------------------------------------ fp32 rounding
 def test_random_fp32_within_bound_of_float64(dev):
     rng = np.random.default_rng(3)
