@@ -436,6 +436,40 @@ int snx_ranked_relevance(const int32_t* docs, int32_t nq, int32_t R, int32_t nd,
 int snx_bootstrap_means(const double* values, int32_t n, int32_t M, const int32_t* idx, int32_t nboot, double* out,
                         hipStream_t stream);
 
+/* ---- exact dense retrieval (csrc/dense.hip): what the reference does with dense teacher embeddings -- the teacher
+ * scores of ref:scripts/precompute_teacher_scores.py:162-224, the hard-negative search of
+ * ref:scripts/mine_multi_negatives.py:141-222 (torch.mm into a [4096, n_docs] matrix, then torch.topk) and the
+ * SemanticSearcher of ref:benchmark/searchers.py:97-127.  No [nq, nd] score buffer exists here.
+ * Operands: docs E [nd, D] and queries Q [nq, D], fp32, row-major, every value finite; 1 <= D <= 4096; nd < 2^31.
+ * Score definition (part of the ABI, bit-reproducible): s(q,d) = fp32 acc starting at +0, acc = fmaf(Q[q,j], E[d,j], acc)
+ * for j = 0 .. D-1 ascending, then acc + 0.0f (a -0, which arises when a negative product underflows, becomes +0).  The
+ * search computes this chain on v_mfma_f32_32x32x2_f32, the pair scores by a serial fmaf loop: the same bits.  The
+ * results are defined while every partial sum stays finite.
+ * Order: score descending as real numbers, ties lowest doc id first.  EVERY doc is a candidate: negative and zero scores
+ * rank like any other (no score > 0 rule, unlike the sparse search).
+ * Search: per query the top k (1 <= k <= 1024) -> out_doc / out_score [nq,k]; unused slots (k > nd) doc -1, score 0.
+ * target [nq] (or NULL): out_tscore [nq] = s(q, target), bit-equal to the ranked value, out_rank [nq] = 1 + #{d: s_d >
+ * s_t} + #{d < t: s_d == s_t} (>= 1 for a target in [0, nd); 0 and score 0 for one out of range).  chunk_docs: docs per
+ * split of the doc range (0: default; otherwise >= 128, rounded up to a multiple of 128); neither it nor any slicing of
+ * the queries changes a bit.  workspace: snx_dense_search_workspace_bytes(nq, nd, k, chunk_docs) bytes -- it grows with
+ * nq * k * splits, never with nq * nd.
+ * Band search: exclusion rows and ceiling as for snx_sparse_search_band.  Doc d is ADMISSIBLE for q when it is not in
+ * the row and s(q,d) < ceiling[q] (strict, fp32; NULL or +inf admits all, a NaN ceiling nothing); ranks lo .. hi-1
+ * (0 <= lo < hi <= 1024) of the admissible docs go to out_doc / out_score [nq, hi-lo], unused slots doc -1, score 0;
+ * out_found [nq] = filled slots.  workspace: snx_dense_search_band_workspace_bytes(nq, nd, hi, chunk_docs) bytes.
+ * Pair scores: out[i] = s(pair_q[i], pair_d[i]); a pair with an index out of range scores 0. */
+size_t snx_dense_search_workspace_bytes(int32_t nq, int32_t nd, int32_t k, int32_t chunk_docs);
+int snx_dense_search(const float* Q, int32_t nq, const float* E, int32_t nd, int32_t D, const int32_t* target, int32_t k,
+                     int32_t chunk_docs, int32_t* out_doc, float* out_score, int32_t* out_rank, float* out_tscore,
+                     void* workspace, size_t ws_bytes, hipStream_t stream);
+size_t snx_dense_search_band_workspace_bytes(int32_t nq, int32_t nd, int32_t hi, int32_t chunk_docs);
+int snx_dense_search_band(const float* Q, int32_t nq, const float* E, int32_t nd, int32_t D, const int64_t* ex_ptr,
+                          const int32_t* ex_doc, const float* ceiling, int32_t lo, int32_t hi, int32_t chunk_docs,
+                          int32_t* out_doc, float* out_score, int32_t* out_found, void* workspace, size_t ws_bytes,
+                          hipStream_t stream);
+int snx_dense_pair_scores(const float* Q, int32_t nq, const float* E, int32_t nd, int32_t D, const int32_t* pair_q,
+                          const int32_t* pair_d, int64_t npairs, float* out, hipStream_t stream);
+
 /* ---- SPLADELossV33 (ref:src/model/losses.py:183-297) ------------------------------------- */
 /* dims [host] = {B, Bp, k, V, label_off, bf16_mm}: q [B,V], p [Bp,V] (Bp > B: all-gathered
  * positives for cross-GPU in-batch negatives, own rows start at label_off), n [B*k,V]; bf16_mm=1

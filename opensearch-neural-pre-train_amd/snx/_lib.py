@@ -118,6 +118,11 @@ SIGNATURES = {
     "snx_sparse_first_relevant": (I32, [P, P, P, I32, P, P, P, P, P, P, I32, I32, P, P, I32, P, P, P, P, P, SZ, P]),
     "snx_ranked_relevance": (I32, [P, I32, I32, I32, P, P, P, I32, P, P, P, P, P]),
     "snx_bootstrap_means": (I32, [P, I32, I32, P, I32, P, P]),
+    "snx_dense_search_workspace_bytes": (SZ, [I32, I32, I32, I32]),
+    "snx_dense_search": (I32, [P, I32, P, I32, I32, P, I32, I32, P, P, P, P, P, SZ, P]),
+    "snx_dense_search_band_workspace_bytes": (SZ, [I32, I32, I32, I32]),
+    "snx_dense_search_band": (I32, [P, I32, P, I32, I32, P, P, P, I32, I32, I32, P, P, P, P, SZ, P]),
+    "snx_dense_pair_scores": (I32, [P, I32, P, I32, I32, P, P, I64, P, P]),
     "snx_version": (I32, []),
     "snx_prof_enable": (I32, [I32]),
     "snx_prof_num_classes": (I32, []),

@@ -43,6 +43,9 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     # and for the relevance-judgment kernels that keep state in LDS (the score chunk; the bootstrap's per-thread column
     # sums, 16 float64 accumulators that must stay in registers); qr_ranked_kernel holds no LDS and is not listed
     "qrels.hip": ("qr_best_kernel", "qr_count_kernel", "qr_boot_kernel"),
+    # and for the dense search: 64 accumulator registers, the prefetched operands and the merge's sort buffer stay out of
+    # memory; dn_pair_kernel holds no LDS and is not listed
+    "dense.hip": ("dn_search_kernel", "dn_merge_kernel"),
 }
 
 # Kernels held to the global-load / vmcnt rule: nothing may touch a load's destination before a vmcnt wait that retires it.

@@ -17,7 +17,8 @@ serving path (csrc/two_phase.hip, include/snx.h "pruning and two-phase search").
 ``fuse_ranked`` are the lexical BM25 baseline under the model's tokenizer and the rank fusion of the reference's hybrid
 searchers (csrc/hybrid.hip, include/snx.h "BM25 baseline and rank fusion").  ``relevance_csr``,
 ``SparseIndex.first_relevant``, ``ranked_relevance`` and ``bootstrap_means`` score any of these searches against qrels with
-several relevant docs per query (csrc/qrels.hip, include/snx.h "relevance judgments")."""
+several relevant docs per query (csrc/qrels.hip, include/snx.h "relevance judgments").  ``DenseIndex`` is the exact
+inner-product search over dense fp32 embeddings (csrc/dense.hip, include/snx.h "exact dense retrieval")."""
 from __future__ import annotations
 
 import time
@@ -1028,3 +1029,177 @@ def bootstrap_means(values, n_bootstrap: int = 1000, seed: int = 42, device=None
         check(fn("snx_bootstrap_means")(_p(vals), int(n), int(M), _p(didx), nb, _p(out), _stream()),
               "snx_bootstrap_means")
     return out
+
+
+DENSE_DIM_MAX = 4096
+DENSE_CHUNK_MIN = 128                  # docs per split of the dense search, at least (one tile); rounded up to a multiple
+_DENSE_WS_BUDGET = 1 << 30             # bytes of dense search workspace per launch
+
+
+class DenseIndex:
+    """Exact inner-product search over dense fp32 embeddings on the GPU (csrc/dense.hip, include/snx.h "exact dense
+    retrieval"): the reference's SemanticSearcher, its teacher scores and its dense hard-negative search, with no
+    [nq, nd] score matrix.
+
+        index = DenseIndex(dim, device)
+        index.add(emb)                 # fp32 [n, dim] on the device; doc ids = order of addition
+        index.build()
+        scores, docs, rank, tscore = index.search(q, k, targets=None, chunk_docs=0)
+        scores, docs, found = index.search_band(q, lo, hi, exclude=None, ceiling=None, chunk_docs=0)
+        s = index.pair_scores(q, pairs)
+
+    s(q, d) is the fp32 fmaf chain over the dimensions in ascending order from +0 (then + 0.0); the order is score
+    descending, ties lowest doc id first, and EVERY doc is a candidate whatever the sign of its score.  Return types and
+    conventions are ``SparseIndex``'s (unused slots 0 / -1); results are bit-reproducible and independent of
+    ``chunk_docs`` and of how the queries are sliced.  Embeddings must be finite."""
+
+    def __init__(self, dim: int, device):
+        if isinstance(dim, bool) or not isinstance(dim, (int, np.integer)) or not 1 <= int(dim) <= DENSE_DIM_MAX:
+            raise ValueError(f"DenseIndex: dim must be an int in [1, {DENSE_DIM_MAX}]")
+        self.dim = int(dim)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._parts: List[torch.Tensor] = []
+        self.num_docs = 0
+        self.emb: Optional[torch.Tensor] = None
+
+    @property
+    def built(self) -> bool:
+        return self.emb is not None
+
+    def _rows(self, x, who: str, name: str) -> torch.Tensor:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"DenseIndex.{who}: {name} must be an fp32 tensor [n, {self.dim}]")
+        if x.device != self.device:
+            raise ValueError(f"DenseIndex.{who}: {name} must be on {self.device}")
+        if x.numel() and not bool(torch.isfinite(x).all()):
+            raise ValueError(f"DenseIndex.{who}: {name} must be finite")
+        return x.contiguous()
+
+    def add(self, emb: torch.Tensor) -> None:
+        e = self._rows(emb, "add", "emb")
+        if self.num_docs + e.shape[0] >= 2 ** 31:
+            raise ValueError("DenseIndex: doc ids are int32")
+        self._parts.append(e)
+        self.num_docs += int(e.shape[0])
+        self.emb = None                                       # a new batch invalidates a built index
+
+    def build(self) -> "DenseIndex":
+        if len(self._parts) == 1:
+            self.emb = self._parts[0]
+        else:
+            self.emb = torch.cat(self._parts) if self._parts else torch.zeros((0, self.dim), dtype=torch.float32,
+                                                                              device=self.device)
+            self._parts = [self.emb]
+        return self
+
+    def _check(self, who: str, chunk_docs) -> int:
+        if not self.built:
+            raise RuntimeError(f"DenseIndex.{who}: call build() first")
+        chunk_docs = int(chunk_docs)
+        if chunk_docs != 0 and not DENSE_CHUNK_MIN <= chunk_docs < 2 ** 31:
+            raise ValueError(f"DenseIndex.{who}: chunk_docs must be 0 (default) or at least {DENSE_CHUNK_MIN}")
+        return chunk_docs
+
+    def _slices(self, nq: int, sizing: str, k: int, chunk_docs: int, query_slice: int):
+        """(start, rows, workspace bytes) of the launches: slices of the workspace budget, or of ``query_slice``."""
+        if isinstance(query_slice, bool) or int(query_slice) < 0:
+            raise ValueError("DenseIndex: query_slice must be >= 0 (0: default)")
+        size = fn(sizing)
+        per_q = max(1, -(-int(size(max(nq, 1), self.num_docs, k, chunk_docs)) // max(nq, 1)))
+        step = max(1, min(max(nq, 1), _DENSE_WS_BUDGET // per_q))
+        if query_slice:
+            step = min(step, int(query_slice))
+        for s in range(0, nq, step):
+            m = min(step, nq - s)
+            yield s, m, int(size(m, self.num_docs, k, chunk_docs))
+
+    def search(self, q: torch.Tensor, k: int, targets: Optional[torch.Tensor] = None, chunk_docs: int = 0,
+               query_slice: int = 0
+               ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """``q`` fp32 [nq, dim] -> (scores [nq, k] fp32, docs [nq, k] int32, target_rank [nq] int32 | None,
+        target_score [nq] fp32 | None): the top k of ALL docs; given ``targets`` [nq], each target's 1-based rank under the
+        same order (always >= 1) and its score, bit-equal to the ranked value."""
+        chunk_docs = self._check("search", chunk_docs)
+        k = int(k)
+        if not 1 <= k <= K_MAX:
+            raise ValueError(f"DenseIndex.search: k must be in [1, {K_MAX}]")
+        q = self._rows(q, "search", "q")
+        nq, nd, dev = int(q.shape[0]), self.num_docs, self.device
+        tgt = None
+        if targets is not None:
+            if not isinstance(targets, torch.Tensor) or targets.device != dev or targets.dim() != 1 or \
+                    targets.numel() != nq or targets.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"DenseIndex.search: targets must be an int tensor [{nq}] on {dev}")
+            if nq and not bool(((targets >= 0) & (targets < nd)).all()):
+                raise ValueError(f"DenseIndex.search: targets must be doc ids in [0, {nd})")
+            tgt = targets.to(torch.int32).contiguous()
+        scores = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        docs = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        rank = torch.empty(nq, dtype=torch.int32, device=dev) if tgt is not None else None
+        tscore = torch.empty(nq, dtype=torch.float32, device=dev) if tgt is not None else None
+        with torch.cuda.device(dev):
+            for s, m, ws_bytes in self._slices(nq, "snx_dense_search_workspace_bytes", k, chunk_docs, query_slice):
+                ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+                check(fn("snx_dense_search")(
+                    _p(q[s:]), m, _p(self.emb), nd, self.dim, _p(None if tgt is None else tgt[s:]), k, chunk_docs,
+                    _p(docs[s:]), _p(scores[s:]), _p(None if rank is None else rank[s:]),
+                    _p(None if tscore is None else tscore[s:]), _p(ws), ws_bytes, _stream()), "snx_dense_search")
+        return scores, docs, rank, tscore
+
+    def search_band(self, q: torch.Tensor, lo: int, hi: int, exclude=None, ceiling: Optional[torch.Tensor] = None,
+                    chunk_docs: int = 0, query_slice: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Ranks ``lo .. hi-1`` (0-based) of each query's ADMISSIBLE docs -- not in ``exclude[q]``, score <
+        ``ceiling[q]`` (fp32, strict; +inf: none) -- -> (scores [nq, hi-lo] fp32, docs [nq, hi-lo] int32, found [nq]
+        int32); unused slots 0 / -1.  ``exclude`` and ``ceiling`` as for ``SparseIndex.search_band``."""
+        chunk_docs = self._check("search_band", chunk_docs)
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo < hi <= K_MAX:
+            raise ValueError(f"DenseIndex.search_band: need 0 <= lo < hi <= {K_MAX}")
+        q = self._rows(q, "search_band", "q")
+        nq, nd, dev = int(q.shape[0]), self.num_docs, self.device
+        ex_ptr = ex_doc = None
+        if exclude is not None:
+            ex_ptr, ex_doc = exclusion_csr(exclude, nq, nd, dev)
+            if ex_doc.numel() == 0:
+                ex_ptr = ex_doc = None
+        ceil = None
+        if ceiling is not None:
+            if not isinstance(ceiling, torch.Tensor) or ceiling.device != dev or ceiling.dtype != torch.float32 or \
+                    ceiling.dim() != 1 or ceiling.numel() != nq:
+                raise ValueError(f"DenseIndex.search_band: ceiling must be fp32 [{nq}] on {dev}")
+            if nq and bool(torch.isnan(ceiling).any()):
+                raise ValueError("DenseIndex.search_band: ceiling must not be NaN (+inf: no ceiling)")
+            ceil = ceiling.contiguous()
+        w = hi - lo
+        scores = torch.empty((nq, w), dtype=torch.float32, device=dev)
+        docs = torch.empty((nq, w), dtype=torch.int32, device=dev)
+        found = torch.empty(nq, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            for s, m, ws_bytes in self._slices(nq, "snx_dense_search_band_workspace_bytes", hi, chunk_docs, query_slice):
+                ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+                check(fn("snx_dense_search_band")(
+                    _p(q[s:]), m, _p(self.emb), nd, self.dim, _p(None if ex_ptr is None else ex_ptr[s:]), _p(ex_doc),
+                    _p(None if ceil is None else ceil[s:]), lo, hi, chunk_docs, _p(docs[s:]), _p(scores[s:]),
+                    _p(found[s:]), _p(ws), ws_bytes, _stream()), "snx_dense_search_band")
+        return scores, docs, found
+
+    def pair_scores(self, q: torch.Tensor, pairs: torch.Tensor) -> torch.Tensor:
+        """``pairs`` int [n, 2] of (query row, doc id) -> s(q, d) fp32 [n], bit-equal to the scores the searches rank."""
+        self._check("pair_scores", 0)
+        q = self._rows(q, "pair_scores", "q")
+        nq, nd, dev = int(q.shape[0]), self.num_docs, self.device
+        if not isinstance(pairs, torch.Tensor) or pairs.device != dev or pairs.dim() != 2 or pairs.shape[1] != 2 or \
+                pairs.is_floating_point():
+            raise ValueError(f"DenseIndex.pair_scores: pairs must be an int tensor [n, 2] on {dev}")
+        n = int(pairs.shape[0])
+        if n and not bool(((pairs[:, 0] >= 0) & (pairs[:, 0] < nq) & (pairs[:, 1] >= 0) & (pairs[:, 1] < nd)).all()):
+            raise ValueError(f"DenseIndex.pair_scores: pairs must be (query in [0, {nq}), doc in [0, {nd}))")
+        pq = pairs[:, 0].to(torch.int32).contiguous()
+        pd = pairs[:, 1].to(torch.int32).contiguous()
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            check(fn("snx_dense_pair_scores")(_p(q), nq, _p(self.emb), nd, self.dim, _p(pq), _p(pd), n, _p(out),
+                                               _stream()), "snx_dense_pair_scores")
+        return out

@@ -2,7 +2,7 @@
 (snx.retrieval.Bm25Index / fuse_ranked).
 
     python -m src.train.cli.eval_hybrid --checkpoint outputs/train_v33/final_model --val-file data/val.jsonl \\
-        [--sweep] [--dense-run dense.npz]
+        [--sweep] [--dense-run dense.npz | --dense-embeddings emb.npz]
 
 One JSON line per method: ``sparse`` (the model's exact search), ``bm25`` (BM25 over the same token ids: the model's
 tokenizer, the evaluator's truncation and vocabulary filter; not OpenSearch's analyzer) and ``bm25_sparse_rrf``.
@@ -10,7 +10,10 @@ tokenizer, the evaluator's truncation and vocabulary filter; not OpenSearch's an
 0.4 / 0.5 and weighted RRF 0.4 / 0.6.  ``--dense-run`` takes a dense retriever's top lists produced elsewhere -- an .npz
 with ``docs`` int [nq, R] (ids in the evaluator's doc order, -1: unused) and ``scores`` float [nq, R] -- and adds
 ``dense``, ``bm25_dense_rrf``, ``dense_sparse_rrf`` and ``triple_rrf``: the seven rows of
-ref:scripts/run_7way_benchmark.py (the dense encoder itself is not part of this project).  Every retriever contributes
+ref:scripts/run_7way_benchmark.py (the dense encoder itself is not part of this project).  ``--dense-embeddings`` takes
+the embeddings instead -- an .npz with ``docs`` fp32 [nd, D] and ``queries`` fp32 [nq, D] in the evaluator's corpus order
+-- and runs the reference's SemanticSearcher (inner product, ref:benchmark/searchers.py:97-127) here, exactly, on
+snx.retrieval.DenseIndex at the retrieval depth; the two flags exclude each other.  Every retriever contributes
 its top 100 (--retrieval-k) and a fused list returns the top 10.  Each line carries the metrics, the mean union size of
 fused rows and the paired t-test against ``bm25``.  One process (not torchrun)."""
 from __future__ import annotations
@@ -46,8 +49,12 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     ap.add_argument("--b", type=float, default=0.75)
     ap.add_argument("--sweep", action="store_true", help="the reference's linear / weighted-RRF grid over BM25 + sparse")
     ap.add_argument("--dense-run", type=str, default=None, help=".npz with docs [nq, R] and scores [nq, R] of a dense run")
+    ap.add_argument("--dense-embeddings", type=str, default=None,
+                    help=".npz with docs [nd, D] and queries [nq, D] (fp32, corpus order): the dense search runs here")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON lines to this file")
     args = ap.parse_args(argv)
+    if args.dense_run and args.dense_embeddings:
+        ap.error("--dense-run and --dense-embeddings exclude each other")
     if not 1 <= args.retrieval_k <= 1024:
         ap.error("--retrieval-k must lie in [1, 1024]")
     if not args.rrf_k >= 0 or not args.k1 >= 0 or not 0 <= args.b <= 1:
@@ -62,7 +69,7 @@ def rows(args: argparse.Namespace) -> List[Tuple[str, Optional[str], dict, Tuple
            ("bm25_sparse_rrf", "rrf", rrf, ("bm25", "sparse"))]
     if args.sweep:
         out += [(name, method, dict(params), ("bm25", "sparse")) for name, method, params in SWEEP]
-    if args.dense_run:
+    if args.dense_run or args.dense_embeddings:
         out += [("dense", None, {}, ("dense",)), ("bm25_dense_rrf", "rrf", rrf, ("bm25", "dense")),
                 ("dense_sparse_rrf", "rrf", rrf, ("dense", "sparse")),
                 ("triple_rrf", "rrf", rrf, ("bm25", "dense", "sparse"))]       # ref:benchmark/hybrid_searcher.py:517-521
@@ -79,6 +86,23 @@ def load_dense_run(path: str, nq: int, nd: int, depth: int, device):
         raise ValueError(f"{path}: docs and scores must both be [{nq}, R]")
     docs = np.where((docs >= 0) & (docs < nd), docs, -1)[:, :depth].astype(np.int32)
     return torch.from_numpy(docs).to(device), torch.from_numpy(scores[:, :depth].astype(np.float32)).to(device)
+
+
+def search_dense_embeddings(path: str, nq: int, nd: int, depth: int, device):
+    """The dense top lists from embeddings: an exact inner-product search of every query over every doc -> (docs int32
+    [nq, depth], scores fp32 [nq, depth]) on ``device`` (unused slots -1 / 0 when depth > nd)."""
+    import numpy as np
+    import torch
+    from snx.retrieval import DenseIndex
+    z = np.load(path)
+    docs, queries = np.asarray(z["docs"]), np.asarray(z["queries"])
+    if docs.ndim != 2 or queries.ndim != 2 or docs.shape[0] != nd or queries.shape != (nq, docs.shape[1]):
+        raise ValueError(f"{path}: need docs [{nd}, D] and queries [{nq}, D]")
+    index = DenseIndex(int(docs.shape[1]), device)
+    index.add(torch.from_numpy(np.ascontiguousarray(docs, dtype=np.float32)).to(device))
+    index.build()
+    scores, ids, _, _ = index.search(torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32)).to(device), depth)
+    return ids, scores
 
 
 def list_ranks(docs, targets):
@@ -117,6 +141,8 @@ def main(argv: Optional[List[str]] = None) -> List[dict]:
     found["bm25"] = (d, s)
     if args.dense_run:
         found["dense"] = load_dense_run(args.dense_run, nq, nd, depth, device)
+    if args.dense_embeddings:
+        found["dense"] = search_dense_embeddings(args.dense_embeddings, nq, nd, depth, device)
     ranks, totals = {}, {}
     for name, method, params, members in rows(args):
         if method is None:

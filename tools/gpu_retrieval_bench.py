@@ -8,6 +8,7 @@ csrc/retrieval.hip) on synthetic Zipf-skewed data.
     python tools/gpu_retrieval_bench.py --two-phase [--sizes 100000x10000,1000000x10000]
     python tools/gpu_retrieval_bench.py --hybrid [--sizes 100000x10000,1000000x10000]
     python tools/gpu_retrieval_bench.py --qrels [--sizes 100000x2000,1000000x2000]
+    python tools/gpu_retrieval_bench.py --dense [--dense-docs N] [--dense-reps 5]
 
 Docs draw 128 terms (with replacement, duplicates dropped: ~99 distinct) from a Zipf(1.0) law over V = 50000 with
 weights uniform in [0.1, 3); queries draw 64 the same way (~53 distinct).  Retrieval size 10 with a target per query
@@ -40,7 +41,16 @@ relevant docs (mean 4.5), medians of 5 after a warm-up.  SparseIndex.first_relev
 search(k = 1, targets=...) per row position and the minimum of the ranks on the host.  ranked_relevance over the search's
 top 100 against the reference's Python set loop over the same lists on the host (transfer included, first 2000 queries).
 bootstrap_means (1000 resamples, 3 columns; the host-side index draws timed apart) against the reference-style numpy loop,
-one fancy-indexed mean per resample and column."""
+one fancy-indexed mean per resample and column.
+
+--dense: the exact dense search (snx.retrieval.DenseIndex, csrc/dense.hip) at the reference miner's shape, nq = 4096,
+D = 1024, k = 100, over a synthetic L2-normalised Gaussian corpus, against the reference's own form on the same GPU:
+torch.mm(q_batch[4096, D], docs.T) + torch.topk(100) in 4096-query batches (ref:scripts/mine_multi_negatives.py:208-210).
+The corpus is as large as that form's [4096, nd] fp32 score matrix allows (--dense-docs 0: a quarter of the free device
+memory for the matrix, at most 2^22 docs; a multiple of 128).  After a warm-up of both, the two alternate --dense-reps
+times; the row holds every time, the medians, the spread (max - min over the median) and ratio = torch median / ours.
+It also checks that the two top lists agree (same doc at every rank where the neighbouring scores differ by more than the
+fp32 rounding of the sums)."""
 import argparse
 import json
 import os
@@ -401,6 +411,49 @@ def miner_case(n_records, dev):
             "docs_per_s": summ["docs"] / t, "queries_per_s": summ["queries"] / t, "band_fill": summ["band_fill"]}
 
 
+def dense_case(nd, dev, nq=4096, D=1024, k=100, reps=5):
+    import statistics
+    from snx.retrieval import DenseIndex
+    gen = torch.Generator(device=dev).manual_seed(7)
+    if nd <= 0:
+        free, _ = torch.cuda.mem_get_info(dev)
+        nd = min(1 << 22, int(free // 4 // (4 * nq)))
+    nd = max(128, nd // 128 * 128)
+    docs = torch.nn.functional.normalize(torch.randn(nd, D, generator=gen, device=dev), dim=1)
+    q = torch.nn.functional.normalize(torch.randn(nq, D, generator=gen, device=dev), dim=1)
+    t_build, idx = sync_time(lambda: (lambda i: (i.add(docs), i.build())[1])(DenseIndex(D, dev)))
+
+    def ours():
+        return idx.search(q, k)
+
+    def ref():
+        out = []
+        for s in range(0, nq, 4096):
+            out.append(torch.topk(torch.mm(q[s:s + 4096], docs.T), k, dim=1))
+        return torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out])
+
+    sync_time(ours)
+    sync_time(ref)
+    t_ours, t_ref = [], []
+    for _ in range(reps):
+        t, (sc, dc, _, _) = sync_time(ours)
+        t_ours.append(t)
+        t, (rs, rd) = sync_time(ref)
+        t_ref.append(t)
+    # same lists: torch's sums round in another order, so only ranks whose neighbours are further apart than that count
+    gap = torch.minimum((rs[:, :-1] - rs[:, 1:]).abs()[:, :-1], (rs[:, 1:] - rs[:, 2:]).abs())
+    clear = gap > 1e-5
+    agree = float((dc[:, 1:-1].long() == rd[:, 1:-1])[clear].float().mean()) if bool(clear.any()) else 1.0
+    mo, mr = statistics.median(t_ours), statistics.median(t_ref)
+    flop = 2.0 * nq * nd * D
+    return {"dense": {"nd": nd, "nq": nq, "D": D, "k": k, "build_s": t_build, "search_s": t_ours, "torch_mm_topk_s": t_ref,
+                      "search_median_s": mo, "torch_median_s": mr, "search_spread": (max(t_ours) - min(t_ours)) / mo,
+                      "torch_spread": (max(t_ref) - min(t_ref)) / mr, "ratio_torch_over_ours": mr / mo,
+                      "search_tflops": flop / mo / 1e12, "torch_tflops": flop / mr / 1e12,
+                      "score_matrix_bytes_avoided": 4 * min(nq, 4096) * nd, "max_abs_score_diff": float((sc - rs).abs().max()),
+                      "rank_agreement_where_clear": agree}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000x200,100000x10000,1000000x10000")
@@ -412,9 +465,19 @@ def main():
     ap.add_argument("--two-phase", action="store_true", help="search_two_phase, the prune kernel and pruned() vs search")
     ap.add_argument("--hybrid", action="store_true", help="Bm25Index build and search, fuse_ranked vs Python dicts")
     ap.add_argument("--qrels", action="store_true", help="first_relevant, ranked_relevance, bootstrap_means vs host loops")
+    ap.add_argument("--dense", action="store_true", help="DenseIndex.search vs torch.mm + topk at nq 4096, D 1024, k 100")
+    ap.add_argument("--dense-docs", type=int, default=0, help="corpus size (0: what the torch form's score matrix allows)")
+    ap.add_argument("--dense-reps", type=int, default=5)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     rows = []
+    if args.dense:
+        rows.append(dense_case(args.dense_docs, dev, reps=args.dense_reps))
+        print(json.dumps(rows[-1]), flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump({"device": torch.cuda.get_device_name(0), "rows": rows}, f, indent=1)
+        return
     if args.qrels:
         sizes = args.sizes if args.sizes != ap.get_default("sizes") else "100000x2000,1000000x2000"
         for s in sizes.split(","):
