@@ -17,7 +17,7 @@
 //                      << 32 | ~doc) are sorted descending in LDS as sr_merge_kernel does, equal neighbours (a doc given
 //                      twice) collapse, and the first k distinct keys are written in order.
 // Two-phase search = snx_sparse_search over the pruned query rows with k = W, then tp_rescore_kernel with the full
-// rows (snx/retrieval.py SparseIndex.search_two_phase).  No float atomics: byte-identical from run to run.
+// rows (snx/retrieval/sparse.py SparseIndex.search_two_phase).  No float atomics: byte-identical from run to run.
 #include <math.h>
 
 // row_dot, the rank key and bitonic_desc come from sparse_common.h.

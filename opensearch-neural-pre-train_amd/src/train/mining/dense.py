@@ -159,9 +159,10 @@ def mine_dense_negatives(input_files: Sequence[str], output_dir: str, embeddings
     """Mine ``k`` negatives per record from ranks [rank_start, rank_end) of the teacher's dense search and write one file
     per shard to ``output_dir``.  ``index``: an empty dense index; it receives the embedded docs of the corpus.  Returns
     the summary: records, queries, docs, indexed_docs, band_fill, padded, fallback, unchanged."""
+    from snx.retrieval import K_MAX
     k, rank_start, rank_end = int(k), int(rank_start), int(rank_end)
-    if k < 1 or not 0 <= rank_start < rank_end <= 1024:
-        raise ValueError("dense mining: need k >= 1 and 0 <= rank_start < rank_end <= 1024")
+    if k < 1 or not 0 <= rank_start < rank_end <= K_MAX:
+        raise ValueError(f"dense mining: need k >= 1 and 0 <= rank_start < rank_end <= {K_MAX}")
     if sample not in ("first", "random"):
         raise ValueError("dense mining: sample is 'first' or 'random'")
     c = build_corpus(input_files)

@@ -211,7 +211,8 @@ def seismic_case(nd, nq, dev, k=10, top_n=10):
 
 def two_phase_case(nd, nq, dev, k=10, reps=5):
     from statistics import median
-    from snx.retrieval import PRUNE_TYPES, SparseIndex, _keep_flags
+    from snx.retrieval import PRUNE_TYPES, SparseIndex
+    from snx.retrieval.sparse import _keep_flags
     from src.train.eval import overlap_at
     gen = torch.Generator().manual_seed(nd + nq)
     probs = 1.0 / torch.arange(1, V + 1, dtype=torch.float64)
