@@ -470,6 +470,44 @@ int snx_dense_search_band(const float* Q, int32_t nq, const float* E, int32_t nd
 int snx_dense_pair_scores(const float* Q, int32_t nq, const float* E, int32_t nd, int32_t D, const int32_t* pair_q,
                           const int32_t* pair_d, int64_t npairs, float* out, hipStream_t stream);
 
+/* ---- MinHash near-duplicate removal (csrc/minhash.hip): the reference's MinHashDeduplicator
+ * (ref:src/preprocessing/cleaners/deduplicator.py:10-187), whose two Python loops -- num_perm MD5 digests per character
+ * n-gram (ref:deduplicator.py:71-80) and every new row against every kept row (ref:deduplicator.py:135-138) -- keep the
+ * reference's own pipeline from using it (ref:src/preprocessing/pipeline.py:112).  Everything here is integer work and
+ * every result equals the reference's bit for bit.
+ * Signatures: rows are a CSR of Unicode code points, ptr [n+1] int64 and code_points int32, already lowered and stripped
+ * by the host (ref:deduplicator.py:50).  The n-grams of a row are its windows of ngram_size code points; a row shorter
+ * than ngram_size, the empty one included, has the single n-gram that is the whole row (ref:deduplicator.py:51-52).
+ * sig [n, num_perm, 4] uint32: entry i is the minimum over the n-grams of int(md5(f"{i}_{ngram}".encode()).hexdigest(),
+ * 16) (ref:deduplicator.py:76-77), the 128-bit digest read big-endian, stored MOST SIGNIFICANT WORD FIRST: comparing the
+ * four words in order is the integer comparison.  The kernel encodes UTF-8, writes the decimal prefix, pads ONE 64-byte
+ * MD5 block and hashes it.  Precondition: every message (prefix, underscore and the n-gram's UTF-8 bytes) is at most
+ * SNX_MINHASH_MSG_MAX = 55 bytes; a longer one is hashed truncated (nothing is read or written out of bounds, the value
+ * is unspecified) -- snx.minhash computes the batch's longest message and refuses it.  1 <= num_perm <=
+ * SNX_MINHASH_PERM_MAX = 256 (prefixes of at most three digits), ngram_size >= 1; otherwise SNX_E_SHAPE.
+ * Greedy removal (ref:deduplicator.py:112-144, 164-168): rows are taken in order; row i is a DUPLICATE iff an earlier
+ * KEPT row has the same exact-key group, or an earlier KEPT row's signature equals its own at `need` positions or more
+ * (all 128 bits of a position); dropped rows are never compared against.  `need` is the host's integer form of
+ * `matches / num_perm >= threshold` (need <= 0: every kept row matches; need > num_perm: none does).  group [n] int32 or
+ * NULL: the host's id in [0, n) of the row's exact key (ref:deduplicator.py:109-110).  duplicate_of [n] int32: -1 for a
+ * kept row; for a dropped one the kept row with its group when there is one, otherwise the smallest kept index that
+ * reaches `need` -- the first row the reference's loop meets.  The order dependence is resolved in blocks of 512 rows: one
+ * launch compares a block with the kept rows of all earlier blocks (compacted) and with itself, one workgroup then walks
+ * the block in order.  A 32-bit prefilter on the least significant word picks candidates; the count over all 128 bits
+ * decides.  Stream-ordered, no host synchronisation, no kernel waits for another workgroup.
+ * workspace: snx_minhash_dedup_workspace_bytes(n, num_perm) bytes.
+ * First match (the incremental form, ref:deduplicator.py:112-144 called row by row): q_sig [nq, num_perm, 4] against
+ * kept_sig [nk, num_perm, 4] -> out [nq] int32 = the smallest k whose signature reaches `need`, -1 when none; nq <= 65535. */
+#define SNX_MINHASH_MSG_MAX 55
+#define SNX_MINHASH_PERM_MAX 256
+int snx_minhash_signatures(const int64_t* ptr, const int32_t* code_points, int32_t n, int32_t ngram_size,
+                           int32_t num_perm, uint32_t* sig, hipStream_t stream);
+size_t snx_minhash_dedup_workspace_bytes(int32_t n, int32_t num_perm);
+int snx_minhash_dedup(const uint32_t* sig, int32_t n, int32_t num_perm, int32_t need, const int32_t* group,
+                      int32_t* duplicate_of, void* workspace, size_t ws_bytes, hipStream_t stream);
+int snx_minhash_first_match(const uint32_t* q_sig, int32_t nq, const uint32_t* kept_sig, int32_t nk, int32_t num_perm,
+                            int32_t need, int32_t* out, hipStream_t stream);
+
 /* ---- SPLADELossV33 (ref:src/model/losses.py:183-297) ------------------------------------- */
 /* dims [host] = {B, Bp, k, V, label_off, bf16_mm}: q [B,V], p [Bp,V] (Bp > B: all-gathered
  * positives for cross-GPU in-batch negatives, own rows start at label_off), n [B*k,V]; bf16_mm=1

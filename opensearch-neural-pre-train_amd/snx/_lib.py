@@ -123,6 +123,10 @@ SIGNATURES = {
     "snx_dense_search_band_workspace_bytes": (SZ, [I32, I32, I32, I32]),
     "snx_dense_search_band": (I32, [P, I32, P, I32, I32, P, P, P, I32, I32, I32, P, P, P, P, SZ, P]),
     "snx_dense_pair_scores": (I32, [P, I32, P, I32, I32, P, P, I64, P, P]),
+    "snx_minhash_signatures": (I32, [P, P, I32, I32, I32, P, P]),
+    "snx_minhash_dedup_workspace_bytes": (SZ, [I32, I32]),
+    "snx_minhash_dedup": (I32, [P, I32, I32, I32, P, P, P, SZ, P]),
+    "snx_minhash_first_match": (I32, [P, I32, P, I32, I32, I32, P, P]),
     "snx_version": (I32, []),
     "snx_prof_enable": (I32, [I32]),
     "snx_prof_num_classes": (I32, []),
