@@ -43,6 +43,11 @@ typedef struct ihipStream_t* hipStream_t;
 #define SNX_E_SHAPE (-2)
 #define SNX_E_ARG (-3)
 #define SNX_FWD_SAVE_FOR_BACKWARD 1
+/* The caller does not need token_weights (a trainer whose loss reads the pooled vectors only): the decoder runs without
+ * the row half of its epilogue and without the token_weights pass.  `token_weights` (may be NULL) and the arena's token
+ * keys are NOT written, `sparse`, the saved keys and every gradient keep their bits; the arena is sized by
+ * snx_model_workspace_bytes_fwd (no row maxima).  A backward handed a g_token_weights for such an arena returns SNX_E_ARG. */
+#define SNX_FWD_NO_TOKEN_WEIGHTS 2
 
 /* Architecture constants (ref:huggingface/v33/config.json; hf configuration_modernbert.py:113-162).
  * layer l is a global-attention layer iff l % global_every == 0; `window` is the HALF window
@@ -72,6 +77,9 @@ int snx_weight_cache_refresh(const snx_model_desc* d, const void* const* params 
 
 /* Activation arena size for one forward over T token rows (save_for_bwd=0: inference plan). */
 size_t snx_model_workspace_bytes(const snx_model_desc* d, int32_t T, int32_t nseq, int32_t save_for_bwd);
+/* ... for a forward called with `flags` (SNX_FWD_*): smaller with SNX_FWD_NO_TOKEN_WEIGHTS, else the size above.  Every
+ * offset below is the same in both. */
+size_t snx_model_workspace_bytes_fwd(const snx_model_desc* d, int32_t T, int32_t nseq, int32_t flags);
 size_t snx_model_bwd_workspace_bytes(const snx_model_desc* d, int32_t T, int32_t nseq, int32_t max_seqlen);
 /* byte offset, inside a save_for_bwd arena, of the packed arg-max keys u32 [nseq, vocab]
  * (bf16 bits of relu(logit) << 16 | 0xFFFF - row): lets a caller inspect the max-pool routing. */
@@ -700,6 +708,15 @@ int snx_decoder_splade_fwd_rec(const void* Hd, const void* W, const float* bias,
                                const int64_t* mask, float* sparse, uint32_t* keys, float* token_weights,
                                uint32_t* token_keys, void* scratch, int32_t T, int32_t nseq, int32_t max_seqlen, int32_t V,
                                int32_t K, int32_t finalize, hipStream_t stream);
+/* snx_decoder_splade_fwd_rec with forward flags (SNX_FWD_*; 0: exactly that entry point).  SNX_FWD_NO_TOKEN_WEIGHTS:
+ * `sparse` and `keys` with the same bits, the kernels without the row half of their epilogue, no token_weights pass;
+ * token_weights and token_keys are not written (may be NULL), `finalize` means nothing, and `scratch` needs only
+ * snx_splade_head_scratch_bytes_notw(T) bytes (the row tables of the 256x192 form, no row maxima). */
+size_t snx_splade_head_scratch_bytes_notw(int32_t T);
+int snx_decoder_splade_fwd_flags(const void* Hd, const void* W, const float* bias, const int32_t* cu_seqlens,
+                                 const int64_t* mask, float* sparse, uint32_t* keys, float* token_weights,
+                                 uint32_t* token_keys, void* scratch, int32_t T, int32_t nseq, int32_t max_seqlen, int32_t V,
+                                 int32_t K, int32_t finalize, int32_t flags, hipStream_t stream);
 /* arg-max-routed backward: dHd [T,H] bf16 (overwritten), gradE [V,H] += , gradb [V] += ;
  * scratch: snx_splade_bwd_scratch_bytes() bytes (per-row bucket lists). */
 size_t snx_splade_bwd_scratch_bytes(int32_t nseq, int32_t max_seqlen, int32_t V);

@@ -15,6 +15,11 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 #define SNX_E_SHAPE (-2)     // operand shapes do not satisfy the kernel's tiling assumptions
 #define SNX_E_ARG (-3)       // null / inconsistent argument
 
+// what the fused decoder kernels (splade_head.hip, decoder256.hip) do with the per-token ROW maxima, the token_weights half
+// of their epilogue: u16 value bits (inference), column-tagged u32 keys (training forwards that keep token_weights
+// differentiable), or nothing at all (training forwards whose caller drops token_weights: SNX_FWD_NO_TOKEN_WEIGHTS)
+constexpr int RM_BITS = 0, RM_KEYS = 1, RM_NONE = 2;
+
 #define SNX_CHECK_LAUNCH()                                   \
   do {                                                       \
     hipError_t e__ = hipGetLastError();                      \

@@ -4,6 +4,7 @@
 //   key[b, v]   = max over the valid rows s of sequence b of  bf16bits(relu(Hd[b,s,:] . W[v,:] + bias[v])) << 16 | 0xFFFF - s
 //   sparse[b,v] = log1p(value(key));   rowpart[2 nt + wn, t] = max over the 96 columns of half tile (nt, wn) of the value bits
 //   (REC, training forwards: of the column-tagged keys value bits << 16 | 0xFFFF - v, u32; see decoder_splade_kernel)
+//   (RM_NONE, training forwards that drop token_weights: no rowpart at all)
 //
 // The 128x128 kernel (one workgroup per (sequence, vocab tile), two per CU) runs at 0.27 of the MFMA peak: K = 768
 // gives every 128-row chunk a pipeline start-up of its own, and the operand tiles cross the L2 -> LDS path at 65
@@ -138,7 +139,8 @@ struct DecArgs {
   const i32x4* subtab;               // sub-tiles (pre-pass 2)
   const int32_t* hdr;                // hdr[0] = number of sub-tiles
   uint32_t* keys;                    // [nseq, V], zeroed
-  void* rowpart;                     // [2 * ceil(V / 192), T]: one row per 96-column half tile (u16; REC: u32 keys)
+  void* rowpart;                     // [2 * ceil(V / 192), T]: one row per 96-column half tile (u16; REC: u32 keys;
+                                     // RM_NONE: never touched)
   int T, V, K, ntn;                  // ntn = ceil(V / 192)
 };
 
@@ -211,8 +213,11 @@ extern "C" int snx_dec256_trace_set(void* buf) {
 }
 #endif
 
-template <bool REC>
+// RM (common.h): what the epilogue does with the row maxima.  RM_NONE has no row half at all: no row keys, no row-maximum
+// chain, no token-row request, no rowpart store; the column half (packed keys, ties, bias) is the same arithmetic in all three.
+template <int RM>
 __global__ __launch_bounds__(256) void decoder256_kernel(DecArgs g) {
+  constexpr bool REC = RM == RM_KEYS, ROWS = RM != RM_NONE;
 #ifdef SNX_GEMM_TRACE
   const unsigned long long tr_c0 = __builtin_amdgcn_s_memtime(), tr_r0 = __builtin_amdgcn_s_memrealtime();
   unsigned long long tr_epi = 0, tr_tiles = 0;
@@ -366,14 +371,16 @@ __global__ __launch_bounds__(256) void decoder256_kernel(DecArgs g) {
       const int col0 = cp_tile.nt * TV + wn * 96 + (lane & 31);
 #pragma unroll
       for (int j = 0; j < NJ; ++j) pre_bias[j] = col0 + 32 * j < g.V ? g.bias[col0 + 32 * j] : -3.0e38f;
-      const int myrr = 8 * ((lane & 15) >> 2) + 4 * (lane >> 5) + (lane & 3);
+      if (ROWS) {
+        const int myrr = 8 * ((lane & 15) >> 2) + 4 * (lane >> 5) + (lane & 3);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int sub = cp_tile.mt * 8 + wm * 4 + i;
-        pre_tok[i] = -1;
-        if (sub < nsub) {
-          const i32x4 e = g.subtab[sub];
-          if ((lane & 16) && myrr < e[3]) pre_tok[i] = e[1] + g.list[e[1] + e[2] + myrr];
+        for (int i = 0; i < 4; ++i) {
+          const int sub = cp_tile.mt * 8 + wm * 4 + i;
+          pre_tok[i] = -1;
+          if (sub < nsub) {
+            const i32x4 e = g.subtab[sub];
+            if ((lane & 16) && myrr < e[3]) pre_tok[i] = e[1] + g.list[e[1] + e[2] + myrr];
+          }
         }
       }
     }
@@ -467,14 +474,16 @@ __global__ __launch_bounds__(256) void decoder256_kernel(DecArgs g) {
               c1[j] = (int32_t)((w & 0xFFFF0000u) | ctag[j]);
             }
           }
-          // without REC: a row's keys share their tag, so the row maximum of the keys is (max value bits) << 16 | tag
-          const int32_t r0 = REC ? half_max(max(max(max(c0[0], c0[1]), c0[2]), 0)) : half_max(max(max(max(k0[0], k0[1]), k0[2]), 0));
-          const int32_t r1 = REC ? half_max(max(max(max(c1[0], c1[1]), c1[2]), 0)) : half_max(max(max(max(k1[0], k1[1]), k1[2]), 0));
-          mine = (lane & 15) == v ? r0 : mine;
-          mine = (lane & 15) == v + 1 ? r1 : mine;
+          if (ROWS) {                                 // (RM_NONE: the column half above is all there is)
+            // without REC: a row's keys share their tag, so the row maximum of the keys is (max value bits) << 16 | tag
+            const int32_t r0 = REC ? half_max(max(max(max(c0[0], c0[1]), c0[2]), 0)) : half_max(max(max(max(k0[0], k0[1]), k0[2]), 0));
+            const int32_t r1 = REC ? half_max(max(max(max(c1[0], c1[1]), c1[2]), 0)) : half_max(max(max(max(k1[0], k1[1]), k1[2]), 0));
+            mine = (lane & 15) == v ? r0 : mine;
+            mine = (lane & 15) == v + 1 ? r1 : mine;
+          }
           if ((v & 6) == 6) __builtin_amdgcn_sched_barrier(0);   // bound the window: four rows' worth of temporaries
         }
-        if (tok[i] >= 0) {
+        if (ROWS && tok[i] >= 0) {
           if (REC) ((uint32_t*)g.rowpart)[(long)t96 * g.T + tok[i]] = (uint32_t)mine;
           else ((unsigned short*)g.rowpart)[(long)t96 * g.T + tok[i]] = (unsigned short)(mine >> 16);
         }
@@ -523,10 +532,11 @@ size_t snx_dec256_table_bytes(int32_t T) { return (size_t)T * 4 + (size_t)T * 4 
 
 int snx_launch_decoder256(const void* Hd, const void* W, const float* bias, const int32_t* cu_seqlens,
                           const int64_t* mask, float* sparse, uint32_t* keys, void* scratch, size_t rowpart_bytes,
-                          int32_t T, int32_t nseq, int32_t V, int32_t K, bool rec, hipStream_t st) {
+                          int32_t T, int32_t nseq, int32_t V, int32_t K, int rm, hipStream_t st) {
   if ((K % 64) || T <= 0 || nseq <= 0 || V <= 0 || (long)T * K * 2 >= (1L << 32) || (long)V * K * 2 >= (1L << 32))
     return SNX_E_SHAPE;
   if (NJ != 3) return SNX_E_SHAPE;                    // the DMA / read schedule of the K loop is written for NJ = 3
+  if (rm != RM_BITS && rm != RM_KEYS && rm != RM_NONE) return SNX_E_ARG;
   char* base = (char*)scratch + ((rowpart_bytes + 255) & ~(size_t)255);
   int32_t* list = (int32_t*)base;
   int32_t* nvalid = list + T;
@@ -538,20 +548,22 @@ int snx_launch_decoder256(const void* Hd, const void* W, const float* bias, cons
   SNX_CHECK_LAUNCH();
   hipError_t e = hipMemsetAsync(keys, 0, (size_t)nseq * V * 4, st);
   if (e != hipSuccess) return (int)e;
-  static bool attr[2][64] = {};
+  static bool attr[3][64] = {};
   int devid = 0;
   if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return SNX_E_ARG;
-  if (!attr[rec][devid]) {
-    e = hipFuncSetAttribute(rec ? (const void*)decoder256_kernel<true> : (const void*)decoder256_kernel<false>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, RING * SLOT);
+  const void* kern = rm == RM_KEYS ? (const void*)decoder256_kernel<RM_KEYS>
+                     : rm == RM_NONE ? (const void*)decoder256_kernel<RM_NONE> : (const void*)decoder256_kernel<RM_BITS>;
+  if (!attr[rm][devid]) {
+    e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, RING * SLOT);
     if (e != hipSuccess) return (int)e;
-    attr[rec][devid] = true;
+    attr[rm][devid] = true;
   }
   DecArgs g;
   g.Hd = (const bf16_t*)Hd; g.W = (const bf16_t*)W; g.bias = bias; g.list = list; g.subtab = subtab; g.hdr = hdr;
   g.keys = keys; g.rowpart = scratch; g.T = T; g.V = V; g.K = K; g.ntn = cdiv(V, TV);
-  if (rec) hipLaunchKernelGGL(decoder256_kernel<true>, dim3(NWG), dim3(256), RING * SLOT, st, g);
-  else hipLaunchKernelGGL(decoder256_kernel<false>, dim3(NWG), dim3(256), RING * SLOT, st, g);
+  if (rm == RM_KEYS) hipLaunchKernelGGL(decoder256_kernel<RM_KEYS>, dim3(NWG), dim3(256), RING * SLOT, st, g);
+  else if (rm == RM_NONE) hipLaunchKernelGGL(decoder256_kernel<RM_NONE>, dim3(NWG), dim3(256), RING * SLOT, st, g);
+  else hipLaunchKernelGGL(decoder256_kernel<RM_BITS>, dim3(NWG), dim3(256), RING * SLOT, st, g);
   SNX_CHECK_LAUNCH();
   const long total = (long)nseq * V;
   hipLaunchKernelGGL(dec256_finalize_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, keys, sparse, cu_seqlens, list, V,

@@ -77,13 +77,14 @@ struct SavedPlan {
   size_t y[64];                  // GeGLU output (input of mlp.Wo), bf16 [T,I]
   size_t xf, dd, hd;             // final-norm out, head.dense out (pre-GELU), head out: bf16 [T,H]
   size_t keys;                   // u32 [nseq,V]
-  size_t rowpart;                // forward-only scratch of the SPLADE head
   size_t rope_rows[2];           // fp32 [T,32,2]: every token's (cos, sin) row for theta_global / theta_local
   size_t tkeys;                  // u32 [T]: every token's maximum over the vocabulary, value bits << 16 | 0xFFFF - v
+  size_t rowpart;                // forward-only scratch of the SPLADE head; LAST: its size depends on the forward's flags
+                                 // (SNX_FWD_NO_TOKEN_WEIGHTS: no row maxima), no other offset does
   size_t total;
 };
 
-bool plan_saved(const snx_model_desc* d, long T, long nseq, bool save, SavedPlan& s) {
+bool plan_saved(const snx_model_desc* d, long T, long nseq, bool save, SavedPlan& s, bool notw = false) {
   if (d->layers > 64 || d->layers < 1) return false;
   const size_t H = d->hidden, I = d->inter, V = d->vocab, L = d->layers;
   size_t off = 0;
@@ -107,10 +108,10 @@ bool plan_saved(const snx_model_desc* d, long T, long nseq, bool save, SavedPlan
   }
   s.xf = take(T * H * 2); s.dd = take(T * H * 2); s.hd = take(T * H * 2);
   s.keys = take(nseq * V * 4);
-  s.rowpart = take(snx_splade_head_scratch_bytes((int)T, (int)V));
   s.rope_rows[0] = take(T * 256);
   s.rope_rows[1] = take(T * 256);
   s.tkeys = take(T * 4);
+  s.rowpart = take(notw ? snx_splade_head_scratch_bytes_notw((int)T) : snx_splade_head_scratch_bytes((int)T, (int)V));
   s.total = off;
   return true;
 }
@@ -332,6 +333,41 @@ extern "C" size_t snx_model_workspace_bytes(const snx_model_desc* d, int32_t T, 
   return s.total;
 }
 
+extern "C" size_t snx_model_workspace_bytes_fwd(const snx_model_desc* d, int32_t T, int32_t nseq, int32_t flags) {
+  SavedPlan s;
+  if (!desc_ok(d) || T <= 0 || nseq <= 0 ||
+      !plan_saved(d, T, nseq, (flags & SNX_FWD_SAVE_FOR_BACKWARD) != 0, s, (flags & SNX_FWD_NO_TOKEN_WEIGHTS) != 0))
+    return 0;
+  return s.total;
+}
+
+// Arenas whose token keys were NOT written (SNX_FWD_NO_TOKEN_WEIGHTS): a backward handed a token_weights gradient for one of
+// them would route through whatever the arena's memory held before.  Host side, keyed by the arena's address (one thread
+// drives the library): a flagged saving forward enters it, an unflagged one that starts the arena (row0 = 0) removes it.
+// At most 64 arenas are remembered (a micro-step has one; the oldest entry goes first).
+namespace {
+struct NoTwArenas {
+  const void* a[64];
+  int n = 0;
+  int find(const void* p) const {
+    for (int i = 0; i < n; ++i)
+      if (a[i] == p) return i;
+    return -1;
+  }
+  void drop(const void* p) {
+    const int i = find(p);
+    if (i < 0) return;
+    for (int k = i; k + 1 < n; ++k) a[k] = a[k + 1];
+    --n;
+  }
+  void add(const void* p) {
+    if (find(p) >= 0) return;
+    if (n == 64) drop(a[0]);
+    a[n++] = p;
+  }
+} g_notw;
+}  // namespace
+
 extern "C" size_t snx_model_keys_offset(const snx_model_desc* d, int32_t T, int32_t nseq) {
   SavedPlan s;
   if (!desc_ok(d) || T <= 0 || nseq <= 0 || !plan_saved(d, T, nseq, true, s)) return (size_t)-1;
@@ -374,8 +410,9 @@ extern "C" int snx_model_forward_range(const snx_model_desc* d, const void* cons
                                        int32_t T_plan, int32_t nseq_plan, int32_t row0, int32_t seq0, int32_t T,
                                        int32_t nseq, int32_t max_seqlen, int32_t flags, hipStream_t st) {
   if (!desc_ok(d)) return SNX_E_SHAPE;
+  const bool notw = (flags & SNX_FWD_NO_TOKEN_WEIGHTS) != 0;   // token_weights_all may be NULL: it is never written
   if (!params || !wcache || !ids || !mask || !cu_seqlens || !pos || !rope_global || !rope_local || !saved || !sparse_all ||
-      !token_weights_all || T <= 0 || nseq <= 0 || max_seqlen <= 0)
+      (!notw && !token_weights_all) || T <= 0 || nseq <= 0 || max_seqlen <= 0)
     return SNX_E_ARG;
   if (row0 < 0 || seq0 < 0 || (long)row0 + T > T_plan || (long)seq0 + nseq > nseq_plan) return SNX_E_ARG;
   const bool ranged = T != T_plan || nseq != nseq_plan;
@@ -384,7 +421,11 @@ extern "C" int snx_model_forward_range(const snx_model_desc* d, const void* cons
   if (ranged && !save) return SNX_E_ARG;                   // (the no-save plan reuses buffers across layers: nothing to share)
   CachePlan c;
   SavedPlan s;
-  if (!plan_cache(d, c) || !plan_saved(d, T_plan, nseq_plan, save, s)) return SNX_E_SHAPE;
+  if (!plan_cache(d, c) || !plan_saved(d, T_plan, nseq_plan, save, s, notw)) return SNX_E_SHAPE;
+  if (save) {
+    if (notw) g_notw.add(saved);
+    else if (row0 == 0) g_notw.drop(saved);
+  }
   // The forward's non-temporal streams ("stream_nt" bits 1, 2, 8: residual-stream rows, the saved u) are a TRAINING policy:
   // without a backward the stream ping-pongs between two buffers and small inference batches live in the caches -- an nt
   // store would send the next LayerNorm to HBM for them.  (One thread drives the library: the switch is restored on return.)
@@ -402,7 +443,7 @@ extern "C" int snx_model_forward_range(const snx_model_desc* d, const void* cons
     char* at(size_t off, size_t row_bytes) const { return base + off + row0 * row_bytes; }
   } view{(char*)saved, (size_t)row0};
   float* sparse = sparse_all + (size_t)seq0 * V;
-  float* token_weights = token_weights_all + row0;
+  float* token_weights = notw ? nullptr : token_weights_all + row0;
   auto F = [&](int idx) { return (const float*)params[idx]; };
   auto hbuf = [&](int i) { return (float*)view.at(s.h[i], (size_t)H * 4); };
   // shifted views of the per-token bf16 buffers (named as the plan names them)
@@ -476,9 +517,10 @@ extern "C" int snx_model_forward_range(const snx_model_desc* d, const void* cons
     for (int i = 0; i < g[0]; ++i) {
       const int sb = g[1 + 3 * i], ns = g[2 + 3 * i], ml = g[3 + 3 * i];
       if (sb < 0 || ns <= 0 || sb + ns > nseq || ml <= 0 || ml > max_seqlen) return SNX_E_ARG;
-      RC(snx_decoder_splade_fwd_rec(sv.hd(), wc + c.emb, F(p.dec_bias()), cu_seqlens + sb, mask,
-                                    sparse + (size_t)sb * V, keys + (size_t)sb * V, token_weights, tkeys,
-                                    rowpart, T, ns, ml, V, H, i + 1 == g[0], st));
+      // (SNX_FWD_NO_TOKEN_WEIGHTS: the kernels without their row half, no token_weights pass, nothing written to tkeys)
+      RC(snx_decoder_splade_fwd_flags(sv.hd(), wc + c.emb, F(p.dec_bias()), cu_seqlens + sb, mask,
+                                      sparse + (size_t)sb * V, keys + (size_t)sb * V, token_weights, tkeys, rowpart, T, ns,
+                                      ml, V, H, i + 1 == g[0], flags & SNX_FWD_NO_TOKEN_WEIGHTS, st));
     }
   }
   return SNX_OK;
@@ -530,6 +572,7 @@ extern "C" int snx_model_backward_units_range_tw(const snx_model_desc* d, const 
       !g_sparse || !scratch || T <= 0 || nseq <= 0 || max_seqlen <= 0 || T > T_plan || nseq > nseq_plan)
     return SNX_E_ARG;
   if (unit_begin < 0 || unit_end > d->layers + 2 || unit_begin >= unit_end) return SNX_E_ARG;
+  if (g_token_weights && g_notw.find(saved) >= 0) return SNX_E_ARG;   // that forward recorded no token keys
   CachePlan c;
   SavedPlan s;
   BwdPlan b;

@@ -26,14 +26,17 @@
 // REC (training forwards, SNX_FWD_SAVE_FOR_BACKWARD): the row maxima are column-tagged keys
 //   rowkey = bf16_bits(relu(logit)) << 16 | (0xFFFF - v)      (u32 per (tile, token); unsigned max = largest value,
 // ties -> lowest v) instead of bare value bits (u16), so that token_weights_kernel can keep each token's arg-max column
-// for the backward of token_weights.  REC = false compiles to the inference kernel of before.
-template <int BM, bool REC>
+// for the backward of token_weights.  RM_BITS compiles to the inference kernel of before.  RM_NONE (training forwards whose
+// caller drops token_weights, SNX_FWD_NO_TOKEN_WEIGHTS) has no row half: no row keys, no shuffles, no sRow / rowpart store
+// and no second barrier per chunk; the column half is the same arithmetic.
+template <int BM, int RM>
 __global__ __launch_bounds__(256, 2) void decoder_splade_kernel(
     const bf16_t* __restrict__ Hd, const bf16_t* __restrict__ W, const float* __restrict__ bias,
     const int32_t* __restrict__ cu_seqlens, const int64_t* __restrict__ mask, float* __restrict__ sparse,
     uint32_t* __restrict__ keys, void* __restrict__ rowpart, int T, int V, int K, int n_tiles,
     int total_tiles, int nseq) {
   constexpr int BN = 128;
+  constexpr bool REC = RM == RM_KEYS, ROWS = RM != RM_NONE;
   using Core = GemmCore<BM, BN, 2, 2>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint32_t* sBest = (uint32_t*)(smem + Core::LDS_BYTES);           // [2][BN]
@@ -98,17 +101,20 @@ __global__ __launch_bounds__(256, 2) void decoder_splade_kernel(
           if (REC) {
             const uint32_t ck = (bits << 16) | ctag[j];
             rb = ck > rb ? ck : rb;
-          } else {
+          } else if (ROWS) {
             rb = bits > rb ? bits : rb;
           }
         }
-        rb = max(rb, (uint32_t)__shfl_xor((int)rb, 1, 64));
-        rb = max(rb, (uint32_t)__shfl_xor((int)rb, 2, 64));
-        rb = max(rb, (uint32_t)__shfl_xor((int)rb, 4, 64));
-        rb = max(rb, (uint32_t)__shfl_xor((int)rb, 8, 64));
-        if (li == 0) sRow[wn * BM + lrow] = rb;
+        if (ROWS) {
+          rb = max(rb, (uint32_t)__shfl_xor((int)rb, 1, 64));
+          rb = max(rb, (uint32_t)__shfl_xor((int)rb, 2, 64));
+          rb = max(rb, (uint32_t)__shfl_xor((int)rb, 4, 64));
+          rb = max(rb, (uint32_t)__shfl_xor((int)rb, 8, 64));
+          if (li == 0) sRow[wn * BM + lrow] = rb;
+        }
       }
     }
+    if (!ROWS) continue;                              // (the barrier at the top of the next chunk frees the operand tiles)
     __syncthreads();
     for (int rr = threadIdx.x; rr < BM; rr += 256) {
       const int srow = c0 + rr;
@@ -180,7 +186,7 @@ size_t snx_dec256_table_bytes(int32_t T);
 int snx_dec256_rowtiles(int32_t V);                   // rows of the row-maximum array it writes (96-column half tiles)
 int snx_launch_decoder256(const void* Hd, const void* W, const float* bias, const int32_t* cu_seqlens,
                           const int64_t* mask, float* sparse, uint32_t* keys, void* scratch, size_t rowpart_bytes,
-                          int32_t T, int32_t nseq, int32_t V, int32_t K, bool rec, hipStream_t st);
+                          int32_t T, int32_t nseq, int32_t V, int32_t K, int rm, hipStream_t st);
 
 // SNX_DEC256=0 keeps the 128x128 kernel; the 256x192 form wants enough rows to fill its tiles.  (model.hip asks: the
 // 256x192 form takes all sequence groups of a pass in ONE call, the 128x128 kernel one call per group.)
@@ -200,21 +206,26 @@ extern "C" size_t snx_splade_head_scratch_bytes(int32_t T, int32_t V) {
   return rowpart_bytes(T, V) + snx_dec256_table_bytes(T);
 }
 
+// ... with SNX_FWD_NO_TOKEN_WEIGHTS: no row maxima, the pre-pass tables of the 256x192 form alone
+extern "C" size_t snx_splade_head_scratch_bytes_notw(int32_t T) { return snx_dec256_table_bytes(T); }
+
 // `finalize` = 0 skips the token_weights pass (used when several sequence groups of one token
 // buffer are processed by separate calls; the last call finalises all T rows).  token_keys != NULL: record every
 // token's arg-max column (token_weights_kernel<true>); the finalising call writes token_keys[0, T).
-extern "C" int snx_decoder_splade_fwd_rec(const void* Hd, const void* W, const float* bias,
-                                          const int32_t* cu_seqlens, const int64_t* mask, float* sparse,
-                                          uint32_t* keys, float* token_weights, uint32_t* token_keys, void* scratch,
-                                          int32_t T, int32_t nseq, int32_t max_seqlen, int32_t V, int32_t K,
-                                          int32_t finalize, hipStream_t st) {
-  if (!Hd || !W || !bias || !cu_seqlens || !mask || !sparse || !keys || !token_weights || !scratch) return SNX_E_ARG;
+// rm = RM_NONE (snx_decoder_splade_fwd_flags with SNX_FWD_NO_TOKEN_WEIGHTS): the kernels without their row half, no
+// token_weights pass, `scratch` holds the pre-pass tables alone; token_weights, token_keys and `finalize` are not looked at.
+static int decoder_splade_fwd(const void* Hd, const void* W, const float* bias, const int32_t* cu_seqlens,
+                              const int64_t* mask, float* sparse, uint32_t* keys, float* token_weights,
+                              uint32_t* token_keys, void* scratch, int32_t T, int32_t nseq, int32_t max_seqlen, int32_t V,
+                              int32_t K, int32_t finalize, int rm, hipStream_t st) {
+  const bool rec = rm == RM_KEYS, rows = rm != RM_NONE;
+  if (!Hd || !W || !bias || !cu_seqlens || !mask || !sparse || !keys || (rows && !token_weights) || !scratch)
+    return SNX_E_ARG;
   if (T <= 0 || nseq <= 0 || V <= 0 || K <= 0 || (K % 64) || max_seqlen > 65535) return SNX_E_SHAPE;
-  const bool rec = token_keys != nullptr;
   if (rec && V > 65535) return SNX_E_SHAPE;           // the column tag is 16 bits
   const int n_tiles = cdiv(V, 128);
   auto finish = [&](int tiles) -> int {
-    if (!finalize) return SNX_OK;
+    if (!finalize || !rows) return SNX_OK;
     if (rec)
       hipLaunchKernelGGL(token_weights_kernel<true>, dim3(cdiv(T, 256)), dim3(256), 0, st, (const void*)scratch, mask,
                          token_weights, token_keys, T, tiles);
@@ -226,8 +237,8 @@ extern "C" int snx_decoder_splade_fwd_rec(const void* Hd, const void* W, const f
   };
   if (snx_dec256_takes(T)) {
     const int rowtiles = snx_dec256_rowtiles(V);
-    const int rc = snx_launch_decoder256(Hd, W, bias, cu_seqlens, mask, sparse, keys, scratch, rowpart_bytes(T, V), T,
-                                         nseq, V, K, rec, st);
+    const int rc = snx_launch_decoder256(Hd, W, bias, cu_seqlens, mask, sparse, keys, scratch,
+                                         rows ? rowpart_bytes(T, V) : 0, T, nseq, V, K, rm, st);
     if (rc != SNX_E_SHAPE) {
       if (rc != SNX_OK) return rc;
       return finish(rowtiles);
@@ -237,23 +248,47 @@ extern "C" int snx_decoder_splade_fwd_rec(const void* Hd, const void* W, const f
   if (total_l > 0x7fffffffL) return SNX_E_SHAPE;
   const int total = (int)total_l;
   void* rowpart = scratch;
-#define SNX_DEC128(BMV, RECV)                                                                                          \
+#define SNX_DEC128(BMV, RMV)                                                                                           \
   do {                                                                                                                 \
     using Core = GemmCore<BMV, 128, 2, 2>;                                                                             \
     const size_t lds = Core::LDS_BYTES + (2 * 128 + 2 * BMV) * 4;                                                      \
-    hipLaunchKernelGGL((decoder_splade_kernel<BMV, RECV>), dim3(total), dim3(256), lds, st, (const bf16_t*)Hd,         \
+    hipLaunchKernelGGL((decoder_splade_kernel<BMV, RMV>), dim3(total), dim3(256), lds, st, (const bf16_t*)Hd,          \
                        (const bf16_t*)W, bias, cu_seqlens, mask, sparse, keys, rowpart, T, V, K, n_tiles, total, nseq); \
   } while (0)
   if (max_seqlen <= 64) {
-    if (rec) SNX_DEC128(64, true);
-    else SNX_DEC128(64, false);
+    if (rec) SNX_DEC128(64, RM_KEYS);
+    else if (rows) SNX_DEC128(64, RM_BITS);
+    else SNX_DEC128(64, RM_NONE);
   } else {
-    if (rec) SNX_DEC128(128, true);
-    else SNX_DEC128(128, false);
+    if (rec) SNX_DEC128(128, RM_KEYS);
+    else if (rows) SNX_DEC128(128, RM_BITS);
+    else SNX_DEC128(128, RM_NONE);
   }
 #undef SNX_DEC128
   SNX_CHECK_LAUNCH();
   return finish(n_tiles);
+}
+
+extern "C" int snx_decoder_splade_fwd_rec(const void* Hd, const void* W, const float* bias,
+                                          const int32_t* cu_seqlens, const int64_t* mask, float* sparse,
+                                          uint32_t* keys, float* token_weights, uint32_t* token_keys, void* scratch,
+                                          int32_t T, int32_t nseq, int32_t max_seqlen, int32_t V, int32_t K,
+                                          int32_t finalize, hipStream_t st) {
+  return decoder_splade_fwd(Hd, W, bias, cu_seqlens, mask, sparse, keys, token_weights, token_keys, scratch, T, nseq,
+                            max_seqlen, V, K, finalize, token_keys ? RM_KEYS : RM_BITS, st);
+}
+
+// snx_decoder_splade_fwd_rec with forward flags.  SNX_FWD_NO_TOKEN_WEIGHTS (a caller that drops token_weights -- the
+// trainer: the loss reads the pooled vectors only): `sparse` and `keys` with the same bits, nothing of the row half -- no
+// row maxima, no token_weights pass; token_weights and token_keys are not written (may be NULL).
+extern "C" int snx_decoder_splade_fwd_flags(const void* Hd, const void* W, const float* bias, const int32_t* cu_seqlens,
+                                            const int64_t* mask, float* sparse, uint32_t* keys, float* token_weights,
+                                            uint32_t* token_keys, void* scratch, int32_t T, int32_t nseq,
+                                            int32_t max_seqlen, int32_t V, int32_t K, int32_t finalize, int32_t flags,
+                                            hipStream_t st) {
+  const int rm = (flags & SNX_FWD_NO_TOKEN_WEIGHTS) ? RM_NONE : token_keys ? RM_KEYS : RM_BITS;
+  return decoder_splade_fwd(Hd, W, bias, cu_seqlens, mask, sparse, keys, token_weights, token_keys, scratch, T, nseq,
+                            max_seqlen, V, K, finalize, rm, st);
 }
 
 extern "C" int snx_decoder_splade_fwd_ex(const void* Hd, const void* W, const float* bias,

@@ -64,12 +64,15 @@ SIGNATURES = {
     "snx_decoder_splade_fwd_ex": (I32, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, P]),
     "snx_splade_bwd": (I32, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P]),
     "snx_decoder_splade_fwd_rec": (I32, [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, P]),
+    "snx_splade_head_scratch_bytes_notw": (SZ, [I32]),
+    "snx_decoder_splade_fwd_flags": (I32, [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, P]),
     "snx_splade_tw_scratch_bytes": (SZ, [I32, I32]),
     "snx_splade_bwd_tw": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P]),
     "snx_loss_workspace_bytes": (SZ, [I32, I32, I32, I32]),
     "snx_loss_fwd": (I32, [P, P, P, P, P, P, P, P, P, P, P]),
     "snx_loss_bwd": (I32, [P, P, P, P, P, P, P, I32, P, P, P, P]),
     "snx_model_workspace_bytes": (SZ, [P, I32, I32, I32]),
+    "snx_model_workspace_bytes_fwd": (SZ, [P, I32, I32, I32]),
     "snx_model_bwd_workspace_bytes": (SZ, [P, I32, I32, I32]),
     "snx_splade_bwd_scratch_bytes": (SZ, [I32, I32, I32]),
     "snx_model_keys_offset": (SZ, [P, I32, I32]),

@@ -5,6 +5,7 @@ PyTorch here is plumbing only: device memory (caching allocator), the current st
 autograd graph boundary.  All arithmetic happens in libsnx.so."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import logging
 import os
@@ -19,6 +20,7 @@ from ._lib import check, fn
 from .ops import _p, _stream, rope_table
 
 SNX_FWD_SAVE_FOR_BACKWARD = 1
+SNX_FWD_NO_TOKEN_WEIGHTS = 2      # the caller drops token_weights: the decoder runs without its row half (include/snx.h)
 _SEQ_CACHE_ENTRIES = 64
 logger = logging.getLogger(__name__)
 
@@ -88,6 +90,7 @@ class EncoderRuntime:
             raise ValueError(f"expected {n} parameter tensors in canonical order, got {len(self.params)}")
         self._ptr_key = None
         self._ptr_arr = None
+        self._need_tw = True                   # what the forward in progress was asked for (_wanting_token_weights)
         self._wcache: Optional[torch.Tensor] = None
         self._wcache_key = None
         self._rope: Dict[Tuple[int, str], Tuple[torch.Tensor, torch.Tensor]] = {}
@@ -245,8 +248,21 @@ class EncoderRuntime:
         return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
     # ------------------------------------------------------------------ forward / backward
-    def forward_impl(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, save: bool, lengths=None):
-        return self.forward_many_impl([(input_ids, attention_mask)], save, lengths)
+    def forward_impl(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, save: bool, lengths=None,
+                     need_token_weights: bool = True):
+        with self._wanting_token_weights(need_token_weights):
+            return self.forward_many_impl([(input_ids, attention_mask)], save, lengths)
+
+    @contextlib.contextmanager
+    def _wanting_token_weights(self, need: bool):
+        """need_token_weights of the public call, for the forward inside the block.  forward_many_impl and
+        step_arena_place read it from here and keep their (pairs, save, lengths) / (ids, mask) signatures: callers that wrap
+        them (routing capture in the tests, profilers) go on working."""
+        prev, self._need_tw = self._need_tw, bool(need)
+        try:
+            yield
+        finally:
+            self._need_tw = prev
 
     @staticmethod
     def precision() -> str:
@@ -281,10 +297,14 @@ class EncoderRuntime:
     def forward_many_impl(self, pairs, save: bool, lengths=None):
         """One native forward over several [B_i, S_i] batches laid end to end (sequence groups).
         -> sparse [sum B_i, V], token_weights [sum B_i*S_i] (flat, padded layout), arena, aux.
+        Inside ``_wanting_token_weights(False)`` (a caller that drops them): token_weights is None; on the bf16 path the decoder then
+        runs without the row half of its epilogue (SNX_FWD_NO_TOKEN_WEIGHTS: neither token_weights nor the arena's token
+        keys exist, sparse and every gradient keep their bits), the fp32 path computes them and drops them.
         ``lengths`` (optional, one CPU int tensor [B_i] per pair, right-padded inputs): run UNPADDED
         -- only the valid tokens are gathered and computed (the kernels take cu_seqlens); the
         lengths come from the host-side collator output, so no device sync is needed."""
         dev = self._device()
+        need_token_weights = self._need_tw
         fp32 = self.precision() == "fp32"
         if not fp32:
             self.geom.check_supported()
@@ -340,7 +360,9 @@ class EncoderRuntime:
         with torch.cuda.device(dev):            # native launches go to THIS device's current stream
             rg, rl = self._rope_tables(max(smax, 64), dev, hd)
             sparse = torch.empty((nseq, self.geom.vocab_size), dtype=torch.float32, device=dev)
-            tw = torch.empty((T,), dtype=torch.float32, device=dev)
+            notw = not need_token_weights and not fp32
+            tw = None if notw else torch.empty((T,), dtype=torch.float32, device=dev)
+            flags = (SNX_FWD_SAVE_FOR_BACKWARD if save else 0) | (SNX_FWD_NO_TOKEN_WEIGHTS if notw else 0)
             if fp32:
                 nbytes = fn("snx_model_workspace_bytes_f32")(C.byref(self._desc), T, nseq, int(save))
                 saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -349,13 +371,15 @@ class EncoderRuntime:
                                                   SNX_FWD_SAVE_FOR_BACKWARD if save else 0, _stream()), "snx_model_forward_f32")
             else:
                 wc = self._weights()
-                nbytes = fn("snx_model_workspace_bytes")(C.byref(self._desc), T, nseq, int(save))
+                nbytes = fn("snx_model_workspace_bytes_fwd")(C.byref(self._desc), T, nseq, flags)
                 saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
                 check(fn("snx_model_forward")(C.byref(self._desc), self._param_ptrs(), _p(wc), _p(ids), _p(mask), _p(cu),
                                               _p(pos), _p(rg), _p(rl), _p(saved), _p(sparse), _p(tw),
                                               groups if (len(shapes) > 1 or lengths is not None) else None, T, nseq, smax,
-                                              SNX_FWD_SAVE_FOR_BACKWARD if save else 0, _stream()), "snx_model_forward")
-        if scatter is not None:                      # token_weights back to the padded layout (0 at padding)
+                                              flags, _stream()), "snx_model_forward")
+        if not need_token_weights:
+            tw = None
+        elif scatter is not None:                    # token_weights back to the padded layout (0 at padding)
             tw_full = torch.zeros((T_pad,), dtype=torch.float32, device=dev)
             tw_full[scatter] = tw
             tw = tw_full
@@ -517,12 +541,15 @@ class EncoderRuntime:
     def step_arena_place(self, ids: torch.Tensor, mask: torch.Tensor):
         """This pass into the micro-step's shared arena -> (sparse [B, V], token_weights [B*S], arena, index), or None when
         no capacity has been learnt yet or the pass does not fit what is left of it (then it runs on the ordinary path,
-        which also owns the shape / length errors: an input the ordinary path would refuse is never placed)."""
+        which also owns the shape / length errors: an input the ordinary path would refuse is never placed).
+        Inside ``_wanting_token_weights(False)``: token_weights is None and the pass runs with SNX_FWD_NO_TOKEN_WEIGHTS; an arena holds
+        passes of ONE kind (its token keys exist or they do not), a pass of the other kind runs on the ordinary path."""
         if not self._arena_eligible() or ids.dim() != 2 or mask.shape != ids.shape or ids.device != self._device() or \
                 mask.device != ids.device:
             return None
         if ids.shape[1] > self.geom.max_position_embeddings or ids.shape[1] > 8192 or ids.shape[0] < 1 or ids.shape[1] < 1:
             return None                                      # forward_many_impl raises "sequence too long"
+        need_token_weights = self._need_tw
         a = self._arena
         if a is not None and a.placed > 0:
             why = a.stale_reason()
@@ -538,7 +565,12 @@ class EncoderRuntime:
                 self._arena_note("fell_back", f"a pass of {B} x {S} tokens exceeds the learnt capacity {cap}: it runs on "
                                  "the ordinary path (its own backward)")
                 return None
-            a = self._arena = StepArena(self, cap[0], cap[1])
+            a = self._arena = StepArena(self, cap[0], cap[1], notw=not need_token_weights)
+        if a.notw != (not need_token_weights):
+            self._arena_note("fell_back", f"a pass that {'needs' if need_token_weights else 'drops'} token_weights met an "
+                             f"arena whose passes {'drop' if a.notw else 'need'} them: it runs on the ordinary path (its "
+                             "own backward)")
+            return None
         if not a.fits(B, S):
             self._arena_note("fell_back", f"a pass of {B} x {S} tokens does not fit what is left of the arena "
                              f"({a.row0[-1]} of {a.T} rows, {a.seq0[-1]} of {a.nseq} sequences, {a.placed} passes used): it "
@@ -548,22 +580,25 @@ class EncoderRuntime:
         self.arena_stats["placed"] += 1
         return a.place(ids, mask)
 
-    def __call__(self, input_ids, attention_mask):
-        (out,) = self.forward_many([(input_ids, attention_mask)])
+    def __call__(self, input_ids, attention_mask, need_token_weights: bool = True):
+        (out,) = self.forward_many([(input_ids, attention_mask)], need_token_weights=need_token_weights)
         return out
 
-    def forward_many(self, pairs, lengths=None):
+    def forward_many(self, pairs, lengths=None, need_token_weights: bool = True):
         """[(ids [B_i,S_i], mask)] -> [(sparse_repr [B_i,V], token_weights [B_i,S_i])], one native pass.
-        ``lengths``: optional per-pair CPU length tensors -> unpadded (varlen) execution."""
+        ``lengths``: optional per-pair CPU length tensors -> unpadded (varlen) execution.
+        ``need_token_weights=False``: None in place of every token_weights, which are then not computed (a trainer whose
+        loss reads the pooled vectors only; forward_many_impl)."""
         pairs = list(pairs)
         flat = [t for p in pairs for t in p]
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.params):
             # one autograd output per pass: a slice taken OUTSIDE the Function would cost its backward a zero fill of the
             # whole [rows, V] gradient, a copy and an add per pass (three of each per micro-step, 9.6 M floats each)
-            res = _SpladeEncodeFn.apply(self, len(pairs), lengths, *flat, *self.params)
-            sparses, tw = res[:-1], res[-1]
+            res = _SpladeEncodeFn.apply(self, len(pairs), lengths, bool(need_token_weights), *flat, *self.params)
+            sparses, tw = (res[:-1], res[-1]) if need_token_weights else (res, None)
         else:
-            sparse, tw, _, _ = self.forward_many_impl(pairs, save=False, lengths=lengths)
+            with self._wanting_token_weights(need_token_weights):
+                sparse, tw, _, _ = self.forward_many_impl(pairs, save=False, lengths=lengths)
             sparses, r0 = [], 0
             for ids, _ in pairs:
                 sparses.append(sparse[r0:r0 + ids.shape[0]])
@@ -571,7 +606,7 @@ class EncoderRuntime:
         out, t0 = [], 0
         for (ids, _), sp in zip(pairs, sparses):
             B, S = ids.shape
-            out.append((sp, tw[t0:t0 + B * S].view(B, S)))
+            out.append((sp, tw[t0:t0 + B * S].view(B, S) if tw is not None else None))
             t0 += B * S
         return out
 
@@ -597,8 +632,10 @@ class StepArena:
 
     MAX_PASSES = 8
 
-    def __init__(self, rt: "EncoderRuntime", t_cap: int, nseq_cap: int):
+    def __init__(self, rt: "EncoderRuntime", t_cap: int, nseq_cap: int, notw: bool = False):
         self.rt = rt
+        self.notw = bool(notw)                               # its passes run with SNX_FWD_NO_TOKEN_WEIGHTS: no tw, no token keys
+        self.flags = SNX_FWD_SAVE_FOR_BACKWARD | (SNX_FWD_NO_TOKEN_WEIGHTS if self.notw else 0)
         dev = rt._device()
         self.dev = dev
         self.T, self.nseq = int(t_cap), int(nseq_cap)
@@ -606,10 +643,10 @@ class StepArena:
         self.row0, self.seq0 = [0], [0]
         V = rt.geom.vocab_size
         with torch.cuda.device(dev):
-            nbytes = fn("snx_model_workspace_bytes")(C.byref(rt._desc), self.T, self.nseq, 1)
+            nbytes = fn("snx_model_workspace_bytes_fwd")(C.byref(rt._desc), self.T, self.nseq, self.flags)
             self.saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             self.sparse = torch.empty((self.nseq, V), dtype=torch.float32, device=dev)
-            self.tw = torch.empty((self.T,), dtype=torch.float32, device=dev)
+            self.tw = None if self.notw else torch.empty((self.T,), dtype=torch.float32, device=dev)
             self.ids = torch.empty((self.T,), dtype=torch.int64, device=dev)
             self.mask = torch.empty((self.T,), dtype=torch.int64, device=dev)
         self.placed = self.reported = 0
@@ -662,7 +699,7 @@ class StepArena:
                 self.wkey = rt._wcache_key
             check(fn("snx_model_forward_range")(C.byref(rt._desc), rt._param_ptrs(), _p(wc), _p(ids_k), _p(mask_k),
                                                 _p(cu), _p(pos), _p(rg), _p(rl), _p(self.saved), _p(self.sparse), _p(self.tw),
-                                                None, self.T, self.nseq, r0, s0, T, B, S, SNX_FWD_SAVE_FOR_BACKWARD,
+                                                None, self.T, self.nseq, r0, s0, T, B, S, self.flags,
                                                 _stream()), "snx_model_forward_range")
         self.shapes.append((B, S))
         self.row0.append(r0 + T)
@@ -672,7 +709,7 @@ class StepArena:
         self.nodes.append(None)
         self.got.append(False)
         self.placed += 1
-        return self.sparse[s0:s0 + B], self.tw[r0:r0 + T], self, k
+        return self.sparse[s0:s0 + B], (None if self.notw else self.tw[r0:r0 + T]), self, k
 
     def routing_rows(self, k: int) -> torch.Tensor:
         """Arg-max sequence position per (sequence, vocab) entry of pass k (as EncoderRuntime.routing_rows)."""
@@ -794,22 +831,25 @@ def _gather_rows(gs, rows, vocab: int, device) -> torch.Tensor:
 
 class _SpladeEncodeFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rt: EncoderRuntime, n_pairs: int, lengths, *args):
+    def forward(ctx, rt: EncoderRuntime, n_pairs: int, lengths, need_tw: bool, *args):
         pairs = [(args[2 * i], args[2 * i + 1]) for i in range(n_pairs)]
-        ctx.n_in = 2 * n_pairs + 1
+        ctx.n_in = 2 * n_pairs + 2
+        ctx.need_tw = need_tw                            # False: no token_weights output (and no gradient slot for it)
         # an unused token_weights output must arrive as None (no token-direction launch), not as materialised zeros
         ctx.set_materialize_grads(False)
         ctx.rt, ctx.arena, ctx.counted = rt, None, False
         if n_pairs == 1 and lengths is None:
-            placed = rt.step_arena_place(pairs[0][0], pairs[0][1])
+            with rt._wanting_token_weights(need_tw):
+                placed = rt.step_arena_place(pairs[0][0], pairs[0][1])
             if placed is not None:                       # this pass went into the micro-step's shared arena
                 sparse, tw, ctx.arena, ctx.k = placed
                 ctx.arena.attach(ctx.k, ctx)
                 ctx.sync_token = rt.grad_sync.on_forward() if (rt.direct_grads and rt.grad_sync is not None) else None
                 ctx.rows, ctx.vocab = [sparse.shape[0]], sparse.shape[1]
-                return sparse, tw
+                return (sparse, tw) if need_tw else (sparse,)
             ctx.counted = rt.step_arena_observe(pairs[0][0])
-        sparse, tw, saved, aux = rt.forward_many_impl(pairs, save=True, lengths=lengths)
+        with rt._wanting_token_weights(need_tw):
+            sparse, tw, saved, aux = rt.forward_many_impl(pairs, save=True, lengths=lengths)
         ctx.saved_arena, ctx.aux = saved, aux
         # an armed micro-step counts its saving forwards: only the backward of the last outstanding one exchanges
         ctx.sync_token = rt.grad_sync.on_forward() if (rt.direct_grads and rt.grad_sync is not None) else None
@@ -821,16 +861,16 @@ class _SpladeEncodeFn(torch.autograd.Function):
         for b in ctx.rows:
             outs.append(sparse[r0:r0 + b])
             r0 += b
-        return tuple(outs) + (tw,)
+        return tuple(outs) + ((tw,) if need_tw else ())
 
     @staticmethod
     def backward(ctx, *gs):
         rt = ctx.rt
         head = (None, None) + tuple(None for _ in range(ctx.n_in))
         # sparse outputs without a gradient: zeros, as autograd materialised them before token_weights had a backward
-        g_tw = gs[-1]
+        g_tw = gs[-1] if ctx.need_tw else None
         gs = tuple(torch.zeros((b, ctx.vocab), dtype=torch.float32, device=g_tw.device if g_tw is not None else rt._device())
-                   if g is None else g for g, b in zip(gs[:-1], ctx.rows))
+                   if g is None else g for g, b in zip(gs[:-1] if ctx.need_tw else gs, ctx.rows))
         if ctx.arena is not None:
             grads = ctx.arena.report(ctx.k, gs[0], ctx.sync_token, g_tw)
             ctx.arena = None

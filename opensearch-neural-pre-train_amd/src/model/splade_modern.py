@@ -247,19 +247,23 @@ class SPLADEModernBERT(nn.Module):
         return self._runtime
 
     def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor,
-                token_type_ids: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                token_type_ids: Optional[torch.Tensor] = None,
+                need_token_weights: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """-> (sparse_repr [batch, vocab] fp32, token_weights [batch, seq_len] fp32);
-        ``token_type_ids`` is accepted and ignored (ref:splade_modern.py:54,63)."""
-        return self._runtime(input_ids, attention_mask)
+        ``token_type_ids`` is accepted and ignored (ref:splade_modern.py:54,63).
+        ``need_token_weights=False`` (extension; the trainer, whose loss reads sparse_repr only): token_weights is None and
+        is not computed."""
+        return self._runtime(input_ids, attention_mask, need_token_weights=need_token_weights)
 
-    def forward_many(self, batches, lengths=None):
+    def forward_many(self, batches, lengths=None, need_token_weights: bool = True):
         """Extension (not in the reference): encode several (input_ids, attention_mask) batches of
         different sequence length -- e.g. the query, positive and negative batch of one training
         micro-step -- in ONE native pass.  Results are identical to separate ``forward`` calls
         (sequences never interact); larger GEMMs, a third of the launches.
         ``lengths`` (one CPU int tensor per batch, right-padded inputs) switches to UNPADDED execution:
-        padded positions are never computed (rank 2 of SURVEY.md §8(f))."""
-        return self._runtime.forward_many(batches, lengths)
+        padded positions are never computed (rank 2 of SURVEY.md §8(f)).
+        ``need_token_weights=False``: None in place of every token_weights, which are then not computed."""
+        return self._runtime.forward_many(batches, lengths, need_token_weights=need_token_weights)
 
     def encode(self, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
         return self.forward(input_ids, attention_mask)[0]

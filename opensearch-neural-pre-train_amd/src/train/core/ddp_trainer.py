@@ -272,17 +272,18 @@ def micro_step(model, loss_fn: SPLADELossV33, batch: dict, global_step: int, dev
         if os.environ.get("SNX_GATHER_INLINE", "0") == "1":  # A/B and tests: the collective inline on the compute stream
             gather = lambda x: sdist.PendingGather(sdist.all_gather_with_grad(x), None)   # noqa: E731
         gathered = None
+        # the loss reads the pooled vectors only: token_weights (the `_` below, None) are not computed
         if _fuse_passes(model):
             (anchor_repr, _), (positive_repr, _), (negative_repr, _) = unwrap(model).forward_many(
-                [(q_ids, q_mask), (p_ids, p_mask), (n_ids, n_mask)], lengths)
+                [(q_ids, q_mask), (p_ids, p_mask), (n_ids, n_mask)], lengths, need_token_weights=False)
             if xneg:
                 gathered = gather(positive_repr)
         else:
-            anchor_repr, _ = model(q_ids, q_mask)
-            positive_repr, _ = model(p_ids, p_mask)
+            anchor_repr, _ = model(q_ids, q_mask, need_token_weights=False)
+            positive_repr, _ = model(p_ids, p_mask, need_token_weights=False)
             if xneg:
                 gathered = gather(positive_repr)
-            negative_repr, _ = model(n_ids, n_mask)
+            negative_repr, _ = model(n_ids, n_mask, need_token_weights=False)
         if num_negatives > 1:
             negative_repr = negative_repr.view(anchor_repr.shape[0], num_negatives, -1)
         extra = {}
