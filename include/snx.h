@@ -609,17 +609,14 @@ int snx_gemm_tn_accum_group(const snx_tn_problem* probs /*[host]*/, int32_t npro
  * launch's by fp32 summation order (each count is bit-reproducible by itself). */
 /* Process-wide switches of the library (csrc/config.h).  The library reads no environment variable; the Python binding
  * maps its SNX_* variables onto these keys once, at load time (snx/_lib.py), tests and tools call them directly.
- * Keys (default): nt256 (1; 0 off, 2 every eligible shape), nt256_min_m (8192), nt256_coldeal (1: the 64-row units left
- * over after the whole rounds of 256x256 tiles are dealt along column runs, one short tile per workgroup; 0: in tile order;
- * same bits), tn256 (1), tn256_min_m (8192),
+ * Keys (default): nt256 (1; 0 off, 2 every eligible shape), nt256_min_m (8192), tn256 (1), tn256_min_m (8192),
  * dec256 (1), dec256_min_t (2048), bwd_overlap (1), side_prio (1), attn_streaming (0), attn_bwd_onepass (1),
- * attn_interleave (0; 1: the workgroups of a launch's sequence groups interleaved in proportion instead of group by group),
- * splade_dh_panels (64), splade_dw_last (2: the routed decoder backward runs its activation half first, gradient rows and bucket lists non-temporal), f32_gemm64 (0), f32_attn_rows (0), wcache_per_tensor (0), resid_in_ln (1: the Wo GEMMs store
+ * splade_dh_panels (64), f32_gemm64 (0), f32_attn_rows (0), wcache_per_tensor (0), resid_in_ln (1: the Wo GEMMs store
  * bf16 and the residual add happens inside the following LayerNorm; 0: in the GEMMs' fp32 epilogue, same bits),
- * stream_nt (271 = 15 + 256; bitmask of non-temporal accesses for streams nobody reads soon: 1 LayerNorm forward's loads of h and y,
- * 2 its store of h_out, 4 LayerNorm backward's loads of the saved h and of dy, 8 the GeGLU-forward GEMM's stores of the saved
- * u, 256 the weight-gradient GEMM's ordered reduce; 16 / 32 / 64 / 128: measured-level or losing variants kept for A/B -- a
- * cache hint, same bits), nt256_rev (0),
+ * stream_nt (1: non-temporal accesses for the streams nobody reads soon -- LayerNorm forward's loads of h and y and its
+ * store of h_out, LayerNorm backward's loads of the saved h and of dy, the GeGLU-forward GEMM's stores of the saved u, the
+ * weight-gradient GEMM's ordered reduce; 0: none of them; a cache hint, same bits.  A forward without
+ * SNX_FWD_SAVE_FOR_BACKWARD runs its own streams plain whatever the value), nt_pipe (2), nt_pipe_min_m (4096),
  * det_reduce (1: weight gradients -- Linear dW, LayerNorm dw, embedding rows -- summed in a fixed order through the callers'
  * workspaces, bit-reproducible; 0: float atomics in arrival order); diagnostics builds (-DSNX_DIAG) add
  * gemm_cg, gemm_dbg, gemm_mid, tn_splits, nt256_cg, nt256_dbg, nt256_force, tn256_tail_pct, tn256_dbg.  Unknown key or

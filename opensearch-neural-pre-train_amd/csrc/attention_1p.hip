@@ -57,7 +57,6 @@ static_assert(8 * 8192 <= OFF_LSE, "epilogue staging (8 KiB per wave) overlays t
 struct Sched1p {
   int n;
   int seq0[SNX_ATTN_1P_GROUPS], bend[SNX_ATTN_1P_GROUPS];   // first sequence, exclusive prefix end of the group's units
-  int interleave;                                           // 1: the groups' units interleaved in proportion (round 6)
 };
 
 // Inside a plane a row is 32 bytes; rows 8..15 of every 16 swap their two 4-row groups and their two 16-byte halves,
@@ -100,24 +99,19 @@ __device__ unsigned long long* g_attn1p_trace = nullptr;
 #define ATRACE_RT(k)
 #endif
 
-// NTL ("stream_nt" bit 32): q, k, v and dO are read for the last time here (the attention output O is read again by the
-// layer's weight-gradient GEMM): non-temporal loads keep them from displacing the following GEMMs' operands in the caches.
-template <bool NTL>
 __global__ __launch_bounds__(512, 2) void attn_bwd_1p_kernel(
     const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out, const bf16_t* __restrict__ dout,
     const float* __restrict__ lse, const int32_t* __restrict__ cu_seqlens, const int64_t* __restrict__ mask,
     bf16_t* __restrict__ dqkv, const f32x2* __restrict__ rope_tab, const int32_t* __restrict__ pos, int T, int heads,
     int window, float scale, const Sched1p sched) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  auto ld8 = [](const bf16_t* p) __attribute__((always_inline)) {
-    return NTL ? __builtin_nontemporal_load((const bf16x8*)p) : *(const bf16x8*)p;
-  };
+  auto ld8 = [](const bf16_t* p) __attribute__((always_inline)) { return *(const bf16x8*)p; };
   ATRACE(0); ATRACE_RT(12);
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
   int g, unit;
-  block_to_group<SNX_ATTN_1P_GROUPS>(sched.bend, sched.n, sched.interleave, (int)blockIdx.x, g, unit);   // attention_common.h
+  block_to_group<SNX_ATTN_1P_GROUPS>(sched.bend, sched.n, (int)blockIdx.x, g, unit);   // attention_common.h
   const int seq = sched.seq0[g] + unit / heads, head = unit % heads;
   const int s0 = cu_seqlens[seq];
   int slen = cu_seqlens[seq + 1] - s0;
@@ -476,11 +470,9 @@ int attn_bwd_onepass(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, c
     if (b > 0x7fffffffL) return SNX_E_SHAPE;
     sc.bend[i] = (int)b;
   }
-  sc.interleave = g_snx_cfg.attn_interleave != 0 && sc.n > 1;
-  static LdsOptIn optin[2];
-  const bool ntl = (g_snx_cfg.stream_nt & 32) != 0;
-  auto kern = ntl ? attn_bwd_1p_kernel<true> : attn_bwd_1p_kernel<false>;
-  if (const int rc = optin[ntl ? 1 : 0].ensure((const void*)kern, LDS_1P)) return rc;
+  static LdsOptIn optin;
+  auto kern = attn_bwd_1p_kernel;
+  if (const int rc = optin.ensure((const void*)kern, LDS_1P)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)b), dim3(512), LDS_1P, st, qkv, out, dout, lse, cu_seqlens, mask,
                      dqkv, rope_tab, pos, T, heads, window, 0.125f, sc);
   SNX_CHECK_LAUNCH();

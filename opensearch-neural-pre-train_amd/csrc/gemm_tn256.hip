@@ -153,10 +153,6 @@ __device__ __forceinline__ LaneOff lane_offsets(const Tile& t, int wave, int lan
 // DMA instruction k8 (0..7; pair k8 >> 1: dY then X) of the half-step starting at token tok0 into `slot`: rows 8w + 4(k >> 1) .. +3 of
 // sub-tile (k & 1) of the dY slice and of the X slice.  8 DMA instructions per wave and half-step, no branches.  The
 // launcher hands this kernel whole K-steps only (M % 64 == 0; the ragged rest goes to the 128x128 kernel).
-// AUX: cache-policy bits of the LDS-DMA (0 default, 2 = nt: "stream_nt" bit 16 -- every operand of a weight-gradient GEMM is
-// read for the last time; alone the nt form measured level, 489 vs 482 us per layer group, the question in the step is
-// what its 0.7 GB per launch displace from the caches the launch stream's kernels live on)
-template <int AUX>
 __device__ __forceinline__ void request_one(const Tile& t, const LaneOff& o, int tok0, char* slot, int wave, int k8) {
   const int k = k8 >> 1;                              // pair index: rows 8 wave + 4 (k >> 1) .., sub-tile k & 1
   char* d = slot + (wave * 8 + (k >> 1) * 4) * 256 + (k & 1) * SUB;
@@ -164,11 +160,11 @@ __device__ __forceinline__ void request_one(const Tile& t, const LaneOff& o, int
   if (!(k8 & 1)) {
     const int a2 = ((k & 1) && t.n0 + 128 < t.N) ? 256 : 0;
     const char* ba = (const char*)(t.dy + (long)tok0 * t.N) + a2;
-    __builtin_amdgcn_global_load_lds(GLB_PTR(ba + o.a[k >> 1]), LDS_PTR(d), 16, 0, AUX);
+    __builtin_amdgcn_global_load_lds(GLB_PTR(ba + o.a[k >> 1]), LDS_PTR(d), 16, 0, 0);
   } else {
     const int b2 = ((k & 1) && t.k0 + 128 < t.K) ? 256 : 0;
     const char* bb = (const char*)(t.x + (long)tok0 * t.K) + b2;
-    __builtin_amdgcn_global_load_lds(GLB_PTR(bb + o.b[k >> 1]), LDS_PTR(d + PART), 16, 0, AUX);
+    __builtin_amdgcn_global_load_lds(GLB_PTR(bb + o.b[k >> 1]), LDS_PTR(d + PART), 16, 0, 0);
   }
 }
 
@@ -232,7 +228,7 @@ extern "C" int snx_tn256_trace_set(void* buf) {
 
 // SLAB: the flush stores the partial tile into the workspace (ordered reduction); otherwise float atomics into dW.  A
 // template parameter, not a branch: with both flush forms in one kernel hipcc spills 660 bytes per lane.
-template <bool NODMA, bool SLAB, int AUX = 0>
+template <bool NODMA, bool SLAB>
 __global__ __launch_bounds__(256) void gemm_tn256_kernel(TnGroup grp, int M, Sched sch) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
@@ -258,7 +254,7 @@ __global__ __launch_bounds__(256) void gemm_tn256_kernel(TnGroup grp, int M, Sch
   // the MFMA in flight covers 32.
   auto issue = [&](int half, int k8) {
     if (!NODMA)
-      request_one<AUX>(ld_tile, ld_off, (sch.dbg & 4) ? 0 : ld_s * 64 + half * HS, smem + ld_slot * SLOT, wave, k8);
+      request_one(ld_tile, ld_off, (sch.dbg & 4) ? 0 : ld_s * 64 + half * HS, smem + ld_slot * SLOT, wave, k8);
     if (k8 == 7) ld_slot = ld_slot + 1 == RING ? 0 : ld_slot + 1;
   };
   auto issue_all = [&](int half) {
@@ -417,7 +413,7 @@ __global__ __launch_bounds__(256) void gemm_tn256_kernel(TnGroup grp, int M, Sch
 // chunk); a thread owns 4 consecutive k of 4 rows: every access is a whole 16-byte piece of a 1-KiB row.  The slabs were
 // written a moment ago by the GEMM kernel (the group's 60-100 MB sit in the 256-MiB Infinity Cache).  (32-row chunks:
 // 624 workgroups for the layer group = 2.4 per CU, three rounds of ~10 us; 16-row chunks: 1,248.)
-// NT ("stream_nt" bit 256): the slabs are read for the last time and the gradient tile is not read again before the
+// NT ("stream_nt"): the slabs are read for the last time and the gradient tile is not read again before the
 // optimizer -- non-temporal accesses keep both out of the way of the launch stream's operands.
 template <bool NT>
 __global__ __launch_bounds__(256) void tn256_reduce_kernel(TnGroup grp, Sched sch) {
@@ -524,17 +520,16 @@ int snx_launch_tn256(const TnGroup& g128, int M, void* ws, size_t ws_bytes, hipS
     if (!ws || ws_bytes < (size_t)slabs * s.ntiles * (256 * 256 * 4)) return SNX_E_ARG;
     s.ws = (float*)ws;
   }
-  static LdsOptIn optin[5];
+  static LdsOptIn optin[4];
   void (*kern)(TnGroup, int, Sched);
   int which;
   if (s.ws) { which = (dbg & 2) ? 3 : 2; kern = (dbg & 2) ? gemm_tn256_kernel<true, true> : gemm_tn256_kernel<false, true>; }
   else { which = (dbg & 2) ? 1 : 0; kern = (dbg & 2) ? gemm_tn256_kernel<true, false> : gemm_tn256_kernel<false, false>; }
-  if (which == 2 && (g_snx_cfg.stream_nt & 16)) { which = 4; kern = gemm_tn256_kernel<false, true, 2>; }
   if (const int rc = optin[which].ensure((const void*)kern, RING * SLOT)) return rc;
   hipLaunchKernelGGL(kern, dim3(NWG), dim3(256), RING * SLOT, st, g, M, s);
   SNX_CHECK_LAUNCH();
   if (s.ws && !(dbg & 1)) {
-    if (g_snx_cfg.stream_nt & 256) hipLaunchKernelGGL(tn256_reduce_kernel<true>, dim3(s.ntiles, 16), dim3(256), 0, st, g, s);
+    if (g_snx_cfg.stream_nt) hipLaunchKernelGGL(tn256_reduce_kernel<true>, dim3(s.ntiles, 16), dim3(256), 0, st, g, s);
     else hipLaunchKernelGGL(tn256_reduce_kernel<false>, dim3(s.ntiles, 16), dim3(256), 0, st, g, s);
     SNX_CHECK_LAUNCH();
   }

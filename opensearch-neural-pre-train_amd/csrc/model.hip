@@ -228,7 +228,7 @@ struct Side {
       enabled = g_snx_cfg.bwd_overlap ? 1 : 0;
       if (enabled) {
         // LOWEST priority: the weight-gradient workgroups fill the slots the dX chain leaves free (last partial
-        // round of a GEMM, LayerNorm / attention phases) instead of competing with it.  "side_prio" = 0: default.
+        // round of a GEMM, LayerNorm / attention phases) instead of competing with it.  "side_prio" = 0: the default priority.
         int least = 0, greatest = 0;
         const bool low = g_snx_cfg.side_prio != 0;
         if (low && hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
@@ -426,14 +426,7 @@ extern "C" int snx_model_forward_range(const snx_model_desc* d, const void* cons
     if (notw) g_notw.add(saved);
     else if (row0 == 0) g_notw.drop(saved);
   }
-  // The forward's non-temporal streams ("stream_nt" bits 1, 2, 8: residual-stream rows, the saved u) are a TRAINING policy:
-  // without a backward the stream ping-pongs between two buffers and small inference batches live in the caches -- an nt
-  // store would send the next LayerNorm to HBM for them.  (One thread drives the library: the switch is restored on return.)
-  struct NtScope {
-    int saved;
-    explicit NtScope(bool keep) : saved(g_snx_cfg.stream_nt) { if (!keep) g_snx_cfg.stream_nt &= ~(1 | 2 | 8); }
-    ~NtScope() { g_snx_cfg.stream_nt = saved; }
-  } nt_scope(save);
+  SnxPlainForward plain_forward(!save);                   // no backward follows: the forward-side "stream_nt" streams off (config.h)
   PIdx p{d->layers};
   const char* wc = (const char*)wcache;
   const int H = d->hidden, I = d->inter, V = d->vocab, L = d->layers;

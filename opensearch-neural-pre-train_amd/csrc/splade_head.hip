@@ -337,9 +337,9 @@ __device__ __forceinline__ float splade_coef(float g, uint32_t key) {
 // (with one wave per vocab row running its own sweep the gathers touched all of Hd at once and
 // every 1.5 KB row crossed the fabric: 13.6 GB per 192-sequence step, 7.6 TB/s, 1.8 ms).
 // Zero coefficients (most entries once the model is trained) are skipped wave-uniformly.
-// NT ("splade_dw_last"): the read-modify-write of the gradient rows (2 x 153 MB, no reader before the optimizer / the
-// embedding unit at the end of the backward) through non-temporal accesses
-template <int NV, bool NT = false>
+// The read-modify-write of the gradient rows (2 x 153 MB, no reader before the optimizer / the embedding unit at the end
+// of the backward) goes through non-temporal accesses.
+template <int NV>
 __global__ __launch_bounds__(256) void splade_bwd_dw_kernel(const float* __restrict__ g,
                                                             const uint32_t* __restrict__ keys,
                                                             const bf16_t* __restrict__ Hd,
@@ -409,8 +409,7 @@ __global__ __launch_bounds__(256) void splade_bwd_dw_kernel(const float* __restr
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       f32x4* p = (f32x4*)(dst + (i * 64 + lane) * 4);
-      if (NT) __builtin_nontemporal_store(__builtin_nontemporal_load(p) + acc[k][i], p);
-      else *p = *p + acc[k][i];
+      __builtin_nontemporal_store(__builtin_nontemporal_load(p) + acc[k][i], p);
     }
   }
 }
@@ -672,9 +671,9 @@ __global__ __launch_bounds__(256) void splade_dh_items_kernel(const int32_t* __r
   }
 }
 
-// NTL ("splade_dw_last" = 2): the bucket lists (77 MB, read once) through non-temporal loads -- the gather is bound by how
-// fast W_E rows come out of the Infinity Cache, and everything else that passes through it competes with them
-template <int NV, bool NTL = false>
+// The bucket lists (77 MB, read once) come through non-temporal loads -- the gather is bound by how fast W_E rows come out
+// of the Infinity Cache, and everything else that passes through it competes with them
+template <int NV>
 __global__ __launch_bounds__(256) void splade_bwd_dh_panels_kernel(const int32_t* __restrict__ list_v,
                                                                    const float* __restrict__ list_c,
                                                                    const int32_t* __restrict__ row_off,
@@ -724,8 +723,8 @@ __global__ __launch_bounds__(256) void splade_bwd_dh_panels_kernel(const int32_t
       end[j] = live ? ro[row + 1] : 0;
       cbase[j] = cur[j];
       const int e = cbase[j] + lane;
-      cv[j] = e < end[j] ? (NTL ? __builtin_nontemporal_load(lv + e) : lv[e]) : 0x7FFFFFFF;
-      cc[j] = e < end[j] ? (NTL ? __builtin_nontemporal_load(lc + e) : lc[e]) : 0.f;
+      cv[j] = e < end[j] ? __builtin_nontemporal_load(lv + e) : 0x7FFFFFFF;
+      cc[j] = e < end[j] ? __builtin_nontemporal_load(lc + e) : 0.f;
     }
 #pragma unroll 1
     for (int p = 0; p < npanel; ++p) {
@@ -765,8 +764,8 @@ __global__ __launch_bounds__(256) void splade_bwd_dh_panels_kernel(const int32_t
           if (first + n < 64) break;                  // the chunk's next entry belongs to a later panel (or the bucket ended)
           cbase[j] = cur[j];                          // chunk used up: the next 64 entries
           const int e = cbase[j] + lane;
-          cv[j] = e < end[j] ? (NTL ? __builtin_nontemporal_load(lv + e) : lv[e]) : 0x7FFFFFFF;
-          cc[j] = e < end[j] ? (NTL ? __builtin_nontemporal_load(lc + e) : lc[e]) : 0.f;
+          cv[j] = e < end[j] ? __builtin_nontemporal_load(lv + e) : 0x7FFFFFFF;
+          cc[j] = e < end[j] ? __builtin_nontemporal_load(lc + e) : 0.f;
         }
       }
     }
@@ -996,32 +995,17 @@ extern "C" int snx_splade_bwd_tw(const float* g, const uint32_t* keys, const flo
     }
   };
   const int blocks = cdiv(V, 32);               // 4 waves x 8 vocab rows per workgroup
-  // "splade_dw_last" = 1 (round 6): the weight half (dE, db) AFTER the activation half.  The dHd gather below is bound by
-  // how fast W_E rows (77 MB) come out of the Infinity Cache, where the decoder forward has just left them; run first, the
-  // weight half's read-modify-write of the 153 MB gradient matrix pushes them out.  (Then also with non-temporal accesses
-  // to the gradient rows: nobody reads them before the end of the backward.)
-  const bool dw_last = g_snx_cfg.splade_dw_last != 0;
+  // The weight half (dE, db) runs AFTER the activation half.  The dHd gather below is bound by how fast W_E rows (77 MB)
+  // come out of the Infinity Cache, where the decoder forward has just left them; run first, the weight half's
+  // read-modify-write of the 153 MB gradient matrix pushes them out (44.17 against 44.27 ms per micro-step, ABAB).
   auto launch_dw = [&]() {
-    if (dw_last) {
-      switch (H / 256) {
-        case 1: hipLaunchKernelGGL((splade_bwd_dw_kernel<1, true>), dim3(blocks), dim3(256), 0, st, g, keys, (const bf16_t*)Hd, cu_seqlens, gradE, gradb, nseq, V, H); break;
-        case 2: hipLaunchKernelGGL((splade_bwd_dw_kernel<2, true>), dim3(blocks), dim3(256), 0, st, g, keys, (const bf16_t*)Hd, cu_seqlens, gradE, gradb, nseq, V, H); break;
-        case 3: hipLaunchKernelGGL((splade_bwd_dw_kernel<3, true>), dim3(blocks), dim3(256), 0, st, g, keys, (const bf16_t*)Hd, cu_seqlens, gradE, gradb, nseq, V, H); break;
-        default: hipLaunchKernelGGL((splade_bwd_dw_kernel<4, true>), dim3(blocks), dim3(256), 0, st, g, keys, (const bf16_t*)Hd, cu_seqlens, gradE, gradb, nseq, V, H); break;
-      }
-    } else {
-      switch (H / 256) {
-        case 1: hipLaunchKernelGGL(splade_bwd_dw_kernel<1>, dim3(blocks), dim3(256), 0, st, g, keys, (const bf16_t*)Hd, cu_seqlens, gradE, gradb, nseq, V, H); break;
-        case 2: hipLaunchKernelGGL(splade_bwd_dw_kernel<2>, dim3(blocks), dim3(256), 0, st, g, keys, (const bf16_t*)Hd, cu_seqlens, gradE, gradb, nseq, V, H); break;
-        case 3: hipLaunchKernelGGL(splade_bwd_dw_kernel<3>, dim3(blocks), dim3(256), 0, st, g, keys, (const bf16_t*)Hd, cu_seqlens, gradE, gradb, nseq, V, H); break;
-        default: hipLaunchKernelGGL(splade_bwd_dw_kernel<4>, dim3(blocks), dim3(256), 0, st, g, keys, (const bf16_t*)Hd, cu_seqlens, gradE, gradb, nseq, V, H); break;
-      }
+    switch (H / 256) {
+      case 1: hipLaunchKernelGGL(splade_bwd_dw_kernel<1>, dim3(blocks), dim3(256), 0, st, g, keys, (const bf16_t*)Hd, cu_seqlens, gradE, gradb, nseq, V, H); break;
+      case 2: hipLaunchKernelGGL(splade_bwd_dw_kernel<2>, dim3(blocks), dim3(256), 0, st, g, keys, (const bf16_t*)Hd, cu_seqlens, gradE, gradb, nseq, V, H); break;
+      case 3: hipLaunchKernelGGL(splade_bwd_dw_kernel<3>, dim3(blocks), dim3(256), 0, st, g, keys, (const bf16_t*)Hd, cu_seqlens, gradE, gradb, nseq, V, H); break;
+      default: hipLaunchKernelGGL(splade_bwd_dw_kernel<4>, dim3(blocks), dim3(256), 0, st, g, keys, (const bf16_t*)Hd, cu_seqlens, gradE, gradb, nseq, V, H); break;
     }
   };
-  if (!dw_last) {
-    launch_dw();
-    SNX_CHECK_LAUNCH();
-  }
   // dHd: bucket by row, then one wave per token row
   if (max_seqlen > 8192) return SNX_E_SHAPE;
   char* sc = (char*)scratch;
@@ -1048,16 +1032,9 @@ extern "C" int snx_splade_bwd_tw(const float* g, const uint32_t* keys, const flo
     hipLaunchKernelGGL(splade_dh_items_kernel, dim3(1), dim3(256), 0, st, cu_seqlens, items, nseq, max_seqlen);
     SNX_CHECK_LAUNCH();
     const dim3 pgrid(DH_WGS);
-    const bool ntl = g_snx_cfg.splade_dw_last >= 2;
-#define SNX_DH_PANELS(NVV)                                                                                                  \
-  do {                                                                                                                      \
-    if (ntl)                                                                                                                \
-      hipLaunchKernelGGL((splade_bwd_dh_panels_kernel<NVV, true>), pgrid, dim3(256), 0, st, list_v, list_c, row_off, items,  \
-                         (const bf16_t*)W, cu_seqlens, (bf16_t*)dHd, V, H, max_seqlen, nseq, panels, items + nseq + 1, tok_v, tok_c); \
-    else                                                                                                                    \
-      hipLaunchKernelGGL((splade_bwd_dh_panels_kernel<NVV, false>), pgrid, dim3(256), 0, st, list_v, list_c, row_off, items, \
-                         (const bf16_t*)W, cu_seqlens, (bf16_t*)dHd, V, H, max_seqlen, nseq, panels, items + nseq + 1, tok_v, tok_c); \
-  } while (0)
+#define SNX_DH_PANELS(NVV)                                                                                                 \
+  hipLaunchKernelGGL(splade_bwd_dh_panels_kernel<NVV>, pgrid, dim3(256), 0, st, list_v, list_c, row_off, items,            \
+                     (const bf16_t*)W, cu_seqlens, (bf16_t*)dHd, V, H, max_seqlen, nseq, panels, items + nseq + 1, tok_v, tok_c)
     switch (H / 256) {
       case 1: SNX_DH_PANELS(1); break;
       case 2: SNX_DH_PANELS(2); break;
@@ -1066,10 +1043,8 @@ extern "C" int snx_splade_bwd_tw(const float* g, const uint32_t* keys, const flo
     }
 #undef SNX_DH_PANELS
     SNX_CHECK_LAUNCH();
-    if (dw_last) {
-      launch_dw();
-      SNX_CHECK_LAUNCH();
-    }
+    launch_dw();
+    SNX_CHECK_LAUNCH();
     launch_tw_dw();
     SNX_CHECK_LAUNCH();
     return SNX_OK;
@@ -1082,10 +1057,8 @@ extern "C" int snx_splade_bwd_tw(const float* g, const uint32_t* keys, const flo
     default: hipLaunchKernelGGL(splade_bwd_dh_rows_kernel<4>, grid, dim3(256), 0, st, list_v, list_c, row_off, (const bf16_t*)W, cu_seqlens, (bf16_t*)dHd, V, H, max_seqlen, tok_v, tok_c); break;
   }
   SNX_CHECK_LAUNCH();
-  if (dw_last) {
-    launch_dw();
-    SNX_CHECK_LAUNCH();
-  }
+  launch_dw();
+  SNX_CHECK_LAUNCH();
   launch_tw_dw();
   SNX_CHECK_LAUNCH();
   return SNX_OK;

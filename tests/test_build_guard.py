@@ -209,3 +209,8 @@ def test_diagnostics_flavour_compiles_and_the_product_flavour_has_no_diagnostics
         snx.configure(no_such_key=1)
     with pytest.raises(snx.SnxError):
         snx.configure(nt256=7)                           # out of range
+    # keys of concluded experiments (round 6: measured level, variants removed) and the former "stream_nt" bitmask
+    for gone in ({"nt256_rev": 1}, {"attn_interleave": 1}, {"splade_dw_last": 1}, {"nt256_coldeal": 0}, {"stream_nt": 2}):
+        with pytest.raises(snx.SnxError):
+            snx.configure(**gone)
+    assert snx.config("stream_nt") == 1

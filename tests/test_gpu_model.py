@@ -648,6 +648,74 @@ def test_residual_add_in_the_layernorm_equals_the_gemm_epilogue(dev):
         assert torch.equal(g0[n], g1[n]), (n, _grad_stats(g1[n], g0[n]))
 
 
+def test_stream_nt_off_equals_on_bit_for_bit(dev):
+    """snx_configure "stream_nt": 1 (default) sends the streams nobody reads soon through non-temporal accesses, 0 sends
+    none -- a cache hint, so every consumer's outputs are BIT-identical either way.  The four consumers at the smallest
+    shapes that reach them: the LayerNorm with the residual add and the LayerNorm backward (1,061 rows: the last block is
+    partly empty; H = 256), the GeGLU-forward GEMM's saved u on the 256x256 kernel (M = 1,100, N = 512, K = 128, forced
+    on) and the weight-gradient GEMM's ordered reduce (M = 1,088 with "tn256_min_m" = 1024).  And the part of the policy
+    that is not a switch: a forward that saves nothing for a backward runs its streams plain without touching the
+    process-wide value -- same `sparse` as the saving forward of the same model, "stream_nt" unchanged afterwards."""
+    import snx
+    from oracle import splade_oracle as O
+    from snx import ops
+    from snx._lib import check, fn
+    from snx.ops import _p, _stream
+    BF16 = torch.bfloat16
+    g = torch.Generator().manual_seed(77)
+    T, H = 1061, 256
+    h = torch.randn(T, H, generator=g).to(dev)
+    y = torch.randn(T, H, generator=g).to(dev).to(BF16)
+    dy = torch.randn(T, H, generator=g).to(dev).to(BF16)
+    w = (1 + 0.1 * torch.randn(H, generator=g)).to(dev)
+    dh0 = torch.randn(T, H, generator=g).to(dev)
+    a = torch.randn(1100, 128, generator=g).to(dev).to(BF16)
+    wi = (torch.randn(512, 128, generator=g) * 0.05).to(dev).to(BF16)
+    dyt = torch.randn(1088, 512, generator=g).to(dev).to(BF16)
+    xt = torch.randn(1088, 768, generator=g).to(dev).to(BF16)
+
+    def consumers():
+        out = []
+        h_out, x_out = torch.empty_like(h), torch.empty_like(y)
+        check(fn("snx_ln_fwd_add")(_p(h), _p(y), _p(w), _p(h_out), _p(x_out), T, H, 1e-5, _stream()), "snx_ln_fwd_add")
+        out += [h_out, x_out]
+        for overwrite in (False, True):
+            dh, dw, dhb = dh0.clone(), torch.zeros(H, device=dev), torch.empty_like(dy)
+            ops.ln_bwd(dy, h, w, dh, dw, 1e-5, overwrite=overwrite, dh_bf16=dhb)
+            out += [dh, dw, dhb]
+        out += list(ops.gemm_nt_geglu_fwd(a, wi))
+        dwt = torch.zeros(512, 768, device=dev)
+        ops.gemm_tn_accum(dyt, xt, dwt)
+        out.append(dwt)
+        torch.cuda.synchronize()
+        return out
+
+    assert snx.config("stream_nt") == 1
+    tn_min = snx.config("tn256_min_m")
+    try:
+        fn("snx_nt256_configure")(2, 1024)
+        snx.configure(tn256_min_m=1024)
+        on = consumers()
+        snx.configure(stream_nt=0)
+        off = consumers()
+    finally:
+        snx.configure(stream_nt=1, tn256_min_m=tn_min)
+        fn("snx_nt256_configure")(1, 8192)
+    assert len(on) == len(off) == 11
+    for i, (p, q) in enumerate(zip(on, off)):
+        assert torch.isfinite(p.float()).all() and torch.equal(p, q), i
+    # no-save forward against save forward
+    cfg = _small_cfg()
+    m = _build_model(cfg, O.perturb_params(O.init_params(cfg, seed=3), seed=4, scale=2.0, bias_mean=-0.1), dev)
+    ids, mask = O.synth_ids(3, 64, cfg, torch.Generator().manual_seed(9), ragged=True)
+    with torch.autocast(device_type="cuda", dtype=torch.bfloat16):
+        with torch.no_grad():
+            plain, _ = m(ids.to(dev), mask.to(dev))
+        assert snx.config("stream_nt") == 1
+        saved, _ = m(ids.to(dev), mask.to(dev))
+    assert saved.requires_grad and not plain.requires_grad and torch.equal(plain, saved.detach())
+
+
 def test_fused_adamw_matches_torch_adamw(dev):
     """snx_adamw_clip_step == clip_grad_norm_ + torch.optim.AdamW (wd grouping quirk, bias
     correction, clipping active and inactive), and the state dicts are interchangeable."""

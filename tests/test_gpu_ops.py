@@ -651,10 +651,14 @@ def test_gemm_nt256_all_epilogues_equal_the_128_kernel_bit_for_bit(dev, M, N, K)
                                    (9000, 256, 768), (33333, 1280, 320)])
 def test_gemm_nt256_column_run_dealing_of_the_leftover_units(dev, M, N, K):
     """Round 6: the 64-row units left after the whole rounds of tiles are dealt along the leftover tiles' COLUMN runs (one
-    short tile per workgroup, its rows free to cross a row-panel boundary) instead of in tile order (two short tiles for
-    three workgroups in eight at N = 768).  A tile's K loop does not depend on which rows share it: plain store, RoPE and
-    GeGLU-forward outputs must equal the tile-order dealing's bit for bit (and, through the test above, the 128x128
-    kernel's)."""
+    short tile per workgroup, its rows free to cross a row-panel boundary) wherever the launch finds every XCD's leftover
+    tiles inside one super-block of a single column group; every other shape deals them in tile order (two short tiles
+    for three workgroups in eight at N = 768).  A tile's K loop does not depend on which rows share it: plain store, RoPE
+    and GeGLU-forward outputs must equal the 128x128 kernel's bit for bit under either dealing.
+    Which dealing a shape takes follows from the launch arithmetic alone (gemm_nt256.hip launch(), no reserved CUs):
+    column runs for (36864,768,2304), (36864,768,768), (33333,1280,320); tile order for (36864,2304,768), (20037,768,2304),
+    (9000,256,768).  Of the twelve shapes of the test above, (8192,768,768), (20000,2304,192), (36864,768,2304) and
+    (10007,1600,320) take column runs.  A change of shapes must keep both dealings covered."""
     from snx._lib import fn
     ops = _ops()
     g = torch.Generator().manual_seed(M + 3 * N + K)
@@ -667,21 +671,15 @@ def test_gemm_nt256_column_run_dealing_of_the_leftover_units(dev, M, N, K):
     calls = {"store": lambda: (ops.gemm_nt(x, w),), "rope_rows": lambda: (ops.gemm_nt_rope_rows(x, w, tab, pos, rows, rc),),
              "geglu_fwd": lambda: ops.gemm_nt_geglu_fwd(x, w)}
     try:
-        fn("snx_nt256_configure")(2, 1024)
         for name, f in calls.items():
-            assert fn("snx_configure")(b"nt256_coldeal", 0) == 0 and fn("snx_configure")(b"nt256_rev", 0) == 0
+            fn("snx_nt256_configure")(0, 0)
             ref = [t.clone() for t in f()]
-            # ... and "nt256_rev" (the K >= 3 N plain stores walk their row panels from the last to the first): another
-            # tile -> workgroup assignment again, the same tiles
-            for coldeal, rev in ((1, 0), (1, 1), (0, 1)):
-                assert fn("snx_configure")(b"nt256_coldeal", coldeal) == 0 and fn("snx_configure")(b"nt256_rev", rev) == 0
-                got = f()
-                torch.cuda.synchronize()
-                for a, b in zip(ref, got):
-                    assert torch.equal(a, b), (name, M, N, K, coldeal, rev, float((a.float() - b.float()).abs().max()))
+            fn("snx_nt256_configure")(2, 1024)
+            got = f()
+            torch.cuda.synchronize()
+            for a, b in zip(ref, got):
+                assert torch.equal(a, b), (name, M, N, K, float((a.float() - b.float()).abs().max()))
     finally:
-        fn("snx_configure")(b"nt256_coldeal", 1)
-        fn("snx_configure")(b"nt256_rev", 0)
         fn("snx_nt256_configure")(1, 8192)
 
 
@@ -782,13 +780,14 @@ def test_splade_bwd(dev, B, S, V, H, monkeypatch):
     # for vocabulary-ordered buckets): same accumulation order per row, so the same bits
     dHd_rows = torch.full((T, H), float("nan"), dtype=BF16, device=dev)
     import snx
+    panels = snx.config("splade_dh_panels")
     snx.configure(splade_dh_panels=0)
     gE2, gb2 = gE0.clone(), gb0.clone()
     try:
         check(fn("snx_splade_bwd")(_p(gs.to(dev)), _p(keys), _p(hdd), _p(Wd), _p(cud), _p(dHd_rows), _p(gE2), _p(gb2),
                                    _p(scratch), T, B, S, V, H, _stream()), "snx_splade_bwd")
     finally:
-        snx.configure(splade_dh_panels=16)
+        snx.configure(splade_dh_panels=panels)
     assert torch.equal(dHd.view(torch.int16), dHd_rows.view(torch.int16))
     # dense reference through autograd on the bf16 logits
     hl = hdd.float().requires_grad_(True)
@@ -946,20 +945,15 @@ def test_attention_sequence_groups_only_size_the_launch(dev, window):
     d0 = ops.attn_bwd(qkv, out0, dout, lse0, cu, mask, 256, heads, window)
     d1 = ops.attn_bwd(qkv, out0, dout, lse0, cu, mask, 256, heads, window, groups=groups)
     assert torch.equal(d0, d1)
-    # "attn_interleave" = 1 (round 6, opt-in): the groups' blocks interleaved in proportion to their counts instead of group
-    # by group -- another block -> unit bijection, the same units: bit-identical outputs (one-pass and two-pass backward)
+    # the two-pass backward (dQ + dK/dV pair) sizes its launches from the same groups: the same claim
     import snx
     try:
-        snx.configure(attn_interleave=1)
-        out2, lse2 = ops.attn_fwd(qkv, cu, mask, 256, heads, window, groups=groups)
-        d2 = ops.attn_bwd(qkv, out0, dout, lse0, cu, mask, 256, heads, window, groups=groups)
         snx.configure(attn_bwd_onepass=0)
-        d3 = ops.attn_bwd(qkv, out0, dout, lse0, cu, mask, 256, heads, window, groups=groups)
-        snx.configure(attn_interleave=0)
+        d3 = ops.attn_bwd(qkv, out0, dout, lse0, cu, mask, 256, heads, window)
         d4 = ops.attn_bwd(qkv, out0, dout, lse0, cu, mask, 256, heads, window, groups=groups)
     finally:
-        snx.configure(attn_interleave=0, attn_bwd_onepass=1)
-    assert torch.equal(out0, out2) and torch.equal(lse0, lse2) and torch.equal(d0, d2) and torch.equal(d3, d4)
+        snx.configure(attn_bwd_onepass=1)
+    assert torch.equal(d3, d4)
     for bad in ([(0, 7, 64), (8, 4, 256), (11, 3, 100)],      # gap
                 [(0, 7, 64), (7, 4, 256)],                      # does not cover all sequences
                 [(0, 14, 300)],                                 # max_len above max_seqlen
