@@ -516,6 +516,53 @@ int snx_minhash_dedup(const uint32_t* sig, int32_t n, int32_t num_perm, int32_t 
 int snx_minhash_first_match(const uint32_t* q_sig, int32_t nq, const uint32_t* kept_sig, int32_t nk, int32_t num_perm,
                             int32_t need, int32_t* out, hipStream_t stream);
 
+/* ---- Character n-gram TF-IDF (csrc/tfidf.hip): the vectorizer of the reference's lexical hard-negative mining
+ * (ref:scripts/mine_hard_negatives.py:141-146: scikit-learn's TfidfVectorizer(analyzer="char_wb", ngram_range=(2, 3),
+ * max_features=30000, sublinear_tf=True), rows L2-normalised, searched by cosine), which scikit-learn and scipy hold to
+ * 50,000 documents there.  Rows are a CSR of Unicode code points as for the MinHash section: ptr [n+1] int64, code_points
+ * int32 in [0, 0x10FFFF].  The host lowers each text (str.lower) and splits it (str.split); a row is its words joined by
+ * one U+0020, and U+0020 is the only separator the device knows (any run of them, in front, inside or behind, separates).
+ * N-grams: a word w is padded to " " + w + " " (length L >= 3); for n ascending over min_n .. max_n it gives all its
+ * L - n + 1 windows of n code points, or, when L <= n, the whole padded word once and nothing for a larger n.  No window
+ * spans two words: a U+0020 between two words belongs to both padded words (as a 1-gram it counts twice).  An empty row
+ * and a row of U+0020 only have no n-gram.  1 <= min_n <= max_n <= 3, otherwise SNX_E_SHAPE.
+ * Key: an n-gram c0 [c1 [c2]] is the int64 (c0+1) << 42 | (c1+1) << 21 | (c2+1), an absent position 0.  Exact (U+10FFFF + 1
+ * < 2^21), > 0, and ascending key order is the order of the n-gram strings by code point with a prefix first:
+ * scikit-learn's feature order.
+ * Row counts: row r owns the slots [(ptr[r] + 2 r) NS, (ptr[r+1] + 2 (r+1)) NS) of out_key (int64) and out_count (int32),
+ * NS = max_n - min_n + 1 + (min_n == 1); both hold (ptr[n] + 2 n) NS entries.  The front out_cnt[r] slots of a row
+ * receive its distinct keys ascending and how often each occurs; the rest is left unwritten.  One workgroup sorts a row's
+ * slots in LDS when they are at most SNX_TFIDF_LDS_KEYS = 4096 (with the range (2, 3): rows up to 2046 code points); a
+ * longer row is sorted in the workspace by the same code and gives the same result.  longest_row [host]: an upper bound
+ * of the row lengths (a row beyond it comes out empty).  workspace: snx_tfidf_counts_workspace_bytes(longest_row, min_n,
+ * max_n) bytes, 0 when every row fits the LDS form.
+ * Weights (the transform): rows as a CSR of (key ascending, count >= 1), row_ptr [n+1] int64.  feat_key [F] int64 strictly
+ * ascending are the vocabulary, feature id = position; idf [F] float64; tf_table [tmax + 1] float64 is the host's term
+ * frequency function, tf_table[c] for a count c (1 + log(c) for sublinear tf, c otherwise; no logarithm is computed on the
+ * device, as for snx_bm25_weights), every count <= tmax (a larger one is read as tmax).  A key found in feat_key by binary
+ * search is KNOWN, the others are dropped.  u_i = tf_table[c_i] * idf[f_i] in float64, w_i = fp32(u_i / sqrt(sum_j u_j^2)):
+ * the squares are summed in float64 per lane of one wave over the row's entries i = lane, lane + 64, ... ascending, from +0,
+ * then folded by the xor tree 32, 16, .. 1 -- a fixed order, so the bits repeat from run to run; against a float64 sum in
+ * another order a weight differs by at most one fp32 ulp.  Row r's known entries go to the front out_cnt[r] places of
+ * out_fid (int32, ascending) and out_w (fp32, > 0 for idf > 0) from row_ptr[r]; a row with no known key is empty.
+ * Compaction: rows whose filled fronts start at src_ptr[r] move to dst_ptr[r] .. dst_ptr[r+1], the CSR that
+ * snx_sparse_index_build and snx_sparse_search take.
+ * The fit between the two steps -- the distinct keys of a corpus with total count and document frequency, the max_features
+ * keys of largest total count (ties: lowest key), idf = log((1 + n_docs) / (1 + df)) + 1 in float64 with numpy -- is the
+ * Python layer's (snx.retrieval.TfidfIndex): one device-wide sort per corpus.  Stream-ordered, no host synchronisation. */
+#define SNX_TFIDF_LDS_KEYS 4096
+size_t snx_tfidf_counts_workspace_bytes(int64_t longest_row, int32_t min_n, int32_t max_n);
+int snx_tfidf_row_counts(const int64_t* ptr, const int32_t* code_points, int32_t n, int64_t longest_row, int32_t min_n,
+                         int32_t max_n, int64_t* out_key, int32_t* out_count, int32_t* out_cnt, void* workspace,
+                         size_t ws_bytes, hipStream_t stream);
+int snx_tfidf_weights(const int64_t* row_ptr, const int64_t* key, const int32_t* count, int32_t n, const int64_t* feat_key,
+                      const double* idf, int32_t F, const double* tf_table, int32_t tmax, int32_t* out_fid, float* out_w,
+                      int32_t* out_cnt, hipStream_t stream);
+int snx_tfidf_compact_counts(const int64_t* src_ptr, const int64_t* dst_ptr, int32_t n, const int64_t* src_key,
+                             const int32_t* src_count, int64_t* dst_key, int32_t* dst_count, hipStream_t stream);
+int snx_tfidf_compact_rows(const int64_t* src_ptr, const int64_t* dst_ptr, int32_t n, const int32_t* src_fid,
+                           const float* src_w, int32_t* dst_fid, float* dst_w, hipStream_t stream);
+
 /* ---- SPLADELossV33 (ref:src/model/losses.py:183-297) ------------------------------------- */
 /* dims [host] = {B, Bp, k, V, label_off, bf16_mm}: q [B,V], p [Bp,V] (Bp > B: all-gathered
  * positives for cross-GPU in-batch negatives, own rows start at label_off), n [B*k,V]; bf16_mm=1

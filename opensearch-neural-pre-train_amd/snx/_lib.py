@@ -130,6 +130,11 @@ SIGNATURES = {
     "snx_minhash_dedup_workspace_bytes": (SZ, [I32, I32]),
     "snx_minhash_dedup": (I32, [P, I32, I32, I32, P, P, P, SZ, P]),
     "snx_minhash_first_match": (I32, [P, I32, P, I32, I32, I32, P, P]),
+    "snx_tfidf_counts_workspace_bytes": (SZ, [I64, I32, I32]),
+    "snx_tfidf_row_counts": (I32, [P, P, I32, I64, I32, I32, P, P, P, P, SZ, P]),
+    "snx_tfidf_weights": (I32, [P, P, P, I32, P, P, I32, P, I32, P, P, P, P]),
+    "snx_tfidf_compact_counts": (I32, [P, P, I32, P, P, P, P, P]),
+    "snx_tfidf_compact_rows": (I32, [P, P, I32, P, P, P, P, P]),
     "snx_version": (I32, []),
     "snx_prof_enable": (I32, [I32]),
     "snx_prof_num_classes": (I32, []),

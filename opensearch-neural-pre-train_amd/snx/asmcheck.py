@@ -49,6 +49,9 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     # and for MinHash: the MD5 block and the 128-bit minimum, the 32 match counters, and the resolving wave's kept bits stay
     # in registers; the stage, append and first-match kernels hold no LDS and are not listed
     "minhash.hip": ("mh_sig_kernel", "mh_match_kernel", "mh_resolve_kernel"),
+    # and for the TF-IDF row kernel, both forms: the 64-bit keys live in LDS (or the workspace), the window's code points
+    # and the scan state in registers; the weight and compaction kernels hold no LDS and are not listed
+    "tfidf.hip": ("tf_count_kernel",),
 }
 
 # Kernels held to the global-load / vmcnt rule: nothing may touch a load's destination before a vmcnt wait that retires it.

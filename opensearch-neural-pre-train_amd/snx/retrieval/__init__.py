@@ -18,7 +18,9 @@ serving path (csrc/two_phase.hip, include/snx.h "pruning and two-phase search").
 searchers (csrc/hybrid.hip, include/snx.h "BM25 baseline and rank fusion").  ``relevance_csr``,
 ``SparseIndex.first_relevant``, ``ranked_relevance`` and ``bootstrap_means`` score any of these searches against qrels with
 several relevant docs per query (csrc/qrels.hip, include/snx.h "relevance judgments").  ``DenseIndex`` is the exact
-inner-product search over dense fp32 embeddings (csrc/dense.hip, include/snx.h "exact dense retrieval")."""
+inner-product search over dense fp32 embeddings (csrc/dense.hip, include/snx.h "exact dense retrieval").  ``TfidfIndex`` is
+the character n-gram TF-IDF vectorizer of the reference's lexical hard-negative mining over a ``SparseIndex``
+(csrc/tfidf.hip, include/snx.h "Character n-gram TF-IDF")."""
 from ._common import K_MAX, exclusion_csr
 from .dense import DENSE_CHUNK_MIN, DENSE_DIM_MAX, DenseIndex
 from .hybrid import (FUSE_L_MAX, FUSE_METHODS, FUSE_TOP_K_MAX, Bm25Index, bm25_idf, fuse_ranked, term_counts,
@@ -27,3 +29,5 @@ from .qrels import (BOOTSTRAP_M_MAX, BOOTSTRAP_SEGMENT, CUTOFFS_MAX, RANKED_R_MA
                     discount_table, ranked_relevance, relevance_csr)
 from .seismic import SEISMIC_Q_MAX, SeismicIndex
 from .sparse import CHUNK_MAX, PRUNE_TYPES, WINDOW_MAX, SparseIndex, pack_rows, prune_rows, two_phase_window
+from .tfidf import (TfidfIndex, keys_to_ngrams, lds_row_capacity, row_counts, select_features, tfidf_idf, weight_rows,
+                    word_rows)

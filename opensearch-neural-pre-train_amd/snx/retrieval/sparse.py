@@ -229,6 +229,30 @@ class SparseIndex:
                     "snx_sparse_search")
         return scores, docs, rank, tscore
 
+    def search_csr(self, cnt: torch.Tensor, terms: torch.Tensor, weights: torch.Tensor, k: int,
+                   targets: Optional[torch.Tensor] = None, chunk_docs: int = 0):
+        """``search`` for queries already packed as ``add_csr`` takes docs (counts int64 [nq], terms int32 ascending
+        within each row, weights fp32 > 0, on the index's device): the same four results, the same bits."""
+        if not self.built:
+            raise RuntimeError("SparseIndex.search_csr: call build() first")
+        k, chunk_docs = int(k), int(chunk_docs)
+        if not 1 <= k <= K_MAX:
+            raise ValueError(f"SparseIndex.search_csr: k must be in [1, {K_MAX}]")
+        check_chunk_docs(chunk_docs, CHUNK_MAX, "SparseIndex.search_csr")
+        if not (cnt.device == terms.device == weights.device == self.device):
+            raise ValueError(f"SparseIndex.search_csr: tensors must be on {self.device}")
+        _check_csr(cnt, terms, weights, "SparseIndex.search_csr", "nq")
+        if terms.numel():
+            row = torch.repeat_interleave(torch.arange(cnt.numel(), device=self.device), cnt)
+            ok = ((terms >= 0) & (terms < self.V)).all() & ((weights > 0) & torch.isfinite(weights)).all()
+            ok &= ((terms[1:] > terms[:-1]) | (row[1:] != row[:-1])).all()
+            if not bool(ok):
+                raise ValueError(f"SparseIndex.search_csr: rows need ascending distinct ids in [0, {self.V}) and "
+                                 "finite weights > 0")
+        nq = int(cnt.numel())
+        tgt = check_targets(targets, nq, self.num_docs, self.device, "SparseIndex.search_csr")
+        return self._search_csr(offsets(cnt), terms.contiguous(), weights.contiguous(), nq, k, tgt, chunk_docs)
+
     def _queries(self, q_vals, q_ids, q_cnt, who: str):
         if not self.built:
             raise RuntimeError(f"SparseIndex.{who}: call build() first")
