@@ -563,6 +563,59 @@ int snx_tfidf_compact_counts(const int64_t* src_ptr, const int64_t* dst_ptr, int
 int snx_tfidf_compact_rows(const int64_t* src_ptr, const int64_t* dst_ptr, int32_t n, const int32_t* src_fid,
                            const float* src_w, int32_t* dst_fid, float* dst_w, hipStream_t stream);
 
+/* ---- Co-occurrence and PMI (csrc/cooc.hip): the reference's src/pmi package -- windowed co-occurrence counts
+ * (ref:src/pmi/cooccurrence.py:206-226) and PMI with Laplace and context-distribution smoothing
+ * (ref:src/pmi/pmi_calculator.py:142-193).  Input is token ids, never text: rows as a CSR, ptr [n_rows+1] int64, ids int32
+ * in [0, V) or -1 for a token outside the vocabulary (it stays in place: in a sliding window it occupies a slot; any id
+ * outside [0, V) is read as -1).  1 <= V, V * V < 2^63; a cell's key is row * V + col in int64.
+ * Windows: win_ptr == NULL: every row is one window (sentence and paragraph mode), window g is row g.  Otherwise sliding
+ * with window_size = w >= 1 and win_ptr [n_rows+1] int64 the running window counts of the rows: a row of n tokens has no
+ * window when n == 0, one (the whole row) when n <= w, else n - w + 1 windows of w tokens starting at 0 .. n - w
+ * (ref:cooccurrence.py:321-331).  The kernel expands the windows; the host never copies the corpus.
+ * A window's contribution: idx = its ids >= 0 in order, repeats included, m = len(idx); m < 2: nothing.  Otherwise for
+ * every position pair i < j: C[idx_i, idx_j] += 1, and when symmetric also C[idx_j, idx_i] += 1.  So a term r times in a
+ * window adds r (r - 1) to its diagonal cell when symmetric and r (r - 1) / 2 when not, and the non-symmetric C[a, b]
+ * counts the pairs with a before b.
+ * Records: a window gives ONE record per distinct (row term a, col term b) with a multiplicity > 0: key = a * V + b,
+ * mult int64 = its additions to C[a, b], m int32 = the window's m (out_m may be NULL).  Symmetric: only a <= b is emitted
+ * (mult r_a r_b, diagonal r (r - 1)); the caller mirrors once after the reduction.  The order of a window's records is
+ * arbitrary; the caller's reduction (sort, integer sums) does not depend on it.
+ * snx_cooc_windows serves the windows [first_window, first_window + n_windows), n_windows < 2^31.  rec_ptr == NULL is
+ * pass 1: out_cnt [n_windows] int64 receives each window's record count.  rec_ptr [n_windows + 1] (the running sums of
+ * those counts, from any start) is pass 2: window i's records go to out_*[rec_ptr[i] - rec_ptr[0] ..).
+ * A window of at most 64 tokens is one wave's, one of at most SNX_COOC_LDS_TOKENS = 4096 one workgroup's in LDS (48 KiB:
+ * three workgroups per CU of 160 KiB); a longer one takes the workspace with the same code and the same result.
+ * longest_window [host]: an upper bound of the window lengths (a window beyond it gives no record); workspace:
+ * snx_cooc_workspace_bytes(longest_window) bytes, 0 when every window fits LDS.
+ * Normalised cells (weight 1 / m): cells as a CSR over (m ascending, adds), cell_ptr [n_cells+1] int64;
+ * out[c] = fp32(sum_i adds_i / m_i) summed in float64 in ascending m from +0: the same bits from run to run.
+ * PMI, all float64, c the fp32 cell value widened, k = laplace: c < min_cooccurrence: c = k when k > 0, else the result is
+ * NONE = 0.0 under use_ppmi and -inf without; p_joint = (c + k) / (total + k * V * V); p1 = marginals[row], p2 =
+ * marginals[col], either 0: NONE; pmi = log(p_joint / (p1 * p2)) as log2 (SNX_COOC_LOG2), log (SNX_COOC_LOGE) or
+ * log(x) / ln_base (SNX_COOC_LOGB); under use_ppmi max(0, pmi).  snx_cooc_pmi_cells: every stored cell of the CSR (indptr
+ * [V+1] int64, indices int32 ascending per row, data fp32) -> out float64 [nnz].  snx_cooc_pmi_pairs: (rows[i], cols[i])
+ * int32 pairs, the cell found by binary search in its row, an absent cell c = 0, a negative (or >= V) index NONE
+ * -> out float64 [n].  marginals float64 [V] and total are the host's (numpy, ref:pmi_calculator.py:92-116).
+ * Stream-ordered, no host synchronisation. */
+#define SNX_COOC_LDS_TOKENS 4096
+#define SNX_COOC_LOG2 0
+#define SNX_COOC_LOGE 1
+#define SNX_COOC_LOGB 2
+size_t snx_cooc_workspace_bytes(int64_t longest_window);
+int snx_cooc_windows(const int64_t* ptr, const int32_t* ids, int32_t n_rows, const int64_t* win_ptr, int64_t window_size,
+                     int64_t first_window, int64_t n_windows, int64_t longest_window, int64_t V, int32_t symmetric,
+                     const int64_t* rec_ptr, int64_t* out_cnt, int64_t* out_key, int64_t* out_mult, int32_t* out_m,
+                     void* workspace, size_t ws_bytes, hipStream_t stream);
+int snx_cooc_normalized_cells(const int64_t* cell_ptr, const int32_t* m, const int64_t* adds, int64_t n_cells, float* out,
+                              hipStream_t stream);
+int snx_cooc_pmi_cells(const int64_t* indptr, const int32_t* indices, const float* data, int64_t V, int64_t nnz,
+                       const double* marginals, double total, double laplace, double min_cooccurrence, int32_t use_ppmi,
+                       int32_t base_mode, double ln_base, double* out, hipStream_t stream);
+int snx_cooc_pmi_pairs(const int64_t* indptr, const int32_t* indices, const float* data, int64_t V, const int32_t* rows,
+                       const int32_t* cols, int64_t n, const double* marginals, double total, double laplace,
+                       double min_cooccurrence, int32_t use_ppmi, int32_t base_mode, double ln_base, double* out,
+                       hipStream_t stream);
+
 /* ---- SPLADELossV33 (ref:src/model/losses.py:183-297) ------------------------------------- */
 /* dims [host] = {B, Bp, k, V, label_off, bf16_mm}: q [B,V], p [Bp,V] (Bp > B: all-gathered
  * positives for cross-GPU in-batch negatives, own rows start at label_off), n [B*k,V]; bf16_mm=1

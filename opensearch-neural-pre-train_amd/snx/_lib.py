@@ -135,6 +135,11 @@ SIGNATURES = {
     "snx_tfidf_weights": (I32, [P, P, P, I32, P, P, I32, P, I32, P, P, P, P]),
     "snx_tfidf_compact_counts": (I32, [P, P, I32, P, P, P, P, P]),
     "snx_tfidf_compact_rows": (I32, [P, P, I32, P, P, P, P, P]),
+    "snx_cooc_workspace_bytes": (SZ, [I64]),
+    "snx_cooc_windows": (I32, [P, P, I32, P, I64, I64, I64, I64, I64, I32, P, P, P, P, P, P, SZ, P]),
+    "snx_cooc_normalized_cells": (I32, [P, P, P, I64, P, P]),
+    "snx_cooc_pmi_cells": (I32, [P, P, P, I64, I64, P, F64, F64, F64, I32, I32, F64, P, P]),
+    "snx_cooc_pmi_pairs": (I32, [P, P, P, I64, P, P, I64, P, F64, F64, F64, I32, I32, F64, P, P]),
     "snx_version": (I32, []),
     "snx_prof_enable": (I32, [I32]),
     "snx_prof_num_classes": (I32, []),

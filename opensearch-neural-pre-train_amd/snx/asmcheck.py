@@ -52,6 +52,9 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     # and for the TF-IDF row kernel, both forms: the 64-bit keys live in LDS (or the workspace), the window's code points
     # and the scan state in registers; the weight and compaction kernels hold no LDS and are not listed
     "tfidf.hip": ("tf_count_kernel",),
+    # and for the co-occurrence window kernel, all three forms: the keys and run starts live in LDS (or the workspace), the
+    # pair's run bounds and its multiplicity in registers; the normalising and PMI kernels hold no LDS and are not listed
+    "cooc.hip": ("co_window_kernel",),
 }
 
 # Kernels held to the global-load / vmcnt rule: nothing may touch a load's destination before a vmcnt wait that retires it.
