@@ -616,6 +616,29 @@ int snx_cooc_pmi_pairs(const int64_t* indptr, const int32_t* indices, const floa
                        double min_cooccurrence, int32_t use_ppmi, int32_t base_mode, double ln_base, double* out,
                        hipStream_t stream);
 
+/* ---- exact L2 nearest neighbours (csrc/infogain.hip): the distance work of the reference's information-gain filter of
+ * synonym pairs (ref:src/information_gain.py:156-195, 340-364: a float64 cdist of every target and every source against the
+ * whole corpus of term embeddings, then one argsort over the corpus per pair in a Python loop).  The Kozachenko-Leonenko
+ * estimator multiplies log(rho_k) by d and tells a distance of exactly 0 from a tiny one, so the distance is the
+ * difference form in float64; the Gram form (|a|^2 + |b|^2 - 2 a.b) is ruled out, and with it MFMA.
+ * Operands: corpus E [n, D] and queries fp32, row-major, every value finite; 1 <= D <= 4096; n < 2^31.
+ * Distance (part of the ABI, bit-reproducible): d2(q, c) = float64 acc starting at +0.0; for j = 0 .. D-1 ascending
+ * t = (double)q[j] - (double)c[j], acc = fma(t, t, acc).  Tiling, splits and which kernel computes it change no bit; a row
+ * against an identical row gives exactly 0.0.  Order: d2 ascending, ties lowest corpus id first.
+ * snx_l2_knn: per query the k nearest (1 <= k <= SNX_L2_KMAX = 256) -> out_id int32 / out_d2 float64 [nq, k]; unused slots
+ * (k > n) id -1, d2 +inf.  chunk_rows: corpus rows per split (0: default; otherwise rounded up to a multiple of 64); neither
+ * it nor any slicing of the queries changes a bit.  workspace: snx_l2_knn_workspace_bytes(nq, n, k, chunk_rows) bytes -- it
+ * grows with nq * k * splits, never with nq * n.
+ * snx_l2_gather_sorted: for pair i the distances d2(T[i], E[nb[i, r]]), r < K (1 <= K <= 256), by the same chain, an id
+ * outside [0, n) skipped, the row sorted ascending with +inf in the unused slots -> out_d2 float64 [m, K].
+ * Stream-ordered, no host synchronisation. */
+#define SNX_L2_KMAX 256
+size_t snx_l2_knn_workspace_bytes(int32_t nq, int32_t n, int32_t k, int32_t chunk_rows);
+int snx_l2_knn(const float* Q, int32_t nq, const float* E, int32_t n, int32_t D, int32_t k, int32_t chunk_rows,
+               int32_t* out_id, double* out_d2, void* workspace, size_t ws_bytes, hipStream_t stream);
+int snx_l2_gather_sorted(const float* T, int32_t m, const float* E, int32_t n, int32_t D, const int32_t* nb, int32_t K,
+                         double* out_d2, hipStream_t stream);
+
 /* ---- SPLADELossV33 (ref:src/model/losses.py:183-297) ------------------------------------- */
 /* dims [host] = {B, Bp, k, V, label_off, bf16_mm}: q [B,V], p [Bp,V] (Bp > B: all-gathered
  * positives for cross-GPU in-batch negatives, own rows start at label_off), n [B*k,V]; bf16_mm=1

@@ -140,6 +140,9 @@ SIGNATURES = {
     "snx_cooc_normalized_cells": (I32, [P, P, P, I64, P, P]),
     "snx_cooc_pmi_cells": (I32, [P, P, P, I64, I64, P, F64, F64, F64, I32, I32, F64, P, P]),
     "snx_cooc_pmi_pairs": (I32, [P, P, P, I64, P, P, I64, P, F64, F64, F64, I32, I32, F64, P, P]),
+    "snx_l2_knn_workspace_bytes": (SZ, [I32, I32, I32, I32]),
+    "snx_l2_knn": (I32, [P, I32, P, I32, I32, I32, I32, P, P, P, SZ, P]),
+    "snx_l2_gather_sorted": (I32, [P, I32, P, I32, I32, P, I32, P, P]),
     "snx_version": (I32, []),
     "snx_prof_enable": (I32, [I32]),
     "snx_prof_num_classes": (I32, []),

@@ -55,6 +55,9 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     # and for the co-occurrence window kernel, all three forms: the keys and run starts live in LDS (or the workspace), the
     # pair's run bounds and its multiplicity in registers; the normalising and PMI kernels hold no LDS and are not listed
     "cooc.hip": ("co_window_kernel",),
+    # and for the exact L2 search: the 16 float64 accumulators (32 registers) and the prefetched slices stay in registers,
+    # the sort and merge buffers in LDS; the gather keeps its staged rows in LDS and one accumulator per thread
+    "infogain.hip": ("l2_search_kernel", "l2_merge_kernel", "l2_gather_kernel"),
 }
 
 # Kernels held to the global-load / vmcnt rule: nothing may touch a load's destination before a vmcnt wait that retires it.
