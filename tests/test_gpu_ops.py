@@ -802,6 +802,19 @@ def test_splade_bwd(dev, B, S, V, H, monkeypatch):
         cos = float(gg @ rr / (gg.norm() * rr.norm() + 1e-30))
         rel = float((gg - rr).norm() / (rr.norm() + 1e-30))
         assert cos > 0.999 and rel < 2e-2, (name, cos, rel)
+    # per element (tests/splade_bwd_reference.py): the same keys, g rebuilt from their logits so that every coefficient
+    # is an exact bf16 value -- fp32 summation order and dHd's one rounding are then the only errors, and the bound is
+    # derived; one dropped or misrouted entry, invisible to cos / rel above, is orders of magnitude outside it
+    from tests import splade_bwd_reference as R
+    kc = keys.cpu()
+    gx, _ = R.build_exact_g(R.decode_keys(kc)[0], g)
+    ref = R.splade_bwd_reference(gx, kc, None, None, hd, W, cu, gE0.cpu(), gb0.cpu())
+    dHd3 = torch.full((T, H), float("nan"), dtype=BF16, device=dev)
+    gE3, gb3, gxd = gE0.clone(), gb0.clone(), gx.to(dev)
+    check(fn("snx_splade_bwd")(_p(gxd), _p(keys), _p(hdd), _p(Wd), _p(cud), _p(dHd3), _p(gE3), _p(gb3),
+                               _p(scratch), T, B, S, V, H, _stream()), "snx_splade_bwd")
+    ratios = R.check_routed(dHd3, gE3, gb3, ref, gE0, gb0, what=f"splade_bwd {(B, S, V, H)}")
+    print(f"splade_bwd {(B, S, V, H)}: worst err / bound ratio", ratios)
 
 
 def _interleave_cols(x, I):
