@@ -639,6 +639,45 @@ int snx_l2_knn(const float* Q, int32_t nq, const float* E, int32_t n, int32_t D,
 int snx_l2_gather_sorted(const float* T, int32_t m, const float* E, int32_t n, int32_t D, const int32_t* nb, int32_t K,
                          double* out_d2, hipStream_t stream);
 
+/* ---- term-expansion evaluation (csrc/expansion.hip): graded judgments of a source term's expansion, scored against the
+ * model's own ranking of the vocabulary (ref:src/evaluation/ranking_metrics.py:435-680: per query a clone of the row, one
+ * masked element per special id, torch.topk, up to 100 .item() pairs and a Python walk per metric and cutoff).
+ * THE RANKING OF A ROW (part of the ABI): rep [B, V] fp32 contiguous, excluded [V] uint8.  Entry v is RANKED when
+ * rep[v] > 0 and excluded[v] == 0 (NaN, -0.0 and negatives are not > 0).  Ranked entries are ordered by weight descending,
+ * ties lowest id first -- the rule of snx_sparse_topk -- and the list is cut after max_k.  The position of a ranked entry t
+ * is 1 + #{ranked v: rep[v] > rep[t]} + #{ranked v < t: rep[v] == rep[t]}: the kernel counts, it does not sort.  This is the
+ * reference's _sparse_to_ranking (specials to -inf, topk(min(max_k, V)), values <= 0 dropped) wherever torch.topk's
+ * unspecified order among equal weights does not matter.
+ * Judgments, a CSR over the rows: j_ptr [B+1] int64 (starts at 0, does not decrease, ends at nj; a violation reads and
+ * writes nothing out of bounds, its result is otherwise unspecified), j_tok [nj] int32 (per row distinct, any order; an id
+ * outside [0, V) is never read through and is simply unranked), j_grade [nj] uint8 (gain grade 0 .. 3), j_rel [nj] uint8
+ * (non-zero: the entry counts for out_first and out_hits).  Grade and relevance are separate inputs because the
+ * reference's recall / MRR set and its DCG grade map are built differently (snx.expansion).  No cap on a row's judgments.
+ * max_k >= 1.  cutoffs [host] int32, 1 <= ncut <= 8 entries >= 1, strictly ascending; an entry may exceed max_k and then
+ * means the whole cut list.  gain [3, G] float64, the caller's device table, G >= min(max_k, cutoffs[ncut-1]):
+ * gain[(g-1) * G + (p-1)] is the DCG term of grade g at position p.  The Python layer fills it with
+ * (2**g - 1) / math.log2(p + 1); the kernel computes no logarithm and no division (as disc of snx_ranked_relevance).
+ * Outputs: out_rank [nj] int32 = the entry's position, 0 when it is not in the cut list; out_nranked [B] int32 =
+ * min(max_k, ranked entries of the row); out_first [B] int32 = smallest position among the row's j_rel members, 0 if none;
+ * out_hits [B, ncut] int32 = j_rel members at positions <= cutoffs[j]; out_dcg [B, ncut] float64 = the left fold from +0.0,
+ * in ascending position order, of gain[grade-1][p-1] over the row's judged entries with grade > 0 and position
+ * p <= cutoffs[j], every add rounded on its own.
+ * slices: column slices a row is split into over workgroups (0: the call chooses from B and V; otherwise forced, at most
+ * V).  The slices' partial counts are integers added by atomics into the workspace, which the call itself clears on the
+ * stream: the slicing changes no bit.  Stream-ordered, no host synchronisation.
+ * workspace: snx_expansion_workspace_bytes(B, nj) bytes.  snx_expansion_ranks: the first two outputs alone.
+ * Null pointers, bad cutoffs, G too small, nj < 0, slices < 0, a missing or short workspace: SNX_E_ARG; B < 0, V outside
+ * [1, 2^30], max_k < 1: SNX_E_SHAPE.  B * V may exceed 2^31.  B == 0 launches nothing. */
+size_t snx_expansion_workspace_bytes(int32_t B, int64_t nj);
+int snx_expansion_ranks(const float* rep, int32_t B, int32_t V, const uint8_t* excluded, const int64_t* j_ptr,
+                        const int32_t* j_tok, int64_t nj, int32_t max_k, int32_t slices, int32_t* out_rank,
+                        int32_t* out_nranked, void* workspace, size_t ws_bytes, hipStream_t stream);
+int snx_expansion_metrics(const float* rep, int32_t B, int32_t V, const uint8_t* excluded, const int64_t* j_ptr,
+                          const int32_t* j_tok, const uint8_t* j_grade, const uint8_t* j_rel, int64_t nj, int32_t max_k,
+                          const int32_t* cutoffs /*[host]*/, int32_t ncut, const double* gain, int32_t G, int32_t slices,
+                          int32_t* out_rank, int32_t* out_nranked, int32_t* out_first, int32_t* out_hits, double* out_dcg,
+                          void* workspace, size_t ws_bytes, hipStream_t stream);
+
 /* ---- SPLADELossV33 (ref:src/model/losses.py:183-297) ------------------------------------- */
 /* dims [host] = {B, Bp, k, V, label_off, bf16_mm}: q [B,V], p [Bp,V] (Bp > B: all-gathered
  * positives for cross-GPU in-batch negatives, own rows start at label_off), n [B*k,V]; bf16_mm=1

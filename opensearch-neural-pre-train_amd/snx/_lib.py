@@ -143,6 +143,9 @@ SIGNATURES = {
     "snx_l2_knn_workspace_bytes": (SZ, [I32, I32, I32, I32]),
     "snx_l2_knn": (I32, [P, I32, P, I32, I32, I32, I32, P, P, P, SZ, P]),
     "snx_l2_gather_sorted": (I32, [P, I32, P, I32, I32, P, I32, P, P]),
+    "snx_expansion_workspace_bytes": (SZ, [I32, I64]),
+    "snx_expansion_ranks": (I32, [P, I32, I32, P, P, P, I64, I32, I32, P, P, P, SZ, P]),
+    "snx_expansion_metrics": (I32, [P, I32, I32, P, P, P, P, P, I64, I32, P, I32, P, I32, I32, P, P, P, P, P, P, SZ, P]),
     "snx_version": (I32, []),
     "snx_prof_enable": (I32, [I32]),
     "snx_prof_num_classes": (I32, []),

@@ -58,6 +58,9 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     # and for the exact L2 search: the 16 float64 accumulators (32 registers) and the prefetched slices stay in registers,
     # the sort and merge buffers in LDS; the gather keeps its staged rows in LDS and one accumulator per thread
     "infogain.hip": ("l2_search_kernel", "l2_merge_kernel", "l2_gather_kernel"),
+    # and for the term-expansion count: the eight keys of a lane, its counter and the thresholds read back from LDS stay in
+    # registers; the finalize kernel holds no LDS and is not listed
+    "expansion.hip": ("ex_count_kernel",),
 }
 
 # Kernels held to the global-load / vmcnt rule: nothing may touch a load's destination before a vmcnt wait that retires it.

@@ -28,10 +28,15 @@ class HashTokenizer:
         names = {0: "<s>", 1: "</s>", self.pad_token_id: "<pad>"}
         return [names.get(i, f"<unused{i}>" if i < 6 else f"w{i}") for i in ids]
 
+    def encode(self, text, add_special_tokens=True):
+        """The ids of one text, as ``__call__`` forms them (src.evaluation resolves judged tokens through this)."""
+        ids = [6 + zlib.crc32(w.encode()) % (self.vocab_size - 7) for w in text.split()]
+        return [0] + ids + [1] if add_special_tokens else ids
+
     def __call__(self, texts, padding=True, truncation=True, max_length=64, return_tensors="pt"):
         rows = []
         for t in texts:
-            ids = [0] + [6 + zlib.crc32(w.encode()) % (self.vocab_size - 7) for w in t.split()] + [1]
+            ids = self.encode(t)
             if truncation and len(ids) > max_length:
                 ids = ids[:max_length - 1] + [1]
             rows.append(ids)
