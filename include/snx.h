@@ -191,6 +191,60 @@ int snx_model_backward_f32_tw(const snx_model_desc* d, const void* const* params
 int snx_gemm_f32(const float* A, int64_t a_row, int64_t a_k, const float* B, int64_t b_row, int64_t b_k, float* C, int64_t ldc,
                  const float* R, int64_t ldr, int32_t M, int32_t N, int32_t K, int32_t accumulate, hipStream_t stream);
 
+/* ---- dense teacher encoder (csrc/teacher.hip): the forward of an XLM-RoBERTa encoder with CLS pooling -- BGE-M3's dense
+ * head, what ref:src/model/teachers/bge_m3.py:66-94 and ref:scripts/precompute_teacher_scores.py:89-159 run through
+ * sentence-transformers.  `xr:` = transformers/models/xlm_roberta/modeling_xlm_roberta.py.  Post-LayerNorm with biases,
+ * learned absolute positions, erf-GELU MLP, no RoPE, no window.  Same contract as the snx_model_* entry points: nothing
+ * allocated inside, caller-owned arena, stream-ordered, shapes checked on the host before any launch.
+ * precision: SNX_TEACHER_BF16 -- GEMM operands and GEMM outputs bf16 (snx_gemm_nt_bf16, snx_attn_fwd), the residual stream
+ * h and all LayerNorm / GELU / softmax arithmetic fp32; SNX_TEACHER_F32 -- no cast point (snx_gemm_f32, fp32 attention).
+ * Constraints: hidden % 256 == 0 (<= 1024), head_dim == 64, heads * 64 == hidden, inter % 64 == 0, layers <= 128. */
+#define SNX_TEACHER_BF16 0
+#define SNX_TEACHER_F32 1
+typedef struct snx_teacher_desc {
+  int32_t vocab, hidden, inter, layers, heads, head_dim;
+  int32_t max_pos, type_vocab, pad_id, reserved0;
+  float ln_eps, reserved1;
+} snx_teacher_desc;
+/* Number of parameter tensors of XLMRobertaModel(add_pooling_layer=False), in the canonical order of `params`:
+ *   word_embeddings, position_embeddings, token_type_embeddings, embeddings.LayerNorm.{weight,bias}, then per layer
+ *   query.{weight,bias}, key.{..}, value.{..}, attention.output.dense.{..}, attention.output.LayerNorm.{..},
+ *   intermediate.dense.{..}, output.dense.{..}, output.LayerNorm.{..}      (5 + 16 layers; all fp32). */
+int32_t snx_teacher_param_count(const snx_teacher_desc* d);
+/* bf16 copies of the matrices, q / k / v stacked to [3 hidden, hidden] (the QKV GEMM's output then IS the [T, 3, heads, 64]
+ * layout of the attention), and the stacked fp32 q / k / v bias [3 hidden].  Both precisions read the cache (the fp32
+ * path its biases only); refresh it whenever the weights change. */
+size_t snx_teacher_weight_cache_bytes(const snx_teacher_desc* d);
+int snx_teacher_weight_cache_refresh(const snx_teacher_desc* d, const void* const* params /*[host] fp32 device ptrs*/,
+                                     void* cache, hipStream_t stream);
+size_t snx_teacher_workspace_bytes(const snx_teacher_desc* d, int32_t T, int32_t nseq, int32_t precision);
+/* ids [T] int64 (unpadded, sequences end to end), pos_ids [T] int32 (XLM-R: cumsum(mask) * mask + pad_id, computed by the
+ * caller on the padded batch) -> cls_out [nseq, hidden] fp32 = last_hidden_state[:, 0], emb_out [nseq, hidden] fp32 =
+ * cls / max(||cls||_2, 1e-12).  Every sequence needs at least one token; max_seqlen = the longest sequence of the call. */
+int snx_teacher_forward(const snx_teacher_desc* d, const void* const* params /*[host]*/, const void* wcache,
+                        const int64_t* ids, const int32_t* pos_ids, const int32_t* cu_seqlens, void* workspace,
+                        float* cls_out, float* emb_out, int32_t T, int32_t nseq, int32_t max_seqlen, int32_t precision,
+                        hipStream_t stream);
+/* The row kernels of the forward, exported for parity tests.  y_f32 != 0: `y` is fp32 (fp32 path), else bf16 (bf16 path);
+ * x_out (bf16, nullable) receives bf16(h_out).  H as `hidden` above.
+ * embed_ln (xr: XLMRobertaEmbeddings): h_out = LN((word[ids[t]] + type0) + pos[pos_ids[t]]) * w + b; ids and pos_ids are
+ * clamped into their tables.
+ * bias_resid_ln (xr: XLMRobertaSelfOutput / XLMRobertaOutput): h_out = LN((y + bias) + h) * w + b; h_out may be h.
+ * bias_rows / bias_gelu: y += bias / y = gelu_erf(y + bias), in place on [T, N], N % 8 == 0, one rounding when y is bf16.
+ * cls_normalize: cls[s] = h[cu_seqlens[s]], emb[s] = cls[s] / max(||cls[s]||_2, 1e-12) (F.normalize).
+ * attn_f32: out [T, heads, 64] = softmax(q k^T / 8) v over the keys of the row's own sequence, qkv fp32 [T, 3, heads, 64]. */
+int snx_teacher_embed_ln(const int64_t* ids, const int32_t* pos_ids, const float* word, const float* pos, const float* type0,
+                         const float* w, const float* b, float* h_out, void* x_out, int32_t T, int32_t H, int32_t vocab,
+                         int32_t max_pos, float eps, hipStream_t stream);
+int snx_teacher_bias_resid_ln(const float* h, const void* y, int32_t y_f32, const float* bias, const float* w, const float* b,
+                              float* h_out, void* x_out, int32_t T, int32_t H, float eps, hipStream_t stream);
+int snx_teacher_bias_rows(void* y, int32_t y_f32, const float* bias, int32_t T, int32_t N, hipStream_t stream);
+int snx_teacher_bias_gelu(void* y, int32_t y_f32, const float* bias, int32_t T, int32_t N, hipStream_t stream);
+int snx_teacher_cls_normalize(const float* h, const int32_t* cu_seqlens, float* cls, float* emb, int32_t T, int32_t nseq,
+                              int32_t H, hipStream_t stream);
+int snx_teacher_attn_f32(const float* qkv, const int32_t* cu_seqlens, float* out, int32_t T, int32_t nseq, int32_t heads,
+                         hipStream_t stream);
+
 /* ---- inference post-processing (ref:benchmark/encoders.py:309-345 NeuralSparseEncoderV33._encode_batch) ---- */
 /* Per row of rep [B,V] fp32: entries with rep > 0 and allowed[v] != 0 survive.  k > 0 and more than k survivors:
  * the k largest, weight descending, ties lowest id first (out_sorted[b] = 1); otherwise all survivors in id

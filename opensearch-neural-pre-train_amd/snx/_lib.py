@@ -146,6 +146,17 @@ SIGNATURES = {
     "snx_expansion_workspace_bytes": (SZ, [I32, I64]),
     "snx_expansion_ranks": (I32, [P, I32, I32, P, P, P, I64, I32, I32, P, P, P, SZ, P]),
     "snx_expansion_metrics": (I32, [P, I32, I32, P, P, P, P, P, I64, I32, P, I32, P, I32, I32, P, P, P, P, P, P, SZ, P]),
+    "snx_teacher_param_count": (I32, [P]),
+    "snx_teacher_weight_cache_bytes": (SZ, [P]),
+    "snx_teacher_weight_cache_refresh": (I32, [P, P, P, P]),
+    "snx_teacher_workspace_bytes": (SZ, [P, I32, I32, I32]),
+    "snx_teacher_forward": (I32, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, P]),
+    "snx_teacher_embed_ln": (I32, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, F32, P]),
+    "snx_teacher_bias_resid_ln": (I32, [P, P, I32, P, P, P, P, P, I32, I32, F32, P]),
+    "snx_teacher_bias_rows": (I32, [P, I32, P, I32, I32, P]),
+    "snx_teacher_bias_gelu": (I32, [P, I32, P, I32, I32, P]),
+    "snx_teacher_cls_normalize": (I32, [P, P, P, P, I32, I32, I32, P]),
+    "snx_teacher_attn_f32": (I32, [P, P, P, I32, I32, I32, P]),
     "snx_version": (I32, []),
     "snx_prof_enable": (I32, [I32]),
     "snx_prof_num_classes": (I32, []),

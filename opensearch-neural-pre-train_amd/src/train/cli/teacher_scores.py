@@ -1,13 +1,18 @@
-"""Teacher scores and dense hard negatives from cached teacher embeddings (src.train.mining.dense), on one GPU.
+"""Teacher embeddings, teacher scores and dense hard negatives (snx.teacher, src.train.mining.dense), on one GPU.
 
+    python -m src.train.cli.teacher_scores encode --model-dir /models/bge-m3 --input-pattern "data/v29.0/train_*.jsonl" \\
+        --output-dir cache [--max-length 256] [--batch-tokens 16384] [--precision bf16|fp32] [--num-shards n --shard-index i]
+    python -m src.train.cli.teacher_scores encode --merge --output-dir cache        # after a sharded run
     python -m src.train.cli.teacher_scores score --embeddings cache/embeddings.npy --text-index cache/text_index.json \\
         --input-pattern "data/v29.0/train_*.jsonl" --output-dir data/v29.0_kd
     python -m src.train.cli.teacher_scores mine --embeddings cache/embeddings.npy --text-index cache/text_index.json \\
         --input-pattern "data/v29.0_kd/train_*.jsonl" --output-dir data/v30.0_multi_neg --k 7 --rank-start 10 --rank-end 50
 
-``score`` is ref:scripts/precompute_teacher_scores.py without the encoder (the cache is its ``embeddings.npy`` /
-``text_index.json``); ``mine`` is ref:scripts/mine_multi_negatives.py.  Flags shared with those scripts keep their names
-and defaults.  Both run as a single process."""
+``encode`` is the encoder of ref:scripts/precompute_teacher_scores.py:49-159 (unique texts in first-occurrence order, BGE-M3
+dense embeddings, L2-normalised) on the native XLM-RoBERTa forward; it writes ``embeddings.npy`` / ``text_index.json``.  A
+sharded run (one process per GPU, ``--num-shards n --shard-index i``) writes ``embeddings.part{i}.npy`` and ``--merge`` joins
+them.  ``score`` is the rest of that script (it reads the cache); ``mine`` is ref:scripts/mine_multi_negatives.py.  Flags
+shared with those scripts keep their names and defaults.  Every subcommand runs as a single process."""
 from __future__ import annotations
 
 import argparse
@@ -37,15 +42,54 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             sp.add_argument("--sample", choices=("first", "random"), default="first")
             sp.add_argument("--seed", type=int, default=42)
             sp.add_argument("--chunk-docs", type=int, default=0)
+    sp = sub.add_parser("encode", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    sp.add_argument("--model-dir", type=str, default=None, help="local HF directory of the teacher (never a model name)")
+    sp.add_argument("--input-pattern", type=str, default="data/v29.0/train_*.jsonl")
+    sp.add_argument("--output-dir", type=str, required=True, help="cache directory")
+    sp.add_argument("--max-length", type=int, default=256)
+    sp.add_argument("--batch-tokens", type=int, default=16384, help="token rows per forward")
+    sp.add_argument("--precision", choices=("bf16", "fp32"), default="bf16")
+    sp.add_argument("--num-shards", type=int, default=1)
+    sp.add_argument("--shard-index", type=int, default=0)
+    sp.add_argument("--merge", action="store_true", help="join the parts of a sharded run into embeddings.npy")
+    sp.add_argument("--device", type=str, default="cuda:0")
     args = ap.parse_args(argv)
+    if args.command == "encode":
+        if not args.merge and not args.model_dir:
+            ap.error("encode needs --model-dir (or --merge)")
+        if args.num_shards < 1 or not 0 <= args.shard_index < args.num_shards or args.max_length < 1 or args.batch_tokens < 1:
+            ap.error("need --num-shards >= 1, 0 <= --shard-index < --num-shards, --max-length >= 1, --batch-tokens >= 1")
     if args.command == "mine" and (args.k < 1 or not 0 <= args.rank_start < args.rank_end <= 1024):
         ap.error("need --k >= 1 and 0 <= --rank-start < --rank-end <= 1024")
     return args
 
 
-def main(argv: Optional[List[str]] = None):
+def encode_main(args: argparse.Namespace, tokenizer=None):
+    """``encode``: (unique texts, rows written), or the merged rows for ``--merge``.  ``tokenizer``: an HF tokenizer to use
+    instead of the one stored in ``--model-dir``."""
+    from src.train.mining import expand_files
+    from src.train.mining.dense import merge_teacher_cache, write_teacher_cache
+    if args.merge:
+        n = merge_teacher_cache(args.output_dir)
+        logger.info(f"merged {n} row(s) into {args.output_dir}/embeddings.npy")
+        return n
+    files = expand_files([args.input_pattern])
+    if not files:
+        raise FileNotFoundError(f"no input files match {args.input_pattern!r}")
+    from src.model.teachers import BGEM3Teacher
+    teacher = BGEM3Teacher(args.model_dir, device=args.device, max_length=args.max_length, normalize_embeddings=True,
+                           tokenizer=tokenizer, precision=args.precision, batch_tokens=args.batch_tokens)
+    out = write_teacher_cache(files, args.output_dir, teacher.encode, teacher.model.config.hidden_size,
+                              num_shards=args.num_shards, shard_index=args.shard_index)
+    logger.info(f"encoded {out[1]} of {out[0]} unique text(s) of {len(files)} file(s) into {args.output_dir}")
+    return out
+
+
+def main(argv: Optional[List[str]] = None, tokenizer=None):
     args = parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s [%(levelname)s] %(message)s")
+    if args.command == "encode":
+        return encode_main(args, tokenizer)
     import torch
     from snx.retrieval import DenseIndex
     from src.train.mining import copy_val_files, expand_files

@@ -1,8 +1,9 @@
 """Teacher scores and dense hard-negative mining from cached teacher embeddings (BGE-M3 in the reference), on the GPU.
 
-The dense encoder is not part of this project: embeddings arrive as the reference's cache, an ``.npy`` array [n, D] plus
-a JSON map ``md5(text)[:16] -> row`` (ref:scripts/mine_multi_negatives.py:45-64).  Everything from the arrays onward is
-here, on ``snx.retrieval.DenseIndex`` (csrc/dense.hip):
+Embeddings arrive as the reference's cache, an ``.npy`` array [n, D] plus a JSON map ``md5(text)[:16] -> row``
+(ref:scripts/mine_multi_negatives.py:45-64); ``write_teacher_cache`` writes that cache from any encoder (the CLI hands it
+``src.model.teachers.BGEM3Teacher.encode``).  Everything from the arrays onward is on ``snx.retrieval.DenseIndex``
+(csrc/dense.hip):
 
   write_teacher_scores   ref:scripts/precompute_teacher_scores.py:162-224 through ``pair_scores``: every record gets
                          ``teacher_pos_score`` / ``teacher_neg_score`` as round(float(s), 6), one output file per shard; a
@@ -53,6 +54,72 @@ def load_teacher_cache(embeddings_npy: str, text_index_json: str) -> Tuple[np.nd
     if text_to_idx and not 0 <= min(text_to_idx.values()) <= max(text_to_idx.values()) < emb.shape[0]:
         raise ValueError(f"{text_index_json}: rows must lie in [0, {emb.shape[0]})")
     return emb, text_to_idx
+
+
+def collect_unique_texts(input_files: Sequence[str]) -> Tuple[List[str], Dict[str, int]]:
+    """The unique texts of the shards in first-occurrence order and the map text hash -> row
+    (ref:scripts/precompute_teacher_scores.py:49-86: ``query``, ``positive``, ``negative`` of every record; here also the
+    entries of a ``negatives`` list, which ``write_teacher_scores`` reads).  Files in sorted order; only strings count."""
+    seen: Dict[str, int] = {}
+    texts: List[str] = []
+    for path in sorted(input_files):
+        for item in _read(path):
+            if not isinstance(item, dict):
+                continue
+            negs = item["negatives"] if isinstance(item.get("negatives"), list) else []
+            for text in [item.get("query"), item.get("positive"), item.get("negative")] + list(negs):
+                if not isinstance(text, str):
+                    continue
+                h = text_hash(text)
+                if h not in seen:
+                    seen[h] = len(texts)
+                    texts.append(text)
+    return texts, seen
+
+
+def shard_range(n: int, num_shards: int, shard_index: int) -> Tuple[int, int]:
+    """Rows [begin, end) of shard ``shard_index`` of ``num_shards`` contiguous, near-equal parts of ``n`` rows."""
+    if num_shards < 1 or not 0 <= shard_index < num_shards:
+        raise ValueError("need num_shards >= 1 and 0 <= shard_index < num_shards")
+    return n * shard_index // num_shards, n * (shard_index + 1) // num_shards
+
+
+def write_teacher_cache(input_files: Sequence[str], output_dir: str, encode, dim: int, num_shards: int = 1,
+                        shard_index: int = 0) -> Tuple[int, int]:
+    """Encode the unique texts of the shards into the cache ``load_teacher_cache`` reads: ``text_index.json`` and
+    ``embeddings.npy`` fp32 [n, dim] -- or, for ``num_shards > 1``, this shard's rows as ``embeddings.part{i}.npy``
+    (``merge_teacher_cache`` joins them).  ``encode(texts) -> array-like [len(texts), dim]``, rows in input order.
+    Returns (unique texts, rows written)."""
+    texts, seen = collect_unique_texts(input_files)
+    b, e = shard_range(len(texts), int(num_shards), int(shard_index))
+    emb = np.zeros((0, dim), np.float32)
+    if e > b:
+        emb = np.ascontiguousarray(_to_host(encode(texts[b:e])), dtype=np.float32)
+    if emb.shape != (e - b, dim):
+        raise ValueError(f"teacher cache: the encoder returned shape {emb.shape}, expected {(e - b, dim)}")
+    os.makedirs(output_dir, exist_ok=True)
+    with open(os.path.join(output_dir, "text_index.json"), "w") as f:
+        json.dump(seen, f)
+    name = "embeddings.npy" if int(num_shards) == 1 else f"embeddings.part{int(shard_index)}.npy"
+    np.save(os.path.join(output_dir, name), emb)
+    return len(texts), e - b
+
+
+def merge_teacher_cache(output_dir: str) -> int:
+    """Join ``embeddings.part{0..k-1}.npy`` of a sharded run into ``embeddings.npy``; the rows must match
+    ``text_index.json``.  Returns the rows."""
+    parts = []
+    while os.path.exists(os.path.join(output_dir, f"embeddings.part{len(parts)}.npy")):
+        parts.append(np.load(os.path.join(output_dir, f"embeddings.part{len(parts)}.npy")))
+    if not parts:
+        raise FileNotFoundError(f"{output_dir}: no embeddings.part0.npy")
+    emb = np.concatenate(parts, axis=0).astype(np.float32, copy=False)
+    with open(os.path.join(output_dir, "text_index.json")) as f:
+        n = len(json.load(f))
+    if emb.shape[0] != n:
+        raise ValueError(f"{output_dir}: the parts hold {emb.shape[0]} rows, text_index.json names {n} (a shard is missing)")
+    np.save(os.path.join(output_dir, "embeddings.npy"), emb)
+    return n
 
 
 def _to_index(index, a: np.ndarray):
