@@ -220,7 +220,9 @@ int snx_teacher_weight_cache_refresh(const snx_teacher_desc* d, const void* cons
 size_t snx_teacher_workspace_bytes(const snx_teacher_desc* d, int32_t T, int32_t nseq, int32_t precision);
 /* ids [T] int64 (unpadded, sequences end to end), pos_ids [T] int32 (XLM-R: cumsum(mask) * mask + pad_id, computed by the
  * caller on the padded batch) -> cls_out [nseq, hidden] fp32 = last_hidden_state[:, 0], emb_out [nseq, hidden] fp32 =
- * cls / max(||cls||_2, 1e-12).  Every sequence needs at least one token; max_seqlen = the longest sequence of the call. */
+ * cls / max(||cls||_2, 1e-12).  Every sequence needs at least one token; max_seqlen = the longest sequence of the call.
+ * cu_seqlens [nseq + 1]: ascending, cu_seqlens[0] = 0, cu_seqlens[nseq] = T, as for snx_model_forward_f32 -- the kernels
+ * trust it. */
 int snx_teacher_forward(const snx_teacher_desc* d, const void* const* params /*[host]*/, const void* wcache,
                         const int64_t* ids, const int32_t* pos_ids, const int32_t* cu_seqlens, void* workspace,
                         float* cls_out, float* emb_out, int32_t T, int32_t nseq, int32_t max_seqlen, int32_t precision,
@@ -232,7 +234,9 @@ int snx_teacher_forward(const snx_teacher_desc* d, const void* const* params /*[
  * bias_resid_ln (xr: XLMRobertaSelfOutput / XLMRobertaOutput): h_out = LN((y + bias) + h) * w + b; h_out may be h.
  * bias_rows / bias_gelu: y += bias / y = gelu_erf(y + bias), in place on [T, N], N % 8 == 0, one rounding when y is bf16.
  * cls_normalize: cls[s] = h[cu_seqlens[s]], emb[s] = cls[s] / max(||cls[s]||_2, 1e-12) (F.normalize).
- * attn_f32: out [T, heads, 64] = softmax(q k^T / 8) v over the keys of the row's own sequence, qkv fp32 [T, 3, heads, 64]. */
+ * attn_f32: out [T, heads, 64] = softmax(q k^T / 8) v over the keys of the row's own sequence, qkv fp32 [T, 3, heads, 64];
+ * the tiled forward of the fp32 path (snx_model_forward_f32) without mask or window.  qkv and out 16-byte aligned;
+ * cu_seqlens as for snx_teacher_forward (ascending, from 0 to T): it is not checked on the device. */
 int snx_teacher_embed_ln(const int64_t* ids, const int32_t* pos_ids, const float* word, const float* pos, const float* type0,
                          const float* w, const float* b, float* h_out, void* x_out, int32_t T, int32_t H, int32_t vocab,
                          int32_t max_pos, float eps, hipStream_t stream);

@@ -56,10 +56,26 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+
+// the sequence of token t in packed rows: the last s with cu[s] <= t (cu ascending, cu[0] = 0; empty sequences are skipped)
+__device__ __forceinline__ int seq_of_token(const int32_t* cu, int nseq, int t) {
+  int lo = 0, hi = nseq - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (cu[mid] <= t) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
 }
 
 // Exact-erf GELU x*Phi(x) and its derivative Phi(x) + x*phi(x) in fp32 (torch's F.gelu default).
@@ -140,3 +156,9 @@ int snx_embed_ln_bwd_x(const float* dh, const int64_t* ids, const float* E, cons
                        int32_t T, int32_t H, int32_t V, float eps, int32_t pad_id, void* ws, size_t ws_bytes,
                        LnDwBatch* defer, int* ndefer, hipStream_t st);
 
+// fp32 attention forward, MFMA-tiled (f32_path.hip): packed qkv [T, 3, heads, hd] -> out [T, heads, hd], and per (head, token)
+// the log-sum-exp.  cu ascending with cu[0] = 0 and cu[nseq] = T; qkv and out 16-byte aligned; hd % 8 == 0 and hd <= 64
+// (SNX_E_SHAPE otherwise).  window < 0: every key of the sequence.
+int snx_attn_f32_fwd_tiled_x(const float* qkv, const int32_t* cu, const int64_t* mask /*NULL: every key visible*/,
+                             float* out, float* lse /*NULL: not stored*/, int T, int nseq, int heads, int hd,
+                             int window, float scale, hipStream_t st);

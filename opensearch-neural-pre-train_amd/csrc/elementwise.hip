@@ -3,11 +3,11 @@
 // in fp32 with the reference's autocast cast points (fp32 residual stream / LayerNorm / RoPE,
 // bf16 GELU and GeGLU product).  References: transformers modeling_modernbert.py:64-71
 // (embeddings), :89-91 (GeGLU), :196-219 (RoPE), :312-314,420,487 (LayerNorm), :489-490 (head).
+// The row-in-registers toolkit (RowVec, DISPATCH_NV, bad_h, ROWS_PER_BLOCK) is rows.h, shared with teacher.hip.
 #include "common.h"
 #include "config.h"
+#include "rows.h"
 #include "snx.h"
-
-#define ROWS_PER_BLOCK 4   // 256 threads = 4 waves = 4 token rows
 
 // ------------------------------------------------------------------------------------------
 // weight cache: fp32 master -> bf16 (and bf16 transposed for the dX GEMMs)
@@ -133,58 +133,8 @@ extern "C" int snx_cast_transpose_bf16(const float* in, void* out, int32_t R, in
 }
 
 // ------------------------------------------------------------------------------------------
-// LayerNorm (no bias), one wave per row; NV = H / 256 float4 per lane
+// LayerNorm (no bias), one wave per row (RowVec, rows.h)
 // ------------------------------------------------------------------------------------------
-template <int NV>
-struct RowVec {
-  f32x4 v[NV];
-  __device__ __forceinline__ void load_f32(const float* p, int lane) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = *(const f32x4*)(p + (i * 64 + lane) * 4);
-  }
-  __device__ __forceinline__ void load_bf16(const bf16_t* p, int lane) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const bf16x4 b = *(const bf16x4*)(p + (i * 64 + lane) * 4);
-      v[i] = (f32x4){bf2f(b[0]), bf2f(b[1]), bf2f(b[2]), bf2f(b[3])};
-    }
-  }
-  __device__ __forceinline__ void store_f32(float* p, int lane) const {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) *(f32x4*)(p + (i * 64 + lane) * 4) = v[i];
-  }
-  // non-temporal forms ("stream_nt", config.h): rows that are read for the last time / written for a reader tens of
-  // milliseconds away should not displace the next GEMM's operands from the L2 and the Infinity Cache
-  __device__ __forceinline__ void load_f32_nt(const float* p, int lane) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = __builtin_nontemporal_load((const f32x4*)(p + (i * 64 + lane) * 4));
-  }
-  __device__ __forceinline__ void load_bf16_nt(const bf16_t* p, int lane) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const bf16x4 b = __builtin_nontemporal_load((const bf16x4*)(p + (i * 64 + lane) * 4));
-      v[i] = (f32x4){bf2f(b[0]), bf2f(b[1]), bf2f(b[2]), bf2f(b[3])};
-    }
-  }
-  __device__ __forceinline__ void store_f32_nt(float* p, int lane) const {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) __builtin_nontemporal_store(v[i], (f32x4*)(p + (i * 64 + lane) * 4));
-  }
-  __device__ __forceinline__ void store_bf16(bf16_t* p, int lane) const {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      bf16x4 b = {f2bf(v[i][0]), f2bf(v[i][1]), f2bf(v[i][2]), f2bf(v[i][3])};
-      *(bf16x4*)(p + (i * 64 + lane) * 4) = b;
-    }
-  }
-  __device__ __forceinline__ float sum() const {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-    return wave_sum(s);
-  }
-};
-
 // normalise in place: x <- (x - mean) * rstd ; returns rstd
 template <int NV>
 __device__ __forceinline__ float ln_normalize(RowVec<NV>& x, int H, float eps) {
@@ -255,17 +205,6 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ h
     x.store_bf16(x_out + (long)t * H, lane);
   }
 }
-
-#define DISPATCH_NV(H, CALL)                 \
-  switch ((H) / 256) {                       \
-    case 1: { constexpr int NV = 1; CALL; } break; \
-    case 2: { constexpr int NV = 2; CALL; } break; \
-    case 3: { constexpr int NV = 3; CALL; } break; \
-    case 4: { constexpr int NV = 4; CALL; } break; \
-    default: return SNX_E_SHAPE;             \
-  }
-
-static inline bool bad_h(int H) { return H <= 0 || (H % 256) != 0 || H > 1024; }
 
 extern "C" int snx_ln_fwd(const float* h, const float* w, void* x_out, int32_t T, int32_t H, float eps,
                           hipStream_t st) {

@@ -10,8 +10,10 @@
 // This is the precision path, not the throughput path: one LDS-tiled GEMM with strided operands (64x64x16 tiles; 128x128x16
 // with register prefetch for large problems, same bits) serves every Linear (forward NT, dX NN, dW TN) and -- with a fused
 // log1p(relu) + max epilogue -- the tied decoder;
-// the attention forward is MFMA-tiled (head_dim % 8 == 0; one wave per (token, head) otherwise and in the backward); the
-// routed SPLADE backward and the attention backward use float atomics.
+// the attention forward is MFMA-tiled (head_dim % 8 == 0; one wave per (token, head) otherwise and in the backward) and,
+// through snx_attn_f32_fwd_tiled_x (common.h), also the fp32 attention of the dense teacher (teacher.hip); the
+// routed SPLADE backward and the attention backward use float atomics.  Arena offsets, RC and the parameter order
+// (modernbert::PIdx, the one model.hip uses) come from runtime.h.
 // Training runs under autocast(bf16) in the reference (ref:src/train/cli/train_v33_ddp.py:337) and on the bf16
 // kernels here; the fp32 backward exists for gradient parity (tests/test_gpu_f32.py: all 137 gradients of the 149 M model
 // against the reference's, and the reference's own two-rank train_epoch run replayed: tests/test_gpu_dist.py).
@@ -20,13 +22,14 @@
 
 #include "common.h"
 #include "config.h"
+#include "runtime.h"
 #include "snx.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+using modernbert::PIdx;
 
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 // ------------------------------------------------------------------------------------------------------------
 // GEMM: C[m, n] (op)= sum_k A(m, k) * B(n, k),  A(m, k) = A[m * a_row + k * a_k],  B(n, k) = B[n * b_row + k * b_k].
@@ -590,13 +593,7 @@ __global__ void geglu_f32_bwd_kernel(const float* __restrict__ u, const float* _
 __global__ void seqid_kernel(const int32_t* __restrict__ cu, int32_t* __restrict__ seqid, int T, int nseq) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= T) return;
-  int lo = 0, hi = nseq - 1;                           // last s with cu[s] <= t
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (cu[mid] <= t) lo = mid;
-    else hi = mid - 1;
-  }
-  seqid[t] = lo;
+  seqid[t] = seq_of_token(cu, nseq, t);
 }
 
 __global__ void tail_finalize_kernel(const unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ twkeys,
@@ -673,6 +670,7 @@ __global__ __launch_bounds__(256) void attn_f32_fwd_kernel(const float* __restri
 // Running maximum / sum / rescale are per lane (two lane-xor-32 exchanges per tile); the contraction over d pairs
 // dimension 8 m + i with 8 m + 4 + i (float4 operand reads).  The wave-per-(token, head) kernel above took 8.3 ms per
 // layer at 64 x 256 tokens (70 % of the fp32 forward); this one is MFMA-shaped work of 13 GFLOP.
+// mask == nullptr: every key of the sequence is visible; lse == nullptr: the log-sum-exp is not stored (both wave-uniform).
 constexpr int AQ = 128, AKT = 64, APITCH = 68;
 
 __global__ __launch_bounds__(256) void attn_f32_fwd_tiled_kernel(const float* __restrict__ qkv, const int32_t* __restrict__ cu,
@@ -720,7 +718,7 @@ __global__ __launch_bounds__(256) void attn_f32_fwd_tiled_kernel(const float* __
       __syncthreads();
       if (window >= 0 && (c0 > wq_hi + window || c0 + AKT - 1 < wq_lo - window)) continue;   // wave-uniform
       const int kb = c0 + lane;
-      const unsigned long long bits = __ballot(kb <= khi && mask[s0 + kb] != 0);
+      const unsigned long long bits = __ballot(kb <= khi && (mask == nullptr || mask[s0 + kb] != 0));
       f32x16 sa[2];
 #pragma unroll
       for (int i = 0; i < 16; ++i) { sa[0][i] = 0.f; sa[1][i] = 0.f; }
@@ -792,7 +790,7 @@ __global__ __launch_bounds__(256) void attn_f32_fwd_tiled_kernel(const float* __
       if (q0 + row < slen)
         *(f32x4*)(out + (long)(s0 + q0 + row) * H + head * hd + 4 * j) = *(const f32x4*)&sm[row * APITCH + 4 * j];
     }
-    if (h == 0 && qok) lse[(long)head * T + s0 + qp] = lrun > 0.f ? mrun + logf(lrun) : 0.f;
+    if (lse && h == 0 && qok) lse[(long)head * T + s0 + qp] = lrun > 0.f ? mrun + logf(lrun) : 0.f;
   }
 }
 
@@ -912,24 +910,6 @@ __global__ void add_f32_kernel(float* __restrict__ dst, const float* __restrict_
 // ------------------------------------------------------------------------------------------------------------
 // arena plans
 // ------------------------------------------------------------------------------------------------------------
-struct PIdx {                        // canonical parameter order (model.hip)
-  int L;
-  int tok_emb() const { return 0; }
-  int emb_norm() const { return 1; }
-  int base(int l) const { return l == 0 ? 2 : 7 + 6 * (l - 1); }
-  int attn_norm(int l) const { return base(l); }
-  int wqkv(int l) const { return base(l) + (l == 0 ? 0 : 1); }
-  int wo(int l) const { return wqkv(l) + 1; }
-  int mlp_norm(int l) const { return wqkv(l) + 2; }
-  int wi(int l) const { return wqkv(l) + 3; }
-  int wo_mlp(int l) const { return wqkv(l) + 4; }
-  int tail() const { return 7 + 6 * (L - 1); }
-  int final_norm() const { return tail(); }
-  int head_dense() const { return tail() + 1; }
-  int head_norm() const { return tail() + 2; }
-  int dec_bias() const { return tail() + 3; }
-};
-
 struct Plan {
   size_t h[129], x_attn[64], qkv[64], attn[64], lse[64], x_mlp[64], u[64], y[64];
   size_t xf, dd, hd, keys, twkeys, seqid, total;
@@ -943,49 +923,42 @@ bool f32_desc_ok(const snx_model_desc* d) {
 
 void plan(const snx_model_desc* d, size_t T, size_t nseq, bool save, Plan& s) {
   const size_t H = d->hidden, I = d->inter, V = d->vocab, L = d->layers;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = al(off + bytes); return o; };
+  Arena a;
   if (save) {
-    for (size_t i = 0; i <= 2 * L; ++i) s.h[i] = take(T * H * 4);
+    for (size_t i = 0; i <= 2 * L; ++i) s.h[i] = a.take(T * H * 4);
     for (size_t l = 0; l < L; ++l) {
-      s.x_attn[l] = l == 0 ? s.h[0] : take(T * H * 4);          // layer 0 has no attn_norm (hf:312: Identity)
-      s.qkv[l] = take(T * 3 * H * 4); s.attn[l] = take(T * H * 4); s.lse[l] = take((size_t)d->heads * T * 4);
-      s.x_mlp[l] = take(T * H * 4); s.u[l] = take(T * 2 * I * 4); s.y[l] = take(T * I * 4);
+      s.x_attn[l] = l == 0 ? s.h[0] : a.take(T * H * 4);          // layer 0 has no attn_norm (hf:312: Identity)
+      s.qkv[l] = a.take(T * 3 * H * 4); s.attn[l] = a.take(T * H * 4); s.lse[l] = a.take((size_t)d->heads * T * 4);
+      s.x_mlp[l] = a.take(T * H * 4); s.u[l] = a.take(T * 2 * I * 4); s.y[l] = a.take(T * I * 4);
     }
   } else {
-    const size_t h0 = take(T * H * 4), h1 = take(T * H * 4), h2 = take(T * H * 4);
+    const size_t h0 = a.take(T * H * 4), h1 = a.take(T * H * 4), h2 = a.take(T * H * 4);
     for (size_t i = 0; i <= 2 * L; ++i) s.h[i] = (i % 3 == 0) ? h0 : (i % 3 == 1) ? h1 : h2;
-    const size_t xa = take(T * H * 4), qkv = take(T * 3 * H * 4), at = take(T * H * 4), ls = take((size_t)d->heads * T * 4);
-    const size_t xm = take(T * H * 4), u = take(T * 2 * I * 4), y = take(T * I * 4);
+    const size_t xa = a.take(T * H * 4), qkv = a.take(T * 3 * H * 4), at = a.take(T * H * 4), ls = a.take((size_t)d->heads * T * 4);
+    const size_t xm = a.take(T * H * 4), u = a.take(T * 2 * I * 4), y = a.take(T * I * 4);
     for (size_t l = 0; l < L; ++l) {
       s.x_attn[l] = l == 0 ? s.h[0] : xa; s.qkv[l] = qkv; s.attn[l] = at; s.lse[l] = ls; s.x_mlp[l] = xm; s.u[l] = u; s.y[l] = y;
     }
   }
-  s.xf = take(T * H * 4); s.dd = take(T * H * 4); s.hd = take(T * H * 4);
-  s.keys = take(nseq * V * 8);
-  s.twkeys = take(T * 8);
-  s.seqid = take(T * 4);
-  s.total = off;
+  s.xf = a.take(T * H * 4); s.dd = a.take(T * H * 4); s.hd = a.take(T * H * 4);
+  s.keys = a.take(nseq * V * 8);
+  s.twkeys = a.take(T * 8);
+  s.seqid = a.take(T * 4);
+  s.total = a.off;
 }
 
 struct BPlan { size_t dh, a, b, c, total; };
 void bplan(const snx_model_desc* d, size_t T, BPlan& p) {
   const size_t H = d->hidden, I = d->inter;
   const size_t wide = 3 * H > 2 * I ? 3 * H : 2 * I;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = al(off + bytes); return o; };
-  p.dh = take(T * H * 4);
-  p.a = take(T * wide * 4);
-  p.b = take(T * wide * 4);
-  p.c = take(T * H * 4);
-  p.total = off;
+  Arena a;
+  p.dh = a.take(T * H * 4);
+  p.a = a.take(T * wide * 4);
+  p.b = a.take(T * wide * 4);
+  p.c = a.take(T * H * 4);
+  p.total = a.off;
 }
 
-#define RC(call)            \
-  do {                      \
-    int rc__ = (call);      \
-    if (rc__) return rc__;  \
-  } while (0)
 #define LAUNCH1D(kern, n, ...)                                                              \
   do {                                                                                      \
     hipLaunchKernelGGL(kern, dim3(cdiv((n), 256)), dim3(256), 0, st, __VA_ARGS__);           \
@@ -998,6 +971,18 @@ void bplan(const snx_model_desc* d, size_t T, BPlan& p) {
   } while (0)
 
 }  // namespace
+
+// the tiled attention forward for every fp32 runtime (declared in common.h; teacher.hip calls it with mask = lse = NULL).
+// Grid: (sequence, head, z), z striding the 128-query blocks of a sequence of the MEAN length, at most 64.
+int snx_attn_f32_fwd_tiled_x(const float* qkv, const int32_t* cu, const int64_t* mask, float* out, float* lse, int T, int nseq,
+                             int heads, int hd, int window, float scale, hipStream_t st) {
+  if (hd % 8 != 0 || hd > 64) return SNX_E_SHAPE;
+  const int zq = max(1, min(64, cdiv(cdiv(T, nseq), AQ)));
+  hipLaunchKernelGGL(attn_f32_fwd_tiled_kernel, dim3(nseq, heads, zq), dim3(256), 0, st, qkv, cu, mask, out, lse, T, heads, hd,
+                     window, scale);
+  SNX_CHECK_LAUNCH();
+  return SNX_OK;
+}
 
 extern "C" size_t snx_model_workspace_bytes_f32(const snx_model_desc* d, int32_t T, int32_t nseq, int32_t save_for_bwd) {
   if (!f32_desc_ok(d) || T <= 0 || nseq <= 0) return 0;
@@ -1048,14 +1033,13 @@ extern "C" int snx_model_forward_f32(const snx_model_desc* d, const void* const*
     const long nrope = (long)T * 2 * d->heads * (hd / 2);
     LAUNCH1D(rope_f32_kernel, nrope, B(s.qkv[l]), (const f32x2*)(global ? rope_global : rope_local), pos, nrope, d->heads, hd, 0);
     if (hd % 8 == 0 && !g_snx_cfg.f32_attn_rows) {
-      const int zq = max(1, min(64, cdiv(cdiv(T, nseq), AQ)));
-      hipLaunchKernelGGL(attn_f32_fwd_tiled_kernel, dim3(nseq, d->heads, zq), dim3(256), 0, st, B(s.qkv[l]), cu_seqlens, mask,
-                         B(s.attn[l]), B(s.lse[l]), T, d->heads, hd, global ? -1 : d->window, scale);
+      RC(snx_attn_f32_fwd_tiled_x(B(s.qkv[l]), cu_seqlens, mask, B(s.attn[l]), B(s.lse[l]), T, nseq, d->heads, hd,
+                                  global ? -1 : d->window, scale, st));
     } else {
       hipLaunchKernelGGL(attn_f32_fwd_kernel, dim3(cdiv((long)T * d->heads, 4)), dim3(256), 0, st, B(s.qkv[l]), cu_seqlens,
                          seqid, mask, B(s.attn[l]), B(s.lse[l]), T, d->heads, hd, global ? -1 : d->window, scale);
+      SNX_CHECK_LAUNCH();
     }
-    SNX_CHECK_LAUNCH();
     RC(linear_fwd(B(s.attn[l]), F(p.wo(l)), hbuf(2 * l), hbuf(2 * l + 1), T, H, H, st));
     LAUNCH_ROWS(ln_f32_kernel<0>, T, hbuf(2 * l + 1), nullptr, F(p.mlp_norm(l)), B(s.x_mlp[l]), T, H, d->ln_eps);
     RC(linear_fwd(B(s.x_mlp[l]), F(p.wi(l)), nullptr, B(s.u[l]), T, 2 * I, H, st));

@@ -8,36 +8,17 @@
 
 #include "common.h"
 #include "config.h"
+#include "runtime.h"
 #include "snx.h"
 
 bool snx_dec256_takes(int32_t T);   // splade_head.hip
 
 namespace {
 
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+using modernbert::PIdx;
 
 struct Dims {
   int V, H, I, L, heads, T, nseq;
-};
-
-// canonical parameter order (== state-dict order with the tied decoder weight listed once)
-struct PIdx {
-  int L;
-  int tok_emb() const { return 0; }
-  int emb_norm() const { return 1; }
-  int base(int l) const { return l == 0 ? 2 : 7 + 6 * (l - 1); }
-  int attn_norm(int l) const { return base(l); }                 // l >= 1 only
-  int wqkv(int l) const { return base(l) + (l == 0 ? 0 : 1); }
-  int wo(int l) const { return wqkv(l) + 1; }
-  int mlp_norm(int l) const { return wqkv(l) + 2; }
-  int wi(int l) const { return wqkv(l) + 3; }
-  int wo_mlp(int l) const { return wqkv(l) + 4; }
-  int tail() const { return 7 + 6 * (L - 1); }
-  int final_norm() const { return tail(); }
-  int head_dense() const { return tail() + 1; }
-  int head_norm() const { return tail() + 2; }
-  int dec_bias() const { return tail() + 3; }
-  int count() const { return tail() + 4; }
 };
 
 // bf16 weight cache: every matrix as stored ([out,in], for the forward NT GEMM) and transposed
@@ -52,17 +33,16 @@ struct CachePlan {
 bool plan_cache(const snx_model_desc* d, CachePlan& c) {
   if (d->layers > 64 || d->layers < 1) return false;
   const size_t H = d->hidden, I = d->inter, V = d->vocab;
-  size_t off = 0;
-  auto take = [&](size_t elems) { size_t o = off; off = al(off + elems * 2); return o; };
-  c.emb = take(V * H);
+  Arena a;
+  c.emb = a.take(V * H * 2);
   for (int l = 0; l < d->layers; ++l) {
-    c.wqkv[l] = take(3 * H * H); c.wqkv_t[l] = take(3 * H * H);
-    c.wo[l] = take(H * H); c.wo_t[l] = take(H * H);
-    c.wi[l] = take(2 * I * H); c.wi_t[l] = take(2 * I * H);
-    c.wom[l] = take(H * I); c.wom_t[l] = take(H * I);
+    c.wqkv[l] = a.take(3 * H * H * 2); c.wqkv_t[l] = a.take(3 * H * H * 2);
+    c.wo[l] = a.take(H * H * 2); c.wo_t[l] = a.take(H * H * 2);
+    c.wi[l] = a.take(2 * I * H * 2); c.wi_t[l] = a.take(2 * I * H * 2);
+    c.wom[l] = a.take(H * I * 2); c.wom_t[l] = a.take(H * I * 2);
   }
-  c.dense = take(H * H); c.dense_t = take(H * H);
-  c.total = off;
+  c.dense = a.take(H * H * 2); c.dense_t = a.take(H * H * 2);
+  c.total = a.off;
   return true;
 }
 
@@ -87,32 +67,31 @@ struct SavedPlan {
 bool plan_saved(const snx_model_desc* d, long T, long nseq, bool save, SavedPlan& s, bool notw = false) {
   if (d->layers > 64 || d->layers < 1) return false;
   const size_t H = d->hidden, I = d->inter, V = d->vocab, L = d->layers;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = al(off + bytes); return o; };
+  Arena a;
   if (save) {
-    for (size_t i = 0; i <= 2 * L; ++i) s.h[i] = take(T * H * 4);
+    for (size_t i = 0; i <= 2 * L; ++i) s.h[i] = a.take(T * H * 4);
     for (size_t l = 0; l < L; ++l) {
-      s.x_attn[l] = take(T * H * 2); s.x_mlp[l] = take(T * H * 2);
-      s.qkv[l] = take(T * 3 * H * 2); s.attn[l] = take(T * H * 2);
-      s.lse[l] = take((size_t)d->heads * T * 4);
-      s.u[l] = take(T * 2 * I * 2); s.y[l] = take(T * I * 2);
+      s.x_attn[l] = a.take(T * H * 2); s.x_mlp[l] = a.take(T * H * 2);
+      s.qkv[l] = a.take(T * 3 * H * 2); s.attn[l] = a.take(T * H * 2);
+      s.lse[l] = a.take((size_t)d->heads * T * 4);
+      s.u[l] = a.take(T * 2 * I * 2); s.y[l] = a.take(T * I * 2);
     }
   } else {                       // inference: ping-pong the stream, reuse one set of layer buffers
-    const size_t h0 = take(T * H * 4), h1 = take(T * H * 4);
+    const size_t h0 = a.take(T * H * 4), h1 = a.take(T * H * 4);
     for (size_t i = 0; i <= 2 * L; ++i) s.h[i] = (i & 1) ? h1 : h0;
-    const size_t xa = take(T * H * 2), xm = take(T * H * 2), qkv = take(T * 3 * H * 2), at = take(T * H * 2);
-    const size_t ls = take((size_t)d->heads * T * 4), u = take(T * 2 * I * 2), y = take(T * I * 2);
+    const size_t xa = a.take(T * H * 2), xm = a.take(T * H * 2), qkv = a.take(T * 3 * H * 2), at = a.take(T * H * 2);
+    const size_t ls = a.take((size_t)d->heads * T * 4), u = a.take(T * 2 * I * 2), y = a.take(T * I * 2);
     for (size_t l = 0; l < L; ++l) {
       s.x_attn[l] = xa; s.x_mlp[l] = xm; s.qkv[l] = qkv; s.attn[l] = at; s.lse[l] = ls; s.u[l] = u; s.y[l] = y;
     }
   }
-  s.xf = take(T * H * 2); s.dd = take(T * H * 2); s.hd = take(T * H * 2);
-  s.keys = take(nseq * V * 4);
-  s.rope_rows[0] = take(T * 256);
-  s.rope_rows[1] = take(T * 256);
-  s.tkeys = take(T * 4);
-  s.rowpart = take(notw ? snx_splade_head_scratch_bytes_notw((int)T) : snx_splade_head_scratch_bytes((int)T, (int)V));
-  s.total = off;
+  s.xf = a.take(T * H * 2); s.dd = a.take(T * H * 2); s.hd = a.take(T * H * 2);
+  s.keys = a.take(nseq * V * 4);
+  s.rope_rows[0] = a.take(T * 256);
+  s.rope_rows[1] = a.take(T * 256);
+  s.tkeys = a.take(T * 4);
+  s.rowpart = a.take(notw ? snx_splade_head_scratch_bytes_notw((int)T) : snx_splade_head_scratch_bytes((int)T, (int)V));
+  s.total = a.off;
   return true;
 }
 
@@ -140,30 +119,29 @@ struct BwdPlan {
 
 void plan_bwd(const snx_model_desc* d, long T, long nseq, long max_seqlen, BwdPlan& p) {
   const size_t H = d->hidden, I = d->inter;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = al(off + bytes); return o; };
-  p.dh = take(T * H * 4);
+  Arena a;
+  p.dh = a.take(T * H * 4);
   for (int k = 0; k < 2; ++k) {
-    p.p[k] = take(T * H * 2); p.du[k] = take(T * 2 * I * 2); p.q[k] = take(T * H * 2); p.dqkv[k] = take(T * 3 * H * 2);
+    p.p[k] = a.take(T * H * 2); p.du[k] = a.take(T * 2 * I * 2); p.q[k] = a.take(T * H * 2); p.dqkv[k] = a.take(T * 3 * H * 2);
   }
-  p.b = take(T * H * 2);
-  p.delta = take((size_t)d->heads * T * 4);
-  p.splade = take(snx_splade_bwd_scratch_bytes((int)nseq, (int)max_seqlen, d->vocab));
-  p.splade_tw = take(snx_splade_tw_scratch_bytes((int)T, d->vocab));
+  p.b = a.take(T * H * 2);
+  p.delta = a.take((size_t)d->heads * T * 4);
+  p.splade = a.take(snx_splade_bwd_scratch_bytes((int)nseq, (int)max_seqlen, d->vocab));
+  p.splade_tw = a.take(snx_splade_tw_scratch_bytes((int)T, d->vocab));
   {
     const int Hh = d->hidden, Ii = d->inter;
     const snx_tn_problem layer[4] = {{nullptr, nullptr, nullptr, 3 * Hh, Hh, 0, 0}, {nullptr, nullptr, nullptr, 2 * Ii, Hh, 1, 0},
                                      {nullptr, nullptr, nullptr, Hh, Ii, 0, 0}, {nullptr, nullptr, nullptr, Hh, Hh, 0, 0}};
     p.tnws_side_bytes = snx_gemm_tn_workspace_bytes(layer, 4, (int32_t)T);
     p.tnws_main_bytes = snx_gemm_tn_workspace_bytes(layer + 3, 1, (int32_t)T);
-    p.ln_slot = al(snx_ln_bwd_workspace_bytes((int32_t)T, Hh));
+    p.ln_slot = align256(snx_ln_bwd_workspace_bytes((int32_t)T, Hh));
     p.lnws_emb_bytes = snx_embed_ln_bwd_workspace_bytes((int32_t)T, Hh, d->vocab);
   }
-  p.tnws_side = take(p.tnws_side_bytes);
-  p.tnws_main = take(p.tnws_main_bytes);
-  p.lnws = take(p.ln_slot * (2 * (size_t)d->layers + 2));
-  p.lnws_emb = take(p.lnws_emb_bytes);
-  p.total = off;
+  p.tnws_side = a.take(p.tnws_side_bytes);
+  p.tnws_main = a.take(p.tnws_main_bytes);
+  p.lnws = a.take(p.ln_slot * (2 * (size_t)d->layers + 2));
+  p.lnws_emb = a.take(p.lnws_emb_bytes);
+  p.total = a.off;
 }
 
 bool desc_ok(const snx_model_desc* d) {
@@ -264,12 +242,6 @@ double attn_pairs(const int32_t* groups, int nseq, int max_seqlen, int window) {
   }
   return tot;
 }
-
-#define RC(call)            \
-  do {                      \
-    int rc__ = (call);      \
-    if (rc__) return rc__;  \
-  } while (0)
 
 }  // namespace
 

@@ -15,6 +15,7 @@
 // A helper that depends on the workgroup size takes it as a template parameter (the files use 512, 256 and 64 threads).
 #pragma once
 #include "common.h"
+#include "runtime.h"   // align256
 
 namespace {
 
@@ -29,7 +30,6 @@ constexpr int SR_CHUNK_MAX = 32768;            // 128 KiB of scores + ~14 KiB st
 inline int sr_chunk(int32_t chunk_docs) { return chunk_docs > 0 ? chunk_docs : SR_CHUNK_DEFAULT; }
 inline int sr_nch(int32_t nd, int chunk) { return nd > 0 ? (int)((nd + (long)chunk - 1) / chunk) : 1; }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 template <typename T>                          // int in hybrid.hip, long elsewhere: the loop width shows in the code
 __host__ __device__ inline T pow2_at_least(T n) {
   T p = 1;

@@ -812,12 +812,7 @@ __global__ __launch_bounds__(TWC) void splade_tw_coef_kernel(const float* __rest
   float c = 0.f;
   if (x > 0.f && gt != 0.f && t < cu[nseq]) {
     v = 0xFFFF - (int)(tk & 0xFFFFu);
-    int lo = 0, hi = nseq - 1;                         // sequence of t: last s with cu[s] <= t
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (cu[mid] <= t) lo = mid;
-      else hi = mid - 1;
-    }
+    const int lo = seq_of_token(cu, nseq, t);
     const long e = (long)lo * V + v;
     const uint32_t sk = keys[e];
     const bool same = (sk >> 16) == (tk >> 16) && (int)(0xFFFFu - (sk & 0xFFFFu)) == t - cu[lo];

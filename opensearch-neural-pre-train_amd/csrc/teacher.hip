@@ -2,55 +2,23 @@
 // ref:src/model/teachers/bge_m3.py:66-94, ref:scripts/precompute_teacher_scores.py:89-159 -- what sentence-transformers
 // runs underneath).  `xr:` = transformers/models/xlm_roberta/modeling_xlm_roberta.py.
 //
-// The contractions are the tree's GEMMs and attention (snx_gemm_nt_bf16 / snx_attn_fwd, or snx_gemm_f32 and the fp32
-// attention below); this file holds the glue between them that ModernBERT does not have: learned absolute positions and
-// a token-type row in the embeddings, a bias on every Linear, post-LayerNorm with a bias, erf-GELU on a biased Linear, CLS
-// pooling.  Row kernels: one wave per token row, 16 B per lane, the RowVec idiom of elementwise.hip.
+// The contractions are the tree's GEMMs and attention (snx_gemm_nt_bf16 / snx_attn_fwd, or snx_gemm_f32 and the tiled fp32
+// attention forward of f32_path.hip); this file holds the glue between them that ModernBERT does not have: learned absolute
+// positions and a token-type row in the embeddings, a bias on every Linear, post-LayerNorm with a bias, erf-GELU on a biased
+// Linear, CLS pooling.  Row kernels: one wave per token row, 16 B per lane, on the RowVec toolkit of rows.h (shared with
+// elementwise.hip); arena offsets and RC come from runtime.h.
 //
 // Cast points of the bf16 path: GEMM operands and GEMM outputs are bf16 (a bias added to a bf16 GEMM output that is a GEMM
 // or attention operand is rounded to bf16 again); the residual stream h is fp32, GELU and softmax arithmetic are fp32, a
 // row's LayerNorm is evaluated in fp64 and stored as fp32.  The fp32 path has no cast point.
 #include "common.h"
+#include "rows.h"
+#include "runtime.h"
 #include "snx.h"
 
 namespace {
 
-constexpr int ROWS_PER_BLOCK = 4;   // 256 threads = 4 waves = 4 token rows
 constexpr int EW_MAX_BLOCKS = 2048; // elementwise kernels: grid-stride beyond this
-
-// the row-in-registers idiom of elementwise.hip (its RowVec is local to that file), without the non-temporal forms
-template <int NV>
-struct RowVec {
-  f32x4 v[NV];
-  __device__ __forceinline__ void load_f32(const float* p, int lane) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = *(const f32x4*)(p + (i * 64 + lane) * 4);
-  }
-  __device__ __forceinline__ void load_bf16(const bf16_t* p, int lane) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const bf16x4 b = *(const bf16x4*)(p + (i * 64 + lane) * 4);
-      v[i] = (f32x4){bf2f(b[0]), bf2f(b[1]), bf2f(b[2]), bf2f(b[3])};
-    }
-  }
-  __device__ __forceinline__ void store_f32(float* p, int lane) const {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) *(f32x4*)(p + (i * 64 + lane) * 4) = v[i];
-  }
-  __device__ __forceinline__ void store_bf16(bf16_t* p, int lane) const {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      bf16x4 b = {f2bf(v[i][0]), f2bf(v[i][1]), f2bf(v[i][2]), f2bf(v[i][3])};
-      *(bf16x4*)(p + (i * 64 + lane) * 4) = b;
-    }
-  }
-};
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // A row's LayerNorm input in fp64.  These kernels are bound by their 16-byte loads and stores, the fp64 vector rate is far
 // from a limit at <= 16 elements per lane, and it buys outputs that are the correctly rounded LayerNorm also where
@@ -213,78 +181,11 @@ __global__ __launch_bounds__(256) void teacher_cls_normalize_kernel(const float*
   x.store_f32(emb + (long)s * H, lane);
 }
 
-// fp32 attention of the parity path (xr: XLMRobertaSelfAttention -> SDPA, no mask inside an unpadded sequence): one wave per
-// (token, head), head_dim 64.  Scores with lanes over keys (64 per chunk, online softmax), P V with lanes over the head
-// dimension (probabilities through LDS).  The token's sequence is found by bisection of cu_seqlens.
-__global__ __launch_bounds__(256) void teacher_attn_f32_kernel(const float* __restrict__ qkv, const int32_t* __restrict__ cu,
-                                                               float* __restrict__ out, int T, int nseq, int heads,
-                                                               float scale) {
-  __shared__ float sP[ROWS_PER_BLOCK][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long wid = (long)blockIdx.x * ROWS_PER_BLOCK + wave;
-  if (wid >= (long)T * heads) return;
-  const int t = (int)(wid / heads), head = (int)(wid % heads);
-  int lo = 0, hi = nseq - 1;                             // the last s with cu[s] <= t (empty sequences are skipped)
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (cu[mid] <= t) lo = mid; else hi = mid - 1;
-  }
-  const int s0 = cu[lo];
-  int slen = cu[lo + 1] - s0;
-  if (s0 < 0 || s0 > t) return;                          // malformed cu_seqlens: touch nothing
-  if (slen > T - s0) slen = T - s0;
-  const long rs = 3L * heads * 64;
-  const float* q = qkv + (long)t * rs + head * 64;
-  const float* kb = qkv + (long)s0 * rs + (long)heads * 64 + head * 64;
-  const float* vb = kb + (long)heads * 64;
-  f32x4 qv[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) qv[i] = *(const f32x4*)(q + 4 * i);
-  float m = -INFINITY, l = 0.f, o = 0.f;                 // o: this lane's output dimension
-  for (int c0 = 0; c0 < slen; c0 += 64) {
-    const int kp = c0 + lane;
-    float s = -INFINITY;
-    if (kp < slen) {
-      const float* k = kb + (long)kp * rs;
-      float a = 0.f;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const f32x4 kv = *(const f32x4*)(k + 4 * i);
-        a = fmaf(qv[i][0], kv[0], a); a = fmaf(qv[i][1], kv[1], a);
-        a = fmaf(qv[i][2], kv[2], a); a = fmaf(qv[i][3], kv[3], a);
-      }
-      s = a * scale;
-    }
-    const float mn = fmaxf(m, wave_max(s));              // finite: every chunk holds at least one key
-    const float p = kp < slen ? expf(s - mn) : 0.f;
-    const float alpha = expf(m - mn);                    // first chunk: exp(-inf) = 0
-    l = l * alpha + wave_sum(p);
-    m = mn;
-    sP[wave][lane] = p;
-    __builtin_amdgcn_wave_barrier();
-    o *= alpha;
-    const int n = min(64, slen - c0);
-    for (int j = 0; j < n; ++j) o = fmaf(sP[wave][j], vb[(long)(c0 + j) * rs + lane], o);
-    __builtin_amdgcn_wave_barrier();
-  }
-  out[(long)t * heads * 64 + head * 64 + lane] = l > 0.f ? o / l : 0.f;
-}
-
 __global__ void teacher_fill_ones_kernel(int64_t* __restrict__ p, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = 1;
 }
 
-#define DISPATCH_NV(H, CALL)                       \
-  switch ((H) / 256) {                             \
-    case 1: { constexpr int NV = 1; CALL; } break; \
-    case 2: { constexpr int NV = 2; CALL; } break; \
-    case 3: { constexpr int NV = 3; CALL; } break; \
-    case 4: { constexpr int NV = 4; CALL; } break; \
-    default: return SNX_E_SHAPE;                   \
-  }
-
-inline bool bad_h(int H) { return H <= 0 || (H % 256) != 0 || H > 1024; }
 inline bool misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
 inline int ew_blocks(long items) {
   const long b = (items + 255) / 256;
@@ -338,22 +239,20 @@ struct PIdx {
   static int ln2_b(int l) { return base(l) + 15; }
 };
 
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // weight cache: per layer the bf16 matrices [Wq; Wk; Wv] [3H, H], Wo [H, H], Wi [I, H], Wo2 [H, I], then (after all
 // layers) the stacked fp32 bias [bq; bk; bv] [3H] of every layer
 struct Cache {
   size_t H, I, per_layer, bias0, total;
   explicit Cache(const snx_teacher_desc* d) : H(d->hidden), I(d->inter) {
-    per_layer = al256((4 * H * H + 2 * H * I) * 2);
+    per_layer = align256((4 * H * H + 2 * H * I) * 2);
     bias0 = per_layer * d->layers;
-    total = bias0 + al256(3 * H * 4) * d->layers;
+    total = bias0 + align256(3 * H * 4) * d->layers;
   }
   size_t wqkv(int l) const { return per_layer * l; }
   size_t wo(int l) const { return wqkv(l) + 3 * H * H * 2; }
   size_t wi(int l) const { return wo(l) + H * H * 2; }
   size_t wo2(int l) const { return wi(l) + I * H * 2; }
-  size_t bqkv(int l) const { return bias0 + al256(3 * H * 4) * l; }
+  size_t bqkv(int l) const { return bias0 + align256(3 * H * 4) * l; }
 };
 
 // activation arena of one forward
@@ -361,25 +260,18 @@ struct Plan {
   size_t h, x, qkv, attn, y, u, lse, mask, total;
   Plan(const snx_teacher_desc* d, int T, int f32) {
     const size_t H = d->hidden, I = d->inter, e = f32 ? 4 : 2;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += al256(bytes); return at; };
-    h = take((size_t)T * H * 4);
-    x = f32 ? 0 : take((size_t)T * H * 2);
-    qkv = take((size_t)T * 3 * H * e);
-    attn = take((size_t)T * H * e);
-    y = take((size_t)T * H * e);
-    u = take((size_t)T * I * e);
-    lse = f32 ? 0 : take((size_t)d->heads * T * 4);
-    mask = f32 ? 0 : take((size_t)T * 8);
-    total = o;
+    Arena a;
+    h = a.take((size_t)T * H * 4);
+    x = f32 ? 0 : a.take((size_t)T * H * 2);
+    qkv = a.take((size_t)T * 3 * H * e);
+    attn = a.take((size_t)T * H * e);
+    y = a.take((size_t)T * H * e);
+    u = a.take((size_t)T * I * e);
+    lse = f32 ? 0 : a.take((size_t)d->heads * T * 4);
+    mask = f32 ? 0 : a.take((size_t)T * 8);
+    total = a.off;
   }
 };
-
-#define RC(call)            \
-  do {                      \
-    int rc__ = (call);      \
-    if (rc__) return rc__;  \
-  } while (0)
 
 }  // namespace
 
@@ -440,11 +332,9 @@ extern "C" int snx_teacher_attn_f32(const float* qkv, const int32_t* cu_seqlens,
                                     int32_t heads, hipStream_t st) {
   if (!qkv || !cu_seqlens || !out || T <= 0 || nseq <= 0) return SNX_E_ARG;
   if (heads <= 0) return SNX_E_SHAPE;
-  if (misaligned(qkv)) return SNX_E_ARG;
-  hipLaunchKernelGGL(teacher_attn_f32_kernel, dim3(cdiv((long)T * heads, ROWS_PER_BLOCK)), dim3(256), 0, st, qkv,
-                     cu_seqlens, out, T, nseq, heads, 0.125f);
-  SNX_CHECK_LAUNCH();
-  return SNX_OK;
+  if (misaligned(qkv) || misaligned(out)) return SNX_E_ARG;                // 16-byte loads and stores
+  // xr: XLMRobertaSelfAttention -> SDPA, no mask inside an unpadded sequence, head_dim 64, every layer global
+  return snx_attn_f32_fwd_tiled_x(qkv, cu_seqlens, nullptr, out, nullptr, T, nseq, heads, 64, -1, 0.125f, st);
 }
 
 extern "C" int32_t snx_teacher_param_count(const snx_teacher_desc* d) {

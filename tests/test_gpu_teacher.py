@@ -146,12 +146,18 @@ def test_cls_normalize(H):
     _assert_f32(emb.cpu()[keep], ref[keep], "cls_normalize emb")
 
 
-def test_attn_f32_against_float64_sdpa():
+# the edges of the tiled forward this entry point runs (csrc/f32_path.hip): 128-query blocks, 64-key tiles, a grid whose third
+# dimension follows the MEAN sequence length
+@pytest.mark.parametrize("lens,heads", [([1, 2, 65, 257], 4),            # more than one block and tile, nothing a multiple
+                                        ([1], 1),                        # T = 1: one block, one key
+                                        ([128, 129, 64, 63], 4),         # exact and off-by-one query blocks and key tiles
+                                        ([3] * 40, 4)],                  # mean length far below one query block
+                         ids=["ragged", "one_token", "block_edges", "forty_short"])
+def test_attn_f32_against_float64_sdpa(lens, heads):
     gen = torch.Generator().manual_seed(500)
-    lens, heads = [1, 2, 65, 257], 4
     T = sum(lens)
     qkv = torch.randn(T, 3, heads, 64, generator=gen)
-    cu = torch.tensor([0, 1, 3, 68, 325], dtype=torch.int32)
+    cu = torch.tensor([0] + lens, dtype=torch.int32).cumsum(0, dtype=torch.int32)
     out = torch.empty(T, heads, 64, device=DEV)
     dqkv, dcu = qkv.to(DEV), cu.to(DEV)
     _call("snx_teacher_attn_f32", _p(dqkv), _p(dcu), _p(out), T, len(lens), heads)
