@@ -756,6 +756,47 @@ int snx_loss_bwd(const float* q, const float* p, const float* n, const float* go
                  const int32_t* dims /*[host]*/, void* workspace, int32_t use_kd, float* dq, float* dp, float* dn,
                  hipStream_t stream);
 
+/* ---- IDF (csrc/idf.hip): document frequencies, the IDF-aware FLOPS penalty and the inference-free ("doc-only") query.
+ * Logarithms are the host's (snx/idf.py: float64, one rounding to fp32); nothing here calls libm.
+ *
+ * snx_idf_doc_freq -- replaces the counting loop of ref:tools/idf-compute/src/main.rs:150-180 (a HashSet per document,
+ * one increment per distinct id).  input_ids, attention_mask [n, S] int64; df [V] int64 is ADDED to (the caller zeroes it
+ * once; batches accumulate): df[t] += the number of rows that hold t at a position with mask != 0.  Ids outside [0, V) are
+ * ignored (main.rs:166-174); there is no `allowed` filter and no cap on S.  num_docs (device int64, or NULL) += n: every row
+ * is a document, also one with no counted position (the tool counts every non-empty text; emptiness is the caller's to
+ * decide before tokenising).  Integer atomics: exact and independent of order.  1 <= V <= 2^20 (the presence bitmap is
+ * V bits of LDS), S >= 1, n >= 0, otherwise SNX_E_SHAPE; n == 0 launches nothing.
+ *
+ * snx_idf_flops_fwd -- replaces the penalty of ref:docs/concepts/04-loss-functions.md §5 ("V26": sum_j w_j * mean_j) in the
+ * form of ref:scripts/test_idf_math.py:176-215 with the quadratic term of SPLADELossV33 (ref:src/model/losses.py:136-152)
+ * beside it.  x [R, V] fp32 (row stride V), w [V] fp32:
+ *   a_j  = (x[0,j] + x[1,j] + ... + x[R-1,j]) / (float)R     fp32, rows ascending, one IEEE division (as snx_loss_fwd)
+ *   t1_j = w_j * |a_j|,  t2_j = w_j * (a_j * a_j)             fp32, every product rounded on its own
+ *   S1 = sum_j t1_j, S2 = sum_j t2_j                          float64, in an order fixed by (R, V) alone
+ *   P  = (float)fma((double)beta, S2, S1)
+ * out3 = {(float)S1, (float)S2, P}; loss (device scalar, or NULL): loss[0] = loss[0] + lambda * P, the product rounded to
+ * fp32 first.  a is kept in the first V floats of `workspace` (snx_idf_flops_workspace_bytes(V) bytes, 8-byte aligned) for
+ * the backward.  No float atomics, no host synchronisation: two runs give the same bits.
+ *
+ * snx_idf_flops_bwd_accum -- the gradient torch.autograd derives from that expression, ADDED in place to an existing
+ * gradient block: dx[r, j] += ((w_j * (sign(a_j) + (2 beta) * a_j)) * ((g * lambda) / (float)R)) for every row r, fp32,
+ * every operation rounded on its own (six roundings; 2 beta is exact), sign(0) = 0 as torch's abs backward.  A column whose
+ * coefficient is zero is not written.  g = gout[0], the device scalar snx_loss_bwd takes; `workspace` as the forward left it.
+ *
+ * snx_idf_query_dense -- replaces ref:tests/test_korean_neural_sparse.py:417-427 (the doc-only query vector: idf[token] for
+ * every token of the query, once however often it occurs): q [B, V] fp32, q[b, id] = idf[id] for each id in [0, V) at a
+ * position of row b with mask != 0 and allowed[id] != 0, and 0 elsewhere.  The zero fill is part of the launch.
+ * R < 1, V < 1, S < 1, B < 0: SNX_E_SHAPE; null pointers: SNX_E_ARG. */
+int snx_idf_doc_freq(const int64_t* input_ids, const int64_t* attention_mask, int64_t n, int64_t S, int32_t V, int64_t* df,
+                     int64_t* num_docs, hipStream_t stream);
+size_t snx_idf_flops_workspace_bytes(int32_t V);
+int snx_idf_flops_fwd(const float* x, int32_t R, int32_t V, const float* w, float beta, float lambda, void* workspace,
+                      float* out3, float* loss, hipStream_t stream);
+int snx_idf_flops_bwd_accum(float* dx, int32_t R, int32_t V, const void* workspace, const float* w, float beta,
+                            float lambda, const float* gout, hipStream_t stream);
+int snx_idf_query_dense(const int64_t* input_ids, const int64_t* attention_mask, const uint8_t* allowed, const float* idf,
+                        int32_t B, int64_t S, int32_t V, float* q, hipStream_t stream);
+
 /* ---- individual ops (used by the entry points above; exported for parity tests) ---------- */
 
 /* fp32 -> bf16 (autocast weight / activation cast) and fp32 [R,C] -> bf16 [C,R]. */

@@ -122,7 +122,23 @@ class NeuralSparseEncoderV33:
         return self.encode([text], batch_size=1, top_k=top_k)[0]
 
     @torch.no_grad()
-    def encode_for_query(self, text: str, top_k: int = 100) -> Dict[str, float]:
+    def encode_for_query(self, text: str, top_k: int = 100, idf=None) -> Dict[str, float]:
+        """``idf`` (a [V] table, or the {token: weight} dict of a shipped ``idf.json``): the inference-free query of
+        OpenSearch's doc-only mode (ref:tests/test_korean_neural_sparse.py:417-427) -- {token: idf[token]} for every kept
+        token of the query, once however often it occurs; the model is not run and ``top_k`` does not apply."""
+        if idf is not None:
+            inputs = self.tokenizer([text], return_tensors="pt", padding=True, truncation=True,
+                                    max_length=self.query_max_length)
+            allowed = allowed_token_mask(self._token_lookup, self.special_token_ids, len(self._token_lookup))
+            out: Dict[str, float] = {}
+            for t, m in zip(inputs["input_ids"][0].tolist(), inputs["attention_mask"][0].tolist()):
+                if m == 0 or not 0 <= t < allowed.numel() or not allowed[t]:
+                    continue
+                tok = self._token_lookup[t]
+                w = idf.get(tok) if isinstance(idf, dict) else (float(idf[t]) if t < len(idf) else None)
+                if w is not None and w > 0:
+                    out[tok] = float(w)
+            return out
         inputs = self.tokenizer(text, return_tensors="pt", padding=True, truncation=True,
                                 max_length=self.query_max_length)
         inputs = {k: v.to(self.device) for k, v in inputs.items() if torch.is_tensor(v)}

@@ -71,6 +71,11 @@ SIGNATURES = {
     "snx_loss_workspace_bytes": (SZ, [I32, I32, I32, I32]),
     "snx_loss_fwd": (I32, [P, P, P, P, P, P, P, P, P, P, P]),
     "snx_loss_bwd": (I32, [P, P, P, P, P, P, P, I32, P, P, P, P]),
+    "snx_idf_doc_freq": (I32, [P, P, I64, I64, I32, P, P, P]),
+    "snx_idf_flops_workspace_bytes": (SZ, [I32]),
+    "snx_idf_flops_fwd": (I32, [P, I32, I32, P, F32, F32, P, P, P, P]),
+    "snx_idf_flops_bwd_accum": (I32, [P, I32, I32, P, P, F32, F32, P, P]),
+    "snx_idf_query_dense": (I32, [P, P, P, P, I32, I64, I32, P, P]),
     "snx_model_workspace_bytes": (SZ, [P, I32, I32, I32]),
     "snx_model_workspace_bytes_fwd": (SZ, [P, I32, I32, I32]),
     "snx_model_bwd_workspace_bytes": (SZ, [P, I32, I32, I32]),

@@ -3,7 +3,7 @@
 
     python -m src.train.cli.eval_benchmark --checkpoint outputs/train_v33/final_model --benchmark-dir data/bench \\
         [--methods sparse,bm25,bm25_sparse_rrf,two_phase,seismic] [--top-k 10] [--bootstrap 1000] [--max-queries N] \\
-        [--report OUT.json]
+        [--report OUT.json] [--methods sparse,doc_only --idf outputs/idf_weights/idf]
 
 The directory holds ``corpus.jsonl``, ``queries.jsonl`` and ``qrels.jsonl`` (src.train.eval.load_benchmark_dir).  Every
 method returns its top ``--top-k`` docs per query; a hit is the first returned doc that is in the query's relevant set.
@@ -13,7 +13,10 @@ docs, ``ci`` (bootstrap intervals of recall@1, mrr and ndcg@10: the reference's 
 reference's table, which time an OpenSearch round trip and are not claimed here) and, for ``sparse``,
 ``first_relevant``: the rank of each query's best relevant doc in the WHOLE corpus, not only the top k.  Then one line per
 method pair with the paired t-test over reciprocal first-relevant ranks (hf_runner.run_statistical_tests).  ``--report``
-writes {method: metrics} with the reference's key names.  One process (not torchrun)."""
+writes {method: metrics} with the reference's key names.  One process (not torchrun).
+``doc_only`` (not in the default list; needs ``--idf``, an IDF table of src.train.cli.compute_idf): ``sparse`` over the same
+document index, but the queries are never encoded -- their rows are idf[token] once per distinct kept token
+(snx.idf.idf_query_rows), OpenSearch's inference-free query mode.  It joins the pairwise t-tests like any other method."""
 from __future__ import annotations
 
 import argparse
@@ -21,7 +24,8 @@ import json
 import time
 from typing import List, Optional
 
-METHODS = ("sparse", "bm25", "bm25_sparse_rrf", "two_phase", "seismic")
+METHODS = ("sparse", "bm25", "bm25_sparse_rrf", "two_phase", "seismic")   # the default list
+OPTIONAL_METHODS = ("doc_only",)                                            # run when named; doc_only needs --idf
 RRF_K = 60                   # ref:benchmark/hybrid_searcher.py:621-631
 RETRIEVAL_K = 100            # depth of the two lists a fused row is formed from
 CI_KEYS = ("recall@1", "mrr", "ndcg@10")
@@ -44,11 +48,15 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     ap.add_argument("--doc-max-length", type=int, default=256)
     ap.add_argument("--batch-size", type=int, default=64)
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--idf", type=str, default=None,
+                    help="IDF table for the doc_only method (path without extension: .bin + .json; or a .pt tensor)")
     args = ap.parse_args(argv)
     args.methods = [m for m in args.methods.split(",") if m]
-    bad = [m for m in args.methods if m not in METHODS]
+    bad = [m for m in args.methods if m not in METHODS + OPTIONAL_METHODS]
     if bad or not args.methods or len(set(args.methods)) != len(args.methods):
-        ap.error(f"--methods: distinct names out of {','.join(METHODS)}")
+        ap.error(f"--methods: distinct names out of {','.join(METHODS + OPTIONAL_METHODS)}")
+    if "doc_only" in args.methods and not args.idf:
+        ap.error("--methods doc_only needs --idf PATH")
     if not 10 <= args.top_k <= RETRIEVAL_K:
         ap.error(f"--top-k must lie in [10, {RETRIEVAL_K}] (the metrics read cutoffs 1, 5 and 10)")
     if args.bootstrap < 0:
@@ -64,7 +72,8 @@ def main(argv: Optional[List[str]] = None) -> List[dict]:
     from src.train.cli.mine_negatives import load_model
     from src.train.data.collator import create_tokenizer
     from src.train.eval import (QRELS_CUTOFFS, REPORT_KEYS, BenchmarkEvaluator, bm25_index, bootstrap_confidence_interval,
-                                first_relevant_values, hybrid_params, load_benchmark_dir, paired_t_test, qrels_metrics)
+                                cat_query_rows, first_relevant_values, hybrid_params, load_benchmark_dir, paired_t_test,
+                                qrels_metrics)
     device = torch.device("cuda:0")
     data = load_benchmark_dir(args.benchmark_dir, args.max_queries)
     if not data.queries or not data.docs:
@@ -79,10 +88,20 @@ def main(argv: Optional[List[str]] = None) -> List[dict]:
     if any(m.startswith("bm25") for m in args.methods):
         bm, bm_queries = bm25_index(ev, index.V, hybrid_params({}))
     _, _, fr_rank, nrel = index.first_relevant(*queries, ev.relevant)
+    idf_queries = None
+    if "doc_only" in args.methods:
+        from snx.idf import load_idf
+        table = load_idf(args.idf)[0]
+        if table.shape[0] < index.V:                            # an id the IDF corpus never showed: as rare as the rarest
+            table = np.concatenate([table, np.full(index.V - table.shape[0], table.max(), dtype=np.float32)])
+        ev.query_idf = torch.from_numpy(np.ascontiguousarray(table[:index.V]))
+        idf_queries = cat_query_rows(list(ev._idf_queries(index.V)))
 
     def run(method: str) -> torch.Tensor:
         if method == "sparse":
             return index.search(*queries, k)[1]
+        if method == "doc_only":
+            return index.search(*idf_queries, k)[1]
         if method == "bm25":
             return bm.index.search(*bm_queries, k)[1]
         if method == "bm25_sparse_rrf":                         # list 0 = BM25, as in the reference's hybrid searcher

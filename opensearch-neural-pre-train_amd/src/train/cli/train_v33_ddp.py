@@ -7,6 +7,10 @@ Extra opt-in flags select the MI355X-native data-parallel path:
     --native-dp              one RCCL all-reduce of the flat gradient buffer per optimizer step
                              (default: torch DDP, exactly like the reference)
     --cross-gpu-negatives    all-gather positive vectors for cross-GPU in-batch negatives
+    --idf-weights PATH       IDF-aware FLOPS penalty (SPLADELossIDF) from an IDF table of src.train.cli.compute_idf
+    --query-mode MODE        "encoder" (default) or "idf": doc-only training, the query is idf[token], never encoded
+Both are also read from an optional top-level ``idf:`` section of the YAML (src/train/config/idf.py); without the
+section and the flags the loss is SPLADELossV33.
 Offline: ``model.name`` may be a local directory (config.json [+ weights, tokenizer]); with the hub
 name the A.X-Encoder-base geometry is random-initialised.  ``data.train_files: ["synthetic:N"]``
 together with ``--tokenizer hash:50000`` runs on synthetic text triplets.
@@ -25,6 +29,7 @@ import yaml
 
 from src.model.losses import SPLADELossV33
 from src.model.splade_modern import SPLADEModernBERT
+from src.train.config.idf import build_idf_loss, load_idf_config
 from src.train.config.v33 import V33Config, V33DataConfig, V33LossConfig, V33ModelConfig, V33TrainingConfig
 from src.train.core import ddp_trainer as T
 from src.train.data import load_training_data
@@ -57,6 +62,8 @@ def parse_args() -> argparse.Namespace:
     ap.add_argument("--native-dp", action="store_true")
     ap.add_argument("--cross-gpu-negatives", action="store_true")
     ap.add_argument("--tokenizer", type=str, default=None, help="tokenizer dir or hash:<vocab> (default: model.name)")
+    ap.add_argument("--idf-weights", type=str, default=None, help="IDF table (path without extension, or .pt)")
+    ap.add_argument("--query-mode", type=str, default=None, choices=["encoder", "idf"])
     return ap.parse_args()
 
 
@@ -76,12 +83,33 @@ def load_config(args: argparse.Namespace) -> V33Config:
     return config
 
 
+def load_idf_section(args: argparse.Namespace):
+    """The optional ``idf:`` YAML section and its two flags -> IdfConfig, or None (the V33 loader ignores the key)."""
+    path = Path(args.config)
+    raw = (yaml.safe_load(path.read_text()) or {}) if path.exists() else {}
+    return load_idf_config(raw, getattr(args, "idf_weights", None), getattr(args, "query_mode", None))
+
+
+def build_loss(config: V33Config, idf_config, tokenizer, vocab_size: int):
+    """SPLADELossV33 as ever; SPLADELossIDF when an IdfConfig is present."""
+    kwargs = dict(lambda_q=config.loss.lambda_q, lambda_d=config.loss.lambda_d,
+                  temperature=config.loss.temperature, flops_warmup_steps=config.loss.flops_warmup_steps,
+                  lambda_kd=config.loss.lambda_kd, kd_temperature=config.loss.kd_temperature,
+                  lambda_initial_ratio=config.loss.lambda_initial_ratio,
+                  lambda_margin_mse=config.loss.lambda_margin_mse,
+                  lambda_neg=getattr(config.loss, "lambda_neg", 0.0))
+    if idf_config is None:
+        return SPLADELossV33(**kwargs)
+    return build_idf_loss(idf_config, kwargs, tokenizer, vocab_size)
+
+
 def main() -> None:
     args = parse_args()
     local_rank = T.setup_distributed()
     device = torch.device(f"cuda:{local_rank}")
     world = dist.get_world_size()
     config = load_config(args)
+    idf_config = load_idf_section(args)
     out = Path(config.training.output_dir)
     if T.is_main_process():
         out.mkdir(parents=True, exist_ok=True)
@@ -116,12 +144,10 @@ def main() -> None:
         model = T.DDP(model, device_ids=[local_rank], broadcast_buffers=False, find_unused_parameters=False)
     if args.cross_gpu_negatives:
         os.environ["SNX_CROSS_GPU_NEGATIVES"] = "1"
-    loss_fn = SPLADELossV33(lambda_q=config.loss.lambda_q, lambda_d=config.loss.lambda_d,
-                            temperature=config.loss.temperature, flops_warmup_steps=config.loss.flops_warmup_steps,
-                            lambda_kd=config.loss.lambda_kd, kd_temperature=config.loss.kd_temperature,
-                            lambda_initial_ratio=config.loss.lambda_initial_ratio,
-                            lambda_margin_mse=config.loss.lambda_margin_mse,
-                            lambda_neg=getattr(config.loss, "lambda_neg", 0.0)).to(device)
+    loss_fn = build_loss(config, idf_config, tokenizer, T.unwrap(model).vocab_size).to(device)
+    if idf_config is not None and T.is_main_process():
+        logger.info(f"IDF-aware FLOPS: weights={idf_config.idf_weights_path} alpha={idf_config.idf_alpha} "
+                    f"beta={idf_config.beta} query_mode={idf_config.query_mode}")
     optimizer = T.build_optimizer(model, config)
     steps_per_epoch = len(train_dl) // config.training.gradient_accumulation_steps
     total_steps = steps_per_epoch * config.training.num_epochs
@@ -139,7 +165,8 @@ def main() -> None:
             evaluator = MidTrainingEvaluator(tokenizer=tokenizer, val_file=config.data.val_files[0], max_queries=200,
                                              max_docs=1000, device=str(device),
                                              query_max_length=config.data.query_max_length,
-                                             doc_max_length=config.data.doc_max_length)
+                                             doc_max_length=config.data.doc_max_length,
+                                             query_idf=getattr(loss_fn, "query_idf", None))
             logger.info("Mid-training evaluator initialized")
         except Exception as e:
             logger.warning(f"Could not init evaluator: {e}")

@@ -219,13 +219,14 @@ def _fuse_passes(model) -> bool:
         os.environ.get("SNX_FUSED_PASSES", "1") != "0"
 
 
-def _packed_lengths(batch: dict):
+def _packed_lengths(batch: dict, keys=("query", "positive", "negative")):
     """Sequence lengths for unpadded execution, taken from the collator's CPU masks (no device sync).
-    None when the masks are already on the device, not right-padded, or fully dense, or SNX_PACK=0."""
+    None when the masks are already on the device, not right-padded, or fully dense, or SNX_PACK=0.
+    ``keys``: the passes that run (a doc-only step encodes no query)."""
     if os.environ.get("SNX_PACK", "1") == "0":
         return None
     out, total, valid = [], 0, 0
-    for key in ("query", "positive", "negative"):
+    for key in keys:
         m = batch[key + "_attention_mask"]
         if m.device.type != "cpu":
             return None
@@ -242,11 +243,17 @@ def micro_step(model, loss_fn: SPLADELossV33, batch: dict, global_step: int, dev
                grad_accum: int, cross_gpu_negatives: bool = False, last_of_window: bool = False):
     """One micro-batch: three encoder passes, loss, backward (ref:train_v33_ddp.py:321-364).
     ``last_of_window``: this backward completes an accumulation window -> NativeDataParallel overlaps the
-    gradient exchange with it."""
+    gradient exchange with it.
+    A loss that carries ``query_idf`` (SPLADELossIDF in doc-only mode) gets its anchor from the query's token ids --
+    idf[token], no gradient (snx.idf.idf_query_dense) -- and the encoder runs on the positives and negatives only."""
     nb = device.type == "cuda"
     if isinstance(model, NativeDataParallel):
         model.arm_gradient_sync(last_of_window)
-    lengths = _packed_lengths(batch) if _fuse_passes(model) else None
+    query_idf = getattr(loss_fn, "query_idf", None)
+    doc_only = query_idf is not None
+    lengths = None
+    if _fuse_passes(model):
+        lengths = _packed_lengths(batch, ("positive", "negative") if doc_only else ("query", "positive", "negative"))
     q_ids = batch["query_input_ids"].to(device, non_blocking=nb)
     q_mask = batch["query_attention_mask"].to(device, non_blocking=nb)
     p_ids = batch["positive_input_ids"].to(device, non_blocking=nb)
@@ -273,7 +280,21 @@ def micro_step(model, loss_fn: SPLADELossV33, batch: dict, global_step: int, dev
             gather = lambda x: sdist.PendingGather(sdist.all_gather_with_grad(x), None)   # noqa: E731
         gathered = None
         # the loss reads the pooled vectors only: token_weights (the `_` below, None) are not computed
-        if _fuse_passes(model):
+        if doc_only:
+            from snx.idf import idf_query_dense
+            with torch.no_grad():
+                anchor_repr = idf_query_dense(q_ids, q_mask, loss_fn.query_allowed, query_idf)
+            if _fuse_passes(model):
+                (positive_repr, _), (negative_repr, _) = unwrap(model).forward_many(
+                    [(p_ids, p_mask), (n_ids, n_mask)], lengths, need_token_weights=False)
+                if xneg:
+                    gathered = gather(positive_repr)
+            else:
+                positive_repr, _ = model(p_ids, p_mask, need_token_weights=False)
+                if xneg:
+                    gathered = gather(positive_repr)
+                negative_repr, _ = model(n_ids, n_mask, need_token_weights=False)
+        elif _fuse_passes(model):
             (anchor_repr, _), (positive_repr, _), (negative_repr, _) = unwrap(model).forward_many(
                 [(q_ids, q_mask), (p_ids, p_mask), (n_ids, n_mask)], lengths, need_token_weights=False)
             if xneg:

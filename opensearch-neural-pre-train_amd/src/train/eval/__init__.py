@@ -95,6 +95,21 @@ def metrics_from_ranks(ranks: Sequence[int], k: int = RETRIEVAL_SIZE) -> Dict[st
     return out
 
 
+def _idf_tensor(query_idf) -> Optional[torch.Tensor]:
+    if query_idf is None:
+        return None
+    return torch.as_tensor(query_idf, dtype=torch.float32).detach().contiguous()
+
+
+def cat_query_rows(batches):
+    """(vals, ids, cnt) batches -> one triple.  IDF rows are as wide as their batch is long, so the batches are padded to
+    one width first (weight 0, id -1 in the unused slots); batches of one width are joined as they are."""
+    cap = max(b[0].shape[1] for b in batches)
+    pad = lambda x, v: torch.nn.functional.pad(x, (0, cap - x.shape[1]), value=v)   # noqa: E731
+    return (torch.cat([pad(b[0], 0.0) for b in batches]), torch.cat([pad(b[1], -1) for b in batches]),
+            torch.cat([b[2] for b in batches]))
+
+
 class MidTrainingEvaluator:
     """Retrieval quality of the model being trained, on a fixed corpus built from ``val_file`` (a triplet JSONL read by
     ``load_training_data``, or ``synthetic:N[:k]``).  ``evaluate(model)`` -> recall@1/5/10, mrr@10, ndcg@10,
@@ -103,13 +118,16 @@ class MidTrainingEvaluator:
     two_phase_eval and the bm25_* / hybrid_* / *_p keys of hybrid_eval (BM25 under the same tokenizer, BM25 + sparse
     fusion, paired t-tests).  Queries keep their top
     64 terms, docs every term that survives the inference encoder's filter (ref:benchmark/indexer.py:59); retrieval
-    size 10."""
+    size 10.  ``query_idf`` ([V] fp32): doc-only mode -- the queries are not encoded, their rows are idf[token] once per
+    distinct kept token (snx.idf.idf_query_rows), the way OpenSearch queries an inference-free model; docs unchanged."""
 
     def __init__(self, tokenizer, val_file: str, max_queries: int = 200, max_docs: int = 1000, device: str = "cuda",
                  query_max_length: int = 64, doc_max_length: int = 256, batch_size: int = 64,
-                 seismic: Optional[dict] = None, two_phase: Optional[dict] = None, hybrid: Optional[dict] = None):
+                 seismic: Optional[dict] = None, two_phase: Optional[dict] = None, hybrid: Optional[dict] = None,
+                 query_idf=None):
         from benchmark.encoders import special_token_ids
         from src.train.data import load_training_data
+        self.query_idf = _idf_tensor(query_idf)
         self.seismic = seismic_params(seismic) if seismic is not None else None
         self.two_phase = two_phase_params(two_phase) if two_phase is not None else None
         self.hybrid = hybrid_params(hybrid) if hybrid is not None else None
@@ -147,6 +165,18 @@ class MidTrainingEvaluator:
                                                 None if top_k is None else min(top_k, rep.shape[1]))
             yield vals, ids, cnt
 
+    def _idf_queries(self, V: int):
+        """Batches of (vals, ids, cnt) query rows from the token ids alone: idf[token], the model is not run."""
+        from snx.idf import idf_query_rows
+        idf = self.query_idf.to(self.device)
+        if idf.numel() != V:
+            raise ValueError(f"query_idf holds {idf.numel()} entries, the model's vocabulary {V}")
+        for s in range(0, len(self.corpus.queries), self.batch_size):
+            enc = self.tokenizer(self.corpus.queries[s:s + self.batch_size], padding=True, truncation=True,
+                                 max_length=self.query_max_length, return_tensors="pt")
+            yield idf_query_rows(enc["input_ids"].to(self.device), enc["attention_mask"].to(self.device),
+                                 self._allowed_mask(V), idf)
+
     def encode(self, model):
         """The corpus through ``model`` -> (SparseIndex over the docs, built when there are queries, or None; the query
         rows (vals, ids, cnt) or None).  The model's training mode is restored."""
@@ -161,11 +191,14 @@ class MidTrainingEvaluator:
                     if index is None:
                         index = SparseIndex(vals.shape[1], self.device)
                     index.add(vals, ids, cnt)
-                qb = list(self._encode(model, c.queries, self.query_max_length, QUERY_TOP_K))
+                if getattr(self, "query_idf", None) is not None and index is not None:
+                    qb = list(self._idf_queries(index.V))
+                else:
+                    qb = list(self._encode(model, c.queries, self.query_max_length, QUERY_TOP_K))
                 queries = None
                 if qb and index is not None:
                     index.build()
-                    queries = tuple(torch.cat([b[i] for b in qb]) for i in range(3))
+                    queries = cat_query_rows(qb)
         finally:
             model.train(was_training)
         return index, queries
@@ -505,9 +538,10 @@ class BenchmarkEvaluator(MidTrainingEvaluator):
     validation file; ``relevant`` holds the qrels rows.  It does not score by itself: see src.train.cli.eval_benchmark."""
 
     def __init__(self, tokenizer, data: BenchmarkData, device: str = "cuda", query_max_length: int = 64,
-                 doc_max_length: int = 256, batch_size: int = 64):
+                 doc_max_length: int = 256, batch_size: int = 64, query_idf=None):
         from benchmark.encoders import special_token_ids
         self.seismic = self.two_phase = self.hybrid = self._bm25 = None
+        self.query_idf = _idf_tensor(query_idf)
         self.tokenizer = tokenizer
         self.device = torch.device(device)
         self.query_max_length, self.doc_max_length = int(query_max_length), int(doc_max_length)
