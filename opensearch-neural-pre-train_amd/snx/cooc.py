@@ -15,16 +15,17 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ._lib import check, fn
+from ._abi import CONSTANTS
+from ._lib import call
 from .ops import _p, _stream
 from .retrieval._common import cuda_device, offsets, workspace
 
-LDS_TOKENS = 4096                      # SNX_COOC_LDS_TOKENS of include/snx.h: tokens of a window that LDS holds
+LDS_TOKENS = CONSTANTS["SNX_COOC_LDS_TOKENS"]     # tokens of a window that LDS holds
 WAVE_TOKENS = 64                       # tokens of a window that one wave takes (CO_WAVE of csrc/cooc.hip)
 DEFAULT_MAX_RECORDS = 1 << 24          # 16 Mi records of 16 (20 when normalised) bytes
 WINDOW_BLOCK = 1 << 22                 # windows whose record counts one pass-1 launch takes
 V_MAX = 3037000499                     # the largest V with V * V < 2^63
-LOG2, LOGE, LOGB = 0, 1, 2             # SNX_COOC_LOG2 / LOGE / LOGB
+LOG2, LOGE, LOGB = (CONSTANTS["SNX_COOC_" + n] for n in ("LOG2", "LOGE", "LOGB"))
 
 _SENTENCE_END = re.compile(r"[.!?\n]")
 
@@ -205,12 +206,11 @@ def cooccurrence(ptr, ids, V: int, *, window_size: Optional[int] = None, symmetr
             d_ptr = torch.from_numpy(ptr).to(dev)
             d_ids = torch.from_numpy(ids).to(dev) if ids.size else None
             ws, ws_bytes = workspace("snx_cooc_workspace_bytes", dev, longest)
-            call = fn("snx_cooc_windows")
             for b0 in range(0, nwin, WINDOW_BLOCK):
                 nb = min(WINDOW_BLOCK, nwin - b0)
                 cnt = torch.empty(nb, dtype=torch.long, device=dev)
-                check(call(_p(d_ptr), _p(d_ids), n_rows, _p(d_win), w or 0, b0, nb, longest, V, int(bool(symmetric)), None,
-                           _p(cnt), None, None, None, _p(ws), ws_bytes, _stream()), "snx_cooc_windows")
+                call("snx_cooc_windows", _p(d_ptr), _p(d_ids), n_rows, _p(d_win), w or 0, b0, nb, longest, V,
+                     int(bool(symmetric)), None, _p(cnt), None, None, None, _p(ws), ws_bytes, _stream())
                 cum = offsets(cnt)
                 s = 0
                 while s < nb:                                 # chunks of whole windows within max_records
@@ -222,9 +222,9 @@ def cooccurrence(ptr, ids, V: int, *, window_size: Optional[int] = None, symmetr
                         adds = torch.empty(nrec, dtype=torch.long, device=dev)
                         m = torch.empty(nrec, dtype=torch.int32, device=dev) if normalize else None
                         rec_ptr = cum[s:e + 1].contiguous()
-                        check(call(_p(d_ptr), _p(d_ids), n_rows, _p(d_win), w or 0, b0 + s, e - s, longest, V,
-                                   int(bool(symmetric)), _p(rec_ptr), None, _p(key), _p(adds), _p(m), _p(ws), ws_bytes,
-                                   _stream()), "snx_cooc_windows")
+                        call("snx_cooc_windows", _p(d_ptr), _p(d_ids), n_rows, _p(d_win), w or 0, b0 + s, e - s, longest, V,
+                             int(bool(symmetric)), _p(rec_ptr), None, _p(key), _p(adds), _p(m), _p(ws), ws_bytes,
+                             _stream())
                         parts.append(_reduce(key, m, adds, span))
                         if sum(int(p[0].numel()) for p in parts) > 2 * max(merged, max_records):
                             merge()
@@ -239,8 +239,7 @@ def cooccurrence(ptr, ids, V: int, *, window_size: Optional[int] = None, symmetr
             key, per_cell = torch.unique_consecutive(key, return_counts=True)
             value = torch.empty(key.numel(), dtype=torch.float32, device=dev)
             cell_ptr = offsets(per_cell)
-            check(fn("snx_cooc_normalized_cells")(_p(cell_ptr), _p(m), _p(adds), int(key.numel()), _p(value), _stream()),
-                  "snx_cooc_normalized_cells")
+            call("snx_cooc_normalized_cells", _p(cell_ptr), _p(m), _p(adds), int(key.numel()), _p(value), _stream())
             counts = None
         else:
             counts, value = adds, adds.to(torch.float32)
@@ -288,8 +287,8 @@ def pmi_values(csr: CooccurrenceCSR, marginals, total: float, config) -> torch.T
     dev, V, mg, scalars = _pmi_args(csr, marginals, total, config, "pmi_values")
     out = torch.empty(csr.nnz, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        check(fn("snx_cooc_pmi_cells")(_p(csr.indptr), _p(csr.indices), _p(csr.data), V, csr.nnz, _p(mg), *scalars, _p(out),
-                                       _stream()), "snx_cooc_pmi_cells")
+        call("snx_cooc_pmi_cells", _p(csr.indptr), _p(csr.indices), _p(csr.data), V, csr.nnz, _p(mg), *scalars, _p(out),
+             _stream())
     return out
 
 
@@ -307,7 +306,6 @@ def pmi_pairs(csr: CooccurrenceCSR, rows, cols, marginals, total: float, config)
     c = c.clamp(min=-1).to(dev, torch.int32).contiguous()
     out = torch.empty(r.numel(), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        check(fn("snx_cooc_pmi_pairs")(_p(csr.indptr), _p(csr.indices if csr.nnz else None),
-                                       _p(csr.data if csr.nnz else None), V, _p(r), _p(c), int(r.numel()), _p(mg), *scalars,
-                                       _p(out), _stream()), "snx_cooc_pmi_pairs")
+        call("snx_cooc_pmi_pairs", _p(csr.indptr), _p(csr.indices if csr.nnz else None),
+             _p(csr.data if csr.nnz else None), V, _p(r), _p(c), int(r.numel()), _p(mg), *scalars, _p(out), _stream())
     return out

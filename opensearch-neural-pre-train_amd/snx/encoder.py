@@ -16,19 +16,15 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple  # noqa: F401
 
 import torch
 
-from ._lib import check, fn
+from ._abi import CONSTANTS, STRUCTS
+from ._lib import call, fn
 from .ops import _p, _stream, rope_table
 
-SNX_FWD_SAVE_FOR_BACKWARD = 1
-SNX_FWD_NO_TOKEN_WEIGHTS = 2      # the caller drops token_weights: the decoder runs without its row half (include/snx.h)
+SNX_FWD_SAVE_FOR_BACKWARD = CONSTANTS["SNX_FWD_SAVE_FOR_BACKWARD"]
+SNX_FWD_NO_TOKEN_WEIGHTS = CONSTANTS["SNX_FWD_NO_TOKEN_WEIGHTS"]  # the decoder runs without its row half
 _SEQ_CACHE_ENTRIES = 64
 logger = logging.getLogger(__name__)
-
-
-class ModelDesc(C.Structure):
-    _fields_ = [("vocab", C.c_int32), ("hidden", C.c_int32), ("inter", C.c_int32), ("layers", C.c_int32),
-                ("heads", C.c_int32), ("head_dim", C.c_int32), ("global_every", C.c_int32), ("window", C.c_int32),
-                ("pad_id", C.c_int32), ("reserved0", C.c_int32), ("ln_eps", C.c_float), ("reserved1", C.c_float)]
+ModelDesc = STRUCTS["snx_model_desc"]
 
 
 @dataclass
@@ -188,8 +184,7 @@ class EncoderRuntime:
             self._wcache = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             self._wcache_key = None
         if key != self._wcache_key:
-            check(fn("snx_weight_cache_refresh")(C.byref(self._desc), ptrs, _p(self._wcache), _stream()),
-                  "snx_weight_cache_refresh")
+            call("snx_weight_cache_refresh", C.byref(self._desc), ptrs, _p(self._wcache), _stream())
             self._wcache_key = key
         return self._wcache
 
@@ -366,17 +361,16 @@ class EncoderRuntime:
             if fp32:
                 nbytes = fn("snx_model_workspace_bytes_f32")(C.byref(self._desc), T, nseq, int(save))
                 saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                check(fn("snx_model_forward_f32")(C.byref(self._desc), self._param_ptrs(), _p(ids), _p(mask), _p(cu), _p(pos),
-                                                  _p(rg), _p(rl), _p(saved), _p(sparse), _p(tw), T, nseq,
-                                                  SNX_FWD_SAVE_FOR_BACKWARD if save else 0, _stream()), "snx_model_forward_f32")
+                call("snx_model_forward_f32", C.byref(self._desc), self._param_ptrs(), _p(ids), _p(mask), _p(cu),
+                     _p(pos), _p(rg), _p(rl), _p(saved), _p(sparse), _p(tw), T, nseq,
+                     SNX_FWD_SAVE_FOR_BACKWARD if save else 0, _stream())
             else:
                 wc = self._weights()
                 nbytes = fn("snx_model_workspace_bytes_fwd")(C.byref(self._desc), T, nseq, flags)
                 saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                check(fn("snx_model_forward")(C.byref(self._desc), self._param_ptrs(), _p(wc), _p(ids), _p(mask), _p(cu),
-                                              _p(pos), _p(rg), _p(rl), _p(saved), _p(sparse), _p(tw),
-                                              groups if (len(shapes) > 1 or lengths is not None) else None, T, nseq, smax,
-                                              flags, _stream()), "snx_model_forward")
+                call("snx_model_forward", C.byref(self._desc), self._param_ptrs(), _p(wc), _p(ids), _p(mask), _p(cu),
+                     _p(pos), _p(rg), _p(rl), _p(saved), _p(sparse), _p(tw),
+                     groups if (len(shapes) > 1 or lengths is not None) else None, T, nseq, smax, flags, _stream())
         if not need_token_weights:
             tw = None
         elif scatter is not None:                    # token_weights back to the padded layout (0 at padding)
@@ -449,10 +443,9 @@ class EncoderRuntime:
 
             def run_all():
                 if fp32:
-                    check(fn("snx_model_backward_f32_tw")(*args32, _stream()), "snx_model_backward_f32_tw")
+                    call("snx_model_backward_f32_tw", *args32, _stream())
                 else:
-                    check(fn("snx_model_backward_units_range_tw")(*args, 0, n_units, None, _stream()),
-                          "snx_model_backward_units_range_tw")
+                    call("snx_model_backward_units_range_tw", *args, 0, n_units, None, _stream())
 
             def run_units(ub, ue):
                 if fp32:                        # one native call; the exchange stream then waits for the launch stream
@@ -461,8 +454,7 @@ class EncoderRuntime:
                     sync.stream.wait_stream(torch.cuda.current_stream(dev))
                     return
                 # the native call makes the exchange stream wait for the launch stream and the weight-gradient stream
-                check(fn("snx_model_backward_units_range_tw")(*args, ub, ue, C.c_void_p(sync.stream.cuda_stream),
-                                                                 _stream()), "snx_model_backward_units_range_tw")
+                call("snx_model_backward_units_range_tw", *args, ub, ue, C.c_void_p(sync.stream.cuda_stream), _stream())
 
             if sync is None:
                 run_all()
@@ -697,10 +689,9 @@ class StepArena:
             wc = rt._weights()
             if k == 0:
                 self.wkey = rt._wcache_key
-            check(fn("snx_model_forward_range")(C.byref(rt._desc), rt._param_ptrs(), _p(wc), _p(ids_k), _p(mask_k),
-                                                _p(cu), _p(pos), _p(rg), _p(rl), _p(self.saved), _p(self.sparse), _p(self.tw),
-                                                None, self.T, self.nseq, r0, s0, T, B, S, self.flags,
-                                                _stream()), "snx_model_forward_range")
+            call("snx_model_forward_range", C.byref(rt._desc), rt._param_ptrs(), _p(wc), _p(ids_k), _p(mask_k), _p(cu),
+                 _p(pos), _p(rg), _p(rl), _p(self.saved), _p(self.sparse), _p(self.tw), None, self.T, self.nseq, r0, s0,
+                 T, B, S, self.flags, _stream())
         self.shapes.append((B, S))
         self.row0.append(r0 + T)
         self.seq0.append(s0 + B)

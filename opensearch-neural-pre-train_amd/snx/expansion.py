@@ -9,7 +9,7 @@ from typing import Sequence, Tuple
 import numpy as np
 import torch
 
-from ._lib import check, fn
+from ._lib import call, fn
 from .ops import _p, _stream
 
 CUTOFFS_MAX = 8
@@ -120,8 +120,8 @@ def judged_ranks(rep: torch.Tensor, excluded: torch.Tensor, j_ptr, j_tok, max_k:
         return rank, nranked
     ws, need = _workspace(B, nj, dev)
     with torch.cuda.device(dev):
-        check(fn("snx_expansion_ranks")(_p(rep), B, V, _p(excluded), _p(d_ptr), _p(d_tok), nj, int(max_k), int(slices),
-                                        _p(rank), _p(nranked), _p(ws), need, _stream()), "snx_expansion_ranks")
+        call("snx_expansion_ranks", _p(rep), B, V, _p(excluded), _p(d_ptr), _p(d_tok), nj, int(max_k), int(slices),
+             _p(rank), _p(nranked), _p(ws), need, _stream())
     return rank, nranked
 
 
@@ -164,8 +164,7 @@ def launch_metrics(rep, excluded, d_ptr, d_tok, d_grade, d_rel, cuts, max_k: int
     ws, need = _workspace(B, nj, dev)
     host = (C.c_int32 * ncut)(*cuts)
     with torch.cuda.device(dev):
-        check(fn("snx_expansion_metrics")(_p(rep), B, V, _p(excluded), _p(d_ptr), _p(d_tok), _p(d_grade), _p(d_rel), nj,
-                                          max_k, C.cast(host, C.c_void_p), ncut, _p(gain), G, slices, _p(rank),
-                                          _p(nranked), _p(first), _p(hits), _p(dcg), _p(ws), need, _stream()),
-              "snx_expansion_metrics")
+        call("snx_expansion_metrics", _p(rep), B, V, _p(excluded), _p(d_ptr), _p(d_tok), _p(d_grade), _p(d_rel), nj,
+             max_k, C.cast(host, C.c_void_p), ncut, _p(gain), G, slices, _p(rank), _p(nranked), _p(first), _p(hits),
+             _p(dcg), _p(ws), need, _stream())
     return rank, nranked, first, hits, dcg

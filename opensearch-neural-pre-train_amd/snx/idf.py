@@ -13,7 +13,7 @@ from typing import Iterable, Optional
 import numpy as np
 import torch
 
-from ._lib import check, fn
+from ._lib import call, fn
 from .loss import _f32c
 from .ops import _chk, _p, _stream
 
@@ -56,7 +56,7 @@ def doc_freq(input_ids: torch.Tensor, attention_mask: torch.Tensor, V: int, out:
         _chk(count, torch.int64, "count", (1,))
     n, S = int(ids.shape[0]), int(ids.shape[1])
     with torch.cuda.device(dev):
-        check(fn("snx_idf_doc_freq")(_p(ids), _p(mask), n, S, V, _p(out), _p(count), _stream()), "snx_idf_doc_freq")
+        call("snx_idf_doc_freq", _p(ids), _p(mask), n, S, V, _p(out), _p(count), _stream())
     return out, int(num_docs) + n
 
 
@@ -240,8 +240,7 @@ def idf_query_dense(input_ids: torch.Tensor, attention_mask: torch.Tensor, allow
     B, S = int(ids.shape[0]), int(ids.shape[1])
     q = torch.empty((B, V), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        check(fn("snx_idf_query_dense")(_p(ids), _p(mask), _p(allowed), _p(idf), B, S, V, _p(q), _stream()),
-              "snx_idf_query_dense")
+        call("snx_idf_query_dense", _p(ids), _p(mask), _p(allowed), _p(idf), B, S, V, _p(q), _stream())
     return q
 
 
@@ -268,8 +267,7 @@ def idf_flops_fwd(x: torch.Tensor, w: torch.Tensor, beta: float, lam: float = 0.
         ws = flops_workspace(V, x.device)
     out3 = torch.empty(3, dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        check(fn("snx_idf_flops_fwd")(_p(x), R, V, _p(w), float(beta), float(lam), _p(ws), _p(out3), _p(loss), _stream()),
-              "snx_idf_flops_fwd")
+        call("snx_idf_flops_fwd", _p(x), R, V, _p(w), float(beta), float(lam), _p(ws), _p(out3), _p(loss), _stream())
     return out3, ws
 
 
@@ -289,8 +287,7 @@ def idf_flops_bwd_accum(dx: torch.Tensor, ws: torch.Tensor, w: torch.Tensor, bet
     _chk(w, torch.float32, "w", (V,))
     _chk(g, torch.float32, "g")
     with torch.cuda.device(dx.device):
-        check(fn("snx_idf_flops_bwd_accum")(_p(dx), R, V, _p(ws), _p(w), float(beta), float(lam), _p(g), _stream()),
-              "snx_idf_flops_bwd_accum")
+        call("snx_idf_flops_bwd_accum", _p(dx), R, V, _p(ws), _p(w), float(beta), float(lam), _p(g), _stream())
     return dx
 
 
@@ -328,15 +325,14 @@ class SpladeLossIdfFn(torch.autograd.Function):
         hpa = (C.c_float * 7)(hp[0], 0.0, 0.0, 0.0, *hp[4:])
         ws = torch.empty(fn("snx_loss_workspace_bytes")(B, Bp, k, V), dtype=torch.uint8, device=q.device)
         out = torch.zeros(18, dtype=torch.float32, device=q.device)
-        check(fn("snx_loss_fwd")(_p(q), _p(p), _p(n), _p(tp), _p(tn), _p(ts), hpa, dims, _p(ws), _p(out), _stream()),
-              "snx_loss_fwd")
+        call("snx_loss_fwd", _p(q), _p(p), _p(n), _p(tp), _p(tn), _p(ts), hpa, dims, _p(ws), _p(out), _stream())
         sides = (q, p[label_off:label_off + B], n)
         pws = [None, None, None]
         for s in range(3):
             if lams[s] != 0.0:
                 pws[s] = flops_workspace(V, q.device)
-                check(fn("snx_idf_flops_fwd")(_p(sides[s]), int(sides[s].shape[0]), V, _p(w), float(beta), lams[s],
-                                              _p(pws[s]), _p(out[9 + 3 * s:]), _p(out), _stream()), "snx_idf_flops_fwd")
+                call("snx_idf_flops_fwd", _p(sides[s]), int(sides[s].shape[0]), V, _p(w), float(beta), lams[s],
+                     _p(pws[s]), _p(out[9 + 3 * s:]), _p(out), _stream())
         ctx.save_for_backward(q, p, n, ws, w, *[x for x in pws if x is not None])
         ctx.have = [x is not None for x in pws]
         ctx.dims, ctx.hp, ctx.use_kd = dims, hpa, int(ts is not None)
@@ -354,13 +350,13 @@ class SpladeLossIdfFn(torch.autograd.Function):
         B, Bp, V = q.shape[0], p.shape[0], q.shape[1]
         g_all = torch.empty((B + Bp + n.shape[0], V), dtype=torch.float32, device=q.device)
         dq, dp, dn = g_all[:B], g_all[B:B + Bp], g_all[B + Bp:]
-        check(fn("snx_loss_bwd")(_p(q), _p(p), _p(n), _p(g), ctx.hp, ctx.dims, _p(ws), ctx.use_kd, _p(dq), _p(dp), _p(dn),
-                                 _stream()), "snx_loss_bwd")
+        call("snx_loss_bwd", _p(q), _p(p), _p(n), _p(g), ctx.hp, ctx.dims, _p(ws), ctx.use_kd, _p(dq), _p(dp), _p(dn),
+             _stream())
         targets = (dq, dp[ctx.label_off:ctx.label_off + B], dn)
         for s in range(3):
             if pws[s] is not None:
-                check(fn("snx_idf_flops_bwd_accum")(_p(targets[s]), int(targets[s].shape[0]), V, _p(pws[s]), _p(w),
-                                                    ctx.beta, ctx.lams[s], _p(g), _stream()), "snx_idf_flops_bwd_accum")
+                call("snx_idf_flops_bwd_accum", _p(targets[s]), int(targets[s].shape[0]), V, _p(pws[s]), _p(w),
+                     ctx.beta, ctx.lams[s], _p(g), _stream())
         return dq, dp, dn, None, None, None, None, None, None, None, None, None
 
 

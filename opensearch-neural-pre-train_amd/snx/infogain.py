@@ -12,11 +12,12 @@ from typing import Tuple
 import numpy as np
 import torch
 
-from ._lib import check, fn
+from ._abi import CONSTANTS
+from ._lib import call
 from .ops import _p, _stream
 from .retrieval._common import cuda_device, slices, step_bytes_mean, workspace
 
-K_MAX = 256                            # SNX_L2_KMAX of include/snx.h
+K_MAX = CONSTANTS["SNX_L2_KMAX"]
 DIM_MAX = 4096
 EULER_GAMMA = 0.5772156649             # the reference's constant in the estimator, ten digits (ref:information_gain.py:149)
 EPS = 1e-10                            # a distance below it means "the query is in the reference set"
@@ -154,8 +155,8 @@ class L2Index:
         with torch.cuda.device(dev):
             for s, m in slices(nq, step):
                 ws, ws_bytes = workspace(sizing, dev, m, self.n, k, chunk_rows)
-                check(fn("snx_l2_knn")(_p(q[s:]), m, _p(self.emb), self.n, self.dim, k, chunk_rows, _p(ids[s:]), _p(d2[s:]),
-                                       _p(ws), ws_bytes, _stream()), "snx_l2_knn")
+                call("snx_l2_knn", _p(q[s:]), m, _p(self.emb), self.n, self.dim, k, chunk_rows, _p(ids[s:]), _p(d2[s:]),
+                     _p(ws), ws_bytes, _stream())
         return d2, ids
 
     def gather_sorted(self, targets, nb_ids) -> torch.Tensor:
@@ -171,8 +172,7 @@ class L2Index:
         m, K = int(nb.shape[0]), int(nb.shape[1])
         out = torch.empty((m, K), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            check(fn("snx_l2_gather_sorted")(_p(t), m, _p(self.emb), self.n, self.dim, _p(nb), K, _p(out), _stream()),
-                  "snx_l2_gather_sorted")
+            call("snx_l2_gather_sorted", _p(t), m, _p(self.emb), self.n, self.dim, _p(nb), K, _p(out), _stream())
         return out
 
 

@@ -6,7 +6,7 @@ from typing import Optional
 
 import torch
 
-from ._lib import check, fn
+from ._lib import call, fn
 from .ops import _p, _stream
 
 
@@ -43,8 +43,7 @@ class SpladeLossFn(torch.autograd.Function):
         nbytes = fn("snx_loss_workspace_bytes")(B, Bp, k, V)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
         out = torch.empty(9, dtype=torch.float32, device=q.device)
-        check(fn("snx_loss_fwd")(_p(q), _p(p), _p(n), _p(tp), _p(tn), _p(ts), hpa, dims, _p(ws), _p(out), _stream()),
-              "snx_loss_fwd")
+        call("snx_loss_fwd", _p(q), _p(p), _p(n), _p(tp), _p(tn), _p(ts), hpa, dims, _p(ws), _p(out), _stream())
         ctx.save_for_backward(q, p, n, ws)
         ctx.dims, ctx.hp, ctx.use_kd = dims, hpa, int(ts is not None)
         loss = out[0].clone()
@@ -60,8 +59,8 @@ class SpladeLossFn(torch.autograd.Function):
         # recognises the adjacent gradients and reads the buffer in place (snx/encoder.py _gather_rows)
         g_all = torch.empty((q.shape[0] + p.shape[0] + n.shape[0], q.shape[1]), dtype=torch.float32, device=q.device)
         dq, dp, dn = g_all[:q.shape[0]], g_all[q.shape[0]:q.shape[0] + p.shape[0]], g_all[q.shape[0] + p.shape[0]:]
-        check(fn("snx_loss_bwd")(_p(q), _p(p), _p(n), _p(g), ctx.hp, ctx.dims, _p(ws), ctx.use_kd, _p(dq), _p(dp), _p(dn),
-                                 _stream()), "snx_loss_bwd")
+        call("snx_loss_bwd", _p(q), _p(p), _p(n), _p(g), ctx.hp, ctx.dims, _p(ws), ctx.use_kd, _p(dq), _p(dp), _p(dn),
+             _stream())
         return dq, dp, dn, None, None, None, None, None, None, None
 
 

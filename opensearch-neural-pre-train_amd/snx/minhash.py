@@ -10,12 +10,13 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ._lib import check, fn
+from ._abi import CONSTANTS
+from ._lib import call
 from .ops import _p, _stream
 from .retrieval._common import cuda_device, workspace
 
-MSG_MAX = 55                           # SNX_MINHASH_MSG_MAX of include/snx.h: one MD5 block holds 55 message bytes
-PERM_MAX = 256                         # SNX_MINHASH_PERM_MAX
+MSG_MAX = CONSTANTS["SNX_MINHASH_MSG_MAX"]        # message bytes that one MD5 block holds
+PERM_MAX = CONSTANTS["SNX_MINHASH_PERM_MAX"]
 FIRST_MATCH_ROWS = 65535               # rows of one snx_minhash_first_match call
 DEDUP_BLOCK = 512                      # rows whose order dependence one workgroup resolves (MH_B of csrc/minhash.hip)
 
@@ -118,8 +119,7 @@ def minhash_signatures(texts: Sequence[str], num_perm: int = 128, ngram_size: in
         d_ptr = torch.from_numpy(ptr).to(dev)
         d_cps = torch.from_numpy(cps).to(dev) if cps.size else None
         with torch.cuda.device(dev):
-            check(fn("snx_minhash_signatures")(_p(d_ptr), _p(d_cps), n, int(ngram_size), int(num_perm), _p(sig),
-                                               _stream()), "snx_minhash_signatures")
+            call("snx_minhash_signatures", _p(d_ptr), _p(d_cps), n, int(ngram_size), int(num_perm), _p(sig), _stream())
     return sig.view(torch.uint32)
 
 
@@ -163,8 +163,8 @@ def greedy_dedup(signatures: torch.Tensor, need: int, exact_group=None) -> torch
     if n:
         ws, ws_bytes = workspace("snx_minhash_dedup_workspace_bytes", dev, int(n), int(P))
         with torch.cuda.device(dev):
-            check(fn("snx_minhash_dedup")(_p(sig), int(n), int(P), min(need, 2 ** 31 - 1), _p(group), _p(dup), _p(ws),
-                                          ws_bytes, _stream()), "snx_minhash_dedup")
+            call("snx_minhash_dedup", _p(sig), int(n), int(P), min(need, 2 ** 31 - 1), _p(group), _p(dup), _p(ws),
+                 ws_bytes, _stream())
     return dup
 
 
@@ -181,6 +181,6 @@ def first_match(signatures: torch.Tensor, kept: Optional[torch.Tensor], need: in
         raise ValueError(f"first_match: at most {FIRST_MATCH_ROWS} rows a call")
     out = torch.empty(nq, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        check(fn("snx_minhash_first_match")(_p(sig), int(nq), _p(k), 0 if k is None else int(k.shape[0]), int(P), need,
-                                            _p(out), _stream()), "snx_minhash_first_match")
+        call("snx_minhash_first_match", _p(sig), int(nq), _p(k), 0 if k is None else int(k.shape[0]), int(P), need,
+             _p(out), _stream())
     return out

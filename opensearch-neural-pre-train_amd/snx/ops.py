@@ -10,7 +10,8 @@ from typing import Optional, Tuple
 
 import torch
 
-from ._lib import check, fn
+from ._abi import STRUCTS
+from ._lib import call, fn
 
 BF16 = torch.bfloat16
 
@@ -39,7 +40,7 @@ def _chk(t: torch.Tensor, dtype, name: str, shape=None):
 def cast_bf16(x: torch.Tensor) -> torch.Tensor:
     _chk(x, torch.float32, "x")
     out = torch.empty(x.shape, dtype=BF16, device=x.device)
-    check(fn("snx_cast_bf16")(_p(x), _p(out), x.numel(), _stream()), "snx_cast_bf16")
+    call("snx_cast_bf16", _p(x), _p(out), x.numel(), _stream())
     return out
 
 
@@ -47,7 +48,7 @@ def cast_transpose_bf16(w: torch.Tensor) -> torch.Tensor:
     _chk(w, torch.float32, "w")
     R, Cc = w.shape
     out = torch.empty((Cc, R), dtype=BF16, device=w.device)
-    check(fn("snx_cast_transpose_bf16")(_p(w), _p(out), R, Cc, _stream()), "snx_cast_transpose_bf16")
+    call("snx_cast_transpose_bf16", _p(w), _p(out), R, Cc, _stream())
     return out
 
 
@@ -60,7 +61,7 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     if K != K2 or K % 64:
         raise ValueError(f"gemm_nt: K mismatch or K % 64 != 0 ({K}, {K2})")
     c = torch.empty((M, N), dtype=BF16, device=a.device)
-    check(fn("snx_gemm_nt_bf16")(_p(a), _p(b), _p(c), M, N, K, _stream()), "snx_gemm_nt_bf16")
+    call("snx_gemm_nt_bf16", _p(a), _p(b), _p(c), M, N, K, _stream())
     return c
 
 
@@ -73,13 +74,11 @@ def gemm_nt_resid(a: torch.Tensor, b: torch.Tensor, h_in: torch.Tensor) -> torch
         raise ValueError("gemm_nt_resid: bad K")
     _chk(h_in, torch.float32, "h_in", (M, N))
     h_out = torch.empty_like(h_in)
-    check(fn("snx_gemm_nt_resid")(_p(a), _p(b), _p(h_in), _p(h_out), M, N, K, _stream()), "snx_gemm_nt_resid")
+    call("snx_gemm_nt_resid", _p(a), _p(b), _p(h_in), _p(h_out), M, N, K, _stream())
     return h_out
 
 
-class TnProblem(C.Structure):
-    _fields_ = [("dY", C.c_void_p), ("X", C.c_void_p), ("dW", C.c_void_p), ("N", C.c_int32), ("K", C.c_int32),
-                ("interleaved", C.c_int32), ("reserved", C.c_int32)]
+TnProblem = STRUCTS["snx_tn_problem"]
 
 
 def _scratch(nbytes: int, device) -> Tuple[Optional[torch.Tensor], int]:
@@ -104,7 +103,7 @@ def gemm_tn_accum(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor) -> None:
     _chk(dw, torch.float32, "dw", (N, K))
     one = (TnProblem * 1)(TnProblem(0, 0, 0, N, K, 0, 0))
     ws, nb = _tn_ws(one, 1, M, dy.device)
-    check(fn("snx_gemm_tn_accum")(_p(dy), _p(x), _p(dw), M, N, K, _p(ws), nb, _stream()), "snx_gemm_tn_accum")
+    call("snx_gemm_tn_accum", _p(dy), _p(x), _p(dw), M, N, K, _p(ws), nb, _stream())
 
 
 def gemm_nt_rope(a: torch.Tensor, b: torch.Tensor, table: torch.Tensor, pos: torch.Tensor, rope_cols: int,
@@ -117,8 +116,7 @@ def gemm_nt_rope(a: torch.Tensor, b: torch.Tensor, table: torch.Tensor, pos: tor
     if b.shape[1] != K or K % 64 or N % 64 or (validate and int(pos.max()) >= table.shape[0]):
         raise ValueError("gemm_nt_rope: bad shapes")
     c = torch.empty((M, N), dtype=BF16, device=a.device)
-    check(fn("snx_gemm_nt_rope")(_p(a), _p(b), _p(c), _p(table), _p(pos), rope_cols, M, N, K, _stream()),
-          "snx_gemm_nt_rope")
+    call("snx_gemm_nt_rope", _p(a), _p(b), _p(c), _p(table), _p(pos), rope_cols, M, N, K, _stream())
     return c
 
 
@@ -127,7 +125,7 @@ def rope_rows(table: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
     _chk(table, torch.float32, "table"); _chk(pos, torch.int32, "pos")
     T = pos.shape[0]
     rows = torch.empty((T, 32, 2), dtype=torch.float32, device=pos.device)
-    check(fn("snx_rope_rows")(_p(table), _p(pos), _p(rows), T, _stream()), "snx_rope_rows")
+    call("snx_rope_rows", _p(table), _p(pos), _p(rows), T, _stream())
     return rows
 
 
@@ -140,8 +138,7 @@ def gemm_nt_rope_rows(a: torch.Tensor, b: torch.Tensor, table: torch.Tensor, pos
     if b.shape[1] != K or K % 64 or N % 64:
         raise ValueError("gemm_nt_rope_rows: bad shapes")
     c = torch.empty((M, N), dtype=BF16, device=a.device)
-    check(fn("snx_gemm_nt_rope_rows")(_p(a), _p(b), _p(c), _p(table), _p(pos), _p(rows), rope_cols, M, N, K, _stream()),
-          "snx_gemm_nt_rope_rows")
+    call("snx_gemm_nt_rope_rows", _p(a), _p(b), _p(c), _p(table), _p(pos), _p(rows), rope_cols, M, N, K, _stream())
     return c
 
 
@@ -151,7 +148,7 @@ def cast_geglu_interleave(wi: torch.Tensor):
     R, Cc = wi.shape
     out = torch.empty((R, Cc), dtype=BF16, device=wi.device)
     out_t = torch.empty((Cc, R), dtype=BF16, device=wi.device)
-    check(fn("snx_cast_geglu_interleave")(_p(wi), _p(out), _p(out_t), R // 2, Cc, _stream()), "snx_cast_geglu_interleave")
+    call("snx_cast_geglu_interleave", _p(wi), _p(out), _p(out_t), R // 2, Cc, _stream())
     return out, out_t
 
 
@@ -163,7 +160,7 @@ def gemm_nt_geglu_fwd(a: torch.Tensor, wi_interleaved: torch.Tensor):
         raise ValueError("gemm_nt_geglu_fwd: bad shapes")
     u = torch.empty((M, N), dtype=BF16, device=a.device)
     y = torch.empty((M, N // 2), dtype=BF16, device=a.device)
-    check(fn("snx_gemm_nt_geglu_fwd")(_p(a), _p(wi_interleaved), _p(u), _p(y), M, N, K, _stream()), "snx_gemm_nt_geglu_fwd")
+    call("snx_gemm_nt_geglu_fwd", _p(a), _p(wi_interleaved), _p(u), _p(y), M, N, K, _stream())
     return u, y
 
 
@@ -175,7 +172,7 @@ def gemm_nt_geglu_bwd(a: torch.Tensor, b: torch.Tensor, u: torch.Tensor):
     if b.shape[1] != K or K % 64 or N % 32:
         raise ValueError("gemm_nt_geglu_bwd: bad shapes")
     du = torch.empty_like(u)
-    check(fn("snx_gemm_nt_geglu_bwd")(_p(a), _p(b), _p(u), _p(du), M, N, K, _stream()), "snx_gemm_nt_geglu_bwd")
+    call("snx_gemm_nt_geglu_bwd", _p(a), _p(b), _p(u), _p(du), M, N, K, _stream())
     return du
 
 
@@ -185,8 +182,7 @@ def gemm_tn_accum_interleaved(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tenso
     _chk(dw, torch.float32, "dw", (N, K))
     one = (TnProblem * 1)(TnProblem(0, 0, 0, N, K, 1, 0))
     ws, nb = _tn_ws(one, 1, M, dy.device)
-    check(fn("snx_gemm_tn_accum_interleaved")(_p(dy), _p(x), _p(dw), M, N, K, _p(ws), nb, _stream()),
-          "snx_gemm_tn_accum_interleaved")
+    call("snx_gemm_tn_accum_interleaved", _p(dy), _p(x), _p(dw), M, N, K, _p(ws), nb, _stream())
 
 
 def gemm_tn_accum_group(problems) -> None:
@@ -204,7 +200,7 @@ def gemm_tn_accum_group(problems) -> None:
         _chk(dw, torch.float32, "dw", (N, K))
         arr[i] = TnProblem(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), N, K, int(bool(inter)), 0)
     ws, nb = _tn_ws(arr, len(problems), M, problems[0][0].device)
-    check(fn("snx_gemm_tn_accum_group")(arr, len(problems), M, _p(ws), nb, _stream()), "snx_gemm_tn_accum_group")
+    call("snx_gemm_tn_accum_group", arr, len(problems), M, _p(ws), nb, _stream())
 
 
 # ----------------------------------------------------------------------------- norms
@@ -212,7 +208,7 @@ def ln_fwd(h: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
     _chk(h, torch.float32, "h"); T, H = h.shape
     _chk(w, torch.float32, "w", (H,))
     x = torch.empty((T, H), dtype=BF16, device=h.device)
-    check(fn("snx_ln_fwd")(_p(h), _p(w), _p(x), T, H, eps, _stream()), "snx_ln_fwd")
+    call("snx_ln_fwd", _p(h), _p(w), _p(x), T, H, eps, _stream())
     return x
 
 
@@ -225,7 +221,7 @@ def embed_ln_fwd(ids: torch.Tensor, E: torch.Tensor, w: torch.Tensor, eps: float
     T = ids.numel()
     h = torch.empty((T, H), dtype=torch.float32, device=E.device)
     x0 = torch.empty((T, H), dtype=BF16, device=E.device)
-    check(fn("snx_embed_ln_fwd")(_p(ids), _p(E), _p(w), _p(h), _p(x0), T, H, eps, _stream()), "snx_embed_ln_fwd")
+    call("snx_embed_ln_fwd", _p(ids), _p(E), _p(w), _p(h), _p(x0), T, H, eps, _stream())
     return h, x0
 
 
@@ -233,7 +229,7 @@ def gelu_ln_fwd(d: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
     _chk(d, BF16, "d"); T, H = d.shape
     _chk(w, torch.float32, "w", (H,))
     x = torch.empty((T, H), dtype=BF16, device=d.device)
-    check(fn("snx_gelu_ln_fwd")(_p(d), _p(w), _p(x), T, H, eps, _stream()), "snx_gelu_ln_fwd")
+    call("snx_gelu_ln_fwd", _p(d), _p(w), _p(x), T, H, eps, _stream())
     return x
 
 
@@ -246,8 +242,8 @@ def ln_bwd(dy: torch.Tensor, h: torch.Tensor, w: torch.Tensor, dh: torch.Tensor,
     if dh_bf16 is not None:
         _chk(dh_bf16, BF16, "dh_bf16", (T, H))
     ws, nb = _scratch(int(fn("snx_ln_bwd_workspace_bytes")(T, H)), h.device)
-    check(fn("snx_ln_bwd")(_p(dy), _p(h), _p(w), _p(dh), _p(dh_bf16), _p(dw), T, H, eps, int(overwrite), _p(ws), nb,
-                           _stream()), "snx_ln_bwd")
+    call("snx_ln_bwd", _p(dy), _p(h), _p(w), _p(dh), _p(dh_bf16), _p(dw), T, H, eps, int(overwrite), _p(ws), nb,
+         _stream())
 
 
 def embed_ln_bwd(dh: torch.Tensor, ids: torch.Tensor, E: torch.Tensor, w: torch.Tensor, gradE: torch.Tensor,
@@ -259,8 +255,8 @@ def embed_ln_bwd(dh: torch.Tensor, ids: torch.Tensor, E: torch.Tensor, w: torch.
         raise ValueError("embed_ln_bwd: ids/dh row mismatch")
     V = E.shape[0]
     ws, nb = _scratch(int(fn("snx_embed_ln_bwd_workspace_bytes")(T, H, V)), dh.device)
-    check(fn("snx_embed_ln_bwd")(_p(dh), _p(ids), _p(E), _p(w), _p(gradE), _p(dw), T, H, V, eps, pad_id, _p(ws), nb,
-                                 _stream()), "snx_embed_ln_bwd")
+    call("snx_embed_ln_bwd", _p(dh), _p(ids), _p(E), _p(w), _p(gradE), _p(dw), T, H, V, eps, pad_id, _p(ws), nb,
+         _stream())
 
 
 def gelu_ln_bwd(dy: torch.Tensor, d: torch.Tensor, w: torch.Tensor, dw: torch.Tensor, eps: float) -> torch.Tensor:
@@ -268,8 +264,7 @@ def gelu_ln_bwd(dy: torch.Tensor, d: torch.Tensor, w: torch.Tensor, dw: torch.Te
     _chk(dy, BF16, "dy", (T, H)); _chk(w, torch.float32, "w", (H,)); _chk(dw, torch.float32, "dw", (H,))
     dd = torch.empty_like(d)
     ws, nb = _scratch(int(fn("snx_ln_bwd_workspace_bytes")(T, H)), d.device)
-    check(fn("snx_gelu_ln_bwd")(_p(dy), _p(d), _p(w), _p(dd), _p(dw), T, H, eps, _p(ws), nb, _stream()),
-          "snx_gelu_ln_bwd")
+    call("snx_gelu_ln_bwd", _p(dy), _p(d), _p(w), _p(dd), _p(dw), T, H, eps, _p(ws), nb, _stream())
     return dd
 
 
@@ -288,13 +283,13 @@ def rope_inplace(qkv: torch.Tensor, table: torch.Tensor, pos: torch.Tensor, head
     _chk(table, torch.float32, "table"); _chk(pos, torch.int32, "pos", (T,))
     if table.shape[1:] != (32, 2) or int(pos.max()) >= table.shape[0] or int(pos.min()) < 0:
         raise ValueError("rope_inplace: position outside the cos/sin table")
-    check(fn("snx_rope_inplace")(_p(qkv), _p(table), _p(pos), T, heads, int(inverse), _stream()), "snx_rope_inplace")
+    call("snx_rope_inplace", _p(qkv), _p(table), _p(pos), T, heads, int(inverse), _stream())
 
 
 def geglu_fwd(u: torch.Tensor) -> torch.Tensor:
     _chk(u, BF16, "u"); T, I2 = u.shape
     y = torch.empty((T, I2 // 2), dtype=BF16, device=u.device)
-    check(fn("snx_geglu_fwd")(_p(u), _p(y), T, I2 // 2, _stream()), "snx_geglu_fwd")
+    call("snx_geglu_fwd", _p(u), _p(y), T, I2 // 2, _stream())
     return y
 
 
@@ -302,7 +297,7 @@ def geglu_bwd(u: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     _chk(u, BF16, "u"); T, I2 = u.shape
     _chk(dy, BF16, "dy", (T, I2 // 2))
     du = torch.empty_like(u)
-    check(fn("snx_geglu_bwd")(_p(u), _p(dy), _p(du), T, I2 // 2, _stream()), "snx_geglu_bwd")
+    call("snx_geglu_bwd", _p(u), _p(dy), _p(du), T, I2 // 2, _stream())
     return du
 
 
@@ -333,8 +328,8 @@ def attn_fwd(qkv: torch.Tensor, cu: torch.Tensor, mask: torch.Tensor, max_seqlen
     nseq = cu.numel() - 1
     out = torch.empty((T, heads * 64), dtype=BF16, device=qkv.device)
     lse = torch.empty((heads, T), dtype=torch.float32, device=qkv.device)
-    check(fn("snx_attn_fwd_ex")(_p(qkv), _p(cu), _p(mask), _p(out), _p(lse), _groups(groups), T, nseq, max_seqlen,
-                                heads, 64, window, _stream()), "snx_attn_fwd_ex")
+    call("snx_attn_fwd_ex", _p(qkv), _p(cu), _p(mask), _p(out), _p(lse), _groups(groups), T, nseq, max_seqlen, heads,
+         64, window, _stream())
     return out, lse
 
 
@@ -359,9 +354,8 @@ def attn_bwd(qkv, out, dout, lse, cu, mask, max_seqlen: int, heads: int, window:
     delta = torch.empty((heads, T), dtype=torch.float32, device=qkv.device)
     if rope_table is not None:
         _chk(rope_table, torch.float32, "rope_table"); _chk(pos, torch.int32, "pos", (T,))
-    check(fn("snx_attn_bwd_ex")(_p(qkv), _p(out), _p(dout), _p(lse), _p(cu), _p(mask), _p(delta), _p(dqkv),
-                                _p(rope_table), _p(pos), _groups(groups), T, nseq, max_seqlen, heads, 64, window,
-                                _stream()), "snx_attn_bwd_ex")
+    call("snx_attn_bwd_ex", _p(qkv), _p(out), _p(dout), _p(lse), _p(cu), _p(mask), _p(delta), _p(dqkv), _p(rope_table),
+         _p(pos), _groups(groups), T, nseq, max_seqlen, heads, 64, window, _stream())
     return dqkv
 
 
@@ -384,8 +378,8 @@ def decoder_splade_fwd(hd: torch.Tensor, w_bf16: torch.Tensor, bias: torch.Tenso
     tw = torch.empty((T,), dtype=torch.float32, device=hd.device)
     nbytes = fn("snx_splade_head_scratch_bytes")(T, V)
     scratch = torch.empty((nbytes,), dtype=torch.uint8, device=hd.device)
-    check(fn("snx_decoder_splade_fwd")(_p(hd), _p(w_bf16), _p(bias), _p(cu), _p(mask), _p(sparse), _p(keys), _p(tw),
-                                       _p(scratch), T, nseq, max_seqlen, V, K, _stream()), "snx_decoder_splade_fwd")
+    call("snx_decoder_splade_fwd", _p(hd), _p(w_bf16), _p(bias), _p(cu), _p(mask), _p(sparse), _p(keys), _p(tw),
+         _p(scratch), T, nseq, max_seqlen, V, K, _stream())
     return sparse, keys, tw
 
 
@@ -409,9 +403,8 @@ def decoder_splade_fwd_tw(hd: torch.Tensor, w_bf16: torch.Tensor, bias: torch.Te
     tw = torch.empty((T,), dtype=torch.float32, device=hd.device)
     tkeys = torch.empty((T,), dtype=torch.int32, device=hd.device)
     scratch = torch.empty((fn("snx_splade_head_scratch_bytes")(T, V),), dtype=torch.uint8, device=hd.device)
-    check(fn("snx_decoder_splade_fwd_rec")(_p(hd), _p(w_bf16), _p(bias), _p(cu), _p(mask), _p(sparse), _p(keys), _p(tw),
-                                           _p(tkeys), _p(scratch), T, nseq, max_seqlen, V, K, 1, _stream()),
-          "snx_decoder_splade_fwd_rec")
+    call("snx_decoder_splade_fwd_rec", _p(hd), _p(w_bf16), _p(bias), _p(cu), _p(mask), _p(sparse), _p(keys), _p(tw),
+         _p(tkeys), _p(scratch), T, nseq, max_seqlen, V, K, 1, _stream())
     return sparse, keys, tw, tkeys
 
 
@@ -430,8 +423,8 @@ def splade_bwd_tw(g: torch.Tensor, keys: torch.Tensor, g_tw: Optional[torch.Tens
     gradb = torch.zeros((V,), dtype=torch.float32, device=hd.device)
     scratch = torch.empty((fn("snx_splade_bwd_scratch_bytes")(nseq, max_seqlen, V),), dtype=torch.uint8, device=hd.device)
     tws = torch.empty((fn("snx_splade_tw_scratch_bytes")(T, V),), dtype=torch.uint8, device=hd.device)
-    check(fn("snx_splade_bwd_tw")(_p(g), _p(keys), _p(g_tw), _p(tkeys), _p(hd), _p(w_bf16), _p(cu), _p(dhd), _p(gradE),
-                                  _p(gradb), _p(scratch), _p(tws), T, nseq, max_seqlen, V, H, _stream()), "snx_splade_bwd_tw")
+    call("snx_splade_bwd_tw", _p(g), _p(keys), _p(g_tw), _p(tkeys), _p(hd), _p(w_bf16), _p(cu), _p(dhd), _p(gradE),
+         _p(gradb), _p(scratch), _p(tws), T, nseq, max_seqlen, V, H, _stream())
     return dhd, gradE, gradb
 
 
@@ -453,6 +446,5 @@ def sparse_topk(rep: torch.Tensor, allowed: torch.Tensor, k: Optional[int] = Non
     ids = torch.empty((B, cap), dtype=torch.int32, device=rep.device)
     cnt = torch.empty((B,), dtype=torch.int32, device=rep.device)
     srt = torch.empty((B,), dtype=torch.int32, device=rep.device)
-    check(fn("snx_sparse_topk")(_p(rep), _p(allowed), _p(vals), _p(ids), _p(cnt), _p(srt), B, V, min(kk, V), cap,
-                                _stream()), "snx_sparse_topk")
+    call("snx_sparse_topk", _p(rep), _p(allowed), _p(vals), _p(ids), _p(cnt), _p(srt), B, V, min(kk, V), cap, _stream())
     return vals, ids, cnt, srt

@@ -12,7 +12,7 @@ from typing import List
 
 import torch
 
-from ._lib import check, fn
+from ._lib import call, fn
 from .ops import _p, _stream
 
 
@@ -68,9 +68,8 @@ class FusedAdamW(torch.optim.Optimizer):
         self._steps += 1
         hp = (C.c_float * 6)(lrs.pop(), g0["betas"][0], g0["betas"][1], g0["eps"], self._wd, float(max_norm))
         flat = self.rt.flat_param
-        check(fn("snx_adamw_clip_step")(_p(flat), _p(self.rt.flat_grad), _p(self._m), _p(self._v), flat.numel(), hp,
-                                        self._steps, self._nodecay[0], self._nodecay[1], _p(self._norm),
-                                        _p(self._scratch), _stream()), "snx_adamw_clip_step")
+        call("snx_adamw_clip_step", _p(flat), _p(self.rt.flat_grad), _p(self._m), _p(self._v), flat.numel(), hp,
+             self._steps, self._nodecay[0], self._nodecay[1], _p(self._norm), _p(self._scratch), _stream())
         self.rt.mark_weights_dirty()
         for st in self.state.values():
             st["step"] = torch.tensor(float(self._steps))

@@ -4,7 +4,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from .._lib import check, fn
+from .._lib import call
 from ..ops import _p, _stream
 from ._common import (K_MAX, at, cat_or_empty, check_ceiling, check_pairs, check_query_slice, check_targets, cuda_device,
                       exclusion_or_null, search_outputs, slices, step_bytes_mean, workspace)
@@ -100,9 +100,8 @@ class DenseIndex:
         with torch.cuda.device(dev):
             for s, m in slices(nq, self._step(nq, sizing, k, chunk_docs, query_slice)):
                 ws, ws_bytes = workspace(sizing, dev, m, nd, k, chunk_docs)
-                check(fn("snx_dense_search")(
-                    _p(q[s:]), m, _p(self.emb), nd, self.dim, _p(at(tgt, s)), k, chunk_docs, _p(docs[s:]),
-                    _p(scores[s:]), _p(at(rank, s)), _p(at(tscore, s)), _p(ws), ws_bytes, _stream()), "snx_dense_search")
+                call("snx_dense_search", _p(q[s:]), m, _p(self.emb), nd, self.dim, _p(at(tgt, s)), k, chunk_docs,
+                     _p(docs[s:]), _p(scores[s:]), _p(at(rank, s)), _p(at(tscore, s)), _p(ws), ws_bytes, _stream())
         return scores, docs, rank, tscore
 
     def search_band(self, q: torch.Tensor, lo: int, hi: int, exclude=None, ceiling: Optional[torch.Tensor] = None,
@@ -123,10 +122,9 @@ class DenseIndex:
         with torch.cuda.device(dev):
             for s, m in slices(nq, self._step(nq, sizing, hi, chunk_docs, query_slice)):
                 ws, ws_bytes = workspace(sizing, dev, m, nd, hi, chunk_docs)
-                check(fn("snx_dense_search_band")(
-                    _p(q[s:]), m, _p(self.emb), nd, self.dim, _p(at(ex_ptr, s)), _p(ex_doc), _p(at(ceil, s)), lo, hi,
-                    chunk_docs, _p(docs[s:]), _p(scores[s:]), _p(found[s:]), _p(ws), ws_bytes, _stream()),
-                    "snx_dense_search_band")
+                call("snx_dense_search_band", _p(q[s:]), m, _p(self.emb), nd, self.dim, _p(at(ex_ptr, s)), _p(ex_doc),
+                     _p(at(ceil, s)), lo, hi, chunk_docs, _p(docs[s:]), _p(scores[s:]), _p(found[s:]), _p(ws), ws_bytes,
+                     _stream())
         return scores, docs, found
 
     def pair_scores(self, q: torch.Tensor, pairs: torch.Tensor) -> torch.Tensor:
@@ -138,6 +136,5 @@ class DenseIndex:
         n = int(pq.numel())
         out = torch.empty(n, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            check(fn("snx_dense_pair_scores")(_p(q), nq, _p(self.emb), nd, self.dim, _p(pq), _p(pd), n, _p(out),
-                                               _stream()), "snx_dense_pair_scores")
+            call("snx_dense_pair_scores", _p(q), nq, _p(self.emb), nd, self.dim, _p(pq), _p(pd), n, _p(out), _stream())
         return out

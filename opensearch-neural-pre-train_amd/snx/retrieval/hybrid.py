@@ -5,12 +5,13 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .._lib import check, fn
+from .._abi import CONSTANTS
+from .._lib import call, fn
 from ..ops import _chk, _p, _stream
 from ._common import K_MAX, cat_or_empty, check_targets, cuda_device, offsets
 from .sparse import SparseIndex
 
-FUSE_METHODS = {"rrf": 0, "weighted_rrf": 1, "linear": 2}                         # SNX_FUSE_* of include/snx.h
+FUSE_METHODS = {k: CONSTANTS["SNX_FUSE_" + k.upper()] for k in ("rrf", "weighted_rrf", "linear")}
 FUSE_L_MAX = 4
 FUSE_TOP_K_MAX = 4096
 
@@ -46,8 +47,8 @@ def term_counts(input_ids: torch.Tensor, attention_mask: torch.Tensor, allowed: 
     cnt = torch.empty(n, dtype=torch.int32, device=dev)
     length = torch.empty(n, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        check(fn("snx_term_counts")(_p(ids), _p(mask), _p(allowed), n, S, int(allowed.numel()), _p(term), _p(tf), _p(cnt),
-                                    _p(length), _stream()), "snx_term_counts")
+        call("snx_term_counts", _p(ids), _p(mask), _p(allowed), n, S, int(allowed.numel()), _p(term), _p(tf), _p(cnt),
+             _p(length), _stream())
     return term, tf, cnt, length
 
 
@@ -105,8 +106,7 @@ class Bm25Index:
         live = torch.arange(term.shape[1], device=self.device)[None, :] < cnt[:, None]
         terms = term[live].contiguous()
         with torch.cuda.device(self.device):
-            check(fn("snx_bm25_doc_freq")(_p(terms), int(terms.numel()), self.V, _p(self.doc_freq), _stream()),
-                  "snx_bm25_doc_freq")
+            call("snx_bm25_doc_freq", _p(terms), int(terms.numel()), self.V, _p(self.doc_freq), _stream())
         self._cnt.append(cnt.long())
         self._term.append(terms)
         self._tf.append(tf[live].contiguous())
@@ -128,9 +128,8 @@ class Bm25Index:
         ptr = offsets(cnt)
         w = torch.empty(terms.numel(), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            check(fn("snx_bm25_weights")(_p(ptr), _p(terms), _p(tf), _p(self.doc_len), _p(self.idf), N,
-                                         int(terms.numel()), V, self.avgdl, self.k1, self.b, _p(w), _stream()),
-                  "snx_bm25_weights")
+            call("snx_bm25_weights", _p(ptr), _p(terms), _p(tf), _p(self.doc_len), _p(self.idf), N, int(terms.numel()),
+                 V, self.avgdl, self.k1, self.b, _p(w), _stream())
         index = SparseIndex(V, dev)
         index.add_csr(cnt, terms, w)
         self.index = index.build()
@@ -210,7 +209,6 @@ def fuse_ranked(lists, method: str, top_k: int, targets: Optional[torch.Tensor] 
     rank = torch.empty(nq, dtype=torch.int32, device=dev) if tgt is not None else None
     host = (C.c_double * len(prm))(*prm)
     with torch.cuda.device(dev):
-        check(fn("snx_fuse_ranked")(_p(docs), _p(scores), L, int(nq), int(R), FUSE_METHODS[method],
-                                    C.cast(host, C.c_void_p), _p(tgt), top_k, _p(out_d), _p(out_s), _p(total), _p(rank),
-                                    _stream()), "snx_fuse_ranked")
+        call("snx_fuse_ranked", _p(docs), _p(scores), L, int(nq), int(R), FUSE_METHODS[method],
+             C.cast(host, C.c_void_p), _p(tgt), top_k, _p(out_d), _p(out_s), _p(total), _p(rank), _stream())
     return out_s, out_d, rank, total

@@ -5,14 +5,15 @@ from typing import Tuple
 import numpy as np
 import torch
 
-from .._lib import SnxError, check, fn
+from .._abi import CONSTANTS
+from .._lib import SnxError, call
 from ..ops import _p, _stream
 from ._common import csr_rows, cuda_device
 
 RANKED_R_MAX = 4096
 CUTOFFS_MAX = 8
 BOOTSTRAP_M_MAX = 16
-BOOTSTRAP_SEGMENT = 64                 # SNX_BOOTSTRAP_SEGMENT of include/snx.h: part of the summation order
+BOOTSTRAP_SEGMENT = CONSTANTS["SNX_BOOTSTRAP_SEGMENT"]       # part of the summation order
 
 
 def relevance_csr(relevant, nq: int, nd: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -59,9 +60,8 @@ def ranked_relevance(docs: torch.Tensor, relevant, nd: int, cutoffs=(1, 5, 10)
     dcg = torch.empty((nq, len(cuts)), dtype=torch.float64, device=dev)
     host = (C.c_int32 * len(cuts))(*cuts)
     with torch.cuda.device(dev):
-        check(fn("snx_ranked_relevance")(_p(docs), int(nq), int(R), int(nd), _p(rel_ptr), _p(rel_doc),
-                                         C.cast(host, C.c_void_p), len(cuts), _p(disc), _p(first), _p(hits), _p(dcg),
-                                         _stream()), "snx_ranked_relevance")
+        call("snx_ranked_relevance", _p(docs), int(nq), int(R), int(nd), _p(rel_ptr), _p(rel_doc),
+             C.cast(host, C.c_void_p), len(cuts), _p(disc), _p(first), _p(hits), _p(dcg), _stream())
     return first, hits, dcg
 
 
@@ -115,6 +115,5 @@ def bootstrap_means(values, n_bootstrap: int = 1000, seed: int = 42, device=None
     didx = torch.from_numpy(np.ascontiguousarray(idx)).to(dev)
     out = torch.empty((nb, M), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        check(fn("snx_bootstrap_means")(_p(vals), int(n), int(M), _p(didx), nb, _p(out), _stream()),
-              "snx_bootstrap_means")
+        call("snx_bootstrap_means", _p(vals), int(n), int(M), _p(didx), nb, _p(out), _stream())
     return out

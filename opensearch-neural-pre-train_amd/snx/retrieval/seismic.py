@@ -5,7 +5,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from .._lib import check, fn
+from .._lib import call
 from ..ops import _p, _stream
 from ._common import K_MAX, at, check_query_slice, check_targets, offsets, search_outputs, slices, workspace
 from .sparse import SparseIndex, pack_rows
@@ -66,16 +66,14 @@ class SeismicIndex:
             self.cent_doc = torch.empty(C, dtype=torch.int32, device=dev)
             assign = torch.empty(P, dtype=torch.int32, device=dev)
             cent_size = torch.zeros(C, dtype=torch.int32, device=dev)
-            check(fn("snx_seismic_build_clusters")(
-                _p(index.term_ptr), _p(index.post_doc), _p(index.post_w), _p(index.doc_ptr), _p(index.doc_term),
-                _p(index.doc_w), nd, V, self.n_postings, _p(self.prune_ptr), _p(cent_cnt), _p(self.cent_ptr), P, C,
-                _p(self.prune_doc), _p(self.prune_w), _p(self.cent_doc), _p(assign), _p(cent_size), _stream()),
-                "snx_seismic_build_clusters")
+            call("snx_seismic_build_clusters", _p(index.term_ptr), _p(index.post_doc), _p(index.post_w),
+                 _p(index.doc_ptr), _p(index.doc_term), _p(index.doc_w), nd, V, self.n_postings, _p(self.prune_ptr),
+                 _p(cent_cnt), _p(self.cent_ptr), P, C, _p(self.prune_doc), _p(self.prune_w), _p(self.cent_doc),
+                 _p(assign), _p(cent_size), _stream())
             cursor = offsets(cent_size.long())                 # block start of every centroid (empty: no room)
             self.blk_doc = torch.empty(P, dtype=torch.int32, device=dev)
-            check(fn("snx_seismic_build_blocks")(_p(self.prune_ptr), _p(self.prune_doc), _p(assign), _p(self.cent_ptr),
-                                                  V, P, _p(cursor), _p(self.blk_doc), _stream()),
-                  "snx_seismic_build_blocks")
+            call("snx_seismic_build_blocks", _p(self.prune_ptr), _p(self.prune_doc), _p(assign), _p(self.cent_ptr), V,
+                 P, _p(cursor), _p(self.blk_doc), _stream())
             live = cent_size > 0
             nb = int(live.sum())
             self.blk_ptr = offsets(cent_size[live].long())
@@ -84,18 +82,16 @@ class SeismicIndex:
             self.blk_cent = (torch.arange(C, device=dev) - self.cent_ptr[term_of])[live].to(torch.int32)
             ws, ws_bytes = workspace("snx_seismic_build_workspace_bytes", dev, V, nb)
             sum_cnt = torch.empty(nb, dtype=torch.int32, device=dev)
-            summaries = fn("snx_seismic_build_summaries")
             alpha = float(np.float32(self.summary_prune_ratio))
-            check(summaries(_p(index.doc_ptr), _p(index.doc_term), _p(index.doc_w), nd, V, _p(self.blk_ptr),
-                            _p(self.blk_doc), nb, alpha, None, _p(sum_cnt), None, None, _p(ws), ws_bytes, _stream()),
-                  "snx_seismic_build_summaries")
+            call("snx_seismic_build_summaries", _p(index.doc_ptr), _p(index.doc_term), _p(index.doc_w), nd, V,
+                 _p(self.blk_ptr), _p(self.blk_doc), nb, alpha, None, _p(sum_cnt), None, None, _p(ws), ws_bytes, _stream())
             self.sum_ptr = offsets(sum_cnt.long())
             S = int(self.sum_ptr[-1])
             self.sum_term = torch.empty(S, dtype=torch.int32, device=dev)
             self.sum_w = torch.empty(S, dtype=torch.float32, device=dev)
-            check(summaries(_p(index.doc_ptr), _p(index.doc_term), _p(index.doc_w), nd, V, _p(self.blk_ptr),
-                            _p(self.blk_doc), nb, alpha, _p(self.sum_ptr), _p(sum_cnt), _p(self.sum_term),
-                            _p(self.sum_w), _p(ws), ws_bytes, _stream()), "snx_seismic_build_summaries")
+            call("snx_seismic_build_summaries", _p(index.doc_ptr), _p(index.doc_term), _p(index.doc_w), nd, V,
+                 _p(self.blk_ptr), _p(self.blk_doc), nb, alpha, _p(self.sum_ptr), _p(sum_cnt), _p(self.sum_term),
+                 _p(self.sum_w), _p(ws), ws_bytes, _stream())
             torch.cuda.synchronize(dev)
         self.build_seconds = time.perf_counter() - t0
 
@@ -147,10 +143,9 @@ class SeismicIndex:
         stats = torch.empty((nq, 3), dtype=torch.long, device=dev)
         with torch.cuda.device(dev):
             for s, m in slices(nq, int(query_slice) or _SEISMIC_QUERY_SLICE):
-                check(fn("snx_seismic_search")(
-                    _p(q_ptr[s:]), _p(q_term), _p(q_w), m, max_nnz, _p(self.term_blk_ptr), _p(self.blk_ptr),
-                    _p(self.blk_doc), _p(self.sum_ptr), _p(self.sum_term), _p(self.sum_w), _p(idx.doc_ptr),
-                    _p(idx.doc_term), _p(idx.doc_w), nd, V, _p(at(tgt, s)), k, top_n, hf, _p(docs[s:]), _p(scores[s:]),
-                    _p(at(rank, s)), _p(at(tscore, s)), _p(stats[s:]), _stream()), "snx_seismic_search")
+                call("snx_seismic_search", _p(q_ptr[s:]), _p(q_term), _p(q_w), m, max_nnz, _p(self.term_blk_ptr),
+                     _p(self.blk_ptr), _p(self.blk_doc), _p(self.sum_ptr), _p(self.sum_term), _p(self.sum_w),
+                     _p(idx.doc_ptr), _p(idx.doc_term), _p(idx.doc_w), nd, V, _p(at(tgt, s)), k, top_n, hf,
+                     _p(docs[s:]), _p(scores[s:]), _p(at(rank, s)), _p(at(tscore, s)), _p(stats[s:]), _stream())
         return scores, docs, rank, tscore, {"blocks_total": stats[:, 0], "blocks_scored": stats[:, 1],
                                             "postings_scored": stats[:, 2]}

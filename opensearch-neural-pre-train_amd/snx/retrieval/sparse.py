@@ -5,7 +5,8 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from .._lib import check, fn
+from .._abi import CONSTANTS
+from .._lib import call, check, fn   # the query-sliced launches go through this module's `fn`: the slicing test counts them
 from ..ops import _chk, _p, _stream
 from ._common import (K_MAX, at, cat_or_empty, check_ceiling, check_chunk_docs, check_pairs, check_query_slice,
                       check_targets, cuda_device, exclusion_or_null, offsets, search_outputs, slices, step_blocks,
@@ -14,7 +15,7 @@ from .qrels import relevance_csr
 
 CHUNK_MAX = 32768
 WINDOW_MAX = 1024                      # rescore window cap
-PRUNE_TYPES = {"max_ratio": 0, "abs_value": 1, "top_k": 2, "alpha_mass": 3}       # SNX_PRUNE_* of include/snx.h
+PRUNE_TYPES = {k: CONSTANTS["SNX_PRUNE_" + k.upper()] for k in ("max_ratio", "abs_value", "top_k", "alpha_mass")}
 _SEARCH_WS_BUDGET = 256 << 20          # bytes of search workspace per launch: larger query sets go in slices
 _FIRST_RELEVANT_BLOCKS = 1 << 21       # (query, chunk) workgroups per launch: larger query sets go in slices
 
@@ -82,8 +83,8 @@ def _keep_flags(cnt: torch.Tensor, weights: torch.Tensor, code: int, value: floa
     longest = int(cnt.max()) if n else 0
     ws, ws_bytes = workspace("snx_sparse_prune_workspace_bytes", dev, code, n, longest)
     with torch.cuda.device(dev):
-        check(fn("snx_sparse_prune_rows")(_p(ptr), _p(weights), n, nnz, longest, code, value, _p(keep), _p(kept),
-                                           _p(ws), ws_bytes, _stream()), "snx_sparse_prune_rows")
+        call("snx_sparse_prune_rows", _p(ptr), _p(weights), n, nnz, longest, code, value, _p(keep), _p(kept), _p(ws),
+             ws_bytes, _stream())
     return keep.bool(), kept.long()
 
 
@@ -190,9 +191,8 @@ class SparseIndex:
         post_w = torch.empty(nnz, dtype=torch.float32, device=dev)
         ws, ws_bytes = workspace("snx_sparse_index_workspace_bytes", dev, nd, V)
         with torch.cuda.device(dev):
-            check(fn("snx_sparse_index_build")(_p(self.doc_ptr), _p(self.doc_term), _p(self.doc_w), nd, V, nnz,
-                                                _p(term_ptr), _p(post_doc), _p(post_w), _p(ws), ws_bytes, _stream()),
-                  "snx_sparse_index_build")
+            call("snx_sparse_index_build", _p(self.doc_ptr), _p(self.doc_term), _p(self.doc_w), nd, V, nnz,
+                 _p(term_ptr), _p(post_doc), _p(post_w), _p(ws), ws_bytes, _stream())
         self.term_ptr, self.post_doc, self.post_w = term_ptr, post_doc, post_w
         return self
 
@@ -270,9 +270,8 @@ class SparseIndex:
         n = int(pq.numel())
         out = torch.empty(n, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            check(fn("snx_sparse_pair_scores")(_p(q_ptr), _p(q_term), _p(q_w), nq, _p(self.doc_ptr), _p(self.doc_term),
-                                                _p(self.doc_w), nd, _p(pq), _p(pd), n, _p(out), _stream()),
-                  "snx_sparse_pair_scores")
+            call("snx_sparse_pair_scores", _p(q_ptr), _p(q_term), _p(q_w), nq, _p(self.doc_ptr), _p(self.doc_term),
+                 _p(self.doc_w), nd, _p(pq), _p(pd), n, _p(out), _stream())
         return out
 
     def search_band(self, q_vals: torch.Tensor, q_ids: torch.Tensor, q_cnt: torch.Tensor, lo: int, hi: int,
@@ -338,10 +337,9 @@ class SparseIndex:
         scores, docs, rank, tscore = search_outputs(nq, k, dev, tgt is not None)
         with torch.cuda.device(dev):
             for s, m in slices(nq, int(query_slice) or max(nq, 1)):
-                check(fn("snx_sparse_rescore")(
-                    _p(q_ptr[s:]), _p(q_term), _p(q_w), m, _p(cand[s:]), W, _p(self.doc_ptr), _p(self.doc_term),
-                    _p(self.doc_w), self.num_docs, _p(at(tgt, s)), k, _p(docs[s:]), _p(scores[s:]), _p(at(rank, s)),
-                    _p(at(tscore, s)), _stream()), "snx_sparse_rescore")
+                call("snx_sparse_rescore", _p(q_ptr[s:]), _p(q_term), _p(q_w), m, _p(cand[s:]), W, _p(self.doc_ptr),
+                     _p(self.doc_term), _p(self.doc_w), self.num_docs, _p(at(tgt, s)), k, _p(docs[s:]), _p(scores[s:]),
+                     _p(at(rank, s)), _p(at(tscore, s)), _stream())
         return scores, docs, rank, tscore
 
     def search_two_phase(self, q_vals: torch.Tensor, q_ids: torch.Tensor, q_cnt: torch.Tensor, k: int,

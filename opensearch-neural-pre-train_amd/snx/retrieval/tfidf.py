@@ -10,13 +10,14 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .._lib import check, fn
+from .._abi import CONSTANTS
+from .._lib import call
 from ..minhash import code_point_csr
 from ..ops import _p, _stream
 from ._common import cat_or_empty, cuda_device, offsets, search_outputs, workspace
 from .sparse import SparseIndex
 
-LDS_KEYS = 4096                        # SNX_TFIDF_LDS_KEYS of include/snx.h: slots of a row the LDS form sorts
+LDS_KEYS = CONSTANTS["SNX_TFIDF_LDS_KEYS"]        # slots of a row the LDS form sorts
 NGRAM_MAX = 3
 
 
@@ -109,16 +110,15 @@ def row_counts(ptr: np.ndarray, cps: np.ndarray, ngram_range, device):
     cnt32 = torch.empty(n, dtype=torch.int32, device=dev)
     ws, ws_bytes = workspace("snx_tfidf_counts_workspace_bytes", dev, longest, lo, hi)
     with torch.cuda.device(dev):
-        check(fn("snx_tfidf_row_counts")(_p(d_ptr), _p(d_cps), n, longest, lo, hi, _p(s_key), _p(s_count), _p(cnt32),
-                                         _p(ws), ws_bytes, _stream()), "snx_tfidf_row_counts")
+        call("snx_tfidf_row_counts", _p(d_ptr), _p(d_cps), n, longest, lo, hi, _p(s_key), _p(s_count), _p(cnt32),
+             _p(ws), ws_bytes, _stream())
         cnt = cnt32.long()
         dst = offsets(cnt)
         src = (d_ptr[:-1] + 2 * torch.arange(n, device=dev)) * NS
         nnz = int(dst[-1])
         keys = torch.empty(nnz, dtype=torch.long, device=dev)
         counts = torch.empty(nnz, dtype=torch.int32, device=dev)
-        check(fn("snx_tfidf_compact_counts")(_p(src), _p(dst), n, _p(s_key), _p(s_count), _p(keys), _p(counts), _stream()),
-              "snx_tfidf_compact_counts")
+        call("snx_tfidf_compact_counts", _p(src), _p(dst), n, _p(s_key), _p(s_count), _p(keys), _p(counts), _stream())
     return cnt, keys, counts
 
 
@@ -141,15 +141,14 @@ def weight_rows(cnt: torch.Tensor, keys: torch.Tensor, counts: torch.Tensor, fea
     p_w = torch.empty(nnz, dtype=torch.float32, device=dev)
     known32 = torch.empty(n, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        check(fn("snx_tfidf_weights")(_p(src), _p(keys), _p(counts), n, _p(feature_keys), _p(idf), F, _p(table),
-                                      max(tmax, 1), _p(p_fid), _p(p_w), _p(known32), _stream()), "snx_tfidf_weights")
+        call("snx_tfidf_weights", _p(src), _p(keys), _p(counts), n, _p(feature_keys), _p(idf), F, _p(table),
+             max(tmax, 1), _p(p_fid), _p(p_w), _p(known32), _stream())
         known = known32.long()
         dst = offsets(known)
         m = int(dst[-1])
         fid = torch.empty(m, dtype=torch.int32, device=dev)
         w = torch.empty(m, dtype=torch.float32, device=dev)
-        check(fn("snx_tfidf_compact_rows")(_p(src), _p(dst), n, _p(p_fid), _p(p_w), _p(fid), _p(w), _stream()),
-              "snx_tfidf_compact_rows")
+        call("snx_tfidf_compact_rows", _p(src), _p(dst), n, _p(p_fid), _p(p_w), _p(fid), _p(w), _stream())
     return known, fid, w
 
 

@@ -24,14 +24,11 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.nn.functional as F
 
-PRECISIONS = {"bf16": 0, "fp32": 1}    # SNX_TEACHER_BF16 / SNX_TEACHER_F32
+from ._abi import CONSTANTS, STRUCTS
+
+PRECISIONS = {"bf16": CONSTANTS["SNX_TEACHER_BF16"], "fp32": CONSTANTS["SNX_TEACHER_F32"]}
 DEFAULT_BATCH_TOKENS = 16384           # token rows per forward of ``encode``
-
-
-class TeacherDesc(C.Structure):
-    _fields_ = [("vocab", C.c_int32), ("hidden", C.c_int32), ("inter", C.c_int32), ("layers", C.c_int32),
-                ("heads", C.c_int32), ("head_dim", C.c_int32), ("max_pos", C.c_int32), ("type_vocab", C.c_int32),
-                ("pad_id", C.c_int32), ("reserved0", C.c_int32), ("ln_eps", C.c_float), ("reserved1", C.c_float)]
+TeacherDesc = STRUCTS["snx_teacher_desc"]
 
 
 @dataclass
@@ -268,7 +265,7 @@ class TeacherEncoder:
         self.params = {k: v.to(self.device).contiguous() for k, v in normalize_state_dict(config, state_dict).items()}
         self._ws: Optional[torch.Tensor] = None
         if self.device.type == "cuda":
-            from ._lib import check, fn
+            from ._lib import call, fn
             self._desc = config.desc()
             keys = param_keys(config)
             n = int(fn("snx_teacher_param_count")(C.byref(self._desc)))
@@ -278,9 +275,8 @@ class TeacherEncoder:
             nbytes = int(fn("snx_teacher_weight_cache_bytes")(C.byref(self._desc)))
             with torch.cuda.device(self.device):
                 self._wcache = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                check(fn("snx_teacher_weight_cache_refresh")(C.byref(self._desc), self._ptrs,
-                                                             C.c_void_p(self._wcache.data_ptr()), self._stream()),
-                      "snx_teacher_weight_cache_refresh")
+                call("snx_teacher_weight_cache_refresh", C.byref(self._desc), self._ptrs,
+                     C.c_void_p(self._wcache.data_ptr()), self._stream())
 
     @staticmethod
     def _stream() -> C.c_void_p:
@@ -313,7 +309,7 @@ class TeacherEncoder:
             cls, emb = forward_torch(self.config, self.params, input_ids, attention_mask,
                                      emulate_bf16=self.precision == "bf16")
             return emb if normalize else cls
-        from ._lib import check, fn
+        from ._lib import call, fn
         ids, mask, pos = _check_batch(self.config, input_ids, attention_mask)
         keep = mask.bool()
         lens = mask.sum(dim=1)
@@ -335,9 +331,8 @@ class TeacherEncoder:
             cls = torch.empty((n, H), dtype=torch.float32, device=dev)
             emb = torch.empty((n, H), dtype=torch.float32, device=dev)
             p = lambda t: C.c_void_p(t.data_ptr())                 # noqa: E731
-            check(fn("snx_teacher_forward")(C.byref(self._desc), self._ptrs, p(self._wcache), p(ids_u), p(pos_u), p(cu),
-                                            p(self._ws), p(cls), p(emb), T, n, max_len, prec, self._stream()),
-                  "snx_teacher_forward")
+            call("snx_teacher_forward", C.byref(self._desc), self._ptrs, p(self._wcache), p(ids_u), p(pos_u), p(cu),
+                 p(self._ws), p(cls), p(emb), T, n, max_len, prec, self._stream())
         return emb if normalize else cls
 
     def encode(self, texts: Sequence[str], tokenizer: Callable, batch_size: Optional[int] = None, max_length: int = 512,
