@@ -950,8 +950,11 @@ int snx_attn_bwd_ex(const void* qkv, const void* out, const void* dout, const fl
 
 /* Tied decoder GEMM + SPLADE tail fused (hf:550 + ref:src/model/splade_modern.py:76-86).  From 2,048 token rows on
  * the 256x192 persistent kernel (csrc/decoder256.hip: it zeroes `keys`, builds its row tables in `scratch` and ends
- * with a finalize pass), below the 128x128 kernel (csrc/splade_head.hip); same outputs, any mask.  `scratch`:
- * snx_splade_head_scratch_bytes(T, V) bytes (T = rows of the whole token buffer). */
+ * with a finalize pass), below the 128x128 kernel (csrc/splade_head.hip); same outputs, any mask: bit for bit
+ * when every partial sum of the K loop is exact in fp32 (tests/splade_fwd_reference.py), else up to the order of the
+ * fp32 accumulation.  keys[b, v] = bf16 bits of the maximum over the valid rows << 16 | 0xFFFF - its first sequence
+ * position; a key whose value bits are 0 (no valid row with a positive logit, a fully masked sequence) is 0x0000FFFF in
+ * both forms.  `scratch`: snx_splade_head_scratch_bytes(T, V) bytes (T = rows of the whole token buffer). */
 size_t snx_splade_head_scratch_bytes(int32_t T, int32_t V);
 int snx_decoder_splade_fwd_ex(const void* Hd, const void* W, const float* bias, const int32_t* cu_seqlens,
                               const int64_t* mask, float* sparse, uint32_t* keys, float* token_weights, void* scratch,

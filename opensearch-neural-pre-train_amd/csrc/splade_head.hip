@@ -138,7 +138,10 @@ __global__ __launch_bounds__(256, 2) void decoder_splade_kernel(
     const int col = n0 + c;
     if (col < V) {
       const uint32_t a = sBest[c], b = sBest[BN + c];
-      const uint32_t k = a > b ? a : b;
+      const uint32_t m = a > b ? a : b;
+      // value 0 (no valid row with a positive logit; a fully masked sequence): one key, 0xFFFF = value 0 at row 0, in
+      // both forms (dec256_finalize_kernel) -- the running maximum leaves 0xFFFF - first valid row, or 0, behind
+      const uint32_t k = (m >> 16) ? m : 0xFFFFu;
       keys[(long)seq * V + col] = k;
       sparse[(long)seq * V + col] = log1pf(bits_to_f32(k >> 16));
     }

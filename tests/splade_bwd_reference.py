@@ -231,7 +231,8 @@ def make_case(lens, V, H, seed, routing="random", tokens=None, coincide=0.3, hd_
       one_row      every term of the sequence routed to one row
       round_robin  term v to row v % length
       counts       rows 0..3 get exactly 63, 64, 65 and 128 entries (columns scattered); every other term has x > 0, g = 0
-      masked       key 0 exactly (what the forward writes for a fully masked sequence), g != 0
+      masked       key 0 exactly (value 0 at row 65,535; the forward writes 0x0000FFFF for a fully masked sequence, and the
+                   backward must ignore any key of value 0), g != 0
       gzero        x > 0 everywhere, g = 0 everywhere
     Active keys carry only rows inside their own sequence.  `tokens`: None (no token direction), "spread" (token t takes
     column perm[t % V]: at most ceil(T / V) tokens per column; a fifth masked with 0xFFFF; in `random` sequences a

@@ -146,7 +146,8 @@ def test_null_token_gradient_is_the_sparse_backward_bit_for_bit(dev, name):
 
 def test_end_to_end_keys_of_the_forward_with_an_irregular_mask(dev):
     """keys and token keys from decoder_splade_fwd (holes, left padding, one valid row, a fully masked sequence: its keys
-    are 0, its token keys 0xFFFF), g and g_tw built from the decoded logits by the exact-coefficient builder"""
+    and its token keys are 0xFFFF, value 0 at row / column 0, as include/snx.h states for both forms of the forward), g and
+    g_tw built from the decoded logits by the exact-coefficient builder"""
     from snx import ops
     B, S, V, K = 6, 64, 1000, 256
     T = B * S
@@ -163,7 +164,7 @@ def test_end_to_end_keys_of_the_forward_with_an_irregular_mask(dev):
     cu = torch.arange(B + 1, dtype=torch.int32) * S
     _, keys, _, tkeys = ops.decoder_splade_fwd_tw(Hd.to(dev), W.to(dev), bias.to(dev), cu.to(dev), mask.reshape(-1).to(dev), S)
     keys, tkeys = keys.cpu(), tkeys.cpu()
-    assert (keys[3] == 0).all() and (tkeys.view(B, S)[3] == 0xFFFF).all()
+    assert (keys[3] == 0xFFFF).all() and (tkeys.view(B, S)[3] == 0xFFFF).all()
     x, _ = R.decode_keys(keys)
     g, _ = R.build_exact_g(x, gen)
     assert (g[3] != 0).sum() > V // 2                       # x = 0 with g != 0, on the key value 0 of the forward
