@@ -536,6 +536,54 @@ int snx_dense_search_band(const float* Q, int32_t nq, const float* E, int32_t nd
 int snx_dense_pair_scores(const float* Q, int32_t nq, const float* E, int32_t nd, int32_t D, const int32_t* pair_q,
                           const int32_t* pair_d, int64_t npairs, float* out, hipStream_t stream);
 
+/* ---- IVF-Flat dense retrieval (csrc/ivf.hip): the approximate index of the reference's dense hard-negative miner, which
+ * builds faiss.IndexIVFFlat over BGE-M3 embeddings and searches it with FAISS's default nprobe
+ * (ref:src/preprocessing/miners/bge_m3_miner.py:91-136, 166-249).  The lists here are this index's own (deterministic
+ * spherical k-means, below), not FAISS's: FAISS's sampling and random generator are not reproduced.
+ * Definition.  s(x, y) is the score of the section above (the fp32 fmaf chain over ascending dimensions from +0, then
+ * + 0.0f), with the same bits.  Given centroids C [nlist, D] (fp32, finite; 1 <= nlist <= 65536):
+ *   list(d) = argmax_c s(E[d], C[c]), ties to the lowest c;
+ *   P(q)    = the nprobe best centroids by s(q, C[c]), ties to the lowest c (1 <= nprobe <= min(nlist, 1024));
+ *   result  = the top k (score descending, ties lowest ORIGINAL doc id first) over {d : list(d) in P(q)}, scores s(q, E[d]);
+ *             unused slots doc -1, score 0;
+ *   band    = ranks lo .. hi-1 of the ADMISSIBLE docs of that set (not in the exclusion row, s < ceiling[q]; the rules of
+ *             snx_dense_search_band), out_found [nq] = filled slots.
+ * Hence nprobe == nlist gives snx_dense_search's result, nprobe < nlist gives snx_dense_search_band's with the docs of the
+ * lists outside P(q) excluded, and every score equals snx_dense_pair_scores'.  No result depends on how the queries are
+ * sliced, on the workspace, on split_docs (how a long list is split over workgroups) or on how the docs arrived.
+ * Both list rules are snx_dense_search over the centroids (k = 1 with the docs as queries; k = nprobe with the queries):
+ * the caller runs it and hands the ids over (doc_list [nd]; probe [nq, nprobe], every entry in [0, nlist), no list twice
+ * in a row).
+ * snx_ivf_build: a stable counting sort of the docs by list -> list_ptr [nlist+1] int64, list_doc [nd] int32 (original
+ * ids, ascending inside a list) and, when E_sorted is not NULL, E_sorted [nd, D] = the rows of E in list order.
+ * workspace: snx_ivf_build_workspace_bytes(nd, nlist) bytes.
+ * snx_ivf_search: lo = 0, hi = k is the plain search (ex_ptr, ceiling, out_found may be NULL).  max_list: an upper bound
+ * of the longest list (the caller reads it once after the build; a smaller value is memory-safe and leaves docs
+ * unscanned).  split_docs: docs per split of a list (0: default; otherwise >= 128, rounded up to a multiple of 128).
+ * workspace: snx_ivf_search_workspace_bytes(nq, nd, nlist, nprobe, hi, max_list, split_docs) bytes; it grows with
+ * nq * nprobe * splits * hi, never with nd.
+ * snx_ivf_kmeans_update: one step of spherical k-means.  list_ptr / list_row: the training rows X [n, D] sorted by their
+ * centroid (snx_ivf_build of the assignment with E_sorted NULL).  For centroid c with members r_0 < r_1 < ... and
+ * dimension j: the float64 sum of X[r, j] in this FIXED order -- members ascending, serially inside segments of 1024
+ * consecutive members (starting from 0.0), the segment sums added in ascending segment order (starting from 0.0); the sum
+ * is divided by the member count in float64; the mean vector is divided, in float64, by the sqrt of its sum of squares
+ * (serial over ascending j from 0.0, each square rounded before it is added); the quotient is rounded to fp32.  A zero
+ * mean stays all zeros; a centroid without members keeps C_prev's row.  No float atomics, no dependence on the launch.
+ * The initial centroids of snx.retrieval.IvfFlatIndex are this update applied to single-member lists of the rows
+ * numpy.random.RandomState(seed).permutation(n)[:nlist]. */
+size_t snx_ivf_build_workspace_bytes(int32_t nd, int32_t nlist);
+int snx_ivf_build(const int32_t* doc_list, int32_t nd, int32_t nlist, const float* E, int32_t D, int64_t* list_ptr,
+                  int32_t* list_doc, float* E_sorted, void* workspace, size_t ws_bytes, hipStream_t stream);
+int snx_ivf_kmeans_update(const float* X, int32_t n, int32_t D, const int64_t* list_ptr, const int32_t* list_row,
+                          int32_t nlist, const float* C_prev, float* C_out, hipStream_t stream);
+size_t snx_ivf_search_workspace_bytes(int32_t nq, int32_t nd, int32_t nlist, int32_t nprobe, int32_t hi, int32_t max_list,
+                                      int32_t split_docs);
+int snx_ivf_search(const float* Q, int32_t nq, int32_t D, const float* E_sorted, const int64_t* list_ptr,
+                   const int32_t* list_doc, int32_t nd, int32_t nlist, int32_t max_list, const int32_t* probe,
+                   int32_t nprobe, const int64_t* ex_ptr, const int32_t* ex_doc, const float* ceiling, int32_t lo,
+                   int32_t hi, int32_t split_docs, int32_t* out_doc, float* out_score, int32_t* out_found, void* workspace,
+                   size_t ws_bytes, hipStream_t stream);
+
 /* ---- MinHash near-duplicate removal (csrc/minhash.hip): the reference's MinHashDeduplicator
  * (ref:src/preprocessing/cleaners/deduplicator.py:10-187), whose two Python loops -- num_perm MD5 digests per character
  * n-gram (ref:deduplicator.py:71-80) and every new row against every kept row (ref:deduplicator.py:135-138) -- keep the

@@ -46,6 +46,9 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     # and for the dense search: 64 accumulator registers, the prefetched operands and the merge's sort buffer stay out of
     # memory; dn_pair_kernel holds no LDS and is not listed
     "dense.hip": ("dn_search_kernel", "dn_merge_kernel"),
+    # and for the IVF-Flat fine scan and merge, which hold the same state; the sort, row-copy and k-means kernels keep
+    # nothing that could spill and are not listed
+    "ivf.hip": ("iv_scan_kernel", "iv_merge_kernel"),
     # and for MinHash: the MD5 block and the 128-bit minimum, the 32 match counters, and the resolving wave's kept bits stay
     # in registers; the stage, append and first-match kernels hold no LDS and are not listed
     "minhash.hip": ("mh_sig_kernel", "mh_match_kernel", "mh_resolve_kernel"),

@@ -20,11 +20,14 @@ searchers (csrc/hybrid.hip, include/snx.h "BM25 baseline and rank fusion").  ``r
 several relevant docs per query (csrc/qrels.hip, include/snx.h "relevance judgments").  ``DenseIndex`` is the exact
 inner-product search over dense fp32 embeddings (csrc/dense.hip, include/snx.h "exact dense retrieval").  ``TfidfIndex`` is
 the character n-gram TF-IDF vectorizer of the reference's lexical hard-negative mining over a ``SparseIndex``
-(csrc/tfidf.hip, include/snx.h "Character n-gram TF-IDF")."""
+(csrc/tfidf.hip, include/snx.h "Character n-gram TF-IDF").  ``IvfFlatIndex`` is the approximate IVF-Flat search over the
+same dense embeddings, with ``DenseIndex``'s scores and order inside the probed lists (csrc/ivf.hip, include/snx.h
+"IVF-Flat dense retrieval")."""
 from ._common import K_MAX, exclusion_csr
 from .dense import DENSE_CHUNK_MIN, DENSE_DIM_MAX, DenseIndex
 from .hybrid import (FUSE_L_MAX, FUSE_METHODS, FUSE_TOP_K_MAX, Bm25Index, bm25_idf, fuse_ranked, term_counts,
                      term_counts_max_len)
+from .ivf import IVF_NLIST_MAX, IVF_SPLIT_MIN, IvfFlatIndex
 from .qrels import (BOOTSTRAP_M_MAX, BOOTSTRAP_SEGMENT, CUTOFFS_MAX, RANKED_R_MAX, bootstrap_indices, bootstrap_means,
                     discount_table, ranked_relevance, relevance_csr)
 from .seismic import SEISMIC_Q_MAX, SeismicIndex

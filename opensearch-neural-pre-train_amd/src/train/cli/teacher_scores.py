@@ -6,13 +6,16 @@
     python -m src.train.cli.teacher_scores score --embeddings cache/embeddings.npy --text-index cache/text_index.json \\
         --input-pattern "data/v29.0/train_*.jsonl" --output-dir data/v29.0_kd
     python -m src.train.cli.teacher_scores mine --embeddings cache/embeddings.npy --text-index cache/text_index.json \\
-        --input-pattern "data/v29.0_kd/train_*.jsonl" --output-dir data/v30.0_multi_neg --k 7 --rank-start 10 --rank-end 50
+        --input-pattern "data/v29.0_kd/train_*.jsonl" --output-dir data/v30.0_multi_neg --k 7 --rank-start 10 --rank-end 50 \\
+        [--index flat|ivf --nlist 100 --nprobe 1]
 
 ``encode`` is the encoder of ref:scripts/precompute_teacher_scores.py:49-159 (unique texts in first-occurrence order, BGE-M3
 dense embeddings, L2-normalised) on the native XLM-RoBERTa forward; it writes ``embeddings.npy`` / ``text_index.json``.  A
 sharded run (one process per GPU, ``--num-shards n --shard-index i``) writes ``embeddings.part{i}.npy`` and ``--merge`` joins
 them.  ``score`` is the rest of that script (it reads the cache); ``mine`` is ref:scripts/mine_multi_negatives.py.  Flags
-shared with those scripts keep their names and defaults.  Every subcommand runs as a single process."""
+shared with those scripts keep their names and defaults.  ``mine --index ivf`` searches an ``snx.retrieval.IvfFlatIndex``
+(``--nlist`` lists trained on the corpus rows, ``--nprobe`` of them read per query) instead of every doc; ``--nprobe`` equal
+to the list count writes the files of ``--index flat``.  Every subcommand runs as a single process."""
 from __future__ import annotations
 
 import argparse
@@ -42,6 +45,9 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             sp.add_argument("--sample", choices=("first", "random"), default="first")
             sp.add_argument("--seed", type=int, default=42)
             sp.add_argument("--chunk-docs", type=int, default=0)
+            sp.add_argument("--index", choices=("flat", "ivf"), default="flat", help="exact search, or IVF-Flat")
+            sp.add_argument("--nlist", type=int, default=100, help="IVF lists (clamped to the doc count)")
+            sp.add_argument("--nprobe", type=int, default=1, help="IVF lists read per query")
     sp = sub.add_parser("encode", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     sp.add_argument("--model-dir", type=str, default=None, help="local HF directory of the teacher (never a model name)")
     sp.add_argument("--input-pattern", type=str, default="data/v29.0/train_*.jsonl")
@@ -61,6 +67,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             ap.error("need --num-shards >= 1, 0 <= --shard-index < --num-shards, --max-length >= 1, --batch-tokens >= 1")
     if args.command == "mine" and (args.k < 1 or not 0 <= args.rank_start < args.rank_end <= 1024):
         ap.error("need --k >= 1 and 0 <= --rank-start < --rank-end <= 1024")
+    if args.command == "mine" and not 1 <= args.nprobe <= args.nlist:
+        ap.error("need 1 <= --nprobe <= --nlist")
     return args
 
 
@@ -91,14 +99,17 @@ def main(argv: Optional[List[str]] = None, tokenizer=None):
     if args.command == "encode":
         return encode_main(args, tokenizer)
     import torch
-    from snx.retrieval import DenseIndex
+    from snx.retrieval import DenseIndex, IvfFlatIndex
     from src.train.mining import copy_val_files, expand_files
     from src.train.mining.dense import load_teacher_cache, mine_dense_negatives, write_teacher_scores
     files = expand_files([args.input_pattern])
     if not files:
         raise FileNotFoundError(f"no input files match {args.input_pattern!r}")
     embeddings, text_to_idx = load_teacher_cache(args.embeddings, args.text_index)
-    index = DenseIndex(int(embeddings.shape[1]), torch.device(args.device))
+    if args.command == "mine" and args.index == "ivf":
+        index = IvfFlatIndex(int(embeddings.shape[1]), args.nlist, torch.device(args.device), nprobe=args.nprobe)
+    else:
+        index = DenseIndex(int(embeddings.shape[1]), torch.device(args.device))
     if args.command == "score":
         out = write_teacher_scores(files, args.output_dir, embeddings, text_to_idx, index)
         logger.info(f"scored {out} record(s) of {len(files)} file(s) into {args.output_dir}")
