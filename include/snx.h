@@ -669,6 +669,50 @@ int snx_tfidf_compact_counts(const int64_t* src_ptr, const int64_t* dst_ptr, int
 int snx_tfidf_compact_rows(const int64_t* src_ptr, const int64_t* dst_ptr, int32_t n, const int32_t* src_fid,
                            const float* src_w, int32_t* dst_fid, float* dst_w, hipStream_t stream);
 
+/* ---- WordPiece tokenizer (csrc/wordpiece.hip): the tokenizer the model ships (ref:huggingface/v33/tokenizer.json:
+ * normalizer NFC, BertPreTokenizer, WordPiece, template "<s> $A </s>"), from code points to token ids.  Everything here is
+ * integer work and every result equals the `tokenizers` library's bit for bit.  Rows are a CSR of Unicode code points as
+ * for the MinHash section, ptr [n+1] int64 and code_points int32, NOT lowered and NOT stripped, already in NFC (the host
+ * normalizes; the device knows no normalization); a value outside [0, 0x10FFFF] is read as a word character.
+ * Pre-tokenizer: class [0x110000] uint8 is the host's table over all code points, 0 = word character, 1 = White_Space
+ * (ends the current word and is dropped), 2 = punctuation (ends the current word and is a word of its own).
+ * WordPiece: a word of more than max_word code points is the single id unk_id.  Otherwise at offset st the ends
+ * min(len, st + max_entry) .. st + 1 are tried in that order, a candidate at st > 0 as a continuation entry; the first hit
+ * emits its id and moves st behind it; an offset without a hit makes the WHOLE word the single id unk_id.
+ * Vocabulary: E entries, entry e = (ent_cont[e] in {0, 1}: continuation entry; its code points
+ * ent_cps[ent_ptr[e] .. ent_ptr[e+1]), the continuation prefix left out; ent_id[e]); ent_ptr [E+1], ent_cont [E],
+ * ent_id [E], ent_cps: int32.  slots [n_slots] int32, n_slots a power of two >= E: an open-addressed table of entry
+ * numbers, -1 = free.  The hash of (cont, c_0 .. c_{L-1}), all arithmetic modulo 2^32: h = 0; h = h * 0x9E3779B1 + (c_i + 1)
+ * for each code point; x = h ^ (cont ? 0x85EBCA6B : 0) ^ L * 0xC2B2AE35; x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15;
+ * x *= 0x846CA68B; x ^= x >> 16; the home slot is x & (n_slots - 1), a collision goes on to the next slot (linear probing,
+ * wrapping).  A lookup compares cont, L and the stored code points; the hash only chooses where to start.  The prefix
+ * hashes of a word are computed once, so a candidate's hash is two reads and a multiplication.  1 <= max_entry <= max_word
+ * <= 128, otherwise SNX_E_SHAPE.
+ * Pass 1, snx_wp_pieces: one workgroup per row, a thread per code point, the thread on a word's first code point walks its
+ * word.  pieces [ptr[n]] int32 (caller-owned): the id of the piece that STARTS at a code point, -1 where none does (the
+ * unk of a word stands on its first code point) -- pieces in text order are pieces in row order, no atomic decides a
+ * place.  out_cnt [n] int64: min(pieces of the row, max_pieces) + 2, the length of the framed row; max_pieces < 0: no
+ * limit (max_length m is max_pieces = m - 2).  A row of at most 4096 code points has its code points and prefix hashes in
+ * LDS; a longer row goes through the workspace by the same code and gives the same result.  longest_row [host]: an upper
+ * bound of the row lengths (a row beyond it comes out as bos, eos).  workspace: snx_wp_workspace_bytes(longest_row)
+ * bytes, 0 when every row fits the LDS form.
+ * Pass 2, snx_wp_fill: out_ptr [n+1] int64 = 0 and the running sums of out_cnt (the caller's scan; out_ptr[n] is the one
+ * number the host reads, to size out_ids).  Row r of out_ids (int64) becomes bos_id, its first out_ptr[r+1] - out_ptr[r]
+ * - 2 pieces, eos_id.  A row whose out_ptr span is larger than its pieces + 2 (the caller raised out_cnt) keeps the places
+ * between unwritten: the Python layer puts the rows it tokenized itself there.
+ * Padding, snx_wp_pad: input_ids [n, L] int64 = row r of out_ids, then pad_id; attention_mask [n, L] int64 = 1 on the row,
+ * 0 behind it; a row longer than L is cut at L.  Stream-ordered, nothing allocated, no host synchronisation. */
+size_t snx_wp_workspace_bytes(int64_t longest_row);
+int snx_wp_pieces(const int64_t* ptr, const int32_t* code_points, int32_t n, int64_t longest_row, const uint8_t* cls,
+                  const int32_t* slots, int32_t n_slots, const int32_t* ent_ptr, const int32_t* ent_cps,
+                  const int32_t* ent_cont, const int32_t* ent_id, int32_t n_entries, int32_t max_entry, int32_t max_word,
+                  int32_t unk_id, int64_t max_pieces, int32_t* pieces, int64_t* out_cnt, void* workspace, size_t ws_bytes,
+                  hipStream_t stream);
+int snx_wp_fill(const int64_t* ptr, const int32_t* pieces, int32_t n, const int64_t* out_ptr, int32_t bos_id,
+                int32_t eos_id, int64_t* out_ids, hipStream_t stream);
+int snx_wp_pad(const int64_t* out_ptr, const int64_t* out_ids, int32_t n, int64_t L, int64_t pad_id, int64_t* input_ids,
+               int64_t* attention_mask, hipStream_t stream);
+
 /* ---- Co-occurrence and PMI (csrc/cooc.hip): the reference's src/pmi package -- windowed co-occurrence counts
  * (ref:src/pmi/cooccurrence.py:206-226) and PMI with Laplace and context-distribution smoothing
  * (ref:src/pmi/pmi_calculator.py:142-193).  Input is token ids, never text: rows as a CSR, ptr [n_rows+1] int64, ids int32

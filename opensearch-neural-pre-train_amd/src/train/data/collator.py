@@ -3,8 +3,9 @@ ref:src/train/cli/train_v33_ddp.py:44 from a module that is absent from the refe
 
 Offline rules: a local directory is loaded with ``transformers.AutoTokenizer`` (e.g. an export
 like ref:huggingface/v33/ with its BertTokenizer files); the pseudo-name ``hash:<vocab>`` gives
-the deterministic whitespace-hash tokenizer used for synthetic runs; a hub NAME cannot be
-resolved without a network and raises."""
+the deterministic whitespace-hash tokenizer used for synthetic runs; ``gpu:DIR`` gives the native
+WordPiece tokenizer of ``DIR/tokenizer.json`` on the GPU (snx.wordpiece) and ``wordpiece:DIR`` the same
+class on the host; a hub NAME cannot be resolved without a network and raises."""
 from __future__ import annotations
 
 import os
@@ -60,6 +61,10 @@ class HashTokenizer:
 def create_tokenizer(name: str):
     if isinstance(name, str) and name.startswith("hash:"):
         return HashTokenizer(int(name.split(":")[1]))
+    if isinstance(name, str) and name.startswith(("gpu:", "wordpiece:")):
+        from snx.wordpiece import WordPieceTokenizer
+        kind, path = name.split(":", 1)
+        return WordPieceTokenizer.from_pretrained(path, device="cuda" if kind == "gpu" else "cpu")
     if os.path.isdir(name):
         if os.path.exists(os.path.join(name, "hash_tokenizer.json")):
             import json
