@@ -37,34 +37,14 @@ constexpr int L2_GPITCH = 33;
 constexpr unsigned long long L2_NONE = ~0ull;  // key of an empty slot: above every distance (+inf is 0x7FF0...)
 constexpr uint32_t L2_NOID = 0xFFFFFFFFu;
 
-struct L2Plan {
-  int qtiles, split_tiles, nsplit, cap;
-  long tiles;
-};
-
-inline L2Plan l2_plan(int32_t nq, int32_t n, int32_t k, int32_t chunk_rows) {
-  L2Plan p;
-  p.qtiles = (int)((nq + (long)L2_TILE - 1) / L2_TILE);
-  p.tiles = (n + (long)L2_TILE - 1) / L2_TILE;
-  if (chunk_rows > 0) {
-    p.split_tiles = (int)((chunk_rows + (long)L2_TILE - 1) / L2_TILE);
-  } else {
-    long want = (L2_WG_TARGET + (long)p.qtiles - 1) / (p.qtiles > 0 ? p.qtiles : 1);
-    if (want > L2_SPLITS_MAX) want = L2_SPLITS_MAX;
-    if (want > p.tiles) want = p.tiles;
-    if (want < 1) want = 1;
-    p.split_tiles = (int)((p.tiles + want - 1) / want);
-  }
-  if (p.split_tiles < 1) p.split_tiles = 1;
-  const long ns = (p.tiles + p.split_tiles - 1) / p.split_tiles;
-  p.nsplit = (int)(ns < 1 ? 1 : (ns > 0x7FFFFFFFL ? 0x7FFFFFFFL : ns));
-  p.cap = (int)pow2_at_least((long)(2 * k > 2 * L2_TILE ? 2 * k : 2 * L2_TILE));
-  return p;
+inline SplitPlan l2_plan(int32_t nq, int32_t n, int32_t chunk_rows) {
+  return split_plan(nq, n, chunk_rows, L2_TILE, L2_WG_TARGET, L2_SPLITS_MAX);
 }
+inline int l2_cap(int32_t k) { return (int)pow2_at_least((long)(2 * k > 2 * L2_TILE ? 2 * k : 2 * L2_TILE)); }
 
-inline size_t l2_workspace(int32_t nq, const L2Plan& p) {
-  const size_t lists = (size_t)nq * (size_t)p.nsplit;
-  return align256(lists * (size_t)p.cap * 8) + align256(lists * (size_t)p.cap * 4) + align256(lists * 4);
+inline size_t l2_workspace(int32_t nq, int nsplit, int cap) {
+  const size_t lists = (size_t)nq * (size_t)nsplit;
+  return align256(lists * (size_t)cap * 8) + align256(lists * (size_t)cap * 4) + align256(lists * 4);
 }
 
 __device__ __forceinline__ unsigned long long dbits(double x) { return __builtin_bit_cast(unsigned long long, x); }
@@ -338,7 +318,7 @@ inline int l2_vec(const float* A, const float* B, int32_t D) {
 
 extern "C" size_t snx_l2_knn_workspace_bytes(int32_t nq, int32_t n, int32_t k, int32_t chunk_rows) {
   if (nq <= 0 || n < 0 || k <= 0 || k > SNX_L2_KMAX || chunk_rows < 0) return 0;
-  return l2_workspace(nq, l2_plan(nq, n, k, chunk_rows));
+  return l2_workspace(nq, l2_plan(nq, n, chunk_rows).nsplit, l2_cap(k));
 }
 
 extern "C" int snx_l2_knn(const float* Q, int32_t nq, const float* E, int32_t n, int32_t D, int32_t k, int32_t chunk_rows,
@@ -346,20 +326,21 @@ extern "C" int snx_l2_knn(const float* Q, int32_t nq, const float* E, int32_t n,
   if (nq < 0 || n < 0 || D < 1 || D > L2_DMAX || k < 1 || k > SNX_L2_KMAX || chunk_rows < 0) return SNX_E_SHAPE;
   if (nq == 0) return SNX_OK;
   if (!Q || (n > 0 && !E) || !out_id || !out_d2) return SNX_E_ARG;
-  const L2Plan p = l2_plan(nq, n, k, chunk_rows);
+  const SplitPlan p = l2_plan(nq, n, chunk_rows);
+  const int cap = l2_cap(k);
   const long blocks = (long)p.qtiles * p.nsplit;
   if (blocks > 0x7FFFFFFFL || (long)nq * p.nsplit > 0x7FFFFFFFL) return SNX_E_SHAPE;
-  if (!workspace || ws_bytes < l2_workspace(nq, p)) return SNX_E_ARG;
+  if (!workspace || ws_bytes < l2_workspace(nq, p.nsplit, cap)) return SNX_E_ARG;
   const size_t lists = (size_t)nq * (size_t)p.nsplit;
   char* w = (char*)workspace;
   unsigned long long* candk = (unsigned long long*)w;
-  uint32_t* candi = (uint32_t*)(w + align256(lists * (size_t)p.cap * 8));
-  int32_t* ccount = (int32_t*)((char*)candi + align256(lists * (size_t)p.cap * 4));
+  uint32_t* candi = (uint32_t*)(w + align256(lists * (size_t)cap * 8));
+  int32_t* ccount = (int32_t*)((char*)candi + align256(lists * (size_t)cap * 4));
   hipLaunchKernelGGL(l2_search_kernel, dim3((unsigned)blocks), dim3(L2_THREADS), 0, st, Q, nq, E, n, D, l2_vec(Q, E, D),
-                     p.qtiles, p.split_tiles, p.nsplit, k, p.cap, candk, candi, ccount);
+                     p.qtiles, p.split_tiles, p.nsplit, k, cap, candk, candi, ccount);
   SNX_CHECK_LAUNCH();
   hipLaunchKernelGGL(l2_merge_kernel, dim3((unsigned)nq), dim3(L2_THREADS), 0, st, (const unsigned long long*)candk,
-                     (const uint32_t*)candi, (const int32_t*)ccount, p.nsplit, p.cap, k, out_id, out_d2);
+                     (const uint32_t*)candi, (const int32_t*)ccount, p.nsplit, cap, k, out_id, out_d2);
   SNX_CHECK_LAUNCH();
   return SNX_OK;
 }

@@ -11,33 +11,28 @@
 // counts, per list, query tiles x doc splits and scans that into tile_ptr; iv_scan_kernel is launched with an upper bound
 // of workgroups, each finds its list by binary search in tile_ptr and leaves when there is none, so the host never reads
 // a count.  A workgroup owns up to 128 gathered query rows of one list and one split of the list's docs and walks the split
-// in 128-doc tiles with the 128x128x16 fp32 MFMA loop of dense.hip.  Every score goes through the pair's running
-// threshold into the candidate list of its (pair, split), `cap` entries of (order key << 32 | ~original doc); a list that
-// the next tile could overflow is sorted and cut to k.  Original ids ascend along a list and so along a split: inside one
-// candidate list a later doc that only ties the threshold loses, and `key > threshold` is exact.  That does NOT hold
-// across lists, so every (pair, split) keeps its own candidate list and its own threshold, and iv_merge_kernel selects
-// over a query's nprobe x splits lists by the full 64-bit key: radix_select on the score key, then, when the k-th score
-// is tied, a second radix_select on ~doc among the ties (dn_merge_kernel's "first need_eq in index order" would be wrong
-// here: index order is not doc order across lists).  The band's exclusion rows (binary search by original id) and
-// ceiling are applied in the scan kernel, as in dn_search_kernel.
+// in 128-doc tiles with the 128x128x16 fp32 MFMA loop that dense_common.h holds for this file and dense.hip, together with
+// the order key, the admission of a score, the list compaction and the merge's output tail.  Every score goes through the
+// pair's running threshold into the candidate list of its (pair, split), `cap` entries of (order key << 32 | ~original
+// doc); a list that the next tile could overflow is sorted and cut to k.  Original ids ascend along a list and so along
+// a split: inside one candidate list a later doc that only ties the threshold loses, and `key > threshold` is exact.
+// That does NOT hold across lists, so every (pair, split) keeps its own candidate list and its own threshold, and
+// iv_merge_kernel selects over a query's nprobe x splits lists by the full 64-bit key: radix_select on the score key,
+// then, when the k-th score is tied, a second radix_select on ~doc among the ties (dn_merge_kernel's "first need_eq in
+// index order" would be wrong here: index order is not doc order across lists).  The band's exclusion rows (binary
+// search by original id) and ceiling are applied in the scan kernel, as in dn_search_kernel.
 //
 // k-means update: one workgroup per centroid, one thread per dimension (coalesced over j), float64, in the fixed order of
 // the header: members ascending, serial inside segments of 1024 members, segment sums added in ascending order; no float
 // atomics, no dependence on the launch geometry.  fp contraction is off in that kernel: the numpy reference adds and
 // multiplies separately.
-#include "sparse_common.h"
+#include "dense_common.h"
 #include "snx.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-constexpr int IV_THREADS = 256;
-constexpr int IV_TILE = 128;                   // gathered query rows and doc rows of a workgroup's tile
-constexpr int IV_KT = 16;                      // K per LDS stage
-constexpr int IV_PITCH = 132;                  // LDS row pitch (floats), as dense.hip
-constexpr int IV_CAP_MAX = 2048;               // candidate list entries for k = 1024
-constexpr int IV_DMAX = 4096;
+constexpr int IV_THREADS = 256;                // the sort, row-copy and k-means kernels; the scan's are DN_THREADS
+constexpr int IV_DMAX = DN_DMAX;               // the k-means kernel keeps a row of doubles in LDS
 constexpr int IV_NLIST_MAX = 65536;
 constexpr int IV_SEGS_MAX = 256;               // segments of the counting sort (one workgroup each)
 constexpr int IV_CHUNK = 256;                  // rows ranked at once inside a segment
@@ -237,10 +232,10 @@ struct IvPlan {
 
 inline IvPlan iv_plan(int32_t nq, int32_t nlist, int32_t nprobe, int32_t hi, int32_t max_list, int32_t split_docs) {
   IvPlan p;
-  const long max_tiles = (max_list + (long)IV_TILE - 1) / IV_TILE;
+  const long max_tiles = (max_list + (long)DN_TILE - 1) / DN_TILE;
   long st;
   if (split_docs > 0) {
-    st = (split_docs + (long)IV_TILE - 1) / IV_TILE;
+    st = (split_docs + (long)DN_TILE - 1) / DN_TILE;
   } else {
     st = (max_tiles + IV_SPLITS_MAX - 1) / IV_SPLITS_MAX;
     if (st < IV_SPLIT_TILES_MIN) st = IV_SPLIT_TILES_MIN;
@@ -251,10 +246,10 @@ inline IvPlan iv_plan(int32_t nq, int32_t nlist, int32_t nprobe, int32_t hi, int
   if (smax < 1) smax = 1;
   p.split_tiles = (int)st;
   p.smax = (int)(smax > 0x7FFFFFFFL ? 0x7FFFFFFFL : smax);
-  p.cap = (int)pow2_at_least((long)(2 * hi > 512 ? 2 * hi : 512));
+  p.cap = dn_cap(hi);
   p.pairs = (long)nq * nprobe;
   // sum over the lists of ceil(pairs of the list / 128) is at most pairs / 128 + lists that hold a pair
-  p.blocks = (p.pairs / IV_TILE + (p.pairs < nlist ? p.pairs : (long)nlist)) * smax;
+  p.blocks = (p.pairs / DN_TILE + (p.pairs < nlist ? p.pairs : (long)nlist)) * smax;
   return p;
 }
 
@@ -280,7 +275,7 @@ inline bool iv_search_shape_ok(int32_t nq, int32_t nd, int32_t nlist, int32_t np
                                int32_t split_docs) {
   return nq >= 0 && nd >= 0 && nlist >= 1 && nlist <= IV_NLIST_MAX && nprobe >= 1 && nprobe <= nlist &&
          nprobe <= SR_KMAX && hi >= 1 && hi <= SR_KMAX && max_list >= 0 && max_list <= nd && split_docs >= 0 &&
-         (split_docs == 0 || split_docs >= IV_TILE);
+         (split_docs == 0 || split_docs >= DN_TILE);
 }
 
 // tile_ptr[c] = workgroups of the lists in front of c: query tiles x doc splits of every list that holds both
@@ -290,7 +285,7 @@ __global__ __launch_bounds__(IV_SCAN_THREADS) void iv_tiles_kernel(const int64_t
   __shared__ int64_t part[IV_SCAN_THREADS];
   for (int c = threadIdx.x; c < nlist; c += IV_SCAN_THREADS) {
     const int64_t np = pair_ptr[c + 1] - pair_ptr[c], len = list_ptr[c + 1] - list_ptr[c];
-    const int64_t qt = (np + IV_TILE - 1) / IV_TILE, dt = (len + IV_TILE - 1) / IV_TILE;
+    const int64_t qt = (np + DN_TILE - 1) / DN_TILE, dt = (len + DN_TILE - 1) / DN_TILE;
     int64_t ns = (dt + split_tiles - 1) / split_tiles;
     if (ns > smax) ns = smax;                                // max_list below the longest list: no slot past the workspace
     tile_ptr[c + 1] = np > 0 && len > 0 ? qt * ns : 0;
@@ -300,71 +295,17 @@ __global__ __launch_bounds__(IV_SCAN_THREADS) void iv_tiles_kernel(const int64_t
   iv_block_scan(tile_ptr + 1, nlist, part);
 }
 
-// monotone map fp32 -> uint32 (larger float, larger key) and back, as dense.hip
-__device__ __forceinline__ uint32_t iv_key(float s) {
-  const uint32_t b = fbits(s);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float iv_unkey(uint32_t key) {
-  return bitsf((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-}
-
-// this thread's share of a 128 x 16 operand tile: tile rows r and r + 64, 4 k each.  Docs: rows row0 .. of the list-ordered
-// matrix, rows from `end` on read as zero.  Queries: row r is query qrow[r] (-1: zero).  k past D reads as zero.
-__device__ __forceinline__ void iv_fetch_docs(const float* __restrict__ P, long end, long row0, int D, int k0, int vec,
-                                              int t, float (&v)[8]) {
-  const int kk = k0 + (t & 3) * 4;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const long row = row0 + (t >> 2) + 64 * i;
-    if (row < end && vec && kk < D) {
-      const f32x4 x = *(const f32x4*)(P + row * D + kk);
-      v[4 * i] = x[0]; v[4 * i + 1] = x[1]; v[4 * i + 2] = x[2]; v[4 * i + 3] = x[3];
-    } else {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[4 * i + u] = (row < end && kk + u < D) ? P[row * D + kk + u] : 0.f;
-    }
-  }
-}
-__device__ __forceinline__ void iv_fetch_queries(const float* __restrict__ Q, const int* qrow, int D, int k0, int vec,
-                                                 int t, float (&v)[8]) {
-  const int kk = k0 + (t & 3) * 4;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int q = qrow[(t >> 2) + 64 * i];
-    if (q >= 0 && vec && kk < D) {
-      const f32x4 x = *(const f32x4*)(Q + (long)q * D + kk);
-      v[4 * i] = x[0]; v[4 * i + 1] = x[1]; v[4 * i + 2] = x[2]; v[4 * i + 3] = x[3];
-    } else {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[4 * i + u] = (q >= 0 && kk + u < D) ? Q[(long)q * D + kk + u] : 0.f;
-    }
-  }
-}
-__device__ __forceinline__ void iv_put(int t, const float (&v)[8], float (*S)[IV_PITCH]) {
-  const int kk = (t & 3) * 4;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int r = (t >> 2) + 64 * i;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) S[kk + u][r] = v[4 * i + u];
-  }
-}
-
-__global__ __launch_bounds__(IV_THREADS, 2) void iv_scan_kernel(
+__global__ __launch_bounds__(DN_THREADS, 2) void iv_scan_kernel(
     const float* __restrict__ Q, int32_t nq, int32_t D, int32_t vecq, int32_t vece, const float* __restrict__ Es,
     const int64_t* __restrict__ list_ptr, const int32_t* __restrict__ list_doc, int32_t nlist,
     const int64_t* __restrict__ pair_ptr, const int32_t* __restrict__ pair_order, const int64_t* __restrict__ tile_ptr,
     int32_t nprobe, int32_t split_tiles, int32_t smax, int32_t k, int32_t cap, const int64_t* __restrict__ ex_ptr,
     const int32_t* __restrict__ ex_doc, const float* __restrict__ ceiling, unsigned long long* cand,
     int32_t* __restrict__ ccount) {
-  __shared__ __attribute__((aligned(16))) float As[2][IV_KT][IV_PITCH];
-  __shared__ __attribute__((aligned(16))) float Bs[2][IV_KT][IV_PITCH];
-  __shared__ unsigned long long sbuf[IV_CAP_MAX];
-  __shared__ int64_t exa[IV_TILE], exb[IV_TILE], slot[IV_TILE];
-  __shared__ uint32_t thr[IV_TILE];
-  __shared__ int cnt[IV_TILE], qrow[IV_TILE];
-  __shared__ float ceilv[IV_TILE];
+  __shared__ int64_t exa[DN_TILE], exb[DN_TILE], slot[DN_TILE];
+  __shared__ uint32_t thr[DN_TILE];
+  __shared__ int cnt[DN_TILE], qrow[DN_TILE];
+  __shared__ float ceilv[DN_TILE];
   __shared__ int s_list;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wm = wave >> 1, wn = wave & 1, c = lane & 31, h = lane >> 5;
@@ -386,15 +327,15 @@ __global__ __launch_bounds__(IV_THREADS, 2) void iv_scan_kernel(
   if (l < 0) return;                                         // the launch is an upper bound
   const int64_t local = wg - tile_ptr[l];
   const int64_t np = pair_ptr[l + 1] - pair_ptr[l];
-  const int64_t qt = (np + IV_TILE - 1) / IV_TILE;
+  const int64_t qt = (np + DN_TILE - 1) / DN_TILE;
   const int64_t qtile = local % qt;
   const int split = (int)(local / qt);
-  const int64_t r0 = pair_ptr[l] + qtile * IV_TILE;
-  const int m = (int)min((int64_t)IV_TILE, np - qtile * IV_TILE);
-  const int64_t p0 = list_ptr[l] + (int64_t)split * split_tiles * IV_TILE;
-  const int64_t p1 = min(list_ptr[l + 1], p0 + (int64_t)split_tiles * IV_TILE);
+  const int64_t r0 = pair_ptr[l] + qtile * DN_TILE;
+  const int m = (int)min((int64_t)DN_TILE, np - qtile * DN_TILE);
+  const int64_t p0 = list_ptr[l] + (int64_t)split * split_tiles * DN_TILE;
+  const int64_t p1 = min(list_ptr[l + 1], p0 + (int64_t)split_tiles * DN_TILE);
   const bool has_c = ceiling != nullptr, has_x = ex_ptr != nullptr;
-  if (t < IV_TILE) {
+  if (t < DN_TILE) {
     const int pair = t < m ? pair_order[r0 + t] : -1;
     const bool ok = pair >= 0 && pair / nprobe < nq && split < smax;
     const int q = ok ? pair / nprobe : -1;
@@ -407,59 +348,14 @@ __global__ __launch_bounds__(IV_THREADS, 2) void iv_scan_kernel(
     exb[t] = has_x && ok ? ex_ptr[q + 1] : 0;
   }
   __syncthreads();
-  const int nk = (D + IV_KT - 1) / IV_KT;
+  auto list = [&](int row) { return cand + (size_t)slot[row] * (size_t)cap; };
+  auto compact = [&](int row) { dn_compact(list(row), cnt[row], thr[row], k, cap); };
+  auto query = [&](int r) -> long { return qrow[r]; };
 
-  // sort the list of `row`, keep the best k, raise its threshold
-  auto compact = [&](int row) {
-    const int n = cnt[row];
-    unsigned long long* b = cand + (size_t)slot[row] * (size_t)cap;
-    for (int i = t; i < cap; i += IV_THREADS) sbuf[i] = i < n ? b[i] : 0ull;
-    __syncthreads();
-    bitonic_desc<IV_THREADS, int>(sbuf, cap);
-    const int keep = min(n, k);
-    for (int i = t; i < keep; i += IV_THREADS) b[i] = sbuf[i];
-    if (t == 0) {
-      cnt[row] = keep;
-      if (n >= k) thr[row] = rank_bits(sbuf[k - 1]);
-    }
-    __syncthreads();
-  };
-
-  for (int64_t n0 = p0; n0 < p1; n0 += IV_TILE) {
+  for (int64_t n0 = p0; n0 < p1; n0 += DN_TILE) {
+    auto drow = [&](int r) -> long { return n0 + r < p1 ? n0 + r : -1; };   // rows of the list-ordered matrix
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    float va[8], vb[8];
-    iv_fetch_queries(Q, qrow, D, 0, vecq, t, va);
-    iv_fetch_docs(Es, p1, n0, D, 0, vece, t, vb);
-    iv_put(t, va, As[0]);
-    iv_put(t, vb, Bs[0]);
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      if (kt + 1 < nk) {
-        iv_fetch_queries(Q, qrow, D, (kt + 1) * IV_KT, vecq, t, va);
-        iv_fetch_docs(Es, p1, n0, D, (kt + 1) * IV_KT, vece, t, vb);
-      }
-#pragma unroll
-      for (int s = 0; s < IV_KT / 2; ++s) {                  // k ascending: the ABI's chain
-        const float a0 = As[cur][2 * s + h][wm * 64 + c], a1 = As[cur][2 * s + h][wm * 64 + 32 + c];
-        const float b0 = Bs[cur][2 * s + h][wn * 64 + c], b1 = Bs[cur][2 * s + h][wn * 64 + 32 + c];
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-      }
-      if (kt + 1 < nk) {
-        iv_put(t, va, As[cur ^ 1]);
-        iv_put(t, vb, Bs[cur ^ 1]);
-      }
-      __syncthreads();
-    }
+    dn_tile_scores(Q, query, vecq, Es, drow, vece, D, acc);
     // acc[i][j][r] = s(query of tile row 64 wm + 32 i + (r & 3) + 8 (r >> 2) + 4 h, doc at position n0 + 64 wn + 32 j + c)
     int32_t docj[2];
 #pragma unroll
@@ -480,26 +376,13 @@ __global__ __launch_bounds__(IV_THREADS, 2) void iv_scan_kernel(
           const int32_t doc = docj[j];
           const bool ok = rok && doc >= 0;
           const float s = acc[i][j][r] + 0.0f;
-          const uint32_t key = iv_key(s);
-          const bool pass = ok && key > th && (!has_c || s < cl);      // a NaN ceiling admits nothing
-          if (__ballot(pass) != 0ull && pass) {
-            bool excluded = false;
-            if (has_x) {
-              const int64_t e1 = exb[row];
-              const int64_t p = lower_bound(ex_doc, exa[row], e1, doc);
-              excluded = p < e1 && ex_doc[p] == doc;
-            }
-            if (!excluded) {
-              const int pos = atomicAdd(&cnt[row], 1);
-              if (pos < cap) cand[(size_t)slot[row] * (size_t)cap + pos] = rank_key(key, (uint32_t)doc);
-            }
-          }
+          dn_admit(ok, s, doc, th, has_c, cl, has_x, ex_doc, exa[row], exb[row], cnt[row], list(row), cap);
         }
       }
     __syncthreads();
-    // a tile adds at most IV_TILE entries to a list: compact every list that the next tile could overflow
+    // a tile adds at most DN_TILE entries to a list: compact every list that the next tile could overflow
     for (int row = 0; row < m; ++row)
-      if (__builtin_amdgcn_readfirstlane(cnt[row]) > cap - IV_TILE && qrow[row] >= 0) compact(row);
+      if (__builtin_amdgcn_readfirstlane(cnt[row]) > cap - DN_TILE && qrow[row] >= 0) compact(row);
   }
   for (int row = 0; row < m; ++row)
     if (qrow[row] >= 0) compact(row);
@@ -519,20 +402,14 @@ __global__ __launch_bounds__(SR_THREADS) void iv_merge_kernel(const unsigned lon
   __shared__ int taken;
   const int tid = threadIdx.x, q = blockIdx.x;
   const long base = (long)q * nslot;
-  const unsigned long long* qcand = cand + (size_t)base * (size_t)cap;
-  const int32_t* qcnt = ccount + base;
-  auto at = [&](long f) -> unsigned long long {              // flat index slot * hi + i
-    const int s = (int)(f / hi), i = (int)(f - (long)s * hi);
-    return i < qcnt[s] ? qcand[(size_t)s * (size_t)cap + i] : 0ull;
-  };
-  auto key = [&](long f) -> uint32_t { return rank_bits(at(f)); };
+  const DnLists lists = {cand + (size_t)base * (size_t)cap, ccount + base, cap, hi};
   const long n = (long)nslot * hi;
   uint32_t thr, thr2 = 0u;
   int need_eq, nsel;
-  radix_select(key, n, hi, S, thr, need_eq, nsel);
+  radix_select(lists, n, hi, S, thr, need_eq, nsel);
   if (thr != 0u) {                                           // the hi-th score is tied: the need_eq lowest docs of the tie
     auto tie = [&](long f) -> uint32_t {
-      const unsigned long long e = at(f);
+      const unsigned long long e = lists.at(f);
       return rank_bits(e) == thr ? (uint32_t)(e & 0xFFFFFFFFull) : 0u;
     };
     int ne2, ns2;
@@ -543,7 +420,7 @@ __global__ __launch_bounds__(SR_THREADS) void iv_merge_kernel(const unsigned lon
   if (tid == 0) taken = 0;
   __syncthreads();
   for (long f = tid; f < n; f += SR_THREADS) {
-    const unsigned long long e = at(f);
+    const unsigned long long e = lists.at(f);
     const uint32_t kb = rank_bits(e);
     if (e != 0ull && (kb > thr || (kb == thr && (uint32_t)(e & 0xFFFFFFFFull) >= thr2))) {
       const int pos = atomicAdd(&taken, 1);                  // any order: the sort below settles it, the keys are unique
@@ -552,21 +429,7 @@ __global__ __launch_bounds__(SR_THREADS) void iv_merge_kernel(const unsigned lon
   }
   __syncthreads();
   bitonic_desc<SR_THREADS, int>(sbuf, P);
-  const int w = hi - lo;
-  int32_t* od = out_doc + (long)q * w;
-  float* os = out_score + (long)q * w;
-  for (int j = tid; j < w; j += SR_THREADS) {
-    const int r = lo + j;
-    if (r < nsel) {
-      const unsigned long long e = sbuf[r];
-      os[j] = iv_unkey(rank_bits(e));
-      od[j] = rank_id(e);
-    } else {
-      os[j] = 0.f;
-      od[j] = -1;
-    }
-  }
-  if (out_found && tid == 0) out_found[q] = max(0, nsel - lo);
+  dn_write_ranks(sbuf, nsel, q, lo, hi, out_doc, out_score, out_found);
 }
 
 }  // namespace
@@ -641,7 +504,7 @@ extern "C" int snx_ivf_search(const float* Q, int32_t nq, int32_t D, const float
   SNX_CHECK_LAUNCH();
   if (p.blocks > 0 && nd > 0) {
     const int vecq = D % 4 == 0 && ((uintptr_t)Q & 15) == 0, vece = D % 4 == 0 && ((uintptr_t)E_sorted & 15) == 0;
-    hipLaunchKernelGGL(iv_scan_kernel, dim3((unsigned)p.blocks), dim3(IV_THREADS), 0, st, Q, nq, D, vecq, vece, E_sorted,
+    hipLaunchKernelGGL(iv_scan_kernel, dim3((unsigned)p.blocks), dim3(DN_THREADS), 0, st, Q, nq, D, vecq, vece, E_sorted,
                        list_ptr, list_doc, nlist, (const int64_t*)pair_ptr, (const int32_t*)pair_order,
                        (const int64_t*)tile_ptr, nprobe, p.split_tiles, p.smax, hi, p.cap, ex_ptr, ex_doc, ceiling, cand,
                        ccount);

@@ -8,6 +8,9 @@
 //   SelectSmem, radix_select,        top k of a key sequence under (key desc, index asc), taken in index order
 //   ordered_take
 //   bitonic_desc, block_sum          descending sort of 64-bit keys and an integer sum by the whole workgroup
+// The dense searches (dense.hip, ivf.hip) rank by the same 64-bit key and select with the same functions; what only they
+// share -- the fp32 MFMA tile, its order key, the candidate lists -- is in dense_common.h, which includes this file.  The
+// host's split planner of the tiled searches (split_plan: dense.hip, infogain.hip) sits below, next to pow2_at_least.
 // Not here, because hipcc compiles the kernels differently once these are functions (profiles/retrieval_refactor_isa.txt)
 // and a changed kernel has to be timed against its parent first: the chunk accumulation and target-rank count of
 // sr_chunk_kernel / sb_chunk_kernel / qr_count_kernel, and the merge front of sr_merge_kernel / sb_merge_kernel with its
@@ -34,6 +37,33 @@ template <typename T>                          // int in hybrid.hip, long elsewh
 __host__ __device__ inline T pow2_at_least(T n) {
   T p = 1;
   while (p < n) p <<= 1;
+  return p;
+}
+
+// The tiled searches that split the row range over workgroups (dense.hip, infogain.hip): a workgroup owns `tile` queries
+// and one split of split_tiles tiles of the n rows.  chunk > 0 sets the split length in rows; otherwise as many splits as
+// bring the launch to wg_target workgroups, at most splits_max (the lists per query that the merge has to read).
+struct SplitPlan {
+  int qtiles, split_tiles, nsplit;
+  long tiles;
+};
+
+inline SplitPlan split_plan(int32_t nq, int32_t n, int32_t chunk, int tile, int wg_target, int splits_max) {
+  SplitPlan p;
+  p.qtiles = (int)((nq + (long)tile - 1) / tile);
+  p.tiles = (n + (long)tile - 1) / tile;
+  if (chunk > 0) {
+    p.split_tiles = (int)((chunk + (long)tile - 1) / tile);
+  } else {
+    long want = (wg_target + (long)p.qtiles - 1) / (p.qtiles > 0 ? p.qtiles : 1);
+    if (want > splits_max) want = splits_max;
+    if (want > p.tiles) want = p.tiles;
+    if (want < 1) want = 1;
+    p.split_tiles = (int)((p.tiles + want - 1) / want);
+  }
+  if (p.split_tiles < 1) p.split_tiles = 1;
+  const long ns = (p.tiles + p.split_tiles - 1) / p.split_tiles;
+  p.nsplit = (int)(ns < 1 ? 1 : (ns > 0x7FFFFFFFL ? 0x7FFFFFFFL : ns));
   return p;
 }
 

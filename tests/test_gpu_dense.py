@@ -118,6 +118,33 @@ def test_chunking_and_query_slicing_change_no_bit(dev):
     other = idx.search_band(q, 10, 50, exclude=[[int(x)] for x in t.tolist()], chunk_docs=TILE, query_slice=64)
     for a, b in zip(band, other):
         assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+    # nor does the alignment of the operands: D % 4 == 0 with both bases one float off a 16-byte boundary
+    from snx.retrieval import DenseIndex
+    D, nd, nq, k = 20, 300, 130, 10
+    E = rng.standard_normal((nd, D)).astype(np.float32)
+    Q = rng.standard_normal((nq, D)).astype(np.float32)
+    e, q = torch.from_numpy(E).to(dev), torch.from_numpy(Q).to(dev)
+    e1, q1 = _one_float_off(e), _one_float_off(q)
+    t = torch.from_numpy(rng.integers(0, nd, size=nq)).to(dev)
+    excl = [rng.choice(nd, size=40, replace=False).tolist() for _ in range(nq)]
+    results = []
+    for emb, qq in ((e, q), (e1, q1)):
+        idx = DenseIndex(D, dev)
+        idx.add(emb)                                         # one batch: build() keeps the tensor, and so its base
+        idx.build()
+        assert idx.emb.data_ptr() == emb.data_ptr()
+        results.append(list(idx.search(qq, k, targets=t)) + list(idx.search_band(qq, 2, k, exclude=excl)))
+    for a, b in zip(*results):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+def _one_float_off(x):
+    """The same values in a contiguous view that starts one float into a larger buffer."""
+    flat = torch.empty(x.numel() + 8, dtype=x.dtype, device=x.device)
+    view = flat[1:1 + x.numel()].view(x.shape)
+    view.copy_(x)
+    assert view.is_contiguous() and view.data_ptr() % 16 == 4 and torch.equal(view, x)
+    return view
 
 
 # ------------------------------------------------------------------------------------------------ 4. non-dyadic

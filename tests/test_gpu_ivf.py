@@ -230,6 +230,14 @@ def test_slicing_batches_budget_and_splits_change_no_bit(dev, monkeypatch):
     three = _gpu_index(E, Cn, dev, batches=3)
     assert _same(list(idx.structure().values()), list(three.structure().values()))
     assert _same(base, three.search(q, 100, nprobe=3))
+    # nor does the alignment of the queries: D % 4 == 0, their base one float off a 16-byte boundary, the sorted rows on one
+    from tests.test_gpu_dense import _one_float_off
+    small = _gpu_index(E[:300], E[[0, 100, 200, 299]].copy(), dev, batches=1)
+    q1 = _one_float_off(q)
+    ex = [rng.choice(300, size=40, replace=False).tolist() for _ in range(NQ)]
+    assert small.nlist == 4 and small.list_emb.data_ptr() % 16 == 0
+    assert _same(small.search(q, 10, nprobe=2), small.search(q1, 10, nprobe=2))
+    assert _same(small.search_band(q, 2, 10, exclude=ex, nprobe=2), small.search_band(q1, 2, 10, exclude=ex, nprobe=2))
     monkeypatch.setattr(ivf, "_IVF_SPLIT_DOCS", 128)
     assert _same(base, idx.search(q, 100, nprobe=3)) and _same(band, idx.search_band(q, 10, 50, exclude=excl, nprobe=3))
     monkeypatch.setattr(ivf, "_IVF_WS_BUDGET", 1 << 20)      # a few queries per launch, in the coarse step too
