@@ -10,14 +10,14 @@
 //
 // Search: a workgroup owns 128 queries and one split of the doc range.  It walks the split in tiles of 128 docs with the
 // 128x128x16 fp32 MFMA loop of f32_path.hip (four waves of 2 x 2 accumulators, register prefetch, double-buffered LDS).
-// That loop, the order key, the admission of a score, the list compaction and the merge's output tail live in
-// dense_common.h, which ivf.hip's scan shares.  Every score of a tile goes from the accumulator through the query's
+// That loop, the order key, the admission of a score and the list compaction live in dense_common.h, which ivf.hip's
+// scan shares.  Every score of a tile goes from the accumulator through the query's
 // running threshold key; a wave whose 64 scores of one accumulator register all fail leaves on the ballot.  A survivor
 // is appended (LDS atomic cursor) to the query's candidate list in the workspace, `cap` entries of (order key << 32 |
 // ~doc).  When a list could overflow in the next tile the workgroup sorts it (bitonic, LDS), keeps the best k and raises
 // the threshold to the k-th key (exact: docs ascend along the walk).  At the end every list is sorted and cut to k;
-// dn_merge_kernel selects over the splits as sr_merge_kernel does over chunks (radix_select / ordered_take of
-// sparse_common.h: equal keys are met in doc order).  The target rank is an integer count over the same scores.  The band
+// dn_merge_kernel selects over the splits as sr_merge_kernel does over chunks (merge_lists of sparse_common.h: equal
+// keys are met in doc order).  The target rank is an integer count over the same scores.  The band
 // search is the same kernel: a survivor is dropped when the query's exclusion row holds it (binary search) and a score
 // not below the ceiling never survives.
 #include "dense_common.h"
@@ -120,8 +120,9 @@ __global__ __launch_bounds__(DN_THREADS, 2) void dn_search_kernel(
   }
 }
 
-// the top `hi` over a query's per-split lists (each sorted, at most hi long), ranks lo .. hi-1 written: sr_merge_kernel
-// with lists in place of chunks.  Equal keys are met in doc order (splits ascend, and a list is in search order).
+// the top `hi` over a query's per-split lists (each sorted, at most hi long), ranks lo .. hi-1 written: merge_lists, as
+// sr_merge_kernel runs it over chunks.  Equal keys are met in doc order (splits ascend; a sorted list has its ties
+// lowest doc first).
 __global__ __launch_bounds__(SR_THREADS) void dn_merge_kernel(const unsigned long long* __restrict__ cand,
                                                               const int32_t* __restrict__ ccount,
                                                               const int32_t* __restrict__ rcount, int32_t nd,
@@ -133,7 +134,6 @@ __global__ __launch_bounds__(SR_THREADS) void dn_merge_kernel(const unsigned lon
                                                               float* __restrict__ out_tscore,
                                                               int32_t* __restrict__ out_found) {
   __shared__ SelectSmem S;
-  __shared__ unsigned long long sbuf[SR_KMAX];
   const int tid = threadIdx.x, q = blockIdx.x;
   const long base = (long)q * nsplit;
   if (target) {
@@ -146,17 +146,8 @@ __global__ __launch_bounds__(SR_THREADS) void dn_merge_kernel(const unsigned lon
       if (!valid) out_tscore[q] = 0.f;
     }
   }
-  const DnLists lists = {cand + (size_t)base * (size_t)cap, ccount + base, cap, hi};
-  const long n = (long)nsplit * hi;
-  uint32_t thr;
-  int need_eq, nsel;
-  radix_select(lists, n, hi, S, thr, need_eq, nsel);
-  const int P = pow2_at_least(nsel);
-  for (int i = tid; i < P; i += SR_THREADS) sbuf[i] = 0ull;
-  __syncthreads();
-  ordered_take(lists, n, thr, need_eq, S, [&](long f, int pos) { sbuf[pos] = lists.at(f); });
-  bitonic_desc<SR_THREADS, int>(sbuf, P);
-  dn_write_ranks(sbuf, nsel, q, lo, hi, out_doc, out_score, out_found);
+  const RankLists lists = {cand + (size_t)base * (size_t)cap, ccount + base, cap, hi};
+  merge_lists<dense_unkey>(lists, nsplit, S, q, lo, hi, out_doc, out_score, out_found);
 }
 
 // s(q, d) of a list of pairs by the serial chain, one pair per thread; pair_q NULL: pair i belongs to query i

@@ -3,14 +3,15 @@
 // the dimensions in ascending order from +0, then + 0.0f; results are ordered score descending, then doc ascending, bit
 // for bit; and inside one candidate list docs ascend along the walk, so a later doc that only ties the list's threshold
 // loses to the k already kept and `key > threshold` is exact.  The tests hold the two searches to each other bit for bit,
-// so everything that states that contract -- the order key, the MFMA tile, the admission of a score, the compaction of a
-// list, the merge kernels' view of the lists and their output tail -- lives here once.
-// Not here.  The target-rank count of dn_search_kernel: only that kernel has it.  The selection fronts of the merge
-// kernels: dn_merge_kernel meets its lists in doc order and takes the tie with ordered_take, iv_merge_kernel's lists are
-// not in doc order and it selects the tie by doc id; they are two rules, not one.  gemm_f32_128_kernel (f32_path.hip) runs
-// the same MFMA loop over strided operands with epilogues, under the training goldens.  infogain.hip is the float64
-// difference form on a 64-wide tile with ascending pair keys: it shares the host's split_plan (sparse_common.h) and
-// nothing on the device.
+// so everything that states that contract for the search kernels -- the order key, the MFMA tile, the admission of a
+// score, the compaction of a list -- lives here once.  The merge stage is the sparse searches' too and lives with them
+// in sparse_common.h: the merge kernels' view of the lists (RankLists), their output tail (write_ranks, decoding with
+// dense_unkey here) and, for dn_merge_kernel, whose lists are met in doc order, the whole merge (merge_lists).
+// Not here.  The target-rank count of dn_search_kernel: only that kernel has it.  The selection front of
+// iv_merge_kernel: its lists are not in doc order, so it selects the tie by doc id and not by ordered_take as merge_lists
+// does; they are two rules, not one.  gemm_f32_128_kernel (f32_path.hip) runs the same MFMA loop over strided operands
+// with epilogues, under the training goldens.  infogain.hip is the float64 difference form on a 64-wide tile with
+// ascending pair keys: it shares the host's split_plan (sparse_common.h) and nothing on the device.
 #pragma once
 #include "sparse_common.h"
 
@@ -150,41 +151,6 @@ __device__ __forceinline__ void dn_compact(unsigned long long* list, int& cnt, u
     if (n >= k) thr = rank_bits(sbuf[k - 1]);
   }
   __syncthreads();
-}
-
-// A query's candidate lists as the merge kernels read them: `cap` apart, each sorted and cnt[list] <= hi long, under the
-// flat index f = list * hi + i; past a list's count reads as 0, "no entry".  Called as a function it gives the score key.
-struct DnLists {
-  const unsigned long long* cand;
-  const int32_t* cnt;
-  int cap, hi;
-  __device__ __forceinline__ unsigned long long at(long f) const {
-    const int s = (int)(f / hi), i = (int)(f - (long)s * hi);
-    return i < cnt[s] ? cand[(size_t)s * (size_t)cap + i] : 0ull;
-  }
-  __device__ __forceinline__ uint32_t operator()(long f) const { return rank_bits(at(f)); }
-};
-
-// the output tail of a merge kernel (SR_THREADS): ranks lo .. hi-1 of the nsel selected entries of sbuf, sorted
-// descending, into query q's rows; unused slots 0 / -1; found = the slots used
-__device__ __forceinline__ void dn_write_ranks(const unsigned long long* sbuf, int nsel, int q, int lo, int hi,
-                                               int32_t* __restrict__ out_doc, float* __restrict__ out_score,
-                                               int32_t* __restrict__ out_found) {
-  const int tid = threadIdx.x, w = hi - lo;
-  int32_t* od = out_doc + (long)q * w;
-  float* os = out_score + (long)q * w;
-  for (int j = tid; j < w; j += SR_THREADS) {
-    const int r = lo + j;
-    if (r < nsel) {
-      const unsigned long long e = sbuf[r];
-      os[j] = dense_unkey(rank_bits(e));
-      od[j] = rank_id(e);
-    } else {
-      os[j] = 0.f;
-      od[j] = -1;
-    }
-  }
-  if (out_found && tid == 0) out_found[q] = max(0, nsel - lo);
 }
 
 }  // namespace

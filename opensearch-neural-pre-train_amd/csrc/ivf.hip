@@ -12,13 +12,14 @@
 // of workgroups, each finds its list by binary search in tile_ptr and leaves when there is none, so the host never reads
 // a count.  A workgroup owns up to 128 gathered query rows of one list and one split of the list's docs and walks the split
 // in 128-doc tiles with the 128x128x16 fp32 MFMA loop that dense_common.h holds for this file and dense.hip, together with
-// the order key, the admission of a score, the list compaction and the merge's output tail.  Every score goes through the
+// the order key, the admission of a score and the list compaction; the merge's list view and output tail are those of
+// every merge kernel (sparse_common.h).  Every score goes through the
 // pair's running threshold into the candidate list of its (pair, split), `cap` entries of (order key << 32 | ~original
 // doc); a list that the next tile could overflow is sorted and cut to k.  Original ids ascend along a list and so along
 // a split: inside one candidate list a later doc that only ties the threshold loses, and `key > threshold` is exact.
 // That does NOT hold across lists, so every (pair, split) keeps its own candidate list and its own threshold, and
 // iv_merge_kernel selects over a query's nprobe x splits lists by the full 64-bit key: radix_select on the score key,
-// then, when the k-th score is tied, a second radix_select on ~doc among the ties (dn_merge_kernel's "first need_eq in
+// then, when the k-th score is tied, a second radix_select on ~doc among the ties (merge_lists' "first need_eq in
 // index order" would be wrong here: index order is not doc order across lists).  The band's exclusion rows (binary
 // search by original id) and ceiling are applied in the scan kernel, as in dn_search_kernel.
 //
@@ -402,7 +403,7 @@ __global__ __launch_bounds__(SR_THREADS) void iv_merge_kernel(const unsigned lon
   __shared__ int taken;
   const int tid = threadIdx.x, q = blockIdx.x;
   const long base = (long)q * nslot;
-  const DnLists lists = {cand + (size_t)base * (size_t)cap, ccount + base, cap, hi};
+  const RankLists lists ={cand + (size_t)base * (size_t)cap, ccount + base, cap, hi};
   const long n = (long)nslot * hi;
   uint32_t thr, thr2 = 0u;
   int need_eq, nsel;
@@ -429,7 +430,7 @@ __global__ __launch_bounds__(SR_THREADS) void iv_merge_kernel(const unsigned lon
   }
   __syncthreads();
   bitonic_desc<SR_THREADS, int>(sbuf, P);
-  dn_write_ranks(sbuf, nsel, q, lo, hi, out_doc, out_score, out_found);
+  write_ranks<dense_unkey>(sbuf,nsel, q, lo, hi, out_doc, out_score, out_found);
 }
 
 }  // namespace

@@ -9,6 +9,9 @@
 //   qr_count_kernel     one workgroup per (query, chunk of docs): the LDS score accumulation of retrieval.hip's
 //                       sr_chunk_kernel (same constants, sparse_common.h) and its integer count of the docs in front of
 //                       the best relevant doc.  No selection pass: one accumulation per query whatever the row length.
+//                       Written out here, not accumulate_chunk / count_ahead / block_sum of sparse_common.h: with them
+//                       first_relevant measured up to 1.4 % over the parent against a margin of 1.0 %
+//                       (profiles/sparse_chunk_merge_refactor.txt).  A change to that accumulation is made here too.
 //   qr_rank_kernel      adds the chunks' counts of a query (integers: the chunking changes no bit).
 //   qr_ranked_kernel    one wave per ranked list, 64 positions at a time: every lane tests its entry by binary search in
 //                       the sorted row, a ballot puts the hits in position order, and the wave walks the set bits: one

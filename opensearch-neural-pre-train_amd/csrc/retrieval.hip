@@ -19,10 +19,11 @@
 // doc order, and an integer count gives the chunk's share of the target rank.  sr_merge reduces the chunks of a query
 // the same way (its candidates are in doc order too) and sorts the <= k winners.  Chunk size changes no bit.
 //
-// From sparse_common.h: the chunk constants, lower_bound, the radix select and ordered take, block_sum, the pair score
-// (row_dot_lanes) and the rank key.  The chunk accumulation (sr_chunk_kernel, sb_chunk_kernel; qr_count_kernel in
-// qrels.hip) and the merge front (sr_merge_kernel, sb_merge_kernel) stay written out in their kernels: as functions they
-// compile to other code, which would have to be timed against this one first.
+// From sparse_common.h: the chunk constants, lower_bound, the pair score (row_dot_lanes), block_sum, the chunk stage
+// (accumulate_chunk, count_ahead, select_chunk over radix_select / ordered_take; qr_count_kernel of qrels.hip keeps a
+// written-out copy of the first two, see there) and the merge stage (RankLists, merge_lists with its sort and output tail).  A kernel here keeps
+// what only it does: its target-rank reduction, the band's exclusions and ceiling.  The candidates in the workspace are
+// rank keys (score bits << 32 | ~doc), as the merge sorts them.
 #include "sparse_common.h"
 #include "snx.h"
 
@@ -161,62 +162,18 @@ __global__ __launch_bounds__(SR_THREADS) void sr_chunk_kernel(const int64_t* __r
                                                               int32_t* __restrict__ rcount) {
   extern __shared__ float sc[];                            // [chunk] scores of this chunk's docs
   __shared__ SelectSmem S;
-  __shared__ int64_t seg0[SR_TG], seg1[SR_TG];
-  __shared__ float segw[SR_TG];
-  const int tid = threadIdx.x;
+  __shared__ ChunkSmem C;
   const long qc = blockIdx.x;
   const int q = (int)(qc / nch), c = (int)(qc - (long)q * nch);
   const int c0 = c * chunk;
   const int n = max(0, min(chunk, nd - c0));
-  for (int i = tid; i < n; i += SR_THREADS) sc[i] = 0.f;
-  const int64_t qa = q_ptr[q], qb = q_ptr[q + 1];
-  for (int64_t g = qa; g < qb; g += SR_TG) {
-    const int ng = (int)min((int64_t)SR_TG, qb - g);
-    const int j = tid < SR_TG ? tid : tid - SR_TG;
-    if (j < ng) {                                          // both bounds of every term of the group at once
-      const int32_t term = q_term[g + j];
-      int64_t lo = 0, hi = 0;
-      if ((unsigned)term < (unsigned)V) { lo = term_ptr[term]; hi = term_ptr[term + 1]; }
-      if (tid < SR_TG) {
-        seg0[j] = lower_bound(post_doc, lo, hi, c0);
-        segw[j] = q_w[g + j];
-      } else {
-        seg1[j] = lower_bound(post_doc, lo, hi, c0 + n);
-      }
-    }
-    __syncthreads();                                       // (also orders the zero fill before the first term)
-    for (int jj = 0; jj < ng; ++jj) {                      // ascending term id: the ABI's accumulation order
-      const int64_t e = seg1[jj];
-      const float w = segw[jj];
-      for (int64_t i = seg0[jj] + tid; i < e; i += SR_THREADS) {
-        const int d = post_doc[i] - c0;
-        if ((unsigned)d < (unsigned)n) sc[d] = fmaf(w, post_w[i], sc[d]);
-      }
-      __syncthreads();
-    }
-  }
-  __syncthreads();
-  if (target) {                                            // 1 + #{s_d > s_t} + #{d < t: s_d == s_t}, summed by sr_merge
+  accumulate_chunk(q_term, q_w, q_ptr[q], q_ptr[q + 1], term_ptr, post_doc, post_w, V, c0, n, sc, C);
+  if (target) {                                            // the chunk's share of the target rank, summed by sr_merge_kernel
     const float ts = tscore[q];
-    const int tt = target[q];
-    int local = 0;
-    if (ts > 0.f)
-      for (int i = tid; i < n; i += SR_THREADS) {
-        const float s = sc[i];
-        local += (s > ts) || (s == ts && c0 + i < tt);
-      }
-    const int r = block_sum(local, S.sh[0]);
-    if (tid == 0) rcount[qc] = r;
+    const int r = block_sum(ts > 0.f ? count_ahead(sc, c0, n, ts, target[q]) : 0, S.sh[0]);
+    if (threadIdx.x == 0) rcount[qc] = r;
   }
-  auto key = [&](long i) -> uint32_t { return score_key(sc[i]); };
-  uint32_t thr;
-  int need_eq, nsel;
-  radix_select(key, n, k, S, thr, need_eq, nsel);
-  unsigned long long* out = cand + qc * k;
-  ordered_take(key, n, thr, need_eq, S, [&](long i, int pos) {
-    out[pos] = ((unsigned long long)score_key(sc[i]) << 32) | (uint32_t)(c0 + (int)i);
-  });
-  if (tid == 0) ccount[qc] = nsel;
+  select_chunk([&](long i) -> uint32_t { return score_key(sc[i]); }, c0, n, k, S, cand + qc * k, ccount + qc);
 }
 
 __global__ __launch_bounds__(SR_THREADS) void sr_merge_kernel(const unsigned long long* __restrict__ cand,
@@ -229,7 +186,6 @@ __global__ __launch_bounds__(SR_THREADS) void sr_merge_kernel(const unsigned lon
                                                               float* __restrict__ out_score,
                                                               int32_t* __restrict__ out_rank) {
   __shared__ SelectSmem S;
-  __shared__ unsigned long long sbuf[SR_KMAX];              // (score bits << 32 | ~doc): descending = the ABI's order
   const int tid = threadIdx.x, q = blockIdx.x;
   const long base = (long)q * nch;
   if (target) {
@@ -239,46 +195,8 @@ __global__ __launch_bounds__(SR_THREADS) void sr_merge_kernel(const unsigned lon
     const int tt = target[q];
     if (tid == 0) out_rank[q] = ((unsigned)tt < (unsigned)nd && tscore[q] > 0.f) ? 1 + r : 0;
   }
-  const unsigned long long* qcand = cand + base * k;
-  const int32_t* qcnt = ccount + base;
-  auto key = [&](long f) -> uint32_t {                      // flat index c * k + i: doc order among the valid entries
-    const int c = (int)(f / k), i = (int)(f - (long)c * k);
-    return i < qcnt[c] ? (uint32_t)(qcand[f] >> 32) : 0u;
-  };
-  const long n = (long)nch * k;
-  uint32_t thr;
-  int need_eq, nsel;
-  radix_select(key, n, k, S, thr, need_eq, nsel);
-  const int P = pow2_at_least(nsel);
-  for (int i = tid; i < P; i += SR_THREADS) sbuf[i] = 0ull;
-  __syncthreads();
-  ordered_take(key, n, thr, need_eq, S, [&](long f, int pos) {
-    const unsigned long long e = qcand[f];
-    sbuf[pos] = rank_key((uint32_t)(e >> 32), (uint32_t)e);
-  });
-  for (int size = 2; size <= P; size <<= 1)                 // bitonic sort, descending; written out (see sparse_common.h, bitonic_desc)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < (P >> 1); t += SR_THREADS) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const unsigned long long a = sbuf[lo], b = sbuf[hi];
-        if ((a < b) == desc) { sbuf[lo] = b; sbuf[hi] = a; }
-      }
-      __syncthreads();
-    }
-  int32_t* od = out_doc + (long)q * k;
-  float* os = out_score + (long)q * k;
-  for (int i = tid; i < k; i += SR_THREADS) {
-    if (i < nsel) {
-      const unsigned long long e = sbuf[i];
-      os[i] = bitsf(rank_bits(e));
-      od[i] = rank_id(e);
-    } else {
-      os[i] = 0.f;
-      od[i] = -1;
-    }
-  }
+  const RankLists lists = {cand + base * k, ccount + base, k, k};    // a chunk's k slots: doc order across and inside
+  merge_lists<bitsf>(lists, nch, S, q, 0, k, out_doc, out_score, nullptr);
 }
 
 // s(q, d) of a list of (query, doc) pairs: sr_target_kernel with one pair per workgroup instead of one target per query.
@@ -317,48 +235,20 @@ __global__ __launch_bounds__(SR_THREADS) void sb_chunk_kernel(const int64_t* __r
                                                               int32_t* __restrict__ ccount) {
   extern __shared__ float sc[];
   __shared__ SelectSmem S;
-  __shared__ int64_t seg0[SR_TG], seg1[SR_TG];
-  __shared__ float segw[SR_TG];
+  __shared__ ChunkSmem C;
   const int tid = threadIdx.x;
   const long qc = blockIdx.x;
   const int q = (int)(qc / nch), c = (int)(qc - (long)q * nch);
   const int c0 = c * chunk;
   const int n = max(0, min(chunk, nd - c0));
-  for (int i = tid; i < n; i += SR_THREADS) sc[i] = 0.f;
-  const int64_t qa = q_ptr[q], qb = q_ptr[q + 1];
-  for (int64_t g = qa; g < qb; g += SR_TG) {
-    const int ng = (int)min((int64_t)SR_TG, qb - g);
-    const int j = tid < SR_TG ? tid : tid - SR_TG;
-    if (j < ng) {
-      const int32_t term = q_term[g + j];
-      int64_t lo = 0, hi2 = 0;
-      if ((unsigned)term < (unsigned)V) { lo = term_ptr[term]; hi2 = term_ptr[term + 1]; }
-      if (tid < SR_TG) {
-        seg0[j] = lower_bound(post_doc, lo, hi2, c0);
-        segw[j] = q_w[g + j];
-      } else {
-        seg1[j] = lower_bound(post_doc, lo, hi2, c0 + n);
-      }
-    }
-    __syncthreads();
-    for (int jj = 0; jj < ng; ++jj) {                      // ascending term id: the ABI's accumulation order
-      const int64_t e = seg1[jj];
-      const float w = segw[jj];
-      for (int64_t i = seg0[jj] + tid; i < e; i += SR_THREADS) {
-        const int d = post_doc[i] - c0;
-        if ((unsigned)d < (unsigned)n) sc[d] = fmaf(w, post_w[i], sc[d]);
-      }
-      __syncthreads();
-    }
-  }
-  __syncthreads();
+  accumulate_chunk(q_term, q_w, q_ptr[q], q_ptr[q + 1], term_ptr, post_doc, post_w, V, c0, n, sc, C);
   if (ex_ptr) {                                            // the row's docs in [c0, c0 + n): one binary search per bound
-    if (tid < 2) {
+    if (tid < 2) {                                         // (the staging words of the accumulation are free again)
       const int64_t a = ex_ptr[q], b = ex_ptr[q + 1];
-      seg0[tid] = lower_bound(ex_doc, a, b, tid == 0 ? c0 : c0 + n);
+      C.seg0[tid] = lower_bound(ex_doc, a, b, tid == 0 ? c0 : c0 + n);
     }
     __syncthreads();
-    const int64_t e0 = seg0[0], e1 = seg0[1];
+    const int64_t e0 = C.seg0[0], e1 = C.seg0[1];
     for (int64_t i = e0 + tid; i < e1; i += SR_THREADS) {
       const int d = ex_doc[i] - c0;
       if ((unsigned)d < (unsigned)n) sc[d] = 0.f;
@@ -370,70 +260,20 @@ __global__ __launch_bounds__(SR_THREADS) void sb_chunk_kernel(const int64_t* __r
     const float s = sc[i];
     return s < ceil_q ? score_key(s) : 0u;                 // a NaN ceiling admits nothing
   };
-  uint32_t thr;
-  int need_eq, nsel;
-  radix_select(key, n, hi, S, thr, need_eq, nsel);
-  unsigned long long* out = cand + qc * hi;
-  ordered_take(key, n, thr, need_eq, S, [&](long i, int pos) {
-    out[pos] = ((unsigned long long)score_key(sc[i]) << 32) | (uint32_t)(c0 + (int)i);
-  });
-  if (tid == 0) ccount[qc] = nsel;
+  select_chunk(key, c0, n, hi, S, cand + qc * hi, ccount + qc);
 }
 
-// Band search, merge stage: sr_merge_kernel's selection of the top `hi` over the chunks' candidates, then ranks
-// lo .. hi-1 are written.
+// Band search, merge stage: the top `hi` over the chunks' candidates as in sr_merge_kernel, ranks lo .. hi-1 written.
 __global__ __launch_bounds__(SR_THREADS) void sb_merge_kernel(const unsigned long long* __restrict__ cand,
                                                               const int32_t* __restrict__ ccount, int32_t nch,
                                                               int32_t lo, int32_t hi, int32_t* __restrict__ out_doc,
                                                               float* __restrict__ out_score,
                                                               int32_t* __restrict__ out_found) {
   __shared__ SelectSmem S;
-  __shared__ unsigned long long sbuf[SR_KMAX];
-  const int tid = threadIdx.x, q = blockIdx.x;
+  const int q = blockIdx.x;
   const long base = (long)q * nch;
-  const unsigned long long* qcand = cand + base * hi;
-  const int32_t* qcnt = ccount + base;
-  auto key = [&](long f) -> uint32_t {
-    const int c = (int)(f / hi), i = (int)(f - (long)c * hi);
-    return i < qcnt[c] ? (uint32_t)(qcand[f] >> 32) : 0u;
-  };
-  const long n = (long)nch * hi;
-  uint32_t thr;
-  int need_eq, nsel;
-  radix_select(key, n, hi, S, thr, need_eq, nsel);
-  const int P = pow2_at_least(nsel);
-  for (int i = tid; i < P; i += SR_THREADS) sbuf[i] = 0ull;
-  __syncthreads();
-  ordered_take(key, n, thr, need_eq, S, [&](long f, int pos) {
-    const unsigned long long e = qcand[f];
-    sbuf[pos] = rank_key((uint32_t)(e >> 32), (uint32_t)e);
-  });
-  for (int size = 2; size <= P; size <<= 1)                 // the sort of sr_merge_kernel
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < (P >> 1); t += SR_THREADS) {
-        const int a0 = 2 * t - (t & (stride - 1));
-        const int a1 = a0 + stride;
-        const bool desc = (a0 & size) == 0;
-        const unsigned long long a = sbuf[a0], b = sbuf[a1];
-        if ((a < b) == desc) { sbuf[a0] = b; sbuf[a1] = a; }
-      }
-      __syncthreads();
-    }
-  const int w = hi - lo;
-  int32_t* od = out_doc + (long)q * w;
-  float* os = out_score + (long)q * w;
-  for (int j = tid; j < w; j += SR_THREADS) {
-    const int r = lo + j;
-    if (r < nsel) {
-      const unsigned long long e = sbuf[r];
-      os[j] = bitsf(rank_bits(e));
-      od[j] = rank_id(e);
-    } else {
-      os[j] = 0.f;
-      od[j] = -1;
-    }
-  }
-  if (tid == 0) out_found[q] = max(0, nsel - lo);
+  const RankLists lists = {cand + base * hi, ccount + base, hi, hi};
+  merge_lists<bitsf>(lists, nch, S, q, lo, hi, out_doc, out_score, out_found);
 }
 
 }  // namespace

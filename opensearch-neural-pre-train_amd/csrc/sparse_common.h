@@ -8,14 +8,26 @@
 //   SelectSmem, radix_select,        top k of a key sequence under (key desc, index asc), taken in index order
 //   ordered_take
 //   bitonic_desc, block_sum          descending sort of 64-bit keys and an integer sum by the whole workgroup
+//   ChunkSmem, accumulate_chunk,     the chunk stage of the exact searches (sr_chunk_kernel, sb_chunk_kernel): the scores
+//   count_ahead, select_chunk        of a chunk of docs in LDS by the ABI's chain, a thread's share of the count of docs
+//                                    ranked ahead of a target, and the chunk's top k as rank keys in doc order
+//   RankLists, merge_lists,          the merge stage (sr_merge_kernel, sb_merge_kernel; dn_merge_kernel of dense.hip):
+//   write_ranks                      the top hi over a query's candidate lists, sorted, ranks lo .. hi-1 written.
+//                                    iv_merge_kernel (ivf.hip) selects by another rule and shares the list view and tail
+// These kernels compile to other code than their written-out forms did, so each was timed against its parent before the
+// copies went: profiles/sparse_chunk_merge_refactor.txt.  qr_count_kernel (qrels.hip) failed that timing with the chunk
+// helpers (first_relevant at 1,000,000 docs x 2,000 queries: medians 1.4 % and 0.7 % over the parent's best, margin
+// 1.0 %) and keeps its written-out copy of the accumulation, the count and its wave-array sum; a change to
+// accumulate_chunk or count_ahead has to be made there as well.
 // The dense searches (dense.hip, ivf.hip) rank by the same 64-bit key and select with the same functions; what only they
-// share -- the fp32 MFMA tile, its order key, the candidate lists -- is in dense_common.h, which includes this file.  The
-// host's split planner of the tiled searches (split_plan: dense.hip, infogain.hip) sits below, next to pow2_at_least.
-// Not here, because hipcc compiles the kernels differently once these are functions (profiles/retrieval_refactor_isa.txt)
-// and a changed kernel has to be timed against its parent first: the chunk accumulation and target-rank count of
-// sr_chunk_kernel / sb_chunk_kernel / qr_count_kernel, and the merge front of sr_merge_kernel / sb_merge_kernel with its
-// written-out sort.  Those kernels keep their own copies; what they share is the constants and helpers below.
-// A helper that depends on the workgroup size takes it as a template parameter (the files use 512, 256 and 64 threads).
+// share -- the fp32 MFMA tile, its order key, the candidate lists' compaction -- is in dense_common.h, which includes this
+// file.  The host's split planner of the tiled searches (split_plan: dense.hip, infogain.hip) sits below, next to
+// pow2_at_least.
+// Local on purpose, not here: hybrid.hip's HY_BITONIC and float64 helpers (other comparators); the 8-bit radix selects of
+// sz_prune_kernel and tp_prune_kernel (their bodies differ); tp_prune_kernel's wave-array sum (block_sum's LDS-word form
+// compiles it to more code, profiles/retrieval_refactor_isa.txt); tf_bitonic_asc and infogain's pair sort (ascending).
+// A helper that depends on the workgroup size takes it as a template parameter (the files use 512, 256 and 64 threads);
+// the select, chunk and merge helpers are for SR_THREADS.
 #pragma once
 #include "common.h"
 #include "runtime.h"   // align256
@@ -269,6 +281,130 @@ __device__ void ordered_take(KeyF key, long n, uint32_t thr, int need_eq, Select
     }
     __syncthreads();
   }
+}
+
+// ------------------------------------------------------------------------------------------------ chunk stage
+struct ChunkSmem {
+  int64_t seg0[SR_TG], seg1[SR_TG];  // a term's postings inside the chunk: [seg0, seg1)
+  float segw[SR_TG];                 // its query weight
+};
+
+// sc[d - c0] = s(q, d) for the n docs from c0 on, q the query row [qa, qb): the chunk's scores start at +0 and take
+// fmaf(q_w, d_w, .) term by term in ascending term id, the ABI's chain, with a barrier between terms (a doc appears at
+// most once per posting list, so no float atomics).  The chunk bounds of SR_TG terms are searched at once, the lower one
+// by the first half of the workgroup and the upper one by the second.  Ends on a barrier.
+__device__ __forceinline__ void accumulate_chunk(const int32_t* __restrict__ q_term, const float* __restrict__ q_w,
+                                                 int64_t qa, int64_t qb, const int64_t* __restrict__ term_ptr,
+                                                 const int32_t* __restrict__ post_doc, const float* __restrict__ post_w,
+                                                 int32_t V, int c0, int n, float* sc, ChunkSmem& C) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < n; i += SR_THREADS) sc[i] = 0.f;
+  for (int64_t g = qa; g < qb; g += SR_TG) {
+    const int ng = (int)min((int64_t)SR_TG, qb - g);
+    const int j = tid < SR_TG ? tid : tid - SR_TG;
+    if (j < ng) {
+      const int32_t term = q_term[g + j];
+      int64_t lo = 0, hi = 0;
+      if ((unsigned)term < (unsigned)V) { lo = term_ptr[term]; hi = term_ptr[term + 1]; }
+      if (tid < SR_TG) {
+        C.seg0[j] = lower_bound(post_doc, lo, hi, c0);
+        C.segw[j] = q_w[g + j];
+      } else {
+        C.seg1[j] = lower_bound(post_doc, lo, hi, c0 + n);
+      }
+    }
+    __syncthreads();                                         // (also orders the zero fill before the first term)
+    for (int jj = 0; jj < ng; ++jj) {                        // ascending term id: the ABI's accumulation order
+      const int64_t e = C.seg1[jj];
+      const float w = C.segw[jj];
+      for (int64_t i = C.seg0[jj] + tid; i < e; i += SR_THREADS) {
+        const int d = post_doc[i] - c0;
+        if ((unsigned)d < (unsigned)n) sc[d] = fmaf(w, post_w[i], sc[d]);
+      }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+}
+
+// this thread's share of #{s_d > ts} + #{d < tt : s_d == ts} over the chunk: the docs ranked ahead of doc tt with score ts
+__device__ __forceinline__ int count_ahead(const float* sc, int c0, int n, float ts, int tt) {
+  int local = 0;
+  for (int i = threadIdx.x; i < n; i += SR_THREADS) {
+    const float s = sc[i];
+    local += (s > ts) || (s == ts && c0 + i < tt);
+  }
+  return local;
+}
+
+// the chunk's top k under key(i), i in [0, n), as rank keys of doc c0 + i in doc order into out[0 ..), their number into
+// *count
+template <typename KeyF>
+__device__ __forceinline__ void select_chunk(KeyF key, int c0, int n, int k, SelectSmem& S, unsigned long long* out,
+                                             int32_t* count) {
+  uint32_t thr;
+  int need_eq, nsel;
+  radix_select(key, n, k, S, thr, need_eq, nsel);
+  ordered_take(key, n, thr, need_eq, S, [&](long i, int pos) { out[pos] = rank_key(key(i), (uint32_t)(c0 + (int)i)); });
+  if (threadIdx.x == 0) *count = nsel;
+}
+
+// ------------------------------------------------------------------------------------------------ merge stage
+// A query's candidate lists as the merge kernels read them: `cap` apart, each holding cnt[list] <= hi rank keys, under the
+// flat index f = list * hi + i; past a list's count reads as 0, "no entry".  Called as a function it gives the score key.
+struct RankLists {
+  const unsigned long long* cand;
+  const int32_t* cnt;
+  int cap, hi;
+  __device__ __forceinline__ unsigned long long at(long f) const {
+    const int s = (int)(f / hi), i = (int)(f - (long)s * hi);
+    return i < cnt[s] ? cand[(size_t)s * (size_t)cap + i] : 0ull;
+  }
+  __device__ __forceinline__ uint32_t operator()(long f) const { return rank_bits(at(f)); }
+};
+
+// the output tail of a merge kernel: ranks lo .. hi-1 of the nsel selected entries of sbuf, sorted descending, into query
+// q's rows, the score decoded from its key by Score (bitsf: sparse scores are their bits; dense_unkey: the dense order
+// key); unused slots 0 / -1; found, when asked for = the slots used
+template <float (*Score)(uint32_t)>
+__device__ __forceinline__ void write_ranks(const unsigned long long* sbuf, int nsel, int q, int lo, int hi,
+                                            int32_t* __restrict__ out_doc, float* __restrict__ out_score,
+                                            int32_t* __restrict__ out_found) {
+  const int tid = threadIdx.x, w = hi - lo;
+  int32_t* od = out_doc + (long)q * w;
+  float* os = out_score + (long)q * w;
+  for (int j = tid; j < w; j += SR_THREADS) {
+    const int r = lo + j;
+    if (r < nsel) {
+      const unsigned long long e = sbuf[r];
+      os[j] = Score(rank_bits(e));
+      od[j] = rank_id(e);
+    } else {
+      os[j] = 0.f;
+      od[j] = -1;
+    }
+  }
+  if (out_found && tid == 0) out_found[q] = max(0, nsel - lo);
+}
+
+// The top hi of query q over its nlist lists, which follow each other in doc order and are in doc order inside (equal
+// keys are met lowest doc first, which is what ordered_take's tie rule needs), sorted, ranks lo .. hi-1 written.
+template <float (*Score)(uint32_t)>
+__device__ __forceinline__ void merge_lists(const RankLists& lists, int nlist, SelectSmem& S, int q, int lo, int hi,
+                                            int32_t* __restrict__ out_doc, float* __restrict__ out_score,
+                                            int32_t* __restrict__ out_found) {
+  __shared__ unsigned long long sbuf[SR_KMAX];               // rank keys: descending = the ABI's order
+  const int tid = threadIdx.x;
+  const long n = (long)nlist * hi;
+  uint32_t thr;
+  int need_eq, nsel;
+  radix_select(lists, n, hi, S, thr, need_eq, nsel);
+  const int P = pow2_at_least(nsel);
+  for (int i = tid; i < P; i += SR_THREADS) sbuf[i] = 0ull;
+  __syncthreads();
+  ordered_take(lists, n, thr, need_eq, S, [&](long f, int pos) { sbuf[pos] = lists.at(f); });
+  bitonic_desc<SR_THREADS, int>(sbuf, P);
+  write_ranks<Score>(sbuf, nsel, q, lo, hi, out_doc, out_score, out_found);
 }
 
 }  // namespace

@@ -86,6 +86,14 @@ def test_band_exact_exclusions_ceilings_and_short_bands(dev):
     # a band longer than the admissible set
     sc, dc, fd = _band_case(dev, idx, S, queries, 0, 64, excl, None, 0)
     assert int(fd[5]) < 64 and (dc[5, int(fd[5]):] == -1).all()
+    # one tie run over three chunks (300 = 2 * 128 + 44): every non-empty doc scores 0.25, so rank hi = 140 falls inside
+    # the run and inside the second chunk, and the merge takes the tie's first docs across a chunk boundary
+    docs = _rows(rng, 300, V, 6, np.array([32]), common=7, empty_every=17)
+    queries[5] = (np.array([7]), np.array([0.5]))
+    S = _dense(queries, V) @ _dense(docs, V).T
+    assert (S[5] > 0).sum() > 256 and np.unique(S[5][S[5] > 0]).size == 1
+    _, dc, fd = _band_case(dev, _index(docs, V, dev), S, queries, 5, 140, [[]] * len(queries), None, 128)
+    assert int(fd[5]) == 135 and 128 <= int(dc[5, 134]) < 256
 
 
 @pytest.mark.parametrize("hi", [1, 7])
