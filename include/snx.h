@@ -713,6 +713,49 @@ int snx_wp_fill(const int64_t* ptr, const int32_t* pieces, int32_t n, const int6
 int snx_wp_pad(const int64_t* out_ptr, const int64_t* out_ids, int32_t n, int64_t L, int64_t pad_id, int64_t* input_ids,
                int64_t* attention_mask, hipStream_t stream);
 
+/* ---- Unigram tokenizer (csrc/unigram.hip): the dense teacher's tokenizer, XLM-RoBERTa's tokenizer.json (normalizer
+ * Precompiled = SentencePiece's nmt_nfkc charsmap, WhitespaceSplit + Metaspace, a Unigram model, template "<s> $A </s>"),
+ * from code points to token ids, equal to the `tokenizers` library's bit for bit.  Rows are a CSR of RAW code points, ptr
+ * [n+1] int64 and code_points int32, each row shorter than 2^26.  The device normalizes code point by code point, which is
+ * the library's result for a row without a code point that joins a grapheme cluster; the host keeps the other rows.
+ * Normalizer: nmap [0x110000] int32 is the host's table over all code points, -1 = kept, else offset << 5 | length
+ * (length <= 31, may be 0) of the replacement in pool (int32 code points); a value outside [0, 0x10FFFF] is kept.
+ * snx_ug_norm_count: out_len [n] int64 = 1 + the replacement lengths of the row.  norm_ptr [n+1] int64 = 0 and the running
+ * sums of out_len (the caller's scan; norm_ptr[n] and the largest out_len are read by the host, to size norm and the
+ * workspace).  snx_ug_norm_fill: row r of norm (int32) = U+0020, then the replacements in order.  The leading white space
+ * is the slot of the first word's U+2581: every word of a normalized row has white space in front of it.
+ * Pre-tokenizer: white space is Rust's char::is_whitespace.  A UNIT starts at every U+2581 and at white space that is
+ * directly followed by a word character (neither white space nor U+2581); that first entry is read as U+2581, the unit
+ * goes on over the word characters behind it.  (A word receives a leading U+2581 unless it begins with one and is cut
+ * before every further one.)  Entry 0 of a row must be white space.
+ * Unigram, per unit w[0..len), float64: best[0] = 0; for st ascending and every vocabulary piece w[st..en): cand =
+ * score + best[st] replaces best[en] when that is unset or cand > best[en]; when no piece of ONE code point starts at st,
+ * cand = unk_score + best[st] competes for best[st+1] the same way, with unk_id.  The kernel evaluates the same candidates
+ * end by end, longest piece first, the unknown last: the same order per end, single float64 additions, no multiplication.
+ * The pieces of the best path are read back from the end; consecutive unk_id of one unit fuse into one.
+ * Vocabulary: E entries, entry e = (its code points ent_cps[ent_ptr[e] .. ent_ptr[e+1]), ent_id[e], ent_score[e] float64),
+ * the pieces no unit can hold left out (white space inside, U+2581 behind the first place); slots [n_slots] and the hash
+ * as in the WordPiece section with cont = 0.  1 <= max_entry <= 32 (the hit lengths of a start are one uint32), otherwise
+ * SNX_E_SHAPE.
+ * snx_ug_pieces: one workgroup per row.  pieces [norm_ptr[n]] int32 (caller-owned): the id of the piece that STARTS at an
+ * entry, -1 where none does; out_cnt [n] int64 = min(pieces of the row, max_pieces) + 2 (max_pieces < 0: no limit).  A row
+ * of at most 4096 normalized code points (4097 entries) has its state in LDS, 25 bytes an entry: rows of
+ * up to 512 in 12.7 KiB (seven workgroups per CU), longer ones in 100 KiB (one per CU of 160 KiB).  A longer row goes
+ * through the workspace by the same code and gives the same result.  longest_row [host]: an upper bound of the rows'
+ * entries (a row beyond it comes out as bos, eos).  workspace: snx_ug_workspace_bytes(longest_row) bytes, 0 when every row
+ * fits LDS.  snx_wp_fill(norm_ptr, pieces, ...) and snx_wp_pad finish the rows as for WordPiece.
+ * Stream-ordered, nothing allocated, no host synchronisation. */
+size_t snx_ug_workspace_bytes(int64_t longest_row);
+int snx_ug_norm_count(const int64_t* ptr, const int32_t* code_points, int32_t n, const int32_t* nmap, int64_t* out_len,
+                      hipStream_t stream);
+int snx_ug_norm_fill(const int64_t* ptr, const int32_t* code_points, int32_t n, const int32_t* nmap, const int32_t* pool,
+                     const int64_t* norm_ptr, int32_t* norm, hipStream_t stream);
+int snx_ug_pieces(const int64_t* norm_ptr, const int32_t* norm, int32_t n, int64_t longest_row, const int32_t* slots,
+                  int32_t n_slots, const int32_t* ent_ptr, const int32_t* ent_cps, const int32_t* ent_id,
+                  const double* ent_score, int32_t n_entries, int32_t max_entry, int32_t unk_id, double unk_score,
+                  int64_t max_pieces, int32_t* pieces, int64_t* out_cnt, void* workspace, size_t ws_bytes,
+                  hipStream_t stream);
+
 /* ---- Co-occurrence and PMI (csrc/cooc.hip): the reference's src/pmi package -- windowed co-occurrence counts
  * (ref:src/pmi/cooccurrence.py:206-226) and PMI with Laplace and context-distribution smoothing
  * (ref:src/pmi/pmi_calculator.py:142-193).  Input is token ids, never text: rows as a CSR, ptr [n_rows+1] int64, ids int32

@@ -64,6 +64,9 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     # and for the term-expansion count: the eight keys of a lane, its counter and the thresholds read back from LDS stay in
     # registers; the finalize kernel holds no LDS and is not listed
     "expansion.hip": ("ex_count_kernel",),
+    # and for the Unigram tokenizer: the recurrence's float64 best, the winning piece and the probe's hash state stay in
+    # registers, the row's state in LDS (or the workspace); the count kernel holds nothing that could spill
+    "unigram.hip": ("ug_pieces_kernel", "ug_pieces_long_kernel", "ug_norm_fill_kernel"),
 }
 
 # Kernels held to the global-load / vmcnt rule: nothing may touch a load's destination before a vmcnt wait that retires it.

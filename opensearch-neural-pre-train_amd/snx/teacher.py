@@ -249,6 +249,22 @@ def _check_pooling(model_dir: str) -> None:
         raise ValueError(f"teacher: {path} does not describe CLS pooling (only pooling_mode_cls_token is supported)")
 
 
+def _length_batches(lens: Sequence[int], batch_size: Optional[int], batch_tokens: int):
+    """The batches of ``TeacherEncoder.encode``: the rows sorted by length (stable: equal lengths keep input order) and cut
+    into runs of at most ``batch_tokens`` token rows and ``batch_size`` sequences; a longer single row runs alone."""
+    order = sorted(range(len(lens)), key=lambda i: lens[i])
+    batch: List[int] = []
+    rows = 0
+    for i in order:
+        if batch and (rows + lens[i] > int(batch_tokens) or (batch_size is not None and len(batch) >= int(batch_size))):
+            yield batch
+            batch, rows = [], 0
+        batch.append(i)
+        rows += lens[i]
+    if batch:
+        yield batch
+
+
 class TeacherEncoder:
     """The dense teacher on one device.  ``cuda``: the native forward (csrc/teacher.hip) in ``precision`` "bf16" or "fp32";
     ``cpu``: ``forward_torch`` (with ``emulate_bf16`` for "bf16").  ``state_dict``: XLMRobertaModel's tensors, with or
@@ -301,6 +317,14 @@ class TeacherEncoder:
             return self
         return TeacherEncoder(self.config, self.params, dev, self.precision)
 
+    def _on_my_gpu(self, tokenizer) -> bool:
+        """Does ``tokenizer`` return a CSR of ids (``encode_rows``) on this encoder's GPU?"""
+        dev = getattr(tokenizer, "device", None)
+        if self.device.type != "cuda" or not hasattr(tokenizer, "encode_rows") or not isinstance(dev, torch.device) or \
+                dev.type != "cuda":
+            return False
+        return (dev.index if dev.index is not None else torch.cuda.current_device()) == self.device.index
+
     @torch.no_grad()
     def encode_tokens(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, normalize: bool = True) -> torch.Tensor:
         """A padded batch [n, S] -> fp32 [n, hidden] on the encoder's device: the CLS row of every sequence (its first
@@ -309,17 +333,23 @@ class TeacherEncoder:
             cls, emb = forward_torch(self.config, self.params, input_ids, attention_mask,
                                      emulate_bf16=self.precision == "bf16")
             return emb if normalize else cls
-        from ._lib import call, fn
         ids, mask, pos = _check_batch(self.config, input_ids, attention_mask)
         keep = mask.bool()
         lens = mask.sum(dim=1)
-        n, T, max_len = int(ids.shape[0]), int(lens.sum()), int(lens.max())
-        cu = torch.zeros(n + 1, dtype=torch.int32, device=lens.device)
+        cu = torch.zeros(int(ids.shape[0]) + 1, dtype=torch.int32, device=lens.device)
         cu[1:] = torch.cumsum(lens, 0)
         dev = self.device
-        ids_u = ids[keep].to(dev).contiguous()
-        pos_u = pos[keep].to(torch.int32).to(dev).contiguous()
-        cu = cu.to(dev)
+        return self._forward_unpadded(ids[keep].to(dev).contiguous(), pos[keep].to(torch.int32).to(dev).contiguous(),
+                                      cu.to(dev), int(lens.max()), normalize)
+
+    def _forward_unpadded(self, ids_u: torch.Tensor, pos_u: torch.Tensor, cu: torch.Tensor, max_len: int,
+                          normalize: bool) -> torch.Tensor:
+        """The native forward over unpadded token rows, all on the encoder's GPU: ``ids_u`` int64 [T] and ``pos_u`` int32
+        [T], sequence after sequence; ``cu`` int32 [n + 1] their offsets; ``max_len`` the longest sequence.  The caller
+        has checked ids and positions."""
+        from ._lib import call, fn
+        dev = self.device
+        n, T = int(cu.numel()) - 1, int(ids_u.numel())
         H, prec = self.config.hidden_size, PRECISIONS[self.precision]
         with torch.cuda.device(dev):
             need = int(fn("snx_teacher_workspace_bytes")(C.byref(self._desc), T, n, prec))
@@ -335,37 +365,70 @@ class TeacherEncoder:
                  p(self._ws), p(cls), p(emb), T, n, max_len, prec, self._stream())
         return emb if normalize else cls
 
+    def encode_unpadded(self, ptr: torch.Tensor, ids: torch.Tensor, batch_size: Optional[int] = None,
+                        batch_tokens: int = DEFAULT_BATCH_TOKENS, normalize: bool = True) -> torch.Tensor:
+        """A CSR of token ids on the encoder's GPU (``ptr`` int64 [n + 1], ``ids`` int64, every row <s> ... </s>: a GPU
+        tokenizer's ``encode_rows``) -> fp32 [n, hidden], rows in input order.  The same stable length sort and the same
+        batches as ``encode`` forms from lists, so the same bits.  One host read (the row lengths, with the flag of the id
+        check); ids and positions are gathered from the CSR on the device."""
+        if self.device.type != "cuda" or ptr.device != self.device or ids.device != self.device:
+            raise ValueError("teacher: encode_unpadded needs ptr and ids on the encoder's GPU")
+        n = int(ptr.numel()) - 1
+        out = torch.empty((n, self.config.hidden_size), dtype=torch.float32, device=self.device)
+        if n == 0:
+            return out
+        pad = self.config.pad_token_id
+        with torch.cuda.device(self.device):
+            ptr, ids = ptr.to(torch.long), ids.to(torch.long)
+            row_len = ptr[1:] - ptr[:-1]
+            bad = ((ids < 0) | (ids >= self.config.vocab_size)).any().to(torch.long)
+            *lens, bad = torch.cat((row_len, bad[None])).tolist()      # the one host read
+            if any(l <= 0 for l in lens):
+                raise ValueError("teacher: the tokenizer returned an empty sequence")
+            if bad:
+                raise ValueError(f"teacher: input_ids must lie in [0, {self.config.vocab_size})")
+            if max(lens) + pad >= self.config.max_position_embeddings:
+                raise ValueError(f"teacher: position {max(lens) + pad} >= max_position_embeddings "
+                                 f"{self.config.max_position_embeddings}")
+            for batch in _length_batches(lens, batch_size, batch_tokens):
+                T = sum(lens[j] for j in batch)
+                b = torch.tensor(batch, dtype=torch.long, device=self.device)
+                blen = row_len[b]
+                cu = torch.zeros(len(batch) + 1, dtype=torch.long, device=self.device)
+                torch.cumsum(blen, 0, out=cu[1:])
+                within = torch.arange(T, dtype=torch.long, device=self.device) - \
+                    torch.repeat_interleave(cu[:-1], blen, output_size=T)
+                ids_u = ids[torch.repeat_interleave(ptr[b], blen, output_size=T) + within]
+                pos_u = (within + (pad + 1)).to(torch.int32)
+                out[b] = self._forward_unpadded(ids_u, pos_u, cu.to(torch.int32), max(lens[j] for j in batch), normalize)
+        return out
+
     def encode(self, texts: Sequence[str], tokenizer: Callable, batch_size: Optional[int] = None, max_length: int = 512,
                batch_tokens: int = DEFAULT_BATCH_TOKENS, normalize: bool = True) -> torch.Tensor:
         """Texts -> fp32 [n, hidden] on the encoder's device, rows in input order.  ``tokenizer``: an HF tokenizer (called
         with ``truncation=True, max_length=max_length, padding=False``; its ``input_ids`` carry <s> ... </s>).  The texts are
         sorted by token length and packed into forwards of at most ``batch_tokens`` token rows (and ``batch_size``
-        sequences, when given); a longer single text runs alone."""
+        sequences, when given); a longer single text runs alone.  A tokenizer with ``encode_rows`` that lives on the encoder's
+        GPU (snx.unigram.UnigramTokenizer) hands its CSR of ids to ``encode_unpadded``: same batches, same bits, and the ids
+        never leave the device."""
         texts = list(texts)
         if int(batch_tokens) < 1 or (batch_size is not None and int(batch_size) < 1):
             raise ValueError("teacher: batch_tokens and batch_size must be positive")
         out = torch.empty((len(texts), self.config.hidden_size), dtype=torch.float32, device=self.device)
         if not texts:
             return out
+        if self._on_my_gpu(tokenizer):
+            ptr, ids = tokenizer.encode_rows(texts, int(max_length))
+            return self.encode_unpadded(ptr, ids, batch_size=batch_size, batch_tokens=batch_tokens, normalize=normalize)
         seqs = [list(s) for s in tokenizer(texts, truncation=True, max_length=int(max_length), padding=False)["input_ids"]]
         if any(len(s) == 0 for s in seqs):
             raise ValueError("teacher: the tokenizer returned an empty sequence")
-        order = sorted(range(len(seqs)), key=lambda i: len(seqs[i]))       # stable: equal lengths keep input order
-        batch: List[int] = []
-        rows = 0
-        for i in order + [None]:
-            full = i is None or (batch and (rows + len(seqs[i]) > int(batch_tokens) or
-                                            (batch_size is not None and len(batch) >= int(batch_size))))
-            if full and batch:
-                S = max(len(seqs[j]) for j in batch)
-                ids = torch.full((len(batch), S), self.config.pad_token_id, dtype=torch.long)
-                mask = torch.zeros((len(batch), S), dtype=torch.long)
-                for b, j in enumerate(batch):
-                    ids[b, :len(seqs[j])] = torch.tensor(seqs[j], dtype=torch.long)
-                    mask[b, :len(seqs[j])] = 1
-                out[torch.tensor(batch, device=self.device)] = self.encode_tokens(ids, mask, normalize=normalize)
-                batch, rows = [], 0
-            if i is not None:
-                batch.append(i)
-                rows += len(seqs[i])
+        for batch in _length_batches([len(s) for s in seqs], batch_size, batch_tokens):
+            S = max(len(seqs[j]) for j in batch)
+            ids = torch.full((len(batch), S), self.config.pad_token_id, dtype=torch.long)
+            mask = torch.zeros((len(batch), S), dtype=torch.long)
+            for b, j in enumerate(batch):
+                ids[b, :len(seqs[j])] = torch.tensor(seqs[j], dtype=torch.long)
+                mask[b, :len(seqs[j])] = 1
+            out[torch.tensor(batch, device=self.device)] = self.encode_tokens(ids, mask, normalize=normalize)
         return out

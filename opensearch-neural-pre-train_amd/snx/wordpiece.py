@@ -109,7 +109,7 @@ class WordPieceTokenizer:
                 table_size <<= 1
         table_size = int(table_size)
         if table_size < max(E, 1) or table_size & (table_size - 1):
-            raise ValueError(f"WordPieceTokenizer: table_size must be a power of two >= the {E} vocabulary entries")
+            raise ValueError(f"{type(self).__name__}: table_size must be a power of two >= the {E} vocabulary entries")
         self.table_size = table_size
         self._state = None
         self.last_stats = {"rows": 0, "host_rows": 0, "pack_s": 0.0, "device_s": 0.0}
@@ -176,6 +176,23 @@ class WordPieceTokenizer:
         longest = max((len(k) for _, k, _ in self._entries), default=1)
         self._max_entry = max(1, min(longest, max_word))      # a longer entry can match no word
 
+        self._parse_template(spec)
+
+        self._added: Dict[str, int] = {}
+        for a in spec.get("added_tokens") or []:
+            if a.get("normalized") or a.get("lstrip") or a.get("rstrip") or a.get("single_word"):
+                _refuse("added_tokens", f"{a.get('content')!r}: normalized / lstrip / rstrip / single_word are not supported")
+            if a.get("content"):
+                self._added[str(a["content"])] = int(a["id"])
+        # leftmost-longest, as the library's matcher: at one position the longer content is tried first
+        alts = sorted(self._added, key=len, reverse=True)
+        self._added_re = re.compile("|".join(re.escape(a) for a in alts)) if alts else None
+        self._first_chars = frozenset(a[0] for a in alts)
+        self._id_to_token: Dict[int, str] = {v: k for k, v in self._vocab.items()}
+        self._id_to_token.update({v: k for k, v in self._added.items()})
+
+    def _parse_template(self, spec: dict) -> None:
+        """The frame ``<special> $A <special>`` of post_processor -> ``_bos``, ``_eos``."""
         post = spec.get("post_processor")
         if not isinstance(post, dict) or post.get("type") != "TemplateProcessing":
             _refuse("post_processor", f"type {post.get('type') if isinstance(post, dict) else post!r} is not supported, only "
@@ -198,19 +215,6 @@ class WordPieceTokenizer:
                 _refuse("post_processor.special_tokens", f"{name!r} must have exactly one id")
             frame.append(int(ids[0]))
         self._bos, self._eos = frame
-
-        self._added: Dict[str, int] = {}
-        for a in spec.get("added_tokens") or []:
-            if a.get("normalized") or a.get("lstrip") or a.get("rstrip") or a.get("single_word"):
-                _refuse("added_tokens", f"{a.get('content')!r}: normalized / lstrip / rstrip / single_word are not supported")
-            if a.get("content"):
-                self._added[str(a["content"])] = int(a["id"])
-        # leftmost-longest, as the library's matcher: at one position the longer content is tried first
-        alts = sorted(self._added, key=len, reverse=True)
-        self._added_re = re.compile("|".join(re.escape(a) for a in alts)) if alts else None
-        self._first_chars = frozenset(a[0] for a in alts)
-        self._id_to_token: Dict[int, str] = {v: k for k, v in self._vocab.items()}
-        self._id_to_token.update({v: k for k, v in self._added.items()})
 
     def _roles(self, config: dict, smap: dict) -> None:
         for role in _ROLES:
@@ -332,19 +336,19 @@ class WordPieceTokenizer:
             self._state = st
         return self._state
 
-    @staticmethod
-    def _texts(texts) -> List[str]:
+    @classmethod
+    def _texts(cls, texts) -> List[str]:
         texts = list(texts)
         if any(not isinstance(t, str) for t in texts):
-            raise ValueError("WordPieceTokenizer: texts must be strings")
+            raise ValueError(f"{cls.__name__}: texts must be strings")
         return texts
 
-    @staticmethod
-    def _max_length(max_length) -> Optional[int]:
+    @classmethod
+    def _max_length(cls, max_length) -> Optional[int]:
         if max_length is None:
             return None
         if isinstance(max_length, bool) or int(max_length) < 2:
-            raise ValueError("WordPieceTokenizer: max_length must be >= 2 (the frame alone takes two ids)")
+            raise ValueError(f"{cls.__name__}: max_length must be >= 2 (the frame alone takes two ids)")
         return int(max_length)
 
     def encode_rows(self, texts: Sequence[str], max_length: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -428,25 +432,25 @@ class WordPieceTokenizer:
         if single:
             texts = [texts]
         if return_tensors not in (None, "pt"):
-            raise ValueError("WordPieceTokenizer: return_tensors must be \"pt\" or None")
+            raise ValueError(f"{type(self).__name__}: return_tensors must be \"pt\" or None")
         if padding not in (True, False, "longest", "max_length"):
-            raise ValueError("WordPieceTokenizer: padding must be True, False, \"longest\" or \"max_length\"")
+            raise ValueError(f"{type(self).__name__}: padding must be True, False, \"longest\" or \"max_length\"")
         limit = (max_length if max_length is not None else self.model_max_length) if truncation else None
         ptr, ids, widest = self._encode_rows(texts, limit)
         n = ptr.numel() - 1
         if not padding or return_tensors is None:
             if padding:
-                raise ValueError("WordPieceTokenizer: padded rows are returned as tensors (return_tensors=\"pt\")")
+                raise ValueError(f"{type(self).__name__}: padded rows are returned as tensors (return_tensors=\"pt\")")
             p, flat = ptr.tolist(), ids.tolist()
             rows = [flat[p[r]:p[r + 1]] for r in range(n)]
             masks = [[1] * len(r) for r in rows]
             return {"input_ids": rows[0] if single else rows, "attention_mask": masks[0] if single else masks}
         if padding == "max_length":
             if max_length is None:
-                raise ValueError("WordPieceTokenizer: padding=\"max_length\" needs max_length")
+                raise ValueError(f"{type(self).__name__}: padding=\"max_length\" needs max_length")
             L = int(max_length)
             if widest > L:
-                raise ValueError("WordPieceTokenizer: a row is longer than max_length (truncation=False)")
+                raise ValueError(f"{type(self).__name__}: a row is longer than max_length (truncation=False)")
         else:
             L = widest
         pad = self.pad_token_id if self.pad_token_id is not None else 0

@@ -25,7 +25,8 @@ class BGEM3Teacher(nn.Module):
     """BGE-M3 as teacher model: dense embeddings, soft labels for contrastive distillation, ranking scores.
 
     ``model_dir``: a local HF / sentence-transformers directory (``TeacherEncoder.from_pretrained``), or a ready
-    ``TeacherEncoder``.  ``tokenizer``: an HF tokenizer; default: the one stored in ``model_dir``."""
+    ``TeacherEncoder``.  ``tokenizer``: an HF tokenizer, or ``"gpu:DIR"`` / ``"unigram:DIR"`` for the native Unigram tokenizer
+    of ``DIR/tokenizer.json`` (snx.unigram) on the teacher's GPU / in plain Python; default: the one stored in ``model_dir``."""
 
     def __init__(self, model_dir: Union[str, TeacherEncoder] = "BAAI/bge-m3", device: str = "cuda", max_length: int = 512,
                  normalize_embeddings: bool = True, tokenizer=None, precision: str = "bf16",
@@ -42,6 +43,11 @@ class BGEM3Teacher(nn.Module):
                 raise ValueError("BGEM3Teacher: a ready TeacherEncoder needs tokenizer=...")
         else:
             self.model = TeacherEncoder.from_pretrained(model_dir, device=device, precision=precision)
+        if isinstance(tokenizer, str):
+            if not tokenizer.startswith(("gpu:", "unigram:")):
+                raise ValueError("BGEM3Teacher: a tokenizer given by name must be gpu:DIR or unigram:DIR")
+            from src.train.data.collator import create_tokenizer
+            tokenizer = create_tokenizer(tokenizer, device=self.model.device)
         self.tokenizer = tokenizer if tokenizer is not None else _load_tokenizer(model_dir)
 
     @torch.no_grad()

@@ -1,7 +1,8 @@
 """Teacher embeddings, teacher scores and dense hard negatives (snx.teacher, src.train.mining.dense), on one GPU.
 
     python -m src.train.cli.teacher_scores encode --model-dir /models/bge-m3 --input-pattern "data/v29.0/train_*.jsonl" \\
-        --output-dir cache [--max-length 256] [--batch-tokens 16384] [--precision bf16|fp32] [--num-shards n --shard-index i]
+        --output-dir cache [--max-length 256] [--batch-tokens 16384] [--precision bf16|fp32] [--num-shards n --shard-index i] \\
+        [--tokenizer gpu:TOKENIZER_DIR|unigram:TOKENIZER_DIR]
     python -m src.train.cli.teacher_scores encode --merge --output-dir cache        # after a sharded run
     python -m src.train.cli.teacher_scores score --embeddings cache/embeddings.npy --text-index cache/text_index.json \\
         --input-pattern "data/v29.0/train_*.jsonl" --output-dir data/v29.0_kd
@@ -58,6 +59,10 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     sp.add_argument("--num-shards", type=int, default=1)
     sp.add_argument("--shard-index", type=int, default=0)
     sp.add_argument("--merge", action="store_true", help="join the parts of a sharded run into embeddings.npy")
+    sp.add_argument("--tokenizer", type=str, default=None,
+                    help="gpu:DIR: the native Unigram tokenizer of DIR/tokenizer.json on the GPU, its token ids go to the "
+                         "forward without leaving the device; unigram:DIR: the same ids from plain Python; default: the "
+                         "Hugging Face tokenizer stored in --model-dir")
     sp.add_argument("--device", type=str, default="cuda:0")
     args = ap.parse_args(argv)
     if args.command == "encode":
@@ -65,6 +70,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             ap.error("encode needs --model-dir (or --merge)")
         if args.num_shards < 1 or not 0 <= args.shard_index < args.num_shards or args.max_length < 1 or args.batch_tokens < 1:
             ap.error("need --num-shards >= 1, 0 <= --shard-index < --num-shards, --max-length >= 1, --batch-tokens >= 1")
+        if args.tokenizer is not None and not args.tokenizer.startswith(("gpu:", "unigram:")):
+            ap.error("--tokenizer must be gpu:DIR or unigram:DIR")
     if args.command == "mine" and (args.k < 1 or not 0 <= args.rank_start < args.rank_end <= 1024):
         ap.error("need --k >= 1 and 0 <= --rank-start < --rank-end <= 1024")
     if args.command == "mine" and not 1 <= args.nprobe <= args.nlist:
@@ -74,7 +81,7 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
 
 def encode_main(args: argparse.Namespace, tokenizer=None):
     """``encode``: (unique texts, rows written), or the merged rows for ``--merge``.  ``tokenizer``: an HF tokenizer to use
-    instead of the one stored in ``--model-dir``."""
+    instead of the one stored in ``--model-dir`` (it goes before ``--tokenizer``)."""
     from src.train.mining import expand_files
     from src.train.mining.dense import merge_teacher_cache, write_teacher_cache
     if args.merge:
@@ -85,6 +92,8 @@ def encode_main(args: argparse.Namespace, tokenizer=None):
     if not files:
         raise FileNotFoundError(f"no input files match {args.input_pattern!r}")
     from src.model.teachers import BGEM3Teacher
+    if tokenizer is None and args.tokenizer:
+        tokenizer = args.tokenizer                               # gpu:DIR | unigram:DIR, resolved on the teacher's device
     teacher = BGEM3Teacher(args.model_dir, device=args.device, max_length=args.max_length, normalize_embeddings=True,
                            tokenizer=tokenizer, precision=args.precision, batch_tokens=args.batch_tokens)
     out = write_teacher_cache(files, args.output_dir, teacher.encode, teacher.model.config.hidden_size,

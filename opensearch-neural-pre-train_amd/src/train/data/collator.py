@@ -3,9 +3,10 @@ ref:src/train/cli/train_v33_ddp.py:44 from a module that is absent from the refe
 
 Offline rules: a local directory is loaded with ``transformers.AutoTokenizer`` (e.g. an export
 like ref:huggingface/v33/ with its BertTokenizer files); the pseudo-name ``hash:<vocab>`` gives
-the deterministic whitespace-hash tokenizer used for synthetic runs; ``gpu:DIR`` gives the native
-WordPiece tokenizer of ``DIR/tokenizer.json`` on the GPU (snx.wordpiece) and ``wordpiece:DIR`` the same
-class on the host; a hub NAME cannot be resolved without a network and raises."""
+the deterministic whitespace-hash tokenizer used for synthetic runs; ``gpu:DIR`` gives the native tokenizer of
+``DIR/tokenizer.json`` on the GPU, chosen by its ``model.type``: WordPiece (snx.wordpiece, the student's) or Unigram
+(snx.unigram, the dense teacher's); ``wordpiece:DIR`` and ``unigram:DIR`` give those classes on the host; a hub NAME
+cannot be resolved without a network and raises."""
 from __future__ import annotations
 
 import os
@@ -58,13 +59,28 @@ class HashTokenizer:
             f.write('{"type": "hash", "vocab_size": %d}\n' % self.vocab_size)
 
 
-def create_tokenizer(name: str):
+def _model_type(path: str):
+    """``model.type`` of ``path/tokenizer.json``; None when the file is absent or unreadable (the loader then says why)."""
+    import json
+    try:
+        with open(os.path.join(path, "tokenizer.json"), encoding="utf-8") as f:
+            model = json.load(f).get("model")
+        return model.get("type") if isinstance(model, dict) else None
+    except (OSError, ValueError, AttributeError):
+        return None
+
+
+def create_tokenizer(name: str, device="cuda"):
+    """``device``: the GPU of a ``gpu:DIR`` tokenizer (default: the current one); the other forms ignore it."""
     if isinstance(name, str) and name.startswith("hash:"):
         return HashTokenizer(int(name.split(":")[1]))
-    if isinstance(name, str) and name.startswith(("gpu:", "wordpiece:")):
-        from snx.wordpiece import WordPieceTokenizer
+    if isinstance(name, str) and name.startswith(("gpu:", "wordpiece:", "unigram:")):
         kind, path = name.split(":", 1)
-        return WordPieceTokenizer.from_pretrained(path, device="cuda" if kind == "gpu" else "cpu")
+        if kind == "unigram" or (kind == "gpu" and _model_type(path) == "Unigram"):
+            from snx.unigram import UnigramTokenizer
+            return UnigramTokenizer.from_pretrained(path, device=device if kind == "gpu" else "cpu")
+        from snx.wordpiece import WordPieceTokenizer
+        return WordPieceTokenizer.from_pretrained(path, device=device if kind == "gpu" else "cpu")
     if os.path.isdir(name):
         if os.path.exists(os.path.join(name, "hash_tokenizer.json")):
             import json
