@@ -584,6 +584,59 @@ int snx_ivf_search(const float* Q, int32_t nq, int32_t D, const float* E_sorted,
                    int32_t hi, int32_t split_docs, int32_t* out_doc, float* out_score, int32_t* out_found, void* workspace,
                    size_t ws_bytes, hipStream_t stream);
 
+/* ---- graph dense retrieval (csrc/graph.hip): an approximate inner-product top-k in the ROLE of the HNSW field behind the
+ * reference's dense benchmark rows (ref:benchmark/index_manager.py:98-110: "hnsw", faiss, innerproduct, ef_construction
+ * 128, m 16; queried by ref:benchmark/searchers.py:97-127 and the dense legs of hybrid_searcher.py).  It is NOT FAISS's
+ * graph: FAISS inserts sequentially with a random level per point.  This is a deterministic fixed-degree graph of the
+ * CAGRA family -- kNN lists, rank-based pruning, reverse edges, a best-first beam -- and every result is a pure function
+ * of the embeddings and the parameters.
+ * Definition.  s(x, y) is the score of the exact dense section, with the same bits.  E [nd, D] fp32 finite, 1 <= D <= 4096,
+ * nd < 2^31.
+ *   Neighbour lists  N [nd, knn] int32, degree <= knn <= 128: N[u] = the min(knn, nd-1) docs x != u with the best
+ *     s(E[u], E[x]), ties to the lowest id, the rest of the row -1.  This is snx_dense_search_band with lo = 0, hi = knn and
+ *     the one-entry exclusion row {u}: the caller runs it and hands the ids over (or lists from elsewhere: every row
+ *     distinct ids in [0, nd) other than u, then -1).
+ *   Detours  With v_0 .. v_{K-1} the valid entries of N[u] and rank_w(x) the column of x in N[w] (infinity when absent):
+ *     detour(u, j) = #{ i < j : rank_{v_i}(v_j) < j }, the two-hop routes u -> v_i -> v_j whose two edges both rank better
+ *     than the direct edge (CAGRA's rule).
+ *   Forward list  F[u] = the ids v_j of the min(degree, K) columns j with the smallest (detour(u, j), j), in that order.
+ *   Reverse list  R[v] = the pairs (p, u) with F[u][p] == v, ordered by (p, u) ascending, the first `degree` kept.
+ *   Graph  G [nd, degree] int32: G[v] = the first `degree` distinct ids of F[v][0], R[v][0], F[v][1], R[v][1], ...; when one
+ *     list runs out the other continues; padded with -1.  Integers only: no float arithmetic, and no atomic whose order
+ *     shows in the result.
+ *   Entry sample  entry_i = floor(i * nd / nentry), i = 0 .. nentry-1, in int64; nentry clamped to [min(ef, nd), nd]
+ *     (snx.retrieval.GraphIndex's default: 4 * ceil(sqrt(nd))).
+ *   Seeds  the best min(ef, nentry) docs of the entry sample by s(q, E[entry_i]), ties to the lowest doc id: snx_dense_search
+ *     over the gathered entry rows, run by the caller, ids mapped back -> seeds [nq, nseed] int32 (distinct docs; an id
+ *     outside [0, nd) is skipped).  The kernel scores the seeds itself, to the same bits.
+ *   Walk  1 <= ef <= 1024, 1 <= width <= 8, max_iter >= 0 (0: no cap).  The pool P holds at most ef entries (score, doc,
+ *     expanded), score descending, doc ascending; it starts as the seeds, all unexpanded.  One iteration: take the first
+ *     `width` unexpanded entries of P in pool order and mark them expanded; walk their G rows in parent order, then column
+ *     order; drop -1, every doc already scored for this query (seeds included) and all but the first occurrence of a doc
+ *     inside the batch; score the rest; merge into P and keep the best ef.  The walk stops when P has no unexpanded entry
+ *     or after max_iter iterations; out_iters [nq] (or NULL) = iterations run.
+ *   Result  search: lo = 0, hi = k <= ef: ranks 0 .. k-1 of P.  Band: ranks lo .. hi-1 (hi <= ef) of the ADMISSIBLE entries
+ *     of the final P (not in the exclusion row, s < ceiling[q]: the rules and operands of snx_dense_search_band).  The band
+ *     filter applies to the output only: the walk does not see it.  Unused slots doc -1, score 0; out_found [nq] (or NULL)
+ *     = filled slots.
+ * The kernel's visited filter is a bounded table that stores full doc ids and may forget; it never reports an unscored doc
+ * as scored, and a doc scored twice cannot change P (a scored doc outside P lies below the worst entry of a full P, which
+ * only rises; one inside P is found by its key).  Hence ef >= nd (every doc a seed) gives snx_dense_search's result bit
+ * for bit, every returned score equals snx_dense_pair_scores', and no result depends on how the queries are sliced, on
+ * the workspace or on how the docs arrived.
+ * snx_graph_optimize: N -> G, and F [nd, degree] when `forward` is not NULL.  workspace:
+ * snx_graph_optimize_workspace_bytes(nd, knn, degree) bytes.  snx_graph_search: workspace
+ * snx_graph_search_workspace_bytes(nq, ef, width, degree) bytes (the final pools); it grows with nq * ef, never with nd. */
+size_t snx_graph_optimize_workspace_bytes(int32_t nd, int32_t knn, int32_t degree);
+int snx_graph_optimize(const int32_t* neighbors, int32_t nd, int32_t knn, int32_t degree, int32_t* graph, int32_t* forward,
+                       void* workspace, size_t ws_bytes, hipStream_t stream);
+size_t snx_graph_search_workspace_bytes(int32_t nq, int32_t ef, int32_t width, int32_t degree);
+int snx_graph_search(const float* Q, int32_t nq, int32_t D, const float* E, int32_t nd, const int32_t* graph,
+                     int32_t degree, const int32_t* seeds, int32_t nseed, int32_t ef, int32_t width, int32_t max_iter,
+                     const int64_t* ex_ptr, const int32_t* ex_doc, const float* ceiling, int32_t lo, int32_t hi,
+                     int32_t* out_doc, float* out_score, int32_t* out_found, int32_t* out_iters, void* workspace,
+                     size_t ws_bytes, hipStream_t stream);
+
 /* ---- MinHash near-duplicate removal (csrc/minhash.hip): the reference's MinHashDeduplicator
  * (ref:src/preprocessing/cleaners/deduplicator.py:10-187), whose two Python loops -- num_perm MD5 digests per character
  * n-gram (ref:deduplicator.py:71-80) and every new row against every kept row (ref:deduplicator.py:135-138) -- keep the

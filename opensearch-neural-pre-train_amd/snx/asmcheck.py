@@ -49,6 +49,9 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     # and for the IVF-Flat fine scan and merge, which hold the same state; the sort, row-copy and k-means kernels keep
     # nothing that could spill and are not listed
     "ivf.hip": ("iv_scan_kernel", "iv_merge_kernel"),
+    # and for the graph index: the walk's pool, query row and tables stay in LDS and a lane's accumulator in a register;
+    # the forward kernel keeps its hash and detour counts in LDS; the reverse and interleave kernels hold no LDS
+    "graph.hip": ("gr_forward_kernel", "gr_walk_kernel", "gr_output_kernel"),
     # and for MinHash: the MD5 block and the 128-bit minimum, the 32 match counters, and the resolving wave's kept bits stay
     # in registers; the stage, append and first-match kernels hold no LDS and are not listed
     "minhash.hip": ("mh_sig_kernel", "mh_match_kernel", "mh_resolve_kernel"),

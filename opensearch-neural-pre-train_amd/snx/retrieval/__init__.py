@@ -22,9 +22,12 @@ inner-product search over dense fp32 embeddings (csrc/dense.hip, include/snx.h "
 the character n-gram TF-IDF vectorizer of the reference's lexical hard-negative mining over a ``SparseIndex``
 (csrc/tfidf.hip, include/snx.h "Character n-gram TF-IDF").  ``IvfFlatIndex`` is the approximate IVF-Flat search over the
 same dense embeddings, with ``DenseIndex``'s scores and order inside the probed lists (csrc/ivf.hip, include/snx.h
-"IVF-Flat dense retrieval")."""
+"IVF-Flat dense retrieval").  ``GraphIndex`` is the approximate graph search over them, a deterministic fixed-degree
+graph walked by a best-first beam, again with ``DenseIndex``'s scores and order (csrc/graph.hip, include/snx.h "graph
+dense retrieval")."""
 from ._common import K_MAX, exclusion_csr
 from .dense import DENSE_CHUNK_MIN, DENSE_DIM_MAX, DenseIndex
+from .graph import GRAPH_DEGREE_MAX, GRAPH_EF_MAX, GRAPH_KNN_MAX, GRAPH_WIDTH_MAX, GraphIndex, entry_sample
 from .hybrid import (FUSE_L_MAX, FUSE_METHODS, FUSE_TOP_K_MAX, Bm25Index, bm25_idf, fuse_ranked, term_counts,
                      term_counts_max_len)
 from .ivf import IVF_NLIST_MAX, IVF_SPLIT_MIN, IvfFlatIndex

@@ -2,7 +2,7 @@
 (snx.retrieval.Bm25Index / fuse_ranked).
 
     python -m src.train.cli.eval_hybrid --checkpoint outputs/train_v33/final_model --val-file data/val.jsonl \\
-        [--sweep] [--dense-run dense.npz | --dense-embeddings emb.npz]
+        [--sweep] [--dense-run dense.npz | --dense-embeddings emb.npz [--dense-index flat|graph --ef 0 --degree 32]]
 
 One JSON line per method: ``sparse`` (the model's exact search), ``bm25`` (BM25 over the same token ids: the model's
 tokenizer, the evaluator's truncation and vocabulary filter; not OpenSearch's analyzer) and ``bm25_sparse_rrf``.
@@ -13,7 +13,11 @@ with ``docs`` int [nq, R] (ids in the evaluator's doc order, -1: unused) and ``s
 ref:scripts/run_7way_benchmark.py (the dense encoder itself is not part of this project).  ``--dense-embeddings`` takes
 the embeddings instead -- an .npz with ``docs`` fp32 [nd, D] and ``queries`` fp32 [nq, D] in the evaluator's corpus order
 -- and runs the reference's SemanticSearcher (inner product, ref:benchmark/searchers.py:97-127) here, exactly, on
-snx.retrieval.DenseIndex at the retrieval depth; the two flags exclude each other.  Every retriever contributes
+snx.retrieval.DenseIndex at the retrieval depth; the two flags exclude each other.  ``--dense-index graph`` searches an
+snx.retrieval.GraphIndex instead (``--degree`` links per doc, a beam of ``--ef`` entries, 0: max(100, retrieval depth)),
+the approximate search in the role of the reference's HNSW field (ref:benchmark/index_manager.py:98-110; not FAISS's
+graph); its ``dense`` line also carries ``recall_vs_exact@10`` and ``recall_vs_exact@depth`` against the flat search of the
+same run and ``mean_iterations``.  Every retriever contributes
 its top 100 (--retrieval-k) and a fused list returns the top 10.  Each line carries the metrics, the mean union size of
 fused rows and the paired t-test against ``bm25``.  One process (not torchrun)."""
 from __future__ import annotations
@@ -51,12 +55,20 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     ap.add_argument("--dense-run", type=str, default=None, help=".npz with docs [nq, R] and scores [nq, R] of a dense run")
     ap.add_argument("--dense-embeddings", type=str, default=None,
                     help=".npz with docs [nd, D] and queries [nq, D] (fp32, corpus order): the dense search runs here")
+    ap.add_argument("--dense-index", choices=("flat", "graph"), default="flat",
+                    help="how --dense-embeddings is searched: exactly, or through the graph index")
+    ap.add_argument("--ef", type=int, default=0, help="graph: beam entries (0: max(100, --retrieval-k))")
+    ap.add_argument("--degree", type=int, default=32, help="graph: links per doc (even)")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON lines to this file")
     args = ap.parse_args(argv)
     if args.dense_run and args.dense_embeddings:
         ap.error("--dense-run and --dense-embeddings exclude each other")
     if not 1 <= args.retrieval_k <= 1024:
         ap.error("--retrieval-k must lie in [1, 1024]")
+    if args.dense_index == "graph" and not args.dense_embeddings:
+        ap.error("--dense-index graph needs --dense-embeddings")
+    if not (args.ef == 0 or args.retrieval_k <= args.ef <= 1024) or not 2 <= args.degree <= 64 or args.degree % 2:
+        ap.error("need --ef 0 or --retrieval-k <= --ef <= 1024, and an even --degree in [2, 64]")
     if not args.rrf_k >= 0 or not args.k1 >= 0 or not 0 <= args.b <= 1:
         ap.error("need --rrf-k >= 0, --k1 >= 0 and --b in [0, 1]")
     return args
@@ -88,12 +100,27 @@ def load_dense_run(path: str, nq: int, nd: int, depth: int, device):
     return torch.from_numpy(docs).to(device), torch.from_numpy(scores[:, :depth].astype(np.float32)).to(device)
 
 
-def search_dense_embeddings(path: str, nq: int, nd: int, depth: int, device):
-    """The dense top lists from embeddings: an exact inner-product search of every query over every doc -> (docs int32
-    [nq, depth], scores fp32 [nq, depth]) on ``device`` (unused slots -1 / 0 when depth > nd)."""
+def list_recall(docs, exact, k: int) -> float:
+    """Mean share of the first ``k`` docs of every ``exact`` list that the same query's ``docs`` list holds in its first
+    ``k``; a query without an exact doc counts as 1."""
+    import torch
+    a, b = docs[:, :k].long(), exact[:, :k].long()
+    if not b.shape[0]:
+        return 1.0
+    hit = ((b[:, :, None] == a[:, None, :]) & (b[:, :, None] >= 0)).any(2).sum(1).double()
+    want = (b >= 0).sum(1).double()
+    return float(torch.where(want > 0, hit / want.clamp(min=1), torch.ones_like(want)).mean())
+
+
+def search_dense_embeddings(path: str, nq: int, nd: int, depth: int, device, dense_index: str = "flat", ef: int = 0,
+                            degree: int = 32):
+    """The dense top lists from embeddings -> (docs int32 [nq, depth], scores fp32 [nq, depth], extra fields of the
+    ``dense`` line) on ``device`` (unused slots -1 / 0 when depth > nd).  ``flat``: an exact inner-product search of every
+    query over every doc.  ``graph``: snx.retrieval.GraphIndex with ``degree`` links and a beam of ``ef`` entries (0:
+    max(100, depth)); the extra fields are its recall against the flat lists and the mean iteration count."""
     import numpy as np
     import torch
-    from snx.retrieval import DenseIndex
+    from snx.retrieval import DenseIndex, GraphIndex
     z = np.load(path)
     docs, queries = np.asarray(z["docs"]), np.asarray(z["queries"])
     if docs.ndim != 2 or queries.ndim != 2 or docs.shape[0] != nd or queries.shape != (nq, docs.shape[1]):
@@ -101,8 +128,19 @@ def search_dense_embeddings(path: str, nq: int, nd: int, depth: int, device):
     index = DenseIndex(int(docs.shape[1]), device)
     index.add(torch.from_numpy(np.ascontiguousarray(docs, dtype=np.float32)).to(device))
     index.build()
-    scores, ids, _, _ = index.search(torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32)).to(device), depth)
-    return ids, scores
+    q = torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32)).to(device)
+    scores, ids, _, _ = index.search(q, depth)
+    if dense_index == "flat":
+        return ids, scores, {}
+    ef = ef or max(100, depth)
+    graph = GraphIndex(int(docs.shape[1]), device, degree=degree, knn=2 * degree, ef=ef)
+    graph.add(index.emb)
+    graph.build()
+    g_scores, g_ids = graph.search(q, depth)
+    extra = {"dense_index": "graph", "ef": ef, "degree": degree, "recall_vs_exact@10": list_recall(g_ids, ids, 10),
+             f"recall_vs_exact@{depth}": list_recall(g_ids, ids, depth),
+             "mean_iterations": float(graph.last_iterations.double().mean()) if nq else 0.0}
+    return g_ids, g_scores, extra
 
 
 def list_ranks(docs, targets):
@@ -141,8 +179,11 @@ def main(argv: Optional[List[str]] = None) -> List[dict]:
     found["bm25"] = (d, s)
     if args.dense_run:
         found["dense"] = load_dense_run(args.dense_run, nq, nd, depth, device)
+    dense_extra = {}
     if args.dense_embeddings:
-        found["dense"] = search_dense_embeddings(args.dense_embeddings, nq, nd, depth, device)
+        d, s, dense_extra = search_dense_embeddings(args.dense_embeddings, nq, nd, depth, device, args.dense_index,
+                                                    args.ef, args.degree)
+        found["dense"] = (d, s)
     ranks, totals = {}, {}
     for name, method, params, members in rows(args):
         if method is None:
@@ -163,6 +204,8 @@ def main(argv: Optional[List[str]] = None) -> List[dict]:
                         **metrics_from_ranks(ranks[name]))
             if method is not None:
                 line["total"] = totals[name]
+            if name == "dense":
+                line.update(dense_extra)
             # json has no nan: a t-test without variation (bm25 against itself) is written as null
             line.update(vs_bm25_statistic=None if t["statistic"] != t["statistic"] else t["statistic"],
                         vs_bm25_p=None if t["p_value"] != t["p_value"] else t["p_value"],

@@ -8,7 +8,7 @@
         --input-pattern "data/v29.0/train_*.jsonl" --output-dir data/v29.0_kd
     python -m src.train.cli.teacher_scores mine --embeddings cache/embeddings.npy --text-index cache/text_index.json \\
         --input-pattern "data/v29.0_kd/train_*.jsonl" --output-dir data/v30.0_multi_neg --k 7 --rank-start 10 --rank-end 50 \\
-        [--index flat|ivf --nlist 100 --nprobe 1]
+        [--index flat|ivf|graph --nlist 100 --nprobe 1 --degree 32 --ef 0]
 
 ``encode`` is the encoder of ref:scripts/precompute_teacher_scores.py:49-159 (unique texts in first-occurrence order, BGE-M3
 dense embeddings, L2-normalised) on the native XLM-RoBERTa forward; it writes ``embeddings.npy`` / ``text_index.json``.  A
@@ -16,7 +16,9 @@ sharded run (one process per GPU, ``--num-shards n --shard-index i``) writes ``e
 them.  ``score`` is the rest of that script (it reads the cache); ``mine`` is ref:scripts/mine_multi_negatives.py.  Flags
 shared with those scripts keep their names and defaults.  ``mine --index ivf`` searches an ``snx.retrieval.IvfFlatIndex``
 (``--nlist`` lists trained on the corpus rows, ``--nprobe`` of them read per query) instead of every doc; ``--nprobe`` equal
-to the list count writes the files of ``--index flat``.  Every subcommand runs as a single process."""
+to the list count writes the files of ``--index flat``.  ``mine --index graph`` searches an ``snx.retrieval.GraphIndex``
+(``--degree`` links per doc, a beam of ``--ef`` entries, 0: max(100, --rank-end)); an ``--ef`` of at least the doc count
+writes the files of ``--index flat``.  Every subcommand runs as a single process."""
 from __future__ import annotations
 
 import argparse
@@ -46,9 +48,12 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             sp.add_argument("--sample", choices=("first", "random"), default="first")
             sp.add_argument("--seed", type=int, default=42)
             sp.add_argument("--chunk-docs", type=int, default=0)
-            sp.add_argument("--index", choices=("flat", "ivf"), default="flat", help="exact search, or IVF-Flat")
+            sp.add_argument("--index", choices=("flat", "ivf", "graph"), default="flat",
+                            help="exact search, IVF-Flat, or the graph index")
             sp.add_argument("--nlist", type=int, default=100, help="IVF lists (clamped to the doc count)")
             sp.add_argument("--nprobe", type=int, default=1, help="IVF lists read per query")
+            sp.add_argument("--degree", type=int, default=32, help="graph: links per doc (even)")
+            sp.add_argument("--ef", type=int, default=0, help="graph: beam entries (0: max(100, --rank-end))")
     sp = sub.add_parser("encode", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     sp.add_argument("--model-dir", type=str, default=None, help="local HF directory of the teacher (never a model name)")
     sp.add_argument("--input-pattern", type=str, default="data/v29.0/train_*.jsonl")
@@ -76,6 +81,9 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         ap.error("need --k >= 1 and 0 <= --rank-start < --rank-end <= 1024")
     if args.command == "mine" and not 1 <= args.nprobe <= args.nlist:
         ap.error("need 1 <= --nprobe <= --nlist")
+    if args.command == "mine" and (not (args.ef == 0 or args.rank_end <= args.ef <= 1024) or not 2 <= args.degree <= 64
+                                   or args.degree % 2):
+        ap.error("need --ef 0 or --rank-end <= --ef <= 1024, and an even --degree in [2, 64]")
     return args
 
 
@@ -108,7 +116,7 @@ def main(argv: Optional[List[str]] = None, tokenizer=None):
     if args.command == "encode":
         return encode_main(args, tokenizer)
     import torch
-    from snx.retrieval import DenseIndex, IvfFlatIndex
+    from snx.retrieval import DenseIndex, GraphIndex, IvfFlatIndex
     from src.train.mining import copy_val_files, expand_files
     from src.train.mining.dense import load_teacher_cache, mine_dense_negatives, write_teacher_scores
     files = expand_files([args.input_pattern])
@@ -117,6 +125,9 @@ def main(argv: Optional[List[str]] = None, tokenizer=None):
     embeddings, text_to_idx = load_teacher_cache(args.embeddings, args.text_index)
     if args.command == "mine" and args.index == "ivf":
         index = IvfFlatIndex(int(embeddings.shape[1]), args.nlist, torch.device(args.device), nprobe=args.nprobe)
+    elif args.command == "mine" and args.index == "graph":
+        index = GraphIndex(int(embeddings.shape[1]), torch.device(args.device), degree=args.degree, knn=2 * args.degree,
+                           ef=args.ef or max(100, args.rank_end))
     else:
         index = DenseIndex(int(embeddings.shape[1]), torch.device(args.device))
     if args.command == "score":
