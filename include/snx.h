@@ -536,6 +536,44 @@ int snx_dense_search_band(const float* Q, int32_t nq, const float* E, int32_t nd
 int snx_dense_pair_scores(const float* Q, int32_t nq, const float* E, int32_t nd, int32_t D, const int32_t* pair_q,
                           const int32_t* pair_d, int64_t npairs, float* out, hipStream_t stream);
 
+/* ---- two-phase dense retrieval (csrc/dense_two_phase.hip): the result of the exact dense section with most of the work
+ * on the bf16 MFMA.  Phase 1 scores bf16 copies of the operands and proposes k1 candidates per query; phase 2 scores the
+ * candidates by the exact section's chain on the fp32 operands; a per-query certificate proves, from norms computed once,
+ * that phase 1 hid no better doc.  Operands as in the exact section (fp32, finite, 1 <= D <= 4096, nd < 2^31).
+ * snx_dense2_prepare (once per operand): X [n, D] fp32 -> Xb [n, Dp] bf16 bits, Dp = D rounded up to a multiple of 32,
+ * xhat = x rounded to nearest even (a value past the bf16 range becomes an infinity), columns D .. Dp-1 zero; and per row,
+ * in float64, norm2 = sum x^2, hat2 = sum xhat^2, res2 = sum (x - xhat)^2, each a left fold over ascending j from 0.0
+ * (every square is exact in float64, so each array is bit-reproducible).  Xb must be 16-byte aligned.
+ * snx_dense2_scan: a(q, d) = the fp32 accumulation of qhat[j] * dhat[j] on v_mfma_f32_32x32x16_bf16, k-steps of 16 in
+ * ascending order, then + 0.0f: a pure function of the two bf16 rows.  Per query the k1 best docs (1 <= k1 <= 1024) by
+ * a, descending, ties lowest doc id first -> cand_doc / cand_approx [nq, k1]; unused slots (k1 > nd) doc -1, score 0.
+ * Neither chunk_docs (as in the exact section) nor any slicing of the queries changes a bit.
+ * workspace: snx_dense2_workspace_bytes(nq, nd, k1, chunk_docs) bytes.
+ * snx_dense2_rescore: for every candidate s(q, d) of the exact section, bit for bit; a candidate is ADMISSIBLE under the
+ * rules of snx_dense_search_band (ex_ptr / ex_doc / ceiling, each may be NULL); ranks lo .. hi-1 (0 <= lo < hi <= k1) of the
+ * admissible candidates, score descending, ties lowest doc id first -> out_doc / out_score [nq, hi-lo], unused slots doc
+ * -1, score 0; out_found [nq] = filled slots.  q_norm2 / q_hat2 / q_res2 [nq]: the queries' arrays from
+ * snx_dense2_prepare; doc_norm, doc_hat, doc_res: the maxima over the docs of sqrt(norm2), sqrt(hat2), sqrt(res2).
+ * certified [nq] (uint8).  With n_q, nh_q, r_q the square roots of the query's three values, Dp as above,
+ *   g23 = m / (1 - m) for m = 2 Dp 2^-23,   g24 = m / (1 - m) for m = D 2^-24,
+ *   eps = (n_q doc_res + r_q doc_hat + g23 nh_q doc_hat + g24 n_q doc_norm) (1 + 2^-20) + D 2^-100 (1 + nh_q + doc_hat)
+ * and t = cand_approx[q, k1-1], every doc d outside the candidates has s(q, d) <= t + eps.  certified[q] = 1 when nd <= k1,
+ * or when out_found[q] == hi - lo and the score of rank hi-1 is > t + eps (float64, strict); it is 0 otherwise, and always
+ * 0 when one of the six norms, a candidate's s or a candidate's a is not finite, or when n_q doc_norm or nh_q doc_hat
+ * exceeds 2^127 (the bound takes every product and partial sum of both passes to stay inside the fp32 range).  A certified row equals
+ * snx_dense_search's (snx_dense_search_band's with the same exclusions and ceiling) bit for bit, ties included. */
+int snx_dense2_prepare(const float* X, int32_t n, int32_t D, uint16_t* Xb, double* norm2, double* hat2, double* res2,
+                       hipStream_t stream);
+size_t snx_dense2_workspace_bytes(int32_t nq, int32_t nd, int32_t k1, int32_t chunk_docs);
+int snx_dense2_scan(const uint16_t* Qb, int32_t nq, const uint16_t* Eb, int32_t nd, int32_t D, int32_t k1,
+                    int32_t chunk_docs, int32_t* cand_doc, float* cand_approx, void* workspace, size_t ws_bytes,
+                    hipStream_t stream);
+int snx_dense2_rescore(const float* Q, int32_t nq, const float* E, int32_t nd, int32_t D, const int32_t* cand_doc,
+                       const float* cand_approx, int32_t k1, const double* q_norm2, const double* q_hat2,
+                       const double* q_res2, double doc_norm, double doc_hat, double doc_res, const int64_t* ex_ptr,
+                       const int32_t* ex_doc, const float* ceiling, int32_t lo, int32_t hi, int32_t* out_doc,
+                       float* out_score, int32_t* out_found, uint8_t* certified, hipStream_t stream);
+
 /* ---- IVF-Flat dense retrieval (csrc/ivf.hip): the approximate index of the reference's dense hard-negative miner, which
  * builds faiss.IndexIVFFlat over BGE-M3 embeddings and searches it with FAISS's default nprobe
  * (ref:src/preprocessing/miners/bge_m3_miner.py:91-136, 166-249).  The lists here are this index's own (deterministic

@@ -46,6 +46,9 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     # and for the dense search: 64 accumulator registers, the prefetched operands and the merge's sort buffer stay out of
     # memory; dn_pair_kernel holds no LDS and is not listed
     "dense.hip": ("dn_search_kernel", "dn_merge_kernel"),
+    # and for the bf16 scan of the two-phase search, which holds the same state, and its rescore (sort buffer and query
+    # row in LDS); the prepare kernel keeps three float64 sums and is not listed
+    "dense_two_phase.hip": ("dn2_scan_kernel", "dn2_merge_kernel", "dn2_rescore_kernel"),
     # and for the IVF-Flat fine scan and merge, which hold the same state; the sort, row-copy and k-means kernels keep
     # nothing that could spill and are not listed
     "ivf.hip": ("iv_scan_kernel", "iv_merge_kernel"),

@@ -18,7 +18,10 @@ serving path (csrc/two_phase.hip, include/snx.h "pruning and two-phase search").
 searchers (csrc/hybrid.hip, include/snx.h "BM25 baseline and rank fusion").  ``relevance_csr``,
 ``SparseIndex.first_relevant``, ``ranked_relevance`` and ``bootstrap_means`` score any of these searches against qrels with
 several relevant docs per query (csrc/qrels.hip, include/snx.h "relevance judgments").  ``DenseIndex`` is the exact
-inner-product search over dense fp32 embeddings (csrc/dense.hip, include/snx.h "exact dense retrieval").  ``TfidfIndex`` is
+inner-product search over dense fp32 embeddings (csrc/dense.hip, include/snx.h "exact dense retrieval"); its
+``search_two_phase`` / ``search_band_two_phase`` return the same result through a bf16 first pass, an exact rescore and a
+per-query certificate, on the operands of ``bf16_rows`` (csrc/dense_two_phase.hip, include/snx.h "two-phase dense
+retrieval").  ``TfidfIndex`` is
 the character n-gram TF-IDF vectorizer of the reference's lexical hard-negative mining over a ``SparseIndex``
 (csrc/tfidf.hip, include/snx.h "Character n-gram TF-IDF").  ``IvfFlatIndex`` is the approximate IVF-Flat search over the
 same dense embeddings, with ``DenseIndex``'s scores and order inside the probed lists (csrc/ivf.hip, include/snx.h
@@ -26,7 +29,7 @@ same dense embeddings, with ``DenseIndex``'s scores and order inside the probed 
 graph walked by a best-first beam, again with ``DenseIndex``'s scores and order (csrc/graph.hip, include/snx.h "graph
 dense retrieval")."""
 from ._common import K_MAX, exclusion_csr
-from .dense import DENSE_CHUNK_MIN, DENSE_DIM_MAX, DenseIndex
+from .dense import DENSE_CHUNK_MIN, DENSE_DIM_MAX, DenseIndex, bf16_rows
 from .graph import GRAPH_DEGREE_MAX, GRAPH_EF_MAX, GRAPH_KNN_MAX, GRAPH_WIDTH_MAX, GraphIndex, entry_sample
 from .hybrid import (FUSE_L_MAX, FUSE_METHODS, FUSE_TOP_K_MAX, Bm25Index, bm25_idf, fuse_ranked, term_counts,
                      term_counts_max_len)

@@ -2,7 +2,7 @@
 (snx.retrieval.Bm25Index / fuse_ranked).
 
     python -m src.train.cli.eval_hybrid --checkpoint outputs/train_v33/final_model --val-file data/val.jsonl \\
-        [--sweep] [--dense-run dense.npz | --dense-embeddings emb.npz [--dense-index flat|graph --ef 0 --degree 32]]
+        [--sweep] [--dense-run dense.npz | --dense-embeddings emb.npz [--dense-index flat|flat2|graph --ef 0 --degree 32]]
 
 One JSON line per method: ``sparse`` (the model's exact search), ``bm25`` (BM25 over the same token ids: the model's
 tokenizer, the evaluator's truncation and vocabulary filter; not OpenSearch's analyzer) and ``bm25_sparse_rrf``.
@@ -17,7 +17,9 @@ snx.retrieval.DenseIndex at the retrieval depth; the two flags exclude each othe
 snx.retrieval.GraphIndex instead (``--degree`` links per doc, a beam of ``--ef`` entries, 0: max(100, retrieval depth)),
 the approximate search in the role of the reference's HNSW field (ref:benchmark/index_manager.py:98-110; not FAISS's
 graph); its ``dense`` line also carries ``recall_vs_exact@10`` and ``recall_vs_exact@depth`` against the flat search of the
-same run and ``mean_iterations``.  Every retriever contributes
+same run and ``mean_iterations``.  ``--dense-index flat2`` is the flat search through a bf16 first pass
+(``DenseIndex.search_two_phase(exact=True)``): the same lists bit for bit, and the ``dense`` line adds
+``certified_fraction``, the share of the queries whose list the first pass alone proved exact.  Every retriever contributes
 its top 100 (--retrieval-k) and a fused list returns the top 10.  Each line carries the metrics, the mean union size of
 fused rows and the paired t-test against ``bm25``.  One process (not torchrun)."""
 from __future__ import annotations
@@ -55,8 +57,9 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     ap.add_argument("--dense-run", type=str, default=None, help=".npz with docs [nq, R] and scores [nq, R] of a dense run")
     ap.add_argument("--dense-embeddings", type=str, default=None,
                     help=".npz with docs [nd, D] and queries [nq, D] (fp32, corpus order): the dense search runs here")
-    ap.add_argument("--dense-index", choices=("flat", "graph"), default="flat",
-                    help="how --dense-embeddings is searched: exactly, or through the graph index")
+    ap.add_argument("--dense-index", choices=("flat", "flat2", "graph"), default="flat",
+                    help="how --dense-embeddings is searched: exactly, exactly through a bf16 first pass, or through the "
+                         "graph index")
     ap.add_argument("--ef", type=int, default=0, help="graph: beam entries (0: max(100, --retrieval-k))")
     ap.add_argument("--degree", type=int, default=32, help="graph: links per doc (even)")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON lines to this file")
@@ -65,8 +68,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         ap.error("--dense-run and --dense-embeddings exclude each other")
     if not 1 <= args.retrieval_k <= 1024:
         ap.error("--retrieval-k must lie in [1, 1024]")
-    if args.dense_index == "graph" and not args.dense_embeddings:
-        ap.error("--dense-index graph needs --dense-embeddings")
+    if args.dense_index != "flat" and not args.dense_embeddings:
+        ap.error(f"--dense-index {args.dense_index} needs --dense-embeddings")
     if not (args.ef == 0 or args.retrieval_k <= args.ef <= 1024) or not 2 <= args.degree <= 64 or args.degree % 2:
         ap.error("need --ef 0 or --retrieval-k <= --ef <= 1024, and an even --degree in [2, 64]")
     if not args.rrf_k >= 0 or not args.k1 >= 0 or not 0 <= args.b <= 1:
@@ -116,7 +119,8 @@ def search_dense_embeddings(path: str, nq: int, nd: int, depth: int, device, den
                             degree: int = 32):
     """The dense top lists from embeddings -> (docs int32 [nq, depth], scores fp32 [nq, depth], extra fields of the
     ``dense`` line) on ``device`` (unused slots -1 / 0 when depth > nd).  ``flat``: an exact inner-product search of every
-    query over every doc.  ``graph``: snx.retrieval.GraphIndex with ``degree`` links and a beam of ``ef`` entries (0:
+    query over every doc.  ``flat2``: the same lists from ``search_two_phase(exact=True)``; the extra field is the
+    certified fraction.  ``graph``: snx.retrieval.GraphIndex with ``degree`` links and a beam of ``ef`` entries (0:
     max(100, depth)); the extra fields are its recall against the flat lists and the mean iteration count."""
     import numpy as np
     import torch
@@ -129,6 +133,9 @@ def search_dense_embeddings(path: str, nq: int, nd: int, depth: int, device, den
     index.add(torch.from_numpy(np.ascontiguousarray(docs, dtype=np.float32)).to(device))
     index.build()
     q = torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32)).to(device)
+    if dense_index == "flat2":
+        scores, ids, cert = index.search_two_phase(q, depth, exact=True)
+        return ids, scores, {"dense_index": "flat2", "certified_fraction": float(cert.double().mean()) if nq else 0.0}
     scores, ids, _, _ = index.search(q, depth)
     if dense_index == "flat":
         return ids, scores, {}

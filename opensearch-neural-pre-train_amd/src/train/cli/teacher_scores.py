@@ -8,7 +8,7 @@
         --input-pattern "data/v29.0/train_*.jsonl" --output-dir data/v29.0_kd
     python -m src.train.cli.teacher_scores mine --embeddings cache/embeddings.npy --text-index cache/text_index.json \\
         --input-pattern "data/v29.0_kd/train_*.jsonl" --output-dir data/v30.0_multi_neg --k 7 --rank-start 10 --rank-end 50 \\
-        [--index flat|ivf|graph --nlist 100 --nprobe 1 --degree 32 --ef 0]
+        [--index flat|flat2|ivf|graph --expansion 4 --no-exact --nlist 100 --nprobe 1 --degree 32 --ef 0]
 
 ``encode`` is the encoder of ref:scripts/precompute_teacher_scores.py:49-159 (unique texts in first-occurrence order, BGE-M3
 dense embeddings, L2-normalised) on the native XLM-RoBERTa forward; it writes ``embeddings.npy`` / ``text_index.json``.  A
@@ -18,10 +18,15 @@ shared with those scripts keep their names and defaults.  ``mine --index ivf`` s
 (``--nlist`` lists trained on the corpus rows, ``--nprobe`` of them read per query) instead of every doc; ``--nprobe`` equal
 to the list count writes the files of ``--index flat``.  ``mine --index graph`` searches an ``snx.retrieval.GraphIndex``
 (``--degree`` links per doc, a beam of ``--ef`` entries, 0: max(100, --rank-end)); an ``--ef`` of at least the doc count
-writes the files of ``--index flat``.  Every subcommand runs as a single process."""
+writes the files of ``--index flat``.  ``mine --index flat2`` is the exact search through a bf16 first pass
+(``DenseIndex.search_band_two_phase``: ``--expansion`` times the band's depth in candidates per query, an exact rescore, and
+the exact search for every query the first pass could not certify): it writes the files of ``--index flat`` byte for byte
+and adds ``certified_fraction`` to the stats; ``--no-exact`` keeps the uncertified rows as the first pass left them.  Every
+subcommand runs as a single process."""
 from __future__ import annotations
 
 import argparse
+import json
 import logging
 from typing import List, Optional
 
@@ -48,8 +53,11 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             sp.add_argument("--sample", choices=("first", "random"), default="first")
             sp.add_argument("--seed", type=int, default=42)
             sp.add_argument("--chunk-docs", type=int, default=0)
-            sp.add_argument("--index", choices=("flat", "ivf", "graph"), default="flat",
-                            help="exact search, IVF-Flat, or the graph index")
+            sp.add_argument("--index", choices=("flat", "flat2", "ivf", "graph"), default="flat",
+                            help="exact search, the same through a bf16 first pass, IVF-Flat, or the graph index")
+            sp.add_argument("--expansion", type=float, default=4.0, help="flat2: candidates per wanted rank")
+            sp.add_argument("--no-exact", action="store_true",
+                            help="flat2: keep the rows the first pass could not certify instead of searching them exactly")
             sp.add_argument("--nlist", type=int, default=100, help="IVF lists (clamped to the doc count)")
             sp.add_argument("--nprobe", type=int, default=1, help="IVF lists read per query")
             sp.add_argument("--degree", type=int, default=32, help="graph: links per doc (even)")
@@ -79,6 +87,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             ap.error("--tokenizer must be gpu:DIR or unigram:DIR")
     if args.command == "mine" and (args.k < 1 or not 0 <= args.rank_start < args.rank_end <= 1024):
         ap.error("need --k >= 1 and 0 <= --rank-start < --rank-end <= 1024")
+    if args.command == "mine" and not 1.0 <= args.expansion < float("inf"):
+        ap.error("need a finite --expansion >= 1")
     if args.command == "mine" and not 1 <= args.nprobe <= args.nlist:
         ap.error("need 1 <= --nprobe <= --nlist")
     if args.command == "mine" and (not (args.ef == 0 or args.rank_end <= args.ef <= 1024) or not 2 <= args.degree <= 64
@@ -136,7 +146,10 @@ def main(argv: Optional[List[str]] = None, tokenizer=None):
     else:
         out = mine_dense_negatives(files, args.output_dir, embeddings, text_to_idx, index, k=args.k,
                                    rank_start=args.rank_start, rank_end=args.rank_end, sample=args.sample,
-                                   seed=args.seed, chunk_docs=args.chunk_docs)
+                                   seed=args.seed, chunk_docs=args.chunk_docs,
+                                   **({"two_phase": (args.expansion, not args.no_exact)} if args.index == "flat2" else {}))
+        if args.index == "flat2":
+            logger.info("mine stats: " + json.dumps(out))
     copy_val_files([args.val_pattern], args.output_dir)
     return out
 

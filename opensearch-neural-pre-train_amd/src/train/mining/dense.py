@@ -30,7 +30,7 @@ import hashlib
 import json
 import logging
 import os
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -222,10 +222,13 @@ def write_teacher_scores(input_files: Sequence[str], output_dir: str, embeddings
 
 def mine_dense_negatives(input_files: Sequence[str], output_dir: str, embeddings, text_to_idx: Dict[str, int], index, *,
                          k: int = 7, rank_start: int = 10, rank_end: int = 50, sample: str = "first", seed: int = 0,
-                         chunk_docs: int = 0) -> Dict:
+                         chunk_docs: int = 0, two_phase: Optional[Tuple[float, bool]] = None) -> Dict:
     """Mine ``k`` negatives per record from ranks [rank_start, rank_end) of the teacher's dense search and write one file
     per shard to ``output_dir``.  ``index``: an empty dense index; it receives the embedded docs of the corpus.  Returns
-    the summary: records, queries, docs, indexed_docs, band_fill, padded, fallback, unchanged."""
+    the summary: records, queries, docs, indexed_docs, band_fill, padded, fallback, unchanged.  ``two_phase``:
+    (expansion, exact) sends the band search through ``DenseIndex.search_band_two_phase`` -- with ``exact`` the files are
+    those of the plain search -- and the summary gains ``certified_fraction``, the share of the queries whose band the
+    bf16 pass alone proved exact."""
     from snx.retrieval import K_MAX
     k, rank_start, rank_end = int(k), int(rank_start), int(rank_end)
     if k < 1 or not 0 <= rank_start < rank_end <= K_MAX:
@@ -243,7 +246,7 @@ def mine_dense_negatives(input_files: Sequence[str], output_dir: str, embeddings
     q_search = {q: i for i, q in enumerate(qs)}
     bands: Dict[int, List[Tuple[int, float]]] = {}
     pscore: Dict[Tuple[int, int], float] = {}
-    fill = 0
+    fill, certified = 0, 0.0
     if qs:
         qemb = _to_index(index, _rows(embeddings, [q_row[q] for q in qs]))
         wanted: List[set] = [set() for _ in c.queries]           # docs whose s(q, d) the records need
@@ -256,8 +259,13 @@ def mine_dense_negatives(input_files: Sequence[str], output_dir: str, embeddings
             for (_, _, q, d), s in zip(pairs, ps.tolist()):
                 pscore[(q, d)] = s
         exclude = [[local[d] for d in c.positives[q] if d in local] for q in qs]
-        scores, docs, found = (_to_host(x) for x in index.search_band(qemb, rank_start, rank_end, exclude=exclude,
-                                                                     ceiling=None, chunk_docs=chunk_docs))
+        if two_phase is None:
+            band = index.search_band(qemb, rank_start, rank_end, exclude=exclude, ceiling=None, chunk_docs=chunk_docs)
+        else:
+            *band, cert = index.search_band_two_phase(qemb, rank_start, rank_end, exclude=exclude, ceiling=None,
+                                                      expansion=two_phase[0], exact=two_phase[1], chunk_docs=chunk_docs)
+            certified = float(_to_host(cert).mean())
+        scores, docs, found = (_to_host(x) for x in band)
         for i, q in enumerate(qs):
             f = int(found[i])
             fill += f
@@ -289,6 +297,8 @@ def mine_dense_negatives(input_files: Sequence[str], output_dir: str, embeddings
     summary = {"records": len(c.records), "queries": len(c.queries), "docs": len(c.docs), "indexed_docs": len(kept),
                "band_fill": float(fill / (nq * (rank_end - rank_start))) if nq else 0.0, "padded": counts["padded"],
                "fallback": counts["fallback"], "unchanged": counts["unchanged"]}
+    if two_phase is not None:
+        summary["certified_fraction"] = certified
     logger.info("dense mining: " + " | ".join(f"{key}={v:.4g}" if isinstance(v, float) else f"{key}={v}"
                                              for key, v in summary.items()))
     return summary
