@@ -165,6 +165,29 @@ int snx_model_backward_units_range_tw(const snx_model_desc* d, const void* const
                                       int32_t T, int32_t nseq, int32_t max_seqlen, int32_t unit_begin, int32_t unit_end,
                                       hipStream_t notify, hipStream_t stream);
 
+/* The encoder WITHOUT the SPLADE tail (masked-language-model pre-training reads the head's output and applies a head of
+ * its own, snx_mlm_ce_* below): the launches of snx_model_forward up to and including snx_gelu_ln_fwd -- no decoder runs,
+ * no keys and no token keys are written.  `saved` needs snx_model_workspace_bytes(T, nseq, save_for_bwd); hd [T, hidden]
+ * bf16, bit for bit the decoder's input of snx_model_forward, lies at snx_model_hd_offset() of a save_for_bwd arena. */
+int snx_model_forward_hidden(const snx_model_desc* d, const void* const* params /*[host]*/, const void* wcache,
+                             const int64_t* ids, const int64_t* mask, const int32_t* cu_seqlens, const int32_t* pos,
+                             const float* rope_global, const float* rope_local, void* saved,
+                             const int32_t* groups /*[host] or NULL*/, int32_t T, int32_t nseq, int32_t max_seqlen,
+                             int32_t save_for_bwd, hipStream_t stream);
+/* byte offset, inside a save_for_bwd arena, of hd [T, hidden] bf16 (the head's output, the decoder's input) */
+size_t snx_model_hd_offset(const snx_model_desc* d, int32_t T, int32_t nseq);
+/* snx_model_backward_units_range_tw from the gradient of hd: g_hd [T, hidden] bf16 takes the place of g_sparse /
+ * g_token_weights.  Unit 0 copies it where the SPLADE backward would have written it and runs no SPLADE backward; every
+ * launch behind that is the one of the entry point above.  The gradients of the tied embedding matrix and of decoder.bias
+ * through the caller's head are the caller's to add (before or after: both are accumulated). */
+int snx_model_backward_units_range_hd(const snx_model_desc* d, const void* const* params /*[host]*/,
+                                      void* const* grads /*[host]*/, const void* wcache, const int64_t* ids,
+                                      const int64_t* mask, const int32_t* cu_seqlens, const int32_t* pos,
+                                      const float* rope_global, const float* rope_local, const void* saved,
+                                      const void* g_hd, void* scratch, const int32_t* groups /*[host] or NULL*/,
+                                      int32_t T_plan, int32_t nseq_plan, int32_t T, int32_t nseq, int32_t max_seqlen,
+                                      int32_t unit_begin, int32_t unit_end, hipStream_t notify, hipStream_t stream);
+
 /* ---- fp32 execution (csrc/f32_path.hip): what the reference computes OUTSIDE torch.autocast -- a bare
  * SPLADEModernBERT.forward (ref:src/model/splade_modern.py:50-88), its inference encoder (ref:benchmark/encoders.py:
  * 309-345) and the fp32 leg of the tolerance protocol.  Same contract as the entry points above with fp32 weights
@@ -1227,6 +1250,39 @@ size_t snx_adamw_scratch_bytes(void);
 int snx_adamw_clip_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
                         const float* hp /*[host]*/, int64_t step, int64_t nodecay_begin, int64_t nodecay_end,
                         float* norm_out, void* scratch, hipStream_t stream);
+
+/* ---- masked-language-model pre-training (csrc/mlm.hip) ----
+ * Token masking with the contract of DataCollatorForLanguageModeling.torch_mask_tokens (labels = -100 where no loss is
+ * taken), the draws a pure function of the token: Philox4x32-10, key = the 64-bit seed, counter = (lo32(t), hi32(t),
+ * epoch, 0) with t = sample_index * 65536 + position, outputs r0..r3.  Selected iff attended, id not in special_ids
+ * [host, n_special <= 16] and r0 2^-32 < p; a selected token becomes mask_id if r1 2^-32 < p_mask, the id
+ * (r2 * vocab) >> 32 if r1 2^-32 < p_mask + p_random, else stays.  input_ids, attention_mask, masked_ids, labels [B, S]
+ * int64, sample_index [B] int64.  S > 65535: SNX_E_SHAPE. */
+int snx_mlm_mask_tokens(const int64_t* input_ids, const int64_t* attention_mask, const int64_t* sample_index,
+                        int64_t* masked_ids, int64_t* labels, int32_t B, int32_t S, const int64_t* special_ids /*[host]*/,
+                        int32_t n_special, int64_t mask_id, int32_t vocab, int64_t seed, int32_t epoch, double p,
+                        double p_mask, double p_random, hipStream_t stream);
+/* Vp: the vocabulary rounded up to the 128-column tile of the cross-entropy kernels */
+int64_t snx_mlm_vocab_padded(int32_t V);
+/* E [V, H] bf16 (the weight cache's embedding matrix) -> E^T [H, Vp] bf16, pad columns zero: the operand of dh = g E.
+ * Rebuilt by the caller when the weights change. */
+int snx_mlm_transpose_embeddings(const void* E, void* ET, int32_t V, int32_t H, hipStream_t stream);
+/* Cross-entropy of M gathered rows against the tied decoder:
+ *   z[m,v] = bf16(sum_k h E in fp32 + float(bf16(bias[v]))),  lse[m] = logsumexp_v z[m,v] in fp32 over v < V,
+ *   row_loss[m] = lse[m] - z[m, labels[m]],  loss[0] = sum_m row_loss[m] / M.
+ * h [M, H] bf16, labels [M] int64 in [0, V) (a label outside gives that row, and the loss, NaN), z [M, Vp] bf16 (kept for
+ * the backward; pad columns zero), part: (2 Vp / 128 + 1) * M floats of scratch.  H % 128 == 0, H <= 1024.
+ * M == 0: nothing is launched and nothing written. */
+int snx_mlm_ce_fwd(const void* h, const void* E, const float* bias, const int64_t* labels, void* z, float* part, float* lse,
+                   float* row_loss, float* loss, int32_t M, int32_t V, int32_t H, hipStream_t stream);
+/* Its backward: z becomes g[m,v] = bf16((exp(z - lse) - [v == labels[m]]) * upstream[0] / M) in place, then
+ *   dh [M, H] bf16 = bf16(g E),  dE [V, H] fp32 += g^T h,  dbias [V] fp32 += sum_m g,
+ * every sum in a fixed order (no float atomics).  ET from snx_mlm_transpose_embeddings, upstream [1] fp32 on the device,
+ * ws: snx_mlm_ce_bwd_workspace_bytes() bytes of scratch. */
+size_t snx_mlm_ce_bwd_workspace_bytes(int32_t M, int32_t V, int32_t H);
+int snx_mlm_ce_bwd(void* z, const float* lse, const int64_t* labels, const float* upstream, const void* h, const void* ET,
+                   void* dh, float* dE, float* dbias, void* ws, size_t ws_bytes, int32_t M, int32_t V, int32_t H,
+                   hipStream_t stream);
 
 /* ---- optional per-kernel-class timing inside the model entry points (HIP events recorded on
  * the launch stream around every kernel class; off by default).  snx_prof_read synchronises on

@@ -375,16 +375,18 @@ extern "C" int snx_model_forward(const snx_model_desc* d, const void* const* par
 // row-major, so a pass is the same kernels on shifted pointers; only the attention LSE is head-major ([heads, T_plan]) and
 // keeps T_plan as its stride.  After the last pass the arena is exactly what one fused snx_model_forward over all rows
 // leaves behind, and ONE snx_model_backward over (T_plan, nseq_plan) back-propagates the micro-step.
-extern "C" int snx_model_forward_range(const snx_model_desc* d, const void* const* params, const void* wcache,
-                                       const int64_t* ids, const int64_t* mask, const int32_t* cu_seqlens,
-                                       const int32_t* pos, const float* rope_global, const float* rope_local,
-                                       void* saved, float* sparse_all, float* token_weights_all, const int32_t* groups,
-                                       int32_t T_plan, int32_t nseq_plan, int32_t row0, int32_t seq0, int32_t T,
-                                       int32_t nseq, int32_t max_seqlen, int32_t flags, hipStream_t st) {
+// hidden_only (snx_model_forward_hidden): stop behind the head's LayerNorm -- no decoder, no keys; sparse_all and
+// token_weights_all are not read
+static int forward_range_impl(const snx_model_desc* d, const void* const* params, const void* wcache, const int64_t* ids,
+                              const int64_t* mask, const int32_t* cu_seqlens, const int32_t* pos, const float* rope_global,
+                              const float* rope_local, void* saved, float* sparse_all, float* token_weights_all,
+                              const int32_t* groups, int32_t T_plan, int32_t nseq_plan, int32_t row0, int32_t seq0,
+                              int32_t T, int32_t nseq, int32_t max_seqlen, int32_t flags, bool hidden_only,
+                              hipStream_t st) {
   if (!desc_ok(d)) return SNX_E_SHAPE;
   const bool notw = (flags & SNX_FWD_NO_TOKEN_WEIGHTS) != 0;   // token_weights_all may be NULL: it is never written
-  if (!params || !wcache || !ids || !mask || !cu_seqlens || !pos || !rope_global || !rope_local || !saved || !sparse_all ||
-      (!notw && !token_weights_all) || T <= 0 || nseq <= 0 || max_seqlen <= 0)
+  if (!params || !wcache || !ids || !mask || !cu_seqlens || !pos || !rope_global || !rope_local || !saved ||
+      (!hidden_only && (!sparse_all || (!notw && !token_weights_all))) || T <= 0 || nseq <= 0 || max_seqlen <= 0)
     return SNX_E_ARG;
   if (row0 < 0 || seq0 < 0 || (long)row0 + T > T_plan || (long)seq0 + nseq > nseq_plan) return SNX_E_ARG;
   const bool ranged = T != T_plan || nseq != nseq_plan;
@@ -394,7 +396,7 @@ extern "C" int snx_model_forward_range(const snx_model_desc* d, const void* cons
   CachePlan c;
   SavedPlan s;
   if (!plan_cache(d, c) || !plan_saved(d, T_plan, nseq_plan, save, s, notw)) return SNX_E_SHAPE;
-  if (save) {
+  if (save && !hidden_only) {
     if (notw) g_notw.add(saved);
     else if (row0 == 0) g_notw.drop(saved);
   }
@@ -472,6 +474,7 @@ extern "C" int snx_model_forward_range(const snx_model_desc* d, const void* cons
   if (!ril) { PROF(PC_LN_FWD, TH * 6); RC(snx_ln_fwd(hbuf(2 * L), F(p.final_norm()), sv.xf(), T, H, d->ln_eps, st)); }
   { PROF(PC_GEMM_NT, 2.0 * TH * H); RC(snx_gemm_nt_bf16(sv.xf(), wc + c.dense, sv.dd(), T, H, H, st)); }
   { PROF(PC_LN_FWD, TH * 4); RC(snx_gelu_ln_fwd(sv.dd(), F(p.head_norm()), sv.hd(), T, H, d->ln_eps, st)); }
+  if (hidden_only) return SNX_OK;
   {
     // Sequence groups (e.g. 64-token queries and 256-token documents concatenated in one call)
     // get the decoder tile height that fits their length; groups = {n, (seq_begin, nseq, max_len)*n}.
@@ -489,6 +492,33 @@ extern "C" int snx_model_forward_range(const snx_model_desc* d, const void* cons
     }
   }
   return SNX_OK;
+}
+
+extern "C" int snx_model_forward_range(const snx_model_desc* d, const void* const* params, const void* wcache,
+                                       const int64_t* ids, const int64_t* mask, const int32_t* cu_seqlens,
+                                       const int32_t* pos, const float* rope_global, const float* rope_local,
+                                       void* saved, float* sparse_all, float* token_weights_all, const int32_t* groups,
+                                       int32_t T_plan, int32_t nseq_plan, int32_t row0, int32_t seq0, int32_t T,
+                                       int32_t nseq, int32_t max_seqlen, int32_t flags, hipStream_t st) {
+  return forward_range_impl(d, params, wcache, ids, mask, cu_seqlens, pos, rope_global, rope_local, saved, sparse_all,
+                            token_weights_all, groups, T_plan, nseq_plan, row0, seq0, T, nseq, max_seqlen, flags, false, st);
+}
+
+// The same launches up to and including the head's LayerNorm: hd for a head of the caller's own (csrc/mlm.hip)
+extern "C" int snx_model_forward_hidden(const snx_model_desc* d, const void* const* params, const void* wcache,
+                                        const int64_t* ids, const int64_t* mask, const int32_t* cu_seqlens,
+                                        const int32_t* pos, const float* rope_global, const float* rope_local,
+                                        void* saved, const int32_t* groups, int32_t T, int32_t nseq, int32_t max_seqlen,
+                                        int32_t save_for_bwd, hipStream_t st) {
+  return forward_range_impl(d, params, wcache, ids, mask, cu_seqlens, pos, rope_global, rope_local, saved, nullptr, nullptr,
+                            groups, T, nseq, 0, 0, T, nseq, max_seqlen, save_for_bwd ? SNX_FWD_SAVE_FOR_BACKWARD : 0, true,
+                            st);
+}
+
+extern "C" size_t snx_model_hd_offset(const snx_model_desc* d, int32_t T, int32_t nseq) {
+  SavedPlan s;
+  if (!desc_ok(d) || T <= 0 || nseq <= 0 || !plan_saved(d, T, nseq, true, s)) return (size_t)-1;
+  return s.hd;
 }
 
 // The backward is a chain of L + 2 UNITS in execution order: unit 0 = SPLADE tail + decoder + head + final norm,
@@ -522,19 +552,18 @@ extern "C" int snx_model_backward_units_range(const snx_model_desc* d, const voi
                                            unit_begin, unit_end, notify, st);
 }
 
-// ... and the gradient of token_weights as well: g_token_weights [T] fp32 (row order of the arena, read by unit 0), or
-// NULL (exactly snx_model_backward_units_range)
-extern "C" int snx_model_backward_units_range_tw(const snx_model_desc* d, const void* const* params, void* const* grads,
-                                                 const void* wcache, const int64_t* ids, const int64_t* mask,
-                                                 const int32_t* cu_seqlens, const int32_t* pos, const float* rope_global,
-                                                 const float* rope_local, const void* saved, const float* g_sparse,
-                                                 const float* g_token_weights, void* scratch, const int32_t* groups,
-                                                 int32_t T_plan, int32_t nseq_plan, int32_t T, int32_t nseq,
-                                                 int32_t max_seqlen, int32_t unit_begin, int32_t unit_end,
-                                                 hipStream_t notify, hipStream_t st) {
+// The body of the backward entry points.  g_hd (snx_model_backward_units_range_hd): the gradient of hd [T, H] bf16
+// arrives from the caller's own head; unit 0 copies it into A in place of the SPLADE backward (g_sparse and
+// g_token_weights are then not read)
+static int backward_units_impl(const snx_model_desc* d, const void* const* params, void* const* grads, const void* wcache,
+                               const int64_t* ids, const int64_t* mask, const int32_t* cu_seqlens, const int32_t* pos,
+                               const float* rope_global, const float* rope_local, const void* saved, const float* g_sparse,
+                               const float* g_token_weights, const void* g_hd, void* scratch, const int32_t* groups,
+                               int32_t T_plan, int32_t nseq_plan, int32_t T, int32_t nseq, int32_t max_seqlen,
+                               int32_t unit_begin, int32_t unit_end, hipStream_t notify, hipStream_t st) {
   if (!desc_ok(d)) return SNX_E_SHAPE;
   if (!params || !grads || !wcache || !ids || !mask || !cu_seqlens || !pos || !rope_global || !rope_local || !saved ||
-      !g_sparse || !scratch || T <= 0 || nseq <= 0 || max_seqlen <= 0 || T > T_plan || nseq > nseq_plan)
+      (!g_sparse && !g_hd) || !scratch || T <= 0 || nseq <= 0 || max_seqlen <= 0 || T > T_plan || nseq > nseq_plan)
     return SNX_E_ARG;
   if (unit_begin < 0 || unit_end > d->layers + 2 || unit_begin >= unit_end) return SNX_E_ARG;
   if (g_token_weights && g_notw.find(saved) >= 0) return SNX_E_ARG;   // that forward recorded no token keys
@@ -588,7 +617,10 @@ extern "C" int snx_model_backward_units_range_tw(const snx_model_desc* d, const 
   if (unit_begin == 0) {
     char* A = sc + b.p[(L - 1) & 1];                  // d(mlp.Wo out) of the last layer ends up here
     // SPLADE tail + decoder (sparse routed), head
-    { PROF(PC_SPLADE_BWD, 2.0 * 2.0 * nseq * V * H);
+    if (g_hd) {
+      PROF(PC_CAST, TH * 4);
+      if (hipMemcpyAsync(A, g_hd, (size_t)T * H * 2, hipMemcpyDeviceToDevice, st) != hipSuccess) return SNX_E_ARG;
+    } else { PROF(PC_SPLADE_BWD, 2.0 * 2.0 * nseq * V * H);
       // (round 6, measured and dropped: the weight half -- dE / db -- on the idle side stream beside the activation half:
       // 45.23 against 45.01 ms per micro-step on one box, ABAB; two gathers that share the CUs' wave slots contend more
       // than they hide)
@@ -671,6 +703,35 @@ extern "C" int snx_model_backward_units_range_tw(const snx_model_desc* d, const 
     }
   }
   return SNX_OK;
+}
+
+// ... and the gradient of token_weights as well: g_token_weights [T] fp32 (row order of the arena, read by unit 0), or
+// NULL (exactly snx_model_backward_units_range)
+extern "C" int snx_model_backward_units_range_tw(const snx_model_desc* d, const void* const* params, void* const* grads,
+                                                 const void* wcache, const int64_t* ids, const int64_t* mask,
+                                                 const int32_t* cu_seqlens, const int32_t* pos, const float* rope_global,
+                                                 const float* rope_local, const void* saved, const float* g_sparse,
+                                                 const float* g_token_weights, void* scratch, const int32_t* groups,
+                                                 int32_t T_plan, int32_t nseq_plan, int32_t T, int32_t nseq,
+                                                 int32_t max_seqlen, int32_t unit_begin, int32_t unit_end,
+                                                 hipStream_t notify, hipStream_t st) {
+  if (!g_sparse) return SNX_E_ARG;
+  return backward_units_impl(d, params, grads, wcache, ids, mask, cu_seqlens, pos, rope_global, rope_local, saved, g_sparse,
+                             g_token_weights, nullptr, scratch, groups, T_plan, nseq_plan, T, nseq, max_seqlen, unit_begin,
+                             unit_end, notify, st);
+}
+
+extern "C" int snx_model_backward_units_range_hd(const snx_model_desc* d, const void* const* params, void* const* grads,
+                                                 const void* wcache, const int64_t* ids, const int64_t* mask,
+                                                 const int32_t* cu_seqlens, const int32_t* pos, const float* rope_global,
+                                                 const float* rope_local, const void* saved, const void* g_hd,
+                                                 void* scratch, const int32_t* groups, int32_t T_plan, int32_t nseq_plan,
+                                                 int32_t T, int32_t nseq, int32_t max_seqlen, int32_t unit_begin,
+                                                 int32_t unit_end, hipStream_t notify, hipStream_t st) {
+  if (!g_hd) return SNX_E_ARG;
+  return backward_units_impl(d, params, grads, wcache, ids, mask, cu_seqlens, pos, rope_global, rope_local, saved, nullptr,
+                             nullptr, g_hd, scratch, groups, T_plan, nseq_plan, T, nseq, max_seqlen, unit_begin, unit_end,
+                             notify, st);
 }
 
 extern "C" int snx_model_backward(const snx_model_desc* d, const void* const* params, void* const* grads,

@@ -73,6 +73,9 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     # and for the Unigram tokenizer: the recurrence's float64 best, the winning piece and the probe's hash state stay in
     # registers, the row's state in LDS (or the workspace); the count kernel holds nothing that could spill
     "unigram.hip": ("ug_pieces_kernel", "ug_pieces_long_kernel", "ug_norm_fill_kernel"),
+    # and for the MLM cross-entropy tile: 64 accumulator registers, the tile's logits and the rounded bias stay in registers
+    # through the epilogue; the merge, loss and elementwise kernels read no LDS (or keep nothing that could spill)
+    "mlm.hip": ("mlm_ce_tile_kernel",),
 }
 
 # Kernels held to the global-load / vmcnt rule: nothing may touch a load's destination before a vmcnt wait that retires it.

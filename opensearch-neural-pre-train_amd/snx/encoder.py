@@ -474,6 +474,84 @@ class EncoderRuntime:
                         fn("snx_set_reserved_cus")(0)
         return ret
 
+    # ------------------------------------------------------------------ hidden states (MLM pre-training, snx/mlm.py)
+    def forward_hidden_impl(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, save: bool):
+        """The encoder up to the head's LayerNorm (snx_model_forward_hidden) over one dense [B, S] batch
+        -> hd [B*S, H] bf16 (a view of the arena), arena, aux.  No decoder runs; the micro-step arena takes no part.
+        bf16 path only: the fp32 parity runtime has no MLM head."""
+        if self.precision() == "fp32":
+            raise NotImplementedError("snx: the hidden-state forward (MLM pre-training) exists on the bf16 path only; run "
+                                      "it inside torch.autocast('cuda', torch.bfloat16)")
+        dev = self._device()
+        self.geom.check_supported()
+        if input_ids.dim() != 2 or attention_mask.shape != input_ids.shape:
+            raise ValueError("input_ids and attention_mask must both be [batch, seq_len]")
+        if input_ids.device != dev or attention_mask.device != dev:
+            raise ValueError("inputs must live on the module's device")
+        B, S = int(input_ids.shape[0]), int(input_ids.shape[1])
+        if B < 1 or S < 1 or S > self.geom.max_position_embeddings or S > 8192:
+            raise ValueError("sequence too long (or an empty batch)")
+        ids = input_ids.to(torch.int64).contiguous().view(-1)
+        mask = attention_mask.to(torch.int64).contiguous().view(-1)
+        cu, pos, groups = self._layout([(B, S)], dev)
+        T, H = B * S, self.geom.hidden_size
+        hd_dim = H // self.geom.num_attention_heads
+        with torch.cuda.device(dev):
+            rg, rl = self._rope_tables(max(S, 64), dev, hd_dim)
+            wc = self._weights()
+            # (the arena of a saving forward in both cases: snx_model_hd_offset speaks of that plan)
+            nbytes = fn("snx_model_workspace_bytes")(C.byref(self._desc), T, B, 1)
+            saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            call("snx_model_forward_hidden", C.byref(self._desc), self._param_ptrs(), _p(wc), _p(ids), _p(mask), _p(cu),
+                 _p(pos), _p(rg), _p(rl), _p(saved), None, T, B, S, 1, _stream())
+        off = fn("snx_model_hd_offset")(C.byref(self._desc), T, B)
+        hd = saved[off:off + T * H * 2].view(torch.bfloat16).view(T, H)
+        aux = (ids, mask, cu, pos, rg, rl, T, B, S, None, False, None)
+        return hd, (saved if save else None), aux
+
+    def backward_hidden_impl(self, saved: torch.Tensor, aux, g_hd: torch.Tensor, grads=None):
+        """The backward from dL/d hd [T, H] bf16 (snx_model_backward_units_range_hd).  ``grads``: fp32 tensors in the canonical
+        order to accumulate into (they may already hold the head's gradients of the embedding matrix and the decoder
+        bias); default: the flat gradient in the direct mode, fresh zeros otherwise.  Returns the tensors it wrote."""
+        ids, mask, cu, pos, rg, rl, T, B, S = aux[:9]
+        dev = self._device()
+        if g_hd.shape != (T, self.geom.hidden_size) or g_hd.dtype != torch.bfloat16 or not g_hd.is_contiguous():
+            raise ValueError("g_hd must be a contiguous bf16 [T, hidden] tensor")
+        if grads is None:
+            grads = self.grad_buffers()
+        with torch.cuda.device(dev):
+            nbytes = fn("snx_model_bwd_workspace_bytes")(C.byref(self._desc), T, B, S)
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            call("snx_model_backward_units_range_hd", C.byref(self._desc), self._param_ptrs(), self._grad_ptrs(grads),
+                 _p(self._weights()), _p(ids), _p(mask), _p(cu), _p(pos), _p(rg), _p(rl), _p(saved), _p(g_hd), _p(scratch),
+                 None, T, B, T, B, S, 0, self.geom.num_hidden_layers + 2, None, _stream())
+        return grads
+
+    def grad_buffers(self):
+        """fp32 gradient tensors in the canonical order: the .grad views of the flat gradient in the direct mode, else
+        views of one fresh zero buffer."""
+        if self.direct_grads:
+            return [p.grad for p in self.params]
+        flat = torch.zeros(sum(p.numel() for p in self.params), dtype=torch.float32, device=self._device())
+        out, off = [], 0
+        for p in self.params:
+            out.append(flat[off:off + p.numel()].view_as(p))
+            off += p.numel()
+        return out
+
+    def mlm_embeddings(self):
+        """(E [V, H], E^T [H, Vp]) bf16 for the MLM cross-entropy: E is the weight cache's embedding matrix (its first
+        entry), E^T a copy kept here -- not in the weight cache, whose plan is fixed -- and rebuilt when the weights change."""
+        wc = self._weights()
+        V, H = self.geom.vocab_size, self.geom.hidden_size
+        E = wc[:V * H * 2].view(torch.bfloat16).view(V, H)
+        key = (self._wcache_key, wc.data_ptr())
+        if getattr(self, "_mlm_et_key", None) != key:
+            from . import mlm
+            self._mlm_et = mlm.transpose_embeddings(E)
+            self._mlm_et_key = key
+        return E, self._mlm_et
+
     # ------------------------------------------------------------------ micro-step arena
     def _arena_eligible(self) -> bool:
         return (self.step_arena_on and not self.keep_last_ctx and self.precision() == "bf16" and
