@@ -469,17 +469,24 @@ def _raw(t):
     return t.view(torch.int16 if t.dtype == BF16 else torch.int32)
 
 
+def check_guards(buf, rows, what):
+    """the guard rows before and behind the `rows` middle rows of a guarded buffer are untouched (a scratch buffer, whose
+    contents nobody checks, is held to this alone); returns the sentinel"""
+    raw = _raw(buf)
+    sent = SENT_BF16 if buf.dtype == BF16 else SENT_F32
+    for name, part in (("before", raw[:GUARD_ROWS]), ("behind", raw[GUARD_ROWS + rows:])):
+        bad = (part != sent).nonzero()
+        assert bad.numel() == 0, f"{what}: guard rows {name} the output written at (row, col) {bad[0].tolist()} ({len(bad)} elements)"
+    return sent
+
+
 def check_guarded(buf, iv, what):
     """buf: a guarded buffer (on the CPU) after the run; iv = (lo, hi) of its middle rows.  Guards untouched, every element
     written and finite and inside its interval.  Returns the shares the docstrings record."""
     lo, hi, *extra = iv
     extra = extra[0] if extra else {}
     rows = lo.shape[0]
-    raw = _raw(buf)
-    sent = SENT_BF16 if buf.dtype == BF16 else SENT_F32
-    for name, part in (("before", raw[:GUARD_ROWS]), ("behind", raw[GUARD_ROWS + rows:])):
-        bad = (part != sent).nonzero()
-        assert bad.numel() == 0, f"{what}: guard rows {name} the output written at (row, col) {bad[0].tolist()} ({len(bad)} elements)"
+    sent = check_guards(buf, rows, what)
     mid = buf[GUARD_ROWS:GUARD_ROWS + rows]
     unwritten = (_raw(mid) == sent).nonzero()
     assert unwritten.numel() == 0, f"{what}: {len(unwritten)} elements never written, first {unwritten[0].tolist()}"
