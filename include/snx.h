@@ -736,6 +736,55 @@ int snx_minhash_dedup(const uint32_t* sig, int32_t n, int32_t num_perm, int32_t 
 int snx_minhash_first_match(const uint32_t* q_sig, int32_t nq, const uint32_t* kept_sig, int32_t nk, int32_t num_perm,
                             int32_t need, int32_t* out, hipStream_t stream);
 
+/* ---- Corpus preparation (csrc/textprep.hip): the reference's MLM data script (ref:scripts/prepare_korean_mlm_data.py),
+ * whose clean_text -> split_paragraphs -> is_valid_paragraph (ref:prepare_korean_mlm_data.py:31-53) and SHA-256 dedup
+ * (ref:prepare_korean_mlm_data.py:56-58, 201-217) are single-threaded Python loops over tens of millions of paragraphs.
+ * Everything here is integer work and every output is a pure function of the inputs, bit for bit, run to run.  Rows are
+ * a CSR of Unicode code points as for the MinHash section, ptr [n+1] int64 and code_points int32, NOT lowered and NOT
+ * stripped; every document is shorter than 2^31 code points.
+ * Segmentation, per document (nothing carries from one document into the next):
+ *   blank      U+0020 or U+0009; one whose predecessor is a blank is dropped, a kept one is emitted as U+0020
+ *              (ref:prepare_korean_mlm_data.py:33).
+ *   separator  a maximal run of U+000A of length >= 2 (ref:prepare_korean_mlm_data.py:34, 40); it is removed and cuts
+ *              the document into pieces.  A single U+000A stays in the text.
+ *   strip      the white space of Python's str.isspace (0009-000D 001C-0020 0085 00A0 1680 2000-200A 2028 2029 202F 205F
+ *              3000, a compile-time range test) is removed from both ends of a piece; an empty piece is dropped
+ *              (ref:prepare_korean_mlm_data.py:35, 40).  A piece is emitted from its first to its last code point that
+ *              is not white space.
+ *   hangul     counts U+AC00 .. U+D7AF inclusive (ref:prepare_korean_mlm_data.py:20).
+ * One workgroup per document walks tiles of 256 code points; the blank and separator tests read the neighbouring code
+ * points of the document, the piece state (last separator, first and last non-white-space position, running counts)
+ * is carried from tile to tile.  Three passes, because a trailing white-space run is known to be trailing only at the
+ * piece's end:
+ *   snx_tx_segment_count  doc_pieces [n] int64 = surviving pieces of the document, doc_cps [n] int64 = their code points.
+ *                         The host scans doc_pieces into piece_base [n+1] (0 and the running sums) and reads the two totals.
+ *   snx_tx_segment_meta   for piece k of document d, at p = piece_base[d] + k: par_len [np] int64, par_doc [np] int32 = d,
+ *                         par_hangul [np] int32.  The host scans par_len into par_ptr [np+1].
+ *   snx_tx_segment_fill   par_cps [par_ptr[np]] int32: a code point is written iff its offset in the piece is below the
+ *                         piece's length, which cuts the trailing white space without looking ahead.
+ * SHA-256 of rows: digest [n, 8] uint32 = SHA-256 of the row's UTF-8 bytes (ref:prepare_korean_mlm_data.py:58), MOST
+ * SIGNIFICANT WORD FIRST as the MinHash signatures: the eight words as %08x are hexdigest().  UTF-8 is encoded on the fly
+ * into 64-byte blocks (a code point's bytes may straddle two), any length, 64-bit bit count; the empty row hashes the
+ * empty message.  A value outside [0, 0x10FFFF] or a surrogate is encoded by the same bit rule (the host refuses them).
+ * One lane per row: a wave takes as long as its longest row.
+ * First-occurrence dedup (ref:prepare_korean_mlm_data.py:210-216): first [n] int32 = the smallest row index whose digest
+ * equals row i's in all 256 bits, i itself for a first occurrence.  An open-addressed table of the power of two >= 2 n
+ * slots of row indices: a row claims a free slot by compare-and-swap, or finds a slot whose row has its digest (compared
+ * through the digest array), and lowers the slot to its own index by atomicMin; a second pass reads the minima.  Rows of
+ * equal digest end in the same slot whatever the arrival order, so the result does not depend on it.  n <= 2^29;
+ * workspace: snx_tx_first_equal_workspace_bytes(n) bytes.  Stream-ordered, no host synchronisation, no kernel waits for
+ * another workgroup. */
+int snx_tx_segment_count(const int64_t* ptr, const int32_t* code_points, int32_t n, int64_t* doc_pieces, int64_t* doc_cps,
+                         hipStream_t stream);
+int snx_tx_segment_meta(const int64_t* ptr, const int32_t* code_points, int32_t n, const int64_t* piece_base,
+                        int64_t* par_len, int32_t* par_doc, int32_t* par_hangul, hipStream_t stream);
+int snx_tx_segment_fill(const int64_t* ptr, const int32_t* code_points, int32_t n, const int64_t* piece_base,
+                        const int64_t* par_ptr, int32_t* par_cps, hipStream_t stream);
+int snx_tx_sha256_rows(const int64_t* ptr, const int32_t* code_points, int32_t n, uint32_t* digest, hipStream_t stream);
+size_t snx_tx_first_equal_workspace_bytes(int64_t n);
+int snx_tx_first_equal(const uint32_t* digest, int32_t n, int32_t* first, void* workspace, size_t ws_bytes,
+                       hipStream_t stream);
+
 /* ---- Character n-gram TF-IDF (csrc/tfidf.hip): the vectorizer of the reference's lexical hard-negative mining
  * (ref:scripts/mine_hard_negatives.py:141-146: scikit-learn's TfidfVectorizer(analyzer="char_wb", ngram_range=(2, 3),
  * max_features=30000, sublinear_tf=True), rows L2-normalised, searched by cosine), which scikit-learn and scipy hold to
