@@ -19,7 +19,8 @@
 //   co_pmi_cells_kernel           one thread per stored cell; co_pmi_pairs_kernel one thread per (row, col) pair, the cell
 //                                 found by binary search in the row.
 // No kernel waits for another workgroup; no float atomics; every result is the same bits from run to run.
-#include "sparse_common.h"
+#include "sparse_common.h"   // block_sum
+#include "text_common.h"
 #include "snx.h"
 
 namespace {
@@ -37,21 +38,6 @@ struct CoShared {
   int run;
   unsigned long long ctr;
 };
-
-template <int THREADS>
-__device__ __forceinline__ void co_bitonic_asc(unsigned long long* a, int64_t P) {
-  for (int64_t size = 2; size <= P; size <<= 1)
-    for (int64_t stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int64_t t = threadIdx.x; t < (P >> 1); t += THREADS) {
-        const int64_t lo = 2 * t - (t & (stride - 1));
-        const int64_t hi = lo + stride;
-        const bool asc = (lo & size) == 0;
-        const unsigned long long x = a[lo], y = a[hi];
-        if ((x > y) == asc) { a[lo] = y; a[hi] = x; }
-      }
-      __syncthreads();
-    }
-}
 
 // window g -> its first token and its length.  Rows are windows (win_ptr == NULL), or sliding: win_ptr [n_rows + 1] are the
 // running window counts of the rows, a row of n <= w tokens is one window, a longer one has n - w + 1 of w tokens each.
@@ -93,7 +79,7 @@ __device__ __forceinline__ unsigned long long co_window(const int32_t* __restric
   }
   if (tid == 0) { sh.run = 0; sh.ctr = 0ull; }
   __syncthreads();
-  co_bitonic_asc<THREADS>(a, P);
+  text_bitonic_asc<THREADS>(a, P);
   for (int64_t base = 0; base < len; base += THREADS) {      // block-uniform bounds: the starts of the runs, in order
     const int64_t i = base + tid;
     const unsigned long long k = i < len ? a[i] : CO_NONE;

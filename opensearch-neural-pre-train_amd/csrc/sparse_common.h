@@ -25,7 +25,7 @@
 // pow2_at_least.
 // Local on purpose, not here: hybrid.hip's HY_BITONIC and float64 helpers (other comparators); the 8-bit radix selects of
 // sz_prune_kernel and tp_prune_kernel (their bodies differ); tp_prune_kernel's wave-array sum (block_sum's LDS-word form
-// compiles it to more code, profiles/retrieval_refactor_isa.txt); tf_bitonic_asc and infogain's pair sort (ascending).
+// compiles it to more code, profiles/retrieval_refactor_isa.txt); the ascending sorts (text_common.h's, infogain's pairs).
 // A helper that depends on the workgroup size takes it as a template parameter (the files use 512, 256 and 64 threads);
 // the select, chunk and merge helpers are for SR_THREADS.
 #pragma once

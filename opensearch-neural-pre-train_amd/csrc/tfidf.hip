@@ -17,7 +17,8 @@
 //                           No logarithm here: tf_table is the host's (libm is not bit-reproducible).
 //   tf_compact_kernel       one wave per row: the filled front of a row's slots moves to its place in the CSR.
 // No kernel waits for another workgroup; every result is the same bits from run to run.
-#include "sparse_common.h"
+#include "sparse_common.h"   // block_sum
+#include "text_common.h"
 #include "snx.h"
 
 namespace {
@@ -30,21 +31,6 @@ constexpr unsigned long long TF_NONE = ~0ull;       // no n-gram in this slot: s
 constexpr int32_t TF_SPACE = 0x20;
 
 __host__ __device__ inline int tf_slots_per_pos(int min_n, int max_n) { return max_n - min_n + 1 + (min_n == 1 ? 1 : 0); }
-
-// ascending bitonic sort of a[0..P), P a power of two, by the whole workgroup; a is LDS or the workgroup's workspace slot
-__device__ __forceinline__ void tf_bitonic_asc(unsigned long long* a, int64_t P) {
-  for (int64_t size = 2; size <= P; size <<= 1)
-    for (int64_t stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int64_t t = threadIdx.x; t < (P >> 1); t += TF_THREADS) {
-        const int64_t lo = 2 * t - (t & (stride - 1));
-        const int64_t hi = lo + stride;
-        const bool asc = (lo & size) == 0;
-        const unsigned long long x = a[lo], y = a[hi];
-        if ((x > y) == asc) { a[lo] = y; a[hi] = x; }
-      }
-      __syncthreads();
-    }
-}
 
 // the key of slot e of a row: position s = e / NS of the padded row p (p[i] = t[i-1], a U+0020 in front of and behind t),
 // j = e % NS the n of the window that starts there (the last j of a range from 1: the second copy of a 1-gram U+0020)
@@ -86,7 +72,7 @@ __device__ __forceinline__ void tf_count_row(const int64_t* __restrict__ ptr, co
   for (int64_t e = tid; e < P; e += TF_THREADS) a[e] = e < E ? tf_slot_key(cps + a0, len, e, NS, min_n, max_n) : TF_NONE;
   if (tid == 0) run = 0;
   __syncthreads();
-  tf_bitonic_asc(a, P);
+  text_bitonic_asc<TF_THREADS>(a, P);
   const unsigned long long below = (1ull << lane) - 1ull;
   for (int64_t base = 0; base < E; base += TF_THREADS) {     // block-uniform bounds
     const int64_t i = base + tid;

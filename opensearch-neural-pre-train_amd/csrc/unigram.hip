@@ -20,7 +20,8 @@
 // No atomic and no sort decides an id or a place; the float64 additions are single adds in a fixed order (there is no
 // multiplication to contract with): the result is a pure function of the input.  snx_wp_fill / snx_wp_pad
 // (wordpiece.hip) do the compaction behind bos and the padding.
-#include "sparse_common.h"
+#include "sparse_common.h"   // block_sum
+#include "text_common.h"
 #include "snx.h"
 
 namespace {
@@ -31,7 +32,6 @@ constexpr int UG_MAX_PIECE = 32;                    // longest piece in code poi
 constexpr int UG_LDS_CPS = 4096;                    // 25 bytes an entry: 100 KiB, one workgroup per CU of 160 KiB
 constexpr int UG_SMALL_CPS = 512;                   // 12.7 KiB: LDS admits 12 workgroups per CU, the compiler's occupancy 7
 constexpr int UG_LONG_GROUPS = 64;                  // workgroups (and workspace slots) of the long-row form
-constexpr uint32_t UG_BASE = 0x9E3779B1u;
 constexpr int32_t UG_META = 0x2581;
 
 struct UgVocab {
@@ -67,26 +67,13 @@ __device__ __forceinline__ int32_t ug_map(const int32_t* __restrict__ nmap, int3
 
 // the entry whose code points are first, w[1..L) and whose polynomial hash is h, -1 when the vocabulary has none
 __device__ __forceinline__ int32_t ug_find(const UgVocab& V, uint32_t h, int32_t first, const int32_t* w, int L) {
-  uint32_t x = h ^ ((uint32_t)L * 0xC2B2AE35u);
-  x ^= x >> 16;
-  x *= 0x7FEB352Du;
-  x ^= x >> 15;
-  x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  const uint32_t m = (uint32_t)V.n_slots - 1u;
-  uint32_t s = x & m;
-  for (int32_t probe = 0; probe < V.n_slots; ++probe) {      // bounded: a full table has no free slot to stop at
-    const int32_t e = V.slots[s];
-    if (e < 0 || e >= V.n_entries) return -1;
-    const int32_t b = V.ent_ptr[e];
-    if (V.ent_ptr[e + 1] - b == L && V.ent_cps[b] == first) {
-      int k = 1;
-      while (k < L && V.ent_cps[b + k] == w[k]) ++k;
-      if (k == L) return e;
-    }
-    s = (s + 1u) & m;
-  }
-  return -1;
+  const uint32_t x = text_hash_mix(h ^ ((uint32_t)L * 0xC2B2AE35u));
+  return text_probe(V.slots, V.ent_ptr, V.n_slots, V.n_entries, x, L, [&](int32_t, int32_t b) {
+    if (V.ent_cps[b] != first) return false;
+    int k = 1;
+    while (k < L && V.ent_cps[b + k] == w[k]) ++k;
+    return k == L;
+  });
 }
 
 // does a unit start at entry i of the row t[0..len)?
@@ -149,7 +136,7 @@ __device__ __forceinline__ void ug_row(const UgVocab& V, const uint32_t* pw, con
         uint32_t h = (uint32_t)(UG_META + 1);
         S.hx[i] = h;
         for (int64_t k = i + 1; k < len && ug_word(t[k]); ++k) {
-          h = h * UG_BASE + (uint32_t)(t[k] + 1);
+          h = h * TEXT_HASH_BASE + (uint32_t)(t[k] + 1);
           S.hx[k] = h;
         }
       } else if (!ug_word(c)) {
@@ -172,7 +159,7 @@ __device__ __forceinline__ void ug_row(const UgVocab& V, const uint32_t* pw, con
         for (int L = 1; L <= V.max_entry; ++L) {
           const int64_t k = i + L - 1;
           if (L > 1 && (k >= len || !ug_word(t[k]))) break;
-          p *= UG_BASE;
+          p *= TEXT_HASH_BASE;
           if (ug_find(V, S.hx[k] - hb * p, first, t + i, L) >= 0) m |= 1u << (L - 1);
         }
       }
@@ -190,13 +177,6 @@ __device__ __forceinline__ void ug_row(const UgVocab& V, const uint32_t* pw, con
   if (threadIdx.x == 0) out_cnt[row] = (max_pieces >= 0 ? min((int64_t)total, max_pieces) : (int64_t)total) + 2;
 }
 
-__device__ __forceinline__ void ug_powers(uint32_t* pw, int max_entry) {
-  if (threadIdx.x == 0) {
-    uint32_t p = 1u;
-    for (int L = 0; L <= max_entry; ++L) { pw[L] = p; p *= UG_BASE; }
-  }
-}
-
 // rows of MIN_LEN < len <= CPS + 1 entries (the white-space slot and CPS normalized code points)
 template <int CPS, int MIN_LEN>
 __global__ __launch_bounds__(UG_THREADS) void ug_pieces_kernel(const int64_t* __restrict__ ptr,
@@ -209,13 +189,13 @@ __global__ __launch_bounds__(UG_THREADS) void ug_pieces_kernel(const int64_t* __
   __shared__ uint32_t mask[CPS + 1];
   __shared__ int32_t bid[CPS + 1];
   __shared__ uint8_t blen[CPS + 1];
-  __shared__ uint32_t pw[UG_MAX_PIECE + 1];                  // pw[L] = UG_BASE^L
+  __shared__ uint32_t pw[UG_MAX_PIECE + 1];                  // pw[L] = TEXT_HASH_BASE^L
   __shared__ int slot;
   const int64_t row = blockIdx.x;
   const int64_t a0 = ptr[row], len = ptr[row + 1] - a0;
   if (len <= MIN_LEN || len > CPS + 1) return;               // block-uniform: another form's row
   for (int64_t i = threadIdx.x; i < len; i += UG_THREADS) t[i] = norm[a0 + i];
-  ug_powers(pw, V.max_entry);
+  text_hash_powers(pw, V.max_entry);
   __syncthreads();
   const UgState S{hx, mask, best, bid, blen};
   ug_row(V, pw, t, S, len, max_pieces, pieces + a0, out_cnt, row, slot);
@@ -234,7 +214,7 @@ __global__ __launch_bounds__(UG_THREADS) void ug_pieces_long_kernel(const int64_
                                                                     int64_t* __restrict__ out_cnt) {
   __shared__ uint32_t pw[UG_MAX_PIECE + 1];
   __shared__ int slot;
-  ug_powers(pw, V.max_entry);
+  text_hash_powers(pw, V.max_entry);
   __syncthreads();
   uint8_t* base = ws + (int64_t)blockIdx.x * slot_entries * UG_SLOT_BYTES;
   UgState S;

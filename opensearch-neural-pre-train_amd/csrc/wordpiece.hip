@@ -14,7 +14,8 @@
 //                            row's span in out_ptr, eos behind them.
 //   wp_pad_kernel            the CSR of ids as right-padded input_ids / attention_mask.
 // No atomic decides a place, no kernel waits for another workgroup: the result is a pure function of the input.
-#include "sparse_common.h"
+#include "sparse_common.h"   // block_sum
+#include "text_common.h"
 #include "snx.h"
 
 namespace {
@@ -24,7 +25,6 @@ constexpr int WP_WAVES = WP_THREADS / 64;
 constexpr int WP_LDS_CPS = 4096;                    // 16 KiB of code points + 16 KiB of prefix hashes
 constexpr int WP_LONG_GROUPS = 64;                  // workgroups (and workspace slots) of the long-row form
 constexpr int WP_WORD_MAX = 128;                    // bound of max_word / max_entry: the power table in LDS
-constexpr uint32_t WP_BASE = 0x9E3779B1u;
 constexpr uint8_t WP_SPACE = 1, WP_PUNCT = 2;       // class 0: a word character
 
 struct WpVocab {
@@ -43,12 +43,9 @@ __device__ __forceinline__ uint8_t wp_class(const WpVocab& V, int32_t c) {
 
 // the id of the entry (cont, w[0..L)) whose polynomial hash is h, -1 when the vocabulary has none
 __device__ __forceinline__ int32_t wp_lookup(const WpVocab& V, uint32_t h, int cont, const int32_t* w, int L) {
-  uint32_t x = h ^ (cont ? 0x85EBCA6Bu : 0u) ^ ((uint32_t)L * 0xC2B2AE35u);
-  x ^= x >> 16;
-  x *= 0x7FEB352Du;
-  x ^= x >> 15;
-  x *= 0x846CA68Bu;
-  x ^= x >> 16;
+  const uint32_t x = text_hash_mix(h ^ (cont ? 0x85EBCA6Bu : 0u) ^ ((uint32_t)L * 0xC2B2AE35u));
+  // text_probe's loop, written out: with the shared one (ent_cont in the predicate, ent_id read behind the probe), and
+  // likewise with text_hash_powers, wp_pieces_kernel compiles to other code (profiles/text_front_refactor.txt)
   const uint32_t mask = (uint32_t)V.n_slots - 1u;
   uint32_t s = x & mask;
   for (int32_t probe = 0; probe < V.n_slots; ++probe) {      // bounded: a full table has no free slot to stop at
@@ -76,7 +73,7 @@ __device__ __forceinline__ int wp_word(const WpVocab& V, const uint32_t* pw, con
   if (ok) {
     uint32_t h = 0;
     for (int64_t k = s; k < e; ++k) {
-      h = h * WP_BASE + (uint32_t)(t[k] + 1);
+      h = h * TEXT_HASH_BASE + (uint32_t)(t[k] + 1);
       hx[k] = h;                                             // the hash of t[s..k]
     }
     int64_t st = s;
@@ -127,7 +124,7 @@ __global__ __launch_bounds__(WP_THREADS) void wp_pieces_kernel(const int64_t* __
                                                                int64_t max_pieces, uint32_t* __restrict__ ws,
                                                                int64_t ws_cps, int32_t* __restrict__ pieces,
                                                                int64_t* __restrict__ out_cnt) {
-  __shared__ uint32_t pw[WP_WORD_MAX + 1];                   // pw[L] = WP_BASE^L
+  __shared__ uint32_t pw[WP_WORD_MAX + 1];                   // pw[L] = TEXT_HASH_BASE^L
   __shared__ int slot;
   if constexpr (!LONG) {
     __shared__ int32_t t[WP_LDS_CPS];
@@ -136,16 +133,16 @@ __global__ __launch_bounds__(WP_THREADS) void wp_pieces_kernel(const int64_t* __
     const int64_t a0 = ptr[row], len = ptr[row + 1] - a0;
     if (len > WP_LDS_CPS) return;                            // block-uniform: the long form's row
     for (int64_t i = threadIdx.x; i < len; i += WP_THREADS) t[i] = cps[a0 + i];
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0) {                                  // text_hash_powers written out, as wp_lookup's probe
       uint32_t p = 1u;
-      for (int L = 0; L <= V.max_entry; ++L) { pw[L] = p; p *= WP_BASE; }
+      for (int L = 0; L <= V.max_entry; ++L) { pw[L] = p; p *= TEXT_HASH_BASE; }
     }
     __syncthreads();
     wp_row(V, pw, t, hx, len, max_pieces, pieces + a0, out_cnt, row, slot);
   } else {
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0) {                                  // text_hash_powers written out, as wp_lookup's probe
       uint32_t p = 1u;
-      for (int L = 0; L <= V.max_entry; ++L) { pw[L] = p; p *= WP_BASE; }
+      for (int L = 0; L <= V.max_entry; ++L) { pw[L] = p; p *= TEXT_HASH_BASE; }
     }
     __syncthreads();
     uint32_t* hx = ws + (int64_t)blockIdx.x * ws_cps;

@@ -10,10 +10,11 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import _text
 from ._abi import CONSTANTS
 from ._lib import call
 from .ops import _p, _stream
-from .retrieval._common import cuda_device, workspace
+from .retrieval._common import workspace
 
 MSG_MAX = CONSTANTS["SNX_MINHASH_MSG_MAX"]        # message bytes that one MD5 block holds
 PERM_MAX = CONSTANTS["SNX_MINHASH_PERM_MAX"]
@@ -47,15 +48,7 @@ def code_point_csr(texts: Sequence[str], who: str = "code_point_csr") -> Tuple[n
     texts = list(texts)
     if any(not isinstance(t, str) for t in texts):
         raise ValueError(f"{who}: texts must be strings")
-    low = [t.lower().strip() for t in texts]
-    ptr = np.zeros(len(low) + 1, dtype=np.int64)
-    if low:
-        np.cumsum(np.fromiter((len(t) for t in low), dtype=np.int64, count=len(low)), out=ptr[1:])
-    try:
-        raw = "".join(low).encode("utf-32-le")
-    except UnicodeEncodeError as e:
-        raise ValueError(f"{who}: a text holds a lone surrogate (U+D800..U+DFFF), which has no UTF-8 form") from e
-    return ptr, np.frombuffer(raw, dtype="<u4").astype(np.int32)
+    return _text.code_point_csr([t.lower().strip() for t in texts], who)
 
 
 def longest_message_bytes(ptr: np.ndarray, code_points: np.ndarray, ngram_size: int, num_perm: int) -> int:
@@ -110,14 +103,10 @@ def minhash_signatures(texts: Sequence[str], num_perm: int = 128, ngram_size: in
     row is the minimum over its character n-grams of ``int(md5(f"{i}_{ngram}".encode()).hexdigest(), 16)``
     (ref:deduplicator.py:59-82).  -> uint32 [n, num_perm, 4] on ``device``, most significant word first."""
     ptr, cps = signature_inputs(texts, num_perm, ngram_size)
-    dev = cuda_device(device)
-    if dev.type != "cuda":
-        raise ValueError("minhash_signatures: runs on a GPU")
+    d_ptr, d_cps, dev = _text.csr_to_device(ptr, cps, device, "minhash_signatures", trusted=True)
     n = ptr.size - 1
     sig = torch.empty((n, int(num_perm), 4), dtype=torch.int32, device=dev)
     if n:
-        d_ptr = torch.from_numpy(ptr).to(dev)
-        d_cps = torch.from_numpy(cps).to(dev) if cps.size else None
         with torch.cuda.device(dev):
             call("snx_minhash_signatures", _p(d_ptr), _p(d_cps), n, int(ngram_size), int(num_perm), _p(sig), _stream())
     return sig.view(torch.uint32)

@@ -12,7 +12,7 @@ import torch
 
 from .._abi import CONSTANTS
 from .._lib import call
-from ..minhash import code_point_csr
+from .._text import code_point_csr, csr_to_device
 from ..ops import _p, _stream
 from ._common import cat_or_empty, cuda_device, offsets, search_outputs, workspace
 from .sparse import SparseIndex
@@ -91,19 +91,13 @@ def row_counts(ptr: np.ndarray, cps: np.ndarray, ngram_range, device):
     """Code-point rows -> (cnt int64 [n], keys int64 [nnz] ascending within each row, counts int32 [nnz]) on ``device``
     (snx_tfidf_row_counts, snx_tfidf_compact_counts)."""
     lo, hi = check_ngram_range(ngram_range, "row_counts")
-    dev = cuda_device(device)
-    if dev.type != "cuda":
-        raise ValueError("row_counts: runs on a GPU")
+    d_ptr, d_cps, dev = csr_to_device(ptr, cps, device, "row_counts", trusted=True)
     n = int(ptr.size - 1)
-    if n >= 2 ** 31:
-        raise ValueError("row_counts: at most 2^31 - 1 rows")
     if n == 0:
         return (torch.zeros(0, dtype=torch.long, device=dev), torch.zeros(0, dtype=torch.long, device=dev),
                 torch.zeros(0, dtype=torch.int32, device=dev))
     NS = slots_per_position(lo, hi)
     longest = int((ptr[1:] - ptr[:-1]).max())
-    d_ptr = torch.from_numpy(np.ascontiguousarray(ptr, dtype=np.int64)).to(dev)
-    d_cps = torch.from_numpy(np.ascontiguousarray(cps, dtype=np.int32)).to(dev) if cps.size else None
     slots = (int(ptr[-1]) + 2 * n) * NS
     s_key = torch.empty(slots, dtype=torch.long, device=dev)
     s_count = torch.empty(slots, dtype=torch.int32, device=dev)

@@ -5,44 +5,19 @@ validity filter, the SHA-256 of rows and the first-occurrence dedup of the refer
 The host's part is the text: documents to a CSR of code points and paragraphs back to ``str``.  Nothing is lowered or
 stripped here; the device strips."""
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from ._lib import call
+from ._text import LoneSurrogateError, code_point_csr, csr_to_device  # noqa: F401  (the first two: this module's names too)
 from .ops import _p, _stream
-from .retrieval._common import cuda_device, offsets, workspace
+from .retrieval._common import offsets, workspace
 
 TILE = 256                             # code points of one tile of the segmentation (TX_TILE of csrc/textprep.hip)
 FIRST_EQUAL_MAX = 2 ** 29              # rows of one first_equal call (TX_DEDUP_MAX)
 HANGUL_LO, HANGUL_HI = 0xAC00, 0xD7AF  # the reference's range, inclusive (ref:prepare_korean_mlm_data.py:20)
-
-
-class LoneSurrogateError(ValueError):
-    """A text holds a lone surrogate; ``index`` is the first such text."""
-
-    def __init__(self, message: str, index: int):
-        super().__init__(message)
-        self.index = index
-
-
-def code_point_csr(texts: Sequence[str], who: str = "code_point_csr") -> Tuple[np.ndarray, np.ndarray]:
-    """Every text as it is, as a CSR of Unicode code points: (ptr int64 [n+1], code_points int32).  A lone surrogate
-    raises (it has no UTF-8 form: the reference's ``.encode()`` would)."""
-    texts = list(texts)
-    if any(not isinstance(t, str) for t in texts):
-        raise ValueError(f"{who}: texts must be strings")
-    ptr = np.zeros(len(texts) + 1, dtype=np.int64)
-    if texts:
-        np.cumsum(np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts)), out=ptr[1:])
-    try:
-        raw = "".join(texts).encode("utf-32-le")
-    except UnicodeEncodeError:
-        bad = next(i for i, t in enumerate(texts) if any(0xD800 <= ord(ch) <= 0xDFFF for ch in t))
-        raise LoneSurrogateError(f"{who}: text {bad} holds a lone surrogate (U+D800..U+DFFF), which has no UTF-8 form",
-                                 bad) from None
-    return ptr, np.frombuffer(raw, dtype="<u4").astype(np.int32)
 
 
 @dataclass
@@ -62,30 +37,6 @@ class Paragraphs:
         return self.par_ptr[1:] - self.par_ptr[:-1]
 
 
-def _csr_on(ptr, cps, device, who: str) -> Tuple[torch.Tensor, Optional[torch.Tensor], torch.device]:
-    """(ptr, code_points) as numpy arrays or tensors -> int64 / int32 tensors on one GPU, checked to be a CSR."""
-    if isinstance(ptr, np.ndarray):
-        ptr = torch.from_numpy(np.ascontiguousarray(ptr))
-    if isinstance(cps, np.ndarray):
-        cps = torch.from_numpy(np.ascontiguousarray(cps))
-    if not isinstance(ptr, torch.Tensor) or not isinstance(cps, torch.Tensor) or ptr.dim() != 1 or cps.dim() != 1 or \
-            ptr.dtype != torch.int64 or cps.dtype != torch.int32 or ptr.numel() < 1:
-        raise ValueError(f"{who}: rows are ptr int64 [n+1] and code_points int32")
-    if device is None:
-        device = ptr.device if ptr.is_cuda else cps.device if cps.is_cuda else "cuda"
-    dev = cuda_device(device)
-    if dev.type != "cuda":
-        raise ValueError(f"{who}: runs on a GPU")
-    if ptr.numel() - 1 >= 2 ** 31:
-        raise ValueError(f"{who}: at most 2^31 - 1 rows")
-    ptr, cps = ptr.to(dev).contiguous(), cps.to(dev).contiguous()
-    lens = ptr[1:] - ptr[:-1]
-    if int(ptr[0]) != 0 or int(ptr[-1]) != cps.numel() or (lens.numel() and
-                                                             (int(lens.min()) < 0 or int(lens.max()) >= 2 ** 31)):
-        raise ValueError(f"{who}: ptr must start at 0, not decrease, end at len(code_points), rows shorter than 2^31")
-    return ptr, (cps if cps.numel() else None), dev
-
-
 def segment_paragraphs(docs: Sequence[str], device="cuda") -> Paragraphs:
     """Rules 1-3 of the reference's ``clean_text`` and ``split_paragraphs`` (ref:prepare_korean_mlm_data.py:31-40) on
     the GPU (snx_tx_segment_*): blank runs collapse to one U+0020, runs of two or more U+000A cut a document into pieces,
@@ -95,7 +46,7 @@ def segment_paragraphs(docs: Sequence[str], device="cuda") -> Paragraphs:
 
 def segment_csr(ptr, code_points, device=None) -> Paragraphs:
     """``segment_paragraphs`` of documents that are already a CSR of code points (numpy arrays or tensors)."""
-    d_ptr, d_cps, dev = _csr_on(ptr, code_points, device, "segment_paragraphs")
+    d_ptr, d_cps, dev = csr_to_device(ptr, code_points, device, "segment_paragraphs")
     n = d_ptr.numel() - 1
     i32 = dict(dtype=torch.int32, device=dev)
     if n == 0:
@@ -141,7 +92,7 @@ def sha256_rows(ptr, code_points, device=None) -> torch.Tensor:
     """SHA-256 of the UTF-8 bytes of every row of a code-point CSR on the GPU (snx_tx_sha256_rows) -> uint32 [n, 8], most
     significant word first: ``"".join("%08x" % w for w in row)`` is ``hashlib.sha256(text.encode()).hexdigest()``
     (ref:prepare_korean_mlm_data.py:56-58)."""
-    d_ptr, d_cps, dev = _csr_on(ptr, code_points, device, "sha256_rows")
+    d_ptr, d_cps, dev = csr_to_device(ptr, code_points, device, "sha256_rows")
     if d_cps is not None and not bool(((d_cps >= 0) & (d_cps <= 0x10FFFF) & ((d_cps < 0xD800) | (d_cps > 0xDFFF))).all()):
         raise ValueError("sha256_rows: code points must be Unicode scalar values (no surrogates)")
     n = d_ptr.numel() - 1

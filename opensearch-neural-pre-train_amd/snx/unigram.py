@@ -39,15 +39,16 @@ from __future__ import annotations
 
 import base64
 import functools
-import os
+import os  # noqa: F401  (the fork guard's os.getpid is reached through this module too)
 import re
-import time
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from .wordpiece import WHITE_SPACE, WordPieceTokenizer, _refuse, code_point_rows, entry_hash
+from . import _text
+from ._tokenizer import RowTokenizer, _refuse
+from .wordpiece import WHITE_SPACE
 
 META = "\N{LOWER ONE EIGHTH BLOCK}"    # U+2581
 MAX_PIECE = 32                         # longest piece on the device, in code points (UG_MAX_PIECE of csrc/unigram.hip)
@@ -199,8 +200,12 @@ def _is_double_space_replace(n) -> bool:
     return isinstance(n, dict) and n.get("type") == "Replace" and n.get("pattern") == {"Regex": " {2,}"} and n.get("content") == " "
 
 
-class UnigramTokenizer(WordPieceTokenizer):
-    """``UnigramTokenizer.from_pretrained(dir, device="cuda")``; the call surface of ``WordPieceTokenizer``."""
+class UnigramTokenizer(RowTokenizer):
+    """``UnigramTokenizer.from_pretrained(dir, device="cuda")``; the call surface of the tree's tokenizers
+    (``RowTokenizer``, snx/_tokenizer.py)."""
+
+    _factory_name = "unigram"
+    _added_refused = ("normalized", "single_word")
 
     # ------------------------------------------------------------------------------------------------ loading
     def _parse(self, spec: dict) -> None:
@@ -267,20 +272,12 @@ class UnigramTokenizer(WordPieceTokenizer):
         self._max_entry = max((len(k) for _, k, _ in self._entries), default=1)
         self._longest = max(len(k) for k in self._vocab)
         self._lookup = {k: (v, self._scores[v]) for k, v in self._vocab.items()}
-        self._parse_template(spec)
 
-        self._added: Dict[str, int] = {}
-        for i, a in enumerate(spec.get("added_tokens") or []):
-            for field in ("normalized", "single_word"):
-                if a.get(field):
-                    _refuse(f"added_tokens[{i}].{field}", f"{a.get('content')!r}: true is not supported")
-            if a.get("content"):
-                self._added[str(a["content"])] = int(a["id"])
-        alts = sorted(self._added, key=len, reverse=True)
-        self._added_re = re.compile("|".join(re.escape(a) for a in alts)) if alts else None
-        self._first_chars = frozenset(a[0] for a in alts)
-        self._id_to_token: Dict[int, str] = {v: k for k, v in self._vocab.items()}
-        self._id_to_token.update({v: k for k, v in self._added.items()})
+    def _refuse_added(self, index: int, field: str, content) -> None:
+        _refuse(f"added_tokens[{index}].{field}", f"{content!r}: true is not supported")
+
+    def _parse_added(self, spec: dict) -> None:
+        super()._parse_added(spec)
         _joining_re()                                              # needs `regex`: fail at load time, not at the first row
         self._host_marks = joining_table().copy()
         self._host_marks[[ord(c) for c in self._first_chars]] |= 2
@@ -334,10 +331,7 @@ class UnigramTokenizer(WordPieceTokenizer):
         return self._normalized_pieces(self.charsmap.normalize(text))
 
     def host_row(self, text: str, max_length: Optional[int] = None, normalized: bool = False) -> List[int]:
-        pieces = self._normalized_pieces(text) if normalized else self.host_pieces(text)
-        if max_length is not None:
-            pieces = pieces[:max_length - 2]
-        return [self._bos] + pieces + [self._eos]
+        return self._frame(self._normalized_pieces(text) if normalized else self.host_pieces(text), max_length)
 
     def normalize(self, text: str) -> str:
         """The normalizer's output for ``text`` (added tokens are not looked for)."""
@@ -348,74 +342,27 @@ class UnigramTokenizer(WordPieceTokenizer):
         return _joining_re().search(text) is not None or super()._needs_host(text)
 
     # ------------------------------------------------------------------------------------------------ device
-    def _guard(self) -> None:
-        if os.getpid() != self._pid:
-            raise RuntimeError("UnigramTokenizer: this tokenizer was created in another process and a forked process must not "
-                               "touch the GPU: tokenize in the parent (DataLoader num_workers=0) or use device=\"cpu\" "
-                               "(create_tokenizer(\"unigram:DIR\"))")
-
     def device_tables(self) -> Dict[str, np.ndarray]:
         """The vocabulary as the device reads it (include/snx.h): slots, ent_ptr, ent_cps, ent_id int32, ent_score float64."""
-        mask = self.table_size - 1
-        slots = np.full(self.table_size, -1, dtype=np.int32)
-        ent_ptr = np.zeros(len(self._entries) + 1, dtype=np.int32)
-        cps: List[int] = []
-        for e, (_, key, _) in enumerate(self._entries):
-            k = [ord(ch) for ch in key]
-            cps.extend(k)
-            ent_ptr[e + 1] = len(cps)
-            s = entry_hash(0, k) & mask
-            while slots[s] >= 0:                              # linear probing; table_size >= entries, so a slot is free
-                s = (s + 1) & mask
-            slots[s] = e
-        ids = [i for _, _, i in self._entries]
-        return dict(slots=slots, ent_ptr=ent_ptr, ent_cps=np.asarray(cps, dtype=np.int32),
-                    ent_id=np.asarray(ids, dtype=np.int32), ent_score=np.asarray([self._scores[i] for i in ids], dtype=np.float64))
+        return dict(super().device_tables(),
+                    ent_score=np.asarray([self._scores[i] for _, _, i in self._entries], dtype=np.float64))
 
-    def _device_state(self):
-        if self._state is None:
-            from .retrieval._common import cuda_device
-            dev = cuda_device(self.device)
-            nmap, pool = self.charsmap.code_point_map
-            tables = dict(self.device_tables(), nmap=nmap, pool=pool)
-            st = {k: (torch.from_numpy(np.ascontiguousarray(v)).to(dev) if v.size else None) for k, v in tables.items()}
-            st.update(dev=dev)
-            self._state = st
-        return self._state
+    def _device_arrays(self) -> Dict[str, np.ndarray]:
+        nmap, pool = self.charsmap.code_point_map
+        return dict(self.device_tables(), nmap=nmap, pool=pool)
 
     def encode_rows(self, texts: Sequence[str], max_length: Optional[int] = None,
                     normalized: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
-        """The unpadded form, as ``WordPieceTokenizer.encode_rows``.  ``normalized``: the texts are the normalizer's output
+        """The unpadded form, as ``RowTokenizer.encode_rows``.  ``normalized``: the texts are the normalizer's output
         already; added tokens are not looked for, the charsmap is not applied (on the device: a map that keeps every code
         point) and no row is the host's.  This is the way to a row that holds a literal U+2581: SentencePiece's charsmaps
-        rewrite that one to a space."""
-        return self._encode_rows(texts, max_length, normalized)[:2]
+        rewrite that one to a space.  The device path reads two pairs of numbers back: the size of the normalized text
+        (rows grow and shrink under the charsmap) and the size of the ids."""
+        return self._encode_rows(texts, max_length, normalized=normalized)[:2]
 
-    def _encode_rows(self, texts, max_length, normalized: bool = False) -> Tuple[torch.Tensor, torch.Tensor, int]:
-        """``encode_rows`` and the length of the longest row.  The device path reads two pairs of numbers back: the size of
-        the normalized text (rows grow and shrink under the charsmap) and the size of the ids."""
-        texts = self._texts(texts)
-        max_length = self._max_length(max_length)
+    def _pack(self, texts: List[str], normalized: bool = False) -> Tuple[np.ndarray, np.ndarray, List[int]]:
         n = len(texts)
-        if self.device.type == "cpu":
-            t0 = time.perf_counter()
-            rows = [self.host_row(t, max_length, normalized) for t in texts]
-            ptr = np.zeros(n + 1, dtype=np.int64)
-            if n:
-                np.cumsum([len(r) for r in rows], out=ptr[1:])
-            ids = np.fromiter((i for r in rows for i in r), dtype=np.int64, count=int(ptr[-1]))
-            self.last_stats = {"rows": n, "host_rows": n, "pack_s": time.perf_counter() - t0, "device_s": 0.0}
-            return torch.from_numpy(ptr), torch.from_numpy(ids), max((len(r) for r in rows), default=0)
-        self._guard()
-        from ._lib import call
-        from .ops import _p, _stream
-        from .retrieval._common import offsets, workspace
-        st = self._device_state()
-        dev = st["dev"]
-        if n >= 2 ** 31:
-            raise ValueError("UnigramTokenizer: at most 2^31 - 1 texts a call")
-        t0 = time.perf_counter()
-        ptr, cps = code_point_rows(texts, "UnigramTokenizer")
+        ptr, cps = _text.code_point_csr(texts, "UnigramTokenizer")
         lens = ptr[1:] - ptr[:-1]
         if n and int(lens.max()) >= 2 ** 26:
             raise ValueError("UnigramTokenizer: a text of 2^26 code points or more")
@@ -436,62 +383,37 @@ class UnigramTokenizer(WordPieceTokenizer):
                 cps = cps[np.repeat(~host, lens)]
                 ptr = np.zeros(n + 1, dtype=np.int64)
                 np.cumsum(np.where(host, 0, lens), out=ptr[1:])
-        host_rows = [self.host_row(texts[i], max_length) for i in host_idx]
-        t1 = time.perf_counter()
-        if n == 0:
-            self.last_stats = {"rows": 0, "host_rows": 0, "pack_s": t1 - t0, "device_s": 0.0}
-            return torch.zeros(1, dtype=torch.long, device=dev), torch.zeros(0, dtype=torch.long, device=dev), 0
-        with torch.cuda.device(dev):
-            d_ptr = torch.from_numpy(ptr).to(dev)
-            d_cps = torch.from_numpy(cps).to(dev) if cps.size else None
-            nlen = torch.empty(n, dtype=torch.long, device=dev)
-            if normalized and "keep" not in st:
-                st["keep"] = torch.full((0x110000,), -1, dtype=torch.int32, device=dev)
-            nmap = st["keep"] if normalized else st["nmap"]
-            call("snx_ug_norm_count", _p(d_ptr), _p(d_cps), n, _p(nmap), _p(nlen), _stream())
-            nptr = offsets(nlen)
-            ntotal, longest = torch.stack((nptr[-1], nlen.max())).tolist()       # host read 1: sizes the normalized text
-            if longest >= 2 ** 31:
-                raise ValueError("UnigramTokenizer: a text normalizes to 2^31 code points or more")
-            norm = torch.empty(ntotal, dtype=torch.int32, device=dev)
-            call("snx_ug_norm_fill", _p(d_ptr), _p(d_cps), n, _p(nmap), _p(st["pool"]), _p(nptr), _p(norm), _stream())
-            pieces = torch.empty(ntotal, dtype=torch.int32, device=dev)
-            cnt = torch.empty(n, dtype=torch.long, device=dev)
-            ws, ws_bytes = workspace("snx_ug_workspace_bytes", dev, longest)
-            call("snx_ug_pieces", _p(nptr), _p(norm), n, longest, _p(st["slots"]), self.table_size, _p(st["ent_ptr"]),
-                 _p(st["ent_cps"]), _p(st["ent_id"]), _p(st["ent_score"]), len(self._entries), self._max_entry, self._unk,
-                 self._unk_score, -1 if max_length is None else max_length - 2, _p(pieces), _p(cnt), _p(ws), ws_bytes,
-                 _stream())
-            if host_idx:
-                h_idx = torch.tensor(host_idx, dtype=torch.long, device=dev)
-                h_len = torch.tensor([len(r) for r in host_rows], dtype=torch.long, device=dev)
-                cnt[h_idx] = h_len
-            out_ptr = offsets(cnt)
-            total, widest = torch.stack((out_ptr[-1], cnt.max())).tolist()       # host read 2: sizes out_ids
-            ids = torch.empty(total, dtype=torch.long, device=dev)
-            call("snx_wp_fill", _p(nptr), _p(pieces), n, _p(out_ptr), self._bos, self._eos, _p(ids), _stream())
-            if host_idx:
-                flat = np.fromiter((i for r in host_rows for i in r), dtype=np.int64)
-                within = np.concatenate([np.arange(len(r), dtype=np.int64) for r in host_rows])
-                base = torch.repeat_interleave(out_ptr[h_idx], h_len, output_size=int(flat.size))
-                ids[base + torch.from_numpy(within).to(dev)] = torch.from_numpy(flat).to(dev)
-            torch.cuda.current_stream().synchronize()
-        self.last_stats = {"rows": n, "host_rows": len(host_idx), "pack_s": t1 - t0, "device_s": time.perf_counter() - t1}
-        return out_ptr, ids, widest
+        return ptr, cps, host_idx
+
+    def _device_pieces(self, st, ptr: np.ndarray, d_ptr, d_cps, max_length, normalized: bool = False):
+        from ._lib import call
+        from .ops import _p, _stream
+        from .retrieval._common import offsets, workspace
+        dev, n = st["dev"], ptr.size - 1
+        nlen = torch.empty(n, dtype=torch.long, device=dev)
+        if normalized and "keep" not in st:
+            st["keep"] = torch.full((0x110000,), -1, dtype=torch.int32, device=dev)
+        nmap = st["keep"] if normalized else st["nmap"]
+        call("snx_ug_norm_count", _p(d_ptr), _p(d_cps), n, _p(nmap), _p(nlen), _stream())
+        nptr = offsets(nlen)
+        ntotal, longest = torch.stack((nptr[-1], nlen.max())).tolist()           # host read 1: sizes the normalized text
+        if longest >= 2 ** 31:
+            raise ValueError("UnigramTokenizer: a text normalizes to 2^31 code points or more")
+        norm = torch.empty(ntotal, dtype=torch.int32, device=dev)
+        call("snx_ug_norm_fill", _p(d_ptr), _p(d_cps), n, _p(nmap), _p(st["pool"]), _p(nptr), _p(norm), _stream())
+        pieces = torch.empty(ntotal, dtype=torch.int32, device=dev)
+        cnt = torch.empty(n, dtype=torch.long, device=dev)
+        ws, ws_bytes = workspace("snx_ug_workspace_bytes", dev, longest)
+        call("snx_ug_pieces", _p(nptr), _p(norm), n, longest, _p(st["slots"]), self.table_size, _p(st["ent_ptr"]),
+             _p(st["ent_cps"]), _p(st["ent_id"]), _p(st["ent_score"]), len(self._entries), self._max_entry, self._unk,
+             self._unk_score, -1 if max_length is None else max_length - 2, _p(pieces), _p(cnt), _p(ws), ws_bytes,
+             _stream())
+        return nptr, pieces, cnt                                                 # host read 2 is _finish_rows'
 
     # ------------------------------------------------------------------------------------------------ call surface
     def decode(self, ids, skip_special_tokens: bool = False) -> str:
         """The Metaspace decoder: pieces joined, U+2581 read as a space, the leading one dropped."""
-        if isinstance(ids, torch.Tensor):
-            ids = ids.tolist()
-        special = set(self._added.values())
-        toks = []
-        for i in ids:
-            if skip_special_tokens and int(i) in special:
-                continue
-            tok = self._id_to_token.get(int(i))
-            if tok is not None:
-                toks.append(tok)
+        toks = self._tokens(ids, skip_special_tokens)
         if toks and toks[0].startswith(META):
             toks[0] = toks[0][1:]
         return "".join(toks).replace(META, " ")
