@@ -1157,7 +1157,9 @@ int snx_gemm_tn_accum_interleaved(const void* dY, const void* X, float* dW, int3
  * nn.Linear backward torch runs as four GEMMs) in one launch.  From 8,192 token rows on: the 256x256 persistent kernel
  * (csrc/gemm_tn256.hip: one workgroup per CU, one flush per workgroup); below, and for the ragged
  * rest of M % 64 rows: the concatenated 128x128 output tiles fill whole rounds of the resident workgroups
- * (csrc/gemm.hip).  N, K multiples of 128. */
+ * (csrc/gemm.hip).  The threshold is the process switch "tn256_min_m"; whatever it is set to, the persistent kernel is
+ * taken only where the token range holds one whole 64-row K-step ((M & ~63) >= 64): M < 64 always runs the 128x128
+ * kernel, with the 0 workspace bytes snx_gemm_tn_workspace_bytes() states for it.  N, K multiples of 128. */
 int snx_gemm_tn_accum_group(const snx_tn_problem* probs /*[host]*/, int32_t nprob, int32_t M, void* ws, size_t ws_bytes,
                             hipStream_t stream);
 /* Process-wide launch hint (host state, read at launch time): leave `n` CUs (0..128, rounded up to a multiple of 8)

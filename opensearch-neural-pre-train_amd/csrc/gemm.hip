@@ -557,9 +557,11 @@ static int launch_tn_group(const TnGroup& g, int M, void* ws, size_t ws_bytes, h
   const bool det = g_snx_cfg.det_reduce != 0;
   // long token ranges: the 256x256 persistent form (gemm_tn256.hip); "tn256" = 0 keeps the 128x128 kernel
   const int tn256 = g_snx_cfg.tn256, tn256_min_m = g_snx_cfg.tn256_min_m;
-  if (tn256 && M >= tn256_min_m) {
-    // whole 64-row K-steps there; a ragged rest of the token range (< 64 rows) comes back to this kernel
-    const int M64 = M & ~63;
+  // whole 64-row K-steps there; a ragged rest of the token range (< 64 rows) comes back to this kernel.  A range
+  // without one whole K-step ("tn256_min_m" below 64) has nothing for the 256 form: the 128x128 kernel serves it
+  // with the 0 workspace bytes that tn_group_ws_bytes advertises for it.
+  const int M64 = M & ~63;
+  if (tn256 && M >= tn256_min_m && M64 >= 64) {
     const int rc = snx_launch_tn256(g, M64, ws, ws_bytes, st);
     if (rc == SNX_OK) {
       if (M64 == M) return SNX_OK;
