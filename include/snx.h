@@ -213,6 +213,52 @@ int snx_model_backward_f32_tw(const snx_model_desc* d, const void* const* params
  * (nn.Linear in fp32: forward, dX and dW are the same kernel with different strides). */
 int snx_gemm_f32(const float* A, int64_t a_row, int64_t a_k, const float* B, int64_t b_row, int64_t b_k, float* C, int64_t ldc,
                  const float* R, int64_t ldr, int32_t M, int32_t N, int32_t K, int32_t accumulate, hipStream_t stream);
+/* The steps of the two model entry points above, one call each: snx_model_forward_f32 / snx_model_backward_f32_tw are
+ * sequences of exactly these calls and of snx_gemm_f32's launch, so a test that runs one alone runs what the model runs
+ * (tests/test_gpu_f32_per_element.py).  All tensors fp32 and row-major unless stated; shapes SNX_E_SHAPE, NULLs SNX_E_ARG.
+ * seq_ids: seqid[t] = the sequence of token t (cu_seqlens as above).
+ * ln_fwd: out [T, H] = LN(x) * w; src 0: x = in [T, H]; 1: x = in[ids[t]] (embedding gather, ids int64 [T]); 2: x = gelu(in).
+ * ln_bwd: the backward of ln_fwd for upstream dy [T, H]; dw [H] += sum_t dy xhat (float atomics: dw is accumulated into).
+ *   src 0: dst [T, H] = dx, or += dx with accumulate != 0; src 1: dst[ids[t]] += dx (float atomics), no row for
+ *   ids[t] == pad_id; src 2: dst = dx * gelu'(in).  accumulate != 0 is legal with src 0 only.
+ * rope: rotates the q and k thirds of qkv [T, 3, heads, head_dim] in place, table [max_pos][head_dim / 2][2] (cos, sin),
+ *   pos int32 [T]; inverse != 0: the transposed rotation (the backward).  head_dim even, 2..64.
+ * geglu_fwd: y [T, I] = gelu(u[:, :I]) * u[:, I:], u [T, 2 I]; geglu_bwd: du [T, 2 I] from u and dy [T, I].
+ * attn_fwd: out [T, heads, head_dim], lse [heads, T] of softmax(q k^T / sqrt(head_dim)) v over the keys j of the query's
+ *   own sequence with mask[j] != 0 and (window < 0 or |i - j| <= window); a query that sees no key gives out = 0, lse = 0.
+ *   head_dim % 8 == 0 runs the MFMA-tiled form, where mask == NULL (every key valid) and lse == NULL (not stored) are
+ *   legal and seqid is not read; any other even head_dim, and every one under "f32_attn_rows" = 1, runs one wave per
+ *   (token, head), which needs seqid, mask and lse.
+ * attn_bwd: dqkv [T, 3, heads, head_dim] (zeroed here, then dq written, dk / dv by float atomics) from qkv, the forward's
+ *   out and lse, and dout [T, heads, head_dim].
+ * tail_fwd: the tied decoder and the SPLADE tail: logits = Hd [T, H] E [V, H]^T + bias [V], w = log1p(relu(logits)) * mask;
+ *   keys [nseq, V] (uint64: bits of max_t w << 32 | 0xFFFFFFFF - pos of the FIRST token of the maximum) and twkeys [T]
+ *   (uint64: bits of max_v w << 32 | 0xFFFFFFFF - the FIRST v of the maximum) are zeroed and filled; sparse [nseq, V] and
+ *   token_weights [T] are their high words.
+ * tail_bwd: the routed backward of tail_fwd from its keys / twkeys: for every (b, v) with sparse > 0 and g_sparse != 0,
+ *   c = g_sparse exp(-sparse): dHd[cu_seqlens[b] + pos] += c E[v], gradE[v] += c Hd[token], gradb[v] += c; the same per
+ *   token with g_token_weights [T] (or NULL) through twkeys.  dHd [T, H] is zeroed here; gradE [V, H] and gradb [V] are
+ *   accumulated into (float atomics). */
+int snx_f32_seq_ids(const int32_t* cu_seqlens, int32_t* seqid, int32_t T, int32_t nseq, hipStream_t stream);
+int snx_f32_ln_fwd(const float* in, const int64_t* ids, const float* w, float* out, int32_t T, int32_t H, float eps, int32_t src,
+                   hipStream_t stream);
+int snx_f32_ln_bwd(const float* dy, const float* in, const int64_t* ids, const float* w, float* dst, float* dw, int32_t T,
+                   int32_t H, float eps, int32_t src, int32_t accumulate, int32_t pad_id, hipStream_t stream);
+int snx_f32_rope(float* qkv, const float* table, const int32_t* pos, int32_t T, int32_t heads, int32_t head_dim,
+                 int32_t inverse, hipStream_t stream);
+int snx_f32_geglu_fwd(const float* u, float* y, int32_t T, int32_t I, hipStream_t stream);
+int snx_f32_geglu_bwd(const float* u, const float* dy, float* du, int32_t T, int32_t I, hipStream_t stream);
+int snx_f32_attn_fwd(const float* qkv, const int32_t* cu_seqlens, const int32_t* seqid, const int64_t* mask, float* out,
+                     float* lse, int32_t T, int32_t nseq, int32_t heads, int32_t head_dim, int32_t window, hipStream_t stream);
+int snx_f32_attn_bwd(const float* qkv, const float* out, const float* dout, const float* lse, const int32_t* cu_seqlens,
+                     const int32_t* seqid, const int64_t* mask, float* dqkv, int32_t T, int32_t nseq, int32_t heads,
+                     int32_t head_dim, int32_t window, hipStream_t stream);
+int snx_f32_tail_fwd(const float* Hd, const float* E, const float* bias, const int64_t* mask, const int32_t* seqid,
+                     const int32_t* pos, void* keys, void* twkeys, float* sparse, float* token_weights, int32_t T,
+                     int32_t nseq, int32_t V, int32_t H, hipStream_t stream);
+int snx_f32_tail_bwd(const float* g_sparse, const float* g_token_weights, const void* keys, const void* twkeys,
+                     const float* Hd, const float* E, const int32_t* cu_seqlens, float* dHd, float* gradE, float* gradb,
+                     int32_t T, int32_t nseq, int32_t V, int32_t H, hipStream_t stream);
 
 /* ---- dense teacher encoder (csrc/teacher.hip): the forward of an XLM-RoBERTa encoder with CLS pooling -- BGE-M3's dense
  * head, what ref:src/model/teachers/bge_m3.py:66-94 and ref:scripts/precompute_teacher_scores.py:89-159 run through

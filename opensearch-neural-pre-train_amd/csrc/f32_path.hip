@@ -1006,6 +1006,134 @@ extern "C" int snx_gemm_f32(const float* A, int64_t a_row, int64_t a_k, const fl
   return accumulate ? launch_gemm<1>(g, TailArgs{}, st) : launch_gemm<0>(g, TailArgs{}, st);
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// The steps of the model, one host function each (include/snx.h, fp32 section).  snx_model_forward_f32 and
+// snx_model_backward_f32_tw below are sequences of exactly these calls: what a test runs alone is what the model runs.
+// ------------------------------------------------------------------------------------------------------------
+static bool f32_heads_ok(int32_t heads, int32_t hd) { return heads > 0 && hd >= 2 && hd <= 64 && (hd % 2) == 0; }
+
+extern "C" int snx_f32_seq_ids(const int32_t* cu_seqlens, int32_t* seqid, int32_t T, int32_t nseq, hipStream_t st) {
+  if (!cu_seqlens || !seqid) return SNX_E_ARG;
+  if (T <= 0 || nseq <= 0) return SNX_E_SHAPE;
+  LAUNCH1D(seqid_kernel, T, cu_seqlens, seqid, T, nseq);
+  return SNX_OK;
+}
+
+extern "C" int snx_f32_ln_fwd(const float* in, const int64_t* ids, const float* w, float* out, int32_t T, int32_t H, float eps,
+                              int32_t src, hipStream_t st) {
+  if (!in || !w || !out || (src == 1 && !ids) || src < 0 || src > 2) return SNX_E_ARG;
+  if (T <= 0 || H <= 0) return SNX_E_SHAPE;
+  if (src == 0) LAUNCH_ROWS(ln_f32_kernel<0>, T, in, nullptr, w, out, T, H, eps);
+  else if (src == 1) LAUNCH_ROWS(ln_f32_kernel<1>, T, in, ids, w, out, T, H, eps);
+  else LAUNCH_ROWS(ln_f32_kernel<2>, T, in, nullptr, w, out, T, H, eps);
+  return SNX_OK;
+}
+
+extern "C" int snx_f32_ln_bwd(const float* dy, const float* in, const int64_t* ids, const float* w, float* dst, float* dw,
+                              int32_t T, int32_t H, float eps, int32_t src, int32_t accumulate, int32_t pad_id,
+                              hipStream_t st) {
+  if (!dy || !in || !w || !dst || !dw || (src == 1 && !ids) || src < 0 || src > 2) return SNX_E_ARG;
+  if (accumulate && src != 0) return SNX_E_ARG;                      // src 1 always adds (a scatter), src 2 always writes
+  if (T <= 0 || H <= 0) return SNX_E_SHAPE;
+  if (src == 0 && accumulate) LAUNCH_ROWS((ln_f32_bwd_kernel<0, true>), T, dy, in, nullptr, w, dst, dw, T, H, eps, -1);
+  else if (src == 0) LAUNCH_ROWS((ln_f32_bwd_kernel<0, false>), T, dy, in, nullptr, w, dst, dw, T, H, eps, -1);
+  else if (src == 1) LAUNCH_ROWS((ln_f32_bwd_kernel<1, false>), T, dy, in, ids, w, dst, dw, T, H, eps, pad_id);
+  else LAUNCH_ROWS((ln_f32_bwd_kernel<2, false>), T, dy, in, nullptr, w, dst, dw, T, H, eps, -1);
+  return SNX_OK;
+}
+
+extern "C" int snx_f32_rope(float* qkv, const float* table, const int32_t* pos, int32_t T, int32_t heads, int32_t head_dim,
+                            int32_t inverse, hipStream_t st) {
+  if (!qkv || !table || !pos) return SNX_E_ARG;
+  if (T <= 0 || !f32_heads_ok(heads, head_dim)) return SNX_E_SHAPE;
+  const long nrope = (long)T * 2 * heads * (head_dim / 2);
+  LAUNCH1D(rope_f32_kernel, nrope, qkv, (const f32x2*)table, pos, nrope, heads, head_dim, inverse ? 1 : 0);
+  return SNX_OK;
+}
+
+extern "C" int snx_f32_geglu_fwd(const float* u, float* y, int32_t T, int32_t I, hipStream_t st) {
+  if (!u || !y) return SNX_E_ARG;
+  if (T <= 0 || I <= 0) return SNX_E_SHAPE;
+  LAUNCH1D(geglu_f32_kernel, (long)T * I, u, y, (long)T * I, I);
+  return SNX_OK;
+}
+
+extern "C" int snx_f32_geglu_bwd(const float* u, const float* dy, float* du, int32_t T, int32_t I, hipStream_t st) {
+  if (!u || !dy || !du) return SNX_E_ARG;
+  if (T <= 0 || I <= 0) return SNX_E_SHAPE;
+  LAUNCH1D(geglu_f32_bwd_kernel, (long)T * I, u, dy, du, (long)T * I, I);
+  return SNX_OK;
+}
+
+// tiled when head_dim % 8 == 0 (mask and lse may be NULL there), one wave per (token, head) otherwise and under
+// "f32_attn_rows" (that form needs seqid, mask and lse); scale = 1 / sqrt(head_dim)
+extern "C" int snx_f32_attn_fwd(const float* qkv, const int32_t* cu_seqlens, const int32_t* seqid, const int64_t* mask,
+                                float* out, float* lse, int32_t T, int32_t nseq, int32_t heads, int32_t head_dim,
+                                int32_t window, hipStream_t st) {
+  if (!qkv || !cu_seqlens || !out) return SNX_E_ARG;
+  if (T <= 0 || nseq <= 0 || !f32_heads_ok(heads, head_dim)) return SNX_E_SHAPE;
+  const float scale = 1.0f / sqrtf((float)head_dim);
+  if (head_dim % 8 == 0 && !g_snx_cfg.f32_attn_rows)
+    return snx_attn_f32_fwd_tiled_x(qkv, cu_seqlens, mask, out, lse, T, nseq, heads, head_dim, window, scale, st);
+  if (!seqid || !mask || !lse) return SNX_E_ARG;
+  hipLaunchKernelGGL(attn_f32_fwd_kernel, dim3(cdiv((long)T * heads, 4)), dim3(256), 0, st, qkv, cu_seqlens, seqid, mask, out, lse,
+                     T, heads, head_dim, window, scale);
+  SNX_CHECK_LAUNCH();
+  return SNX_OK;
+}
+
+// dqkv [T, 3, heads, head_dim] is zeroed here, then written (dq) and accumulated into with float atomics (dk, dv)
+extern "C" int snx_f32_attn_bwd(const float* qkv, const float* out, const float* dout, const float* lse,
+                                const int32_t* cu_seqlens, const int32_t* seqid, const int64_t* mask, float* dqkv, int32_t T,
+                                int32_t nseq, int32_t heads, int32_t head_dim, int32_t window, hipStream_t st) {
+  if (!qkv || !out || !dout || !lse || !cu_seqlens || !seqid || !mask || !dqkv) return SNX_E_ARG;
+  if (T <= 0 || nseq <= 0 || !f32_heads_ok(heads, head_dim)) return SNX_E_SHAPE;
+  const float scale = 1.0f / sqrtf((float)head_dim);
+  if (hipMemsetAsync(dqkv, 0, (size_t)T * 3 * heads * head_dim * 4, st) != hipSuccess) return SNX_E_ARG;
+  hipLaunchKernelGGL(attn_f32_bwd_kernel, dim3(cdiv((long)T * heads, 4)), dim3(256), 0, st, qkv, out, dout, lse, cu_seqlens, seqid,
+                     mask, dqkv, T, heads, head_dim, window, scale);
+  SNX_CHECK_LAUNCH();
+  return SNX_OK;
+}
+
+// tied decoder + SPLADE tail: keys [nseq, V] and twkeys [T] (8 bytes each) are zeroed, filled by the EPI-2 GEMM
+// Hd [T, H] E [V, H]^T + bias and decoded into sparse [nseq, V] and token_weights [T]
+extern "C" int snx_f32_tail_fwd(const float* Hd, const float* E, const float* bias, const int64_t* mask, const int32_t* seqid,
+                                const int32_t* pos, void* keys, void* twkeys, float* sparse, float* token_weights, int32_t T,
+                                int32_t nseq, int32_t V, int32_t H, hipStream_t st) {
+  if (!Hd || !E || !bias || !mask || !seqid || !pos || !keys || !twkeys || !sparse || !token_weights) return SNX_E_ARG;
+  if (T <= 0 || nseq <= 0 || V <= 0 || H <= 0) return SNX_E_SHAPE;
+  if (hipMemsetAsync(keys, 0, (size_t)nseq * V * 8, st) != hipSuccess) return SNX_E_ARG;
+  if (hipMemsetAsync(twkeys, 0, (size_t)T * 8, st) != hipSuccess) return SNX_E_ARG;
+  GemmArgs g{Hd, H, 1, E, H, 1, nullptr, 0, nullptr, 0, T, V, H, 0, 0};
+  TailArgs ta{bias, mask, seqid, pos, (unsigned long long*)keys, (unsigned long long*)twkeys, V};
+  RC(launch_gemm<2>(g, ta, st));
+  const long nv = (long)nseq * V;
+  LAUNCH1D(tail_finalize_kernel, nv > T ? nv : T, (const unsigned long long*)keys, (const unsigned long long*)twkeys, sparse,
+           token_weights, nv, T);
+  return SNX_OK;
+}
+
+// routed backward of the above: dHd [T, H] is zeroed and written; gradE [V, H] and gradb [V] are accumulated into.
+// g_token_weights [T] or NULL.
+extern "C" int snx_f32_tail_bwd(const float* g_sparse, const float* g_token_weights, const void* keys, const void* twkeys,
+                                const float* Hd, const float* E, const int32_t* cu_seqlens, float* dHd, float* gradE,
+                                float* gradb, int32_t T, int32_t nseq, int32_t V, int32_t H, hipStream_t st) {
+  if (!g_sparse || !keys || (g_token_weights && !twkeys) || !Hd || !E || !cu_seqlens || !dHd || !gradE || !gradb) return SNX_E_ARG;
+  if (T <= 0 || nseq <= 0 || V <= 0 || H <= 0) return SNX_E_SHAPE;
+  if (hipMemsetAsync(dHd, 0, (size_t)T * H * 4, st) != hipSuccess) return SNX_E_ARG;
+  const long nv = (long)nseq * V;
+  hipLaunchKernelGGL(tail_f32_bwd_kernel, dim3(cdiv(nv, 4)), dim3(256), 0, st, g_sparse, (const unsigned long long*)keys, Hd, E,
+                     cu_seqlens, dHd, gradE, gradb, nv, V, H);
+  SNX_CHECK_LAUNCH();
+  if (g_token_weights) {
+    hipLaunchKernelGGL(tail_f32_tw_bwd_kernel, dim3(cdiv(T, 4)), dim3(256), 0, st, g_token_weights,
+                       (const unsigned long long*)twkeys, Hd, E, dHd, gradE, gradb, T, H);
+    SNX_CHECK_LAUNCH();
+  }
+  return SNX_OK;
+}
+
 extern "C" int snx_model_forward_f32(const snx_model_desc* d, const void* const* params, const int64_t* ids,
                                      const int64_t* mask, const int32_t* cu_seqlens, const int32_t* pos,
                                      const float* rope_global, const float* rope_local, void* saved, float* sparse,
@@ -1023,44 +1151,27 @@ extern "C" int snx_model_forward_f32(const snx_model_desc* d, const void* const*
   auto hbuf = [&](int i) { return (float*)(sv + s.h[i]); };
   auto B = [&](size_t off) { return (float*)(sv + off); };
   int32_t* seqid = (int32_t*)(sv + s.seqid);
-  LAUNCH1D(seqid_kernel, T, cu_seqlens, seqid, T, nseq);
-  LAUNCH_ROWS(ln_f32_kernel<1>, T, F(p.tok_emb()), ids, F(p.emb_norm()), hbuf(0), T, H, d->ln_eps);
-  const float scale = 1.0f / sqrtf((float)hd);
+  RC(snx_f32_seq_ids(cu_seqlens, seqid, T, nseq, st));
+  RC(snx_f32_ln_fwd(F(p.tok_emb()), ids, F(p.emb_norm()), hbuf(0), T, H, d->ln_eps, 1, st));
   for (int l = 0; l < L; ++l) {
     const bool global = (l % d->global_every) == 0;
-    if (l > 0) LAUNCH_ROWS(ln_f32_kernel<0>, T, hbuf(2 * l), nullptr, F(p.attn_norm(l)), B(s.x_attn[l]), T, H, d->ln_eps);
+    if (l > 0) RC(snx_f32_ln_fwd(hbuf(2 * l), nullptr, F(p.attn_norm(l)), B(s.x_attn[l]), T, H, d->ln_eps, 0, st));
     RC(linear_fwd(B(s.x_attn[l]), F(p.wqkv(l)), nullptr, B(s.qkv[l]), T, 3 * H, H, st));
-    const long nrope = (long)T * 2 * d->heads * (hd / 2);
-    LAUNCH1D(rope_f32_kernel, nrope, B(s.qkv[l]), (const f32x2*)(global ? rope_global : rope_local), pos, nrope, d->heads, hd, 0);
-    if (hd % 8 == 0 && !g_snx_cfg.f32_attn_rows) {
-      RC(snx_attn_f32_fwd_tiled_x(B(s.qkv[l]), cu_seqlens, mask, B(s.attn[l]), B(s.lse[l]), T, nseq, d->heads, hd,
-                                  global ? -1 : d->window, scale, st));
-    } else {
-      hipLaunchKernelGGL(attn_f32_fwd_kernel, dim3(cdiv((long)T * d->heads, 4)), dim3(256), 0, st, B(s.qkv[l]), cu_seqlens,
-                         seqid, mask, B(s.attn[l]), B(s.lse[l]), T, d->heads, hd, global ? -1 : d->window, scale);
-      SNX_CHECK_LAUNCH();
-    }
+    RC(snx_f32_rope(B(s.qkv[l]), global ? rope_global : rope_local, pos, T, d->heads, hd, 0, st));
+    RC(snx_f32_attn_fwd(B(s.qkv[l]), cu_seqlens, seqid, mask, B(s.attn[l]), B(s.lse[l]), T, nseq, d->heads, hd,
+                        global ? -1 : d->window, st));
     RC(linear_fwd(B(s.attn[l]), F(p.wo(l)), hbuf(2 * l), hbuf(2 * l + 1), T, H, H, st));
-    LAUNCH_ROWS(ln_f32_kernel<0>, T, hbuf(2 * l + 1), nullptr, F(p.mlp_norm(l)), B(s.x_mlp[l]), T, H, d->ln_eps);
+    RC(snx_f32_ln_fwd(hbuf(2 * l + 1), nullptr, F(p.mlp_norm(l)), B(s.x_mlp[l]), T, H, d->ln_eps, 0, st));
     RC(linear_fwd(B(s.x_mlp[l]), F(p.wi(l)), nullptr, B(s.u[l]), T, 2 * I, H, st));
-    LAUNCH1D(geglu_f32_kernel, (long)T * I, B(s.u[l]), B(s.y[l]), (long)T * I, I);
+    RC(snx_f32_geglu_fwd(B(s.u[l]), B(s.y[l]), T, I, st));
     RC(linear_fwd(B(s.y[l]), F(p.wo_mlp(l)), hbuf(2 * l + 1), hbuf(2 * l + 2), T, H, I, st));
   }
-  LAUNCH_ROWS(ln_f32_kernel<0>, T, hbuf(2 * L), nullptr, F(p.final_norm()), B(s.xf), T, H, d->ln_eps);
+  RC(snx_f32_ln_fwd(hbuf(2 * L), nullptr, F(p.final_norm()), B(s.xf), T, H, d->ln_eps, 0, st));
   RC(linear_fwd(B(s.xf), F(p.head_dense()), nullptr, B(s.dd), T, H, H, st));
-  LAUNCH_ROWS(ln_f32_kernel<2>, T, B(s.dd), nullptr, F(p.head_norm()), B(s.hd), T, H, d->ln_eps);
+  RC(snx_f32_ln_fwd(B(s.dd), nullptr, F(p.head_norm()), B(s.hd), T, H, d->ln_eps, 2, st));
   // tied decoder + SPLADE tail
-  if (hipMemsetAsync(sv + s.keys, 0, (size_t)nseq * V * 8, st) != hipSuccess) return SNX_E_ARG;
-  if (hipMemsetAsync(sv + s.twkeys, 0, (size_t)T * 8, st) != hipSuccess) return SNX_E_ARG;
-  {
-    GemmArgs g{B(s.hd), H, 1, F(p.tok_emb()), H, 1, nullptr, 0, nullptr, 0, T, V, H, 0, 0};
-    TailArgs ta{F(p.dec_bias()), mask, seqid, pos, (unsigned long long*)(sv + s.keys), (unsigned long long*)(sv + s.twkeys), V};
-    RC(launch_gemm<2>(g, ta, st));
-  }
-  const long nv = (long)nseq * V;
-  LAUNCH1D(tail_finalize_kernel, nv > T ? nv : T, (const unsigned long long*)(sv + s.keys), (const unsigned long long*)(sv + s.twkeys), sparse,
-           token_weights, nv, T);
-  return SNX_OK;
+  return snx_f32_tail_fwd(B(s.hd), F(p.tok_emb()), F(p.dec_bias()), mask, seqid, pos, sv + s.keys, sv + s.twkeys, sparse,
+                          token_weights, T, nseq, V, H, st);
 }
 
 extern "C" int snx_model_backward_f32(const snx_model_desc* d, const void* const* params, void* const* grads,
@@ -1097,54 +1208,38 @@ extern "C" int snx_model_backward_f32_tw(const snx_model_desc* d, const void* co
   float* Bb = (float*)(sc + bp.b);
   float* Cc = (float*)(sc + bp.c);
   const int32_t* seqid = (const int32_t*)(sv + s.seqid);
-  const float scale = 1.0f / sqrtf((float)hd);
   const long TH = (long)T * H;
-  // ---- SPLADE tail + tied decoder (routed), head
-  if (hipMemsetAsync(Cc, 0, TH * 4, st) != hipSuccess) return SNX_E_ARG;                  // dHd
-  {
-    const long nv = (long)nseq * V;
-    hipLaunchKernelGGL(tail_f32_bwd_kernel, dim3(cdiv(nv, 4)), dim3(256), 0, st, g_sparse, (const unsigned long long*)(sv + s.keys),
-                       S(s.hd), F(p.tok_emb()), cu_seqlens, Cc, G(p.tok_emb()), G(p.dec_bias()), nv, V, H);
-    SNX_CHECK_LAUNCH();
-  }
-  if (g_token_weights) {
-    hipLaunchKernelGGL(tail_f32_tw_bwd_kernel, dim3(cdiv(T, 4)), dim3(256), 0, st, g_token_weights,
-                       (const unsigned long long*)(sv + s.twkeys), S(s.hd), F(p.tok_emb()), Cc, G(p.tok_emb()),
-                       G(p.dec_bias()), T, H);
-    SNX_CHECK_LAUNCH();
-  }
+  // ---- SPLADE tail + tied decoder (routed), head: Cc = dHd
+  RC(snx_f32_tail_bwd(g_sparse, g_token_weights, sv + s.keys, sv + s.twkeys, S(s.hd), F(p.tok_emb()), cu_seqlens, Cc,
+                      G(p.tok_emb()), G(p.dec_bias()), T, nseq, V, H, st));
   // hd = LN(gelu(dd)) w: A = d(dd)
-  LAUNCH_ROWS((ln_f32_bwd_kernel<2, false>), T, Cc, S(s.dd), nullptr, F(p.head_norm()), A, G(p.head_norm()), T, H, d->ln_eps, -1);
+  RC(snx_f32_ln_bwd(Cc, S(s.dd), nullptr, F(p.head_norm()), A, G(p.head_norm()), T, H, d->ln_eps, 2, 0, -1, st));
   RC(linear_dw(A, S(s.xf), G(p.head_dense()), T, H, H, st));
   RC(linear_dx(A, F(p.head_dense()), Bb, T, H, H, st));                                    // d(xf)
-  LAUNCH_ROWS((ln_f32_bwd_kernel<0, false>), T, Bb, hbuf(2 * L), nullptr, F(p.final_norm()), dh, G(p.final_norm()), T, H, d->ln_eps, -1);
+  RC(snx_f32_ln_bwd(Bb, hbuf(2 * L), nullptr, F(p.final_norm()), dh, G(p.final_norm()), T, H, d->ln_eps, 0, 0, -1, st));
   for (int l = L - 1; l >= 0; --l) {
     const bool global = (l % d->global_every) == 0;
     // ---- MLP: h[2l+2] = h[2l+1] + Wo(gelu(a) g), [a | g] = Wi(LN(h[2l+1]))
     RC(linear_dw(dh, S(s.y[l]), G(p.wo_mlp(l)), T, H, I, st));
     RC(linear_dx(dh, F(p.wo_mlp(l)), A, T, H, I, st));                                     // dy [T, I]
-    LAUNCH1D(geglu_f32_bwd_kernel, (long)T * I, S(s.u[l]), A, Bb, (long)T * I, I);          // du [T, 2I]
+    RC(snx_f32_geglu_bwd(S(s.u[l]), A, Bb, T, I, st));                                     // du [T, 2I]
     RC(linear_dw(Bb, S(s.x_mlp[l]), G(p.wi(l)), T, 2 * I, H, st));
     RC(linear_dx(Bb, F(p.wi(l)), Cc, T, 2 * I, H, st));                                    // d(x_mlp)
-    LAUNCH_ROWS((ln_f32_bwd_kernel<0, true>), T, Cc, hbuf(2 * l + 1), nullptr, F(p.mlp_norm(l)), dh, G(p.mlp_norm(l)), T, H, d->ln_eps, -1);
+    RC(snx_f32_ln_bwd(Cc, hbuf(2 * l + 1), nullptr, F(p.mlp_norm(l)), dh, G(p.mlp_norm(l)), T, H, d->ln_eps, 0, 1, -1, st));
     // ---- attention: h[2l+1] = h[2l] + Wo(attn(rope(Wqkv(LN(h[2l])))))
     RC(linear_dw(dh, S(s.attn[l]), G(p.wo(l)), T, H, H, st));
     RC(linear_dx(dh, F(p.wo(l)), Cc, T, H, H, st));                                        // d(attn out)
-    if (hipMemsetAsync(A, 0, (size_t)T * 3 * H * 4, st) != hipSuccess) return SNX_E_ARG;   // dqkv
-    hipLaunchKernelGGL(attn_f32_bwd_kernel, dim3(cdiv((long)T * d->heads, 4)), dim3(256), 0, st, S(s.qkv[l]), S(s.attn[l]), Cc,
-                       S(s.lse[l]), cu_seqlens, seqid, mask, A, T, d->heads, hd, global ? -1 : d->window, scale);
-    SNX_CHECK_LAUNCH();
-    const long nrope = (long)T * 2 * d->heads * (hd / 2);
-    LAUNCH1D(rope_f32_kernel, nrope, A, (const f32x2*)(global ? rope_global : rope_local), pos, nrope, d->heads, hd, 1);
+    RC(snx_f32_attn_bwd(S(s.qkv[l]), S(s.attn[l]), Cc, S(s.lse[l]), cu_seqlens, seqid, mask, A, T, nseq, d->heads, hd,
+                        global ? -1 : d->window, st));                                     // dqkv
+    RC(snx_f32_rope(A, global ? rope_global : rope_local, pos, T, d->heads, hd, 1, st));
     RC(linear_dw(A, S(s.x_attn[l]), G(p.wqkv(l)), T, 3 * H, H, st));
     RC(linear_dx(A, F(p.wqkv(l)), Cc, T, 3 * H, H, st));                                   // d(x_attn)
     if (l > 0) {
-      LAUNCH_ROWS((ln_f32_bwd_kernel<0, true>), T, Cc, hbuf(2 * l), nullptr, F(p.attn_norm(l)), dh, G(p.attn_norm(l)), T, H, d->ln_eps, -1);
+      RC(snx_f32_ln_bwd(Cc, hbuf(2 * l), nullptr, F(p.attn_norm(l)), dh, G(p.attn_norm(l)), T, H, d->ln_eps, 0, 1, -1, st));
     } else {
       LAUNCH1D(add_f32_kernel, TH, dh, Cc, TH);
     }
   }
-  LAUNCH_ROWS((ln_f32_bwd_kernel<1, false>), T, dh, F(p.tok_emb()), ids, F(p.emb_norm()), G(p.tok_emb()), G(p.emb_norm()), T, H, d->ln_eps,
-              d->pad_id);
-  return SNX_OK;
+  return snx_f32_ln_bwd(dh, F(p.tok_emb()), ids, F(p.emb_norm()), G(p.tok_emb()), G(p.emb_norm()), T, H, d->ln_eps, 1, 0,
+                        d->pad_id, st);
 }

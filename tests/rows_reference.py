@@ -180,14 +180,15 @@ def exact_sum_rows(x):
     return (gexp == 10 ** 6) | (tot <= np.ldexp(1.0, np.where(gexp == 10 ** 6, 0, gexp) + 24))
 
 
-def ln_stats(x, eps, rsq=ULP_RSQ):
-    """x [T, H] float64 holding fp32 values -> xhat, rstd and their bounds (the module docstring, line by line)"""
+def ln_stats(x, eps, rsq=ULP_RSQ, exact=True):
+    """x [T, H] float64 holding fp32 values -> xhat, rstd and their bounds (the module docstring, line by line).
+    exact=False: without the exact-sum shortcut of the mean (rows that are not known to the bit: tests/f32_reference.py)"""
     u = U32
     H = x.shape[-1]
     eps = float(np.float32(eps))
     ax = np.abs(x).sum(-1)
     mean = x.sum(-1) / H
-    exact = exact_sum_rows(x)
+    exact = exact_sum_rows(x) if exact else np.zeros(x.shape[0], dtype=bool)
     Em = np.where(exact, np.where(mean.astype(np.float32).astype(np.float64) == mean, 0.0, u * np.abs(mean)), gamma(H + 1) * ax / H)
     c = x - mean[:, None]
     Em_ = Em[:, None]
@@ -207,18 +208,18 @@ def ln_stats(x, eps, rsq=ULP_RSQ):
     return SimpleNamespace(xh=xh, Exh=Exh, r=r, Er=Er, mean=mean, var=var, Em=Em, c=c)
 
 
-def ln_forward(x, w, eps, rsq=ULP_RSQ):
+def ln_forward(x, w, eps, rsq=ULP_RSQ, exact=True):
     """-> (v, B) of LN(x) before the output cast, and the statistics"""
-    st = ln_stats(x, eps, rsq)
+    st = ln_stats(x, eps, rsq, exact)
     aw = np.abs(w)[None, :]
     return st.xh * w[None, :], F64 * aw * (st.Exh + U32 * (np.abs(st.xh) + st.Exh)), st
 
 
-def ln_backward(x, w, eps, dy, rsq=ULP_RSQ):
+def ln_backward(x, w, eps, dy, rsq=ULP_RSQ, exact=True):
     """-> dx, Edx [T, H] and the per-row terms of dw: p = dy xhat, Ep = |dy| Exh, Ap = |dy| (|xhat| + Exh)"""
     u = U32
     H = x.shape[-1]
-    st = ln_stats(x, eps, rsq)
+    st = ln_stats(x, eps, rsq, exact)
     xh, Exh, axh = st.xh, st.Exh, np.abs(st.xh)
     g = dy * w[None, :]
     ag = np.abs(g)
