@@ -318,6 +318,48 @@ int snx_teacher_cls_normalize(const float* h, const int32_t* cu_seqlens, float* 
 int snx_teacher_attn_f32(const float* qkv, const int32_t* cu_seqlens, float* out, int32_t T, int32_t nseq, int32_t heads,
                          hipStream_t stream);
 
+/* ---- multi-vector teacher scores (csrc/teacher.hip, teacher_mv.hip: the head; csrc/maxsim.hip: the scorer) -- BGE-M3's late-interaction
+ * output on top of the forward above.  For a sequence s of n_s tokens the multi-vector rows are the n_s - 1 rows behind CLS
+ * (the final </s> row is kept):
+ *     mv[s][i] = normalize(W_c h[cu_seqlens[s] + 1 + i] + b_c),   normalize(x) = x / max(||x||_2, 1e-12),
+ * h the last hidden state, W_c [hidden, hidden] and b_c [hidden] the `colbert_linear` of the model directory.  The rows of
+ * all sequences lie end to end in one store without padding: sequence s owns rows mv_ptr[s] .. mv_ptr[s + 1] - 1,
+ * mv_ptr[s] = cu_seqlens[s] - s.  For a pair (a, b) of sequences with Lq and Ld rows
+ *     maxsim(a, b) = (1 / Lq) sum_i max_j <mv[a][i], mv[b][j]>:
+ * dot products accumulated in fp32, the sum over i in ascending i in fp32 (per block of 64 rows, then the blocks in
+ * ascending order), one fp32 division.  A pair with Lq == 0 or Ld == 0 scores 0.0f.  Only a sequence's own rows take part in
+ * its max.  A score is a pure function of the rows of its two sequences: the same bits in every call and every pair list.
+ *
+ * snx_teacher_head_cache_*: the bf16 copy of W_c that the bf16 path's GEMM reads.
+ * snx_teacher_mv_rows: y [T, H] (the head GEMM's output; fp32 when y_f32 != 0, else bf16) -> the store, in y's type: row t
+ * of sequence s lands at row t - s - 1, a sequence's first row is skipped; bias add and normalisation in fp32, one rounding.
+ * snx_teacher_forward_mv: snx_teacher_forward (same cls_out / emb_out, bit for bit), then the head GEMM over the last hidden
+ * state (snx_gemm_nt_bf16: bf16 output; snx_gemm_f32) and snx_teacher_mv_rows into mv_out [T - nseq, hidden], bf16 for
+ * SNX_TEACHER_BF16 and fp32 for SNX_TEACHER_F32.  Its arena is the forward's. */
+size_t snx_teacher_head_cache_bytes(const snx_teacher_desc* d);
+int snx_teacher_head_cache_refresh(const snx_teacher_desc* d, const float* head_w, void* head_cache, hipStream_t stream);
+int snx_teacher_mv_rows(const void* y, int32_t y_f32, const float* bias, const int32_t* cu_seqlens, void* mv, int32_t T,
+                        int32_t nseq, int32_t H, hipStream_t stream);
+size_t snx_teacher_forward_mv_workspace_bytes(const snx_teacher_desc* d, int32_t T, int32_t nseq, int32_t precision);
+int snx_teacher_forward_mv(const snx_teacher_desc* d, const void* const* params /*[host]*/, const void* wcache,
+                           const float* head_w, const float* head_b, const void* head_cache, const int64_t* ids,
+                           const int32_t* pos_ids, const int32_t* cu_seqlens, void* workspace, float* cls_out,
+                           float* emb_out, void* mv_out, int32_t T, int32_t nseq, int32_t max_seqlen, int32_t precision,
+                           hipStream_t stream);
+/* score [npairs] fp32 (device) = maxsim(pair_q[p], pair_d[p]) over the store mv [nrows, D] (device; fp32 when mv_f32 != 0,
+ * else bf16; 16-byte aligned).  mv_ptr [nseq + 1], pair_q and pair_d [npairs] are HOST arrays: they are checked here, before
+ * any launch, and copied into the workspace on the stream.  D % 64 == 0 and D <= 1024, else SNX_E_SHAPE.  SNX_E_ARG: mv_ptr
+ * not ascending from 0 or past nrows, a sequence with more than max_rows rows, a pair index outside [0, nseq).  One launch
+ * when max_rows <= 64, two otherwise.  Nothing of size Lq x Ld is written to memory.
+ * Lifetime of the host arrays: they must be ordinary PAGEABLE memory, and may then be released as soon as the call returns --
+ * hipMemcpyAsync stages a pageable source before it returns (the snx.teacher binding passes ctypes arrays and frees them on
+ * return).  A pinned (hipHostMalloc / registered) array makes the copy truly asynchronous: it would have to stay valid and
+ * unchanged until the stream has passed this call, which nothing here enforces -- do not pass one. */
+size_t snx_maxsim_workspace_bytes(int32_t nseq, int64_t npairs, int32_t max_rows);
+int snx_maxsim_pairs(const void* mv, int32_t mv_f32, int64_t nrows, int32_t D, const int64_t* mv_ptr /*[host]*/, int32_t nseq,
+                     const int32_t* pair_q /*[host]*/, const int32_t* pair_d /*[host]*/, int64_t npairs, int32_t max_rows,
+                     float* score, void* workspace, size_t ws_bytes, hipStream_t stream);
+
 /* ---- inference post-processing (ref:benchmark/encoders.py:309-345 NeuralSparseEncoderV33._encode_batch) ---- */
 /* Per row of rep [B,V] fp32: entries with rep > 0 and allowed[v] != 0 survive.  k > 0 and more than k survivors:
  * the k largest, weight descending, ties lowest id first (out_sorted[b] = 1); otherwise all survivors in id

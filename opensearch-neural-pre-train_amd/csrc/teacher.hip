@@ -11,6 +11,11 @@
 // Cast points of the bf16 path: GEMM operands and GEMM outputs are bf16 (a bias added to a bf16 GEMM output that is a GEMM
 // or attention operand is rounded to bf16 again); the residual stream h is fp32, GELU and softmax arithmetic are fp32, a
 // row's LayerNorm is evaluated in fp64 and stored as fp32.  The fp32 path has no cast point.
+//
+// The multi-vector head (BGE-M3's colbert_linear; snx_teacher_forward_mv): one more GEMM over the last hidden state and the
+// row kernel of teacher_mv.hip, which adds the bias, L2-normalises in fp32 and packs every row but a sequence's first into
+// the store that maxsim.hip scores; the GEMM's output is bf16 on the bf16 path and the stored row is rounded to bf16 once.
+// No kernel of this file was added or changed for it: the device code here is what it was.
 #include "common.h"
 #include "rows.h"
 #include "runtime.h"
@@ -377,10 +382,13 @@ extern "C" size_t snx_teacher_workspace_bytes(const snx_teacher_desc* d, int32_t
   return Plan(d, T, precision == SNX_TEACHER_F32).total;
 }
 
-extern "C" int snx_teacher_forward(const snx_teacher_desc* d, const void* const* params, const void* wcache,
-                                   const int64_t* ids, const int32_t* pos_ids, const int32_t* cu_seqlens, void* workspace,
-                                   float* cls_out, float* emb_out, int32_t T, int32_t nseq, int32_t max_seqlen,
-                                   int32_t precision, hipStream_t st) {
+namespace {
+
+// embeddings and every layer: leaves the last hidden state in the workspace (h fp32, and x = bf16(h) on the bf16 path),
+// then pools: cls_out, emb_out
+int forward_layers(const snx_teacher_desc* d, const void* const* params, const void* wcache, const int64_t* ids,
+                   const int32_t* pos_ids, const int32_t* cu_seqlens, void* workspace, float* cls_out, float* emb_out,
+                   int32_t T, int32_t nseq, int32_t max_seqlen, int32_t precision, hipStream_t st) {
   if (!desc_ok(d)) return SNX_E_SHAPE;
   if (!params || !wcache || !ids || !pos_ids || !cu_seqlens || !workspace || !cls_out || !emb_out || T <= 0 || nseq <= 0 ||
       nseq > T || max_seqlen <= 0 || max_seqlen > T || misaligned(workspace) || misaligned(wcache))
@@ -432,4 +440,52 @@ extern "C" int snx_teacher_forward(const snx_teacher_desc* d, const void* const*
     RC(snx_teacher_bias_resid_ln(h, y, f32, F(PIdx::bo2(l)), F(PIdx::ln2_w(l)), F(PIdx::ln2_b(l)), h, x, T, H, d->ln_eps, st));
   }
   return snx_teacher_cls_normalize(h, cu_seqlens, cls_out, emb_out, T, nseq, H, st);
+}
+
+}  // namespace
+
+extern "C" int snx_teacher_forward(const snx_teacher_desc* d, const void* const* params, const void* wcache,
+                                   const int64_t* ids, const int32_t* pos_ids, const int32_t* cu_seqlens, void* workspace,
+                                   float* cls_out, float* emb_out, int32_t T, int32_t nseq, int32_t max_seqlen,
+                                   int32_t precision, hipStream_t st) {
+  return forward_layers(d, params, wcache, ids, pos_ids, cu_seqlens, workspace, cls_out, emb_out, T, nseq, max_seqlen,
+                        precision, st);
+}
+
+// ---- the multi-vector head (BGE-M3's colbert_linear) ----------------------------------------------------------------
+extern "C" size_t snx_teacher_head_cache_bytes(const snx_teacher_desc* d) {
+  return desc_ok(d) ? align256((size_t)d->hidden * d->hidden * 2) : 0;
+}
+
+extern "C" int snx_teacher_head_cache_refresh(const snx_teacher_desc* d, const float* head_w, void* head_cache,
+                                              hipStream_t st) {
+  if (!desc_ok(d)) return SNX_E_SHAPE;
+  if (!head_w || !head_cache || misaligned(head_w) || misaligned(head_cache)) return SNX_E_ARG;
+  return snx_cast_bf16(head_w, head_cache, (int64_t)d->hidden * d->hidden, st);
+}
+
+// the head's GEMM output lands in the forward's y block, which the layer loop has left free: the same arena
+extern "C" size_t snx_teacher_forward_mv_workspace_bytes(const snx_teacher_desc* d, int32_t T, int32_t nseq,
+                                                         int32_t precision) {
+  return snx_teacher_workspace_bytes(d, T, nseq, precision);
+}
+
+extern "C" int snx_teacher_forward_mv(const snx_teacher_desc* d, const void* const* params, const void* wcache,
+                                      const float* head_w, const float* head_b, const void* head_cache, const int64_t* ids,
+                                      const int32_t* pos_ids, const int32_t* cu_seqlens, void* workspace, float* cls_out,
+                                      float* emb_out, void* mv_out, int32_t T, int32_t nseq, int32_t max_seqlen,
+                                      int32_t precision, hipStream_t st) {
+  if (!head_w || !head_b || !head_cache || !mv_out || misaligned(head_w) || misaligned(head_cache) || misaligned(mv_out))
+    return SNX_E_ARG;
+  RC(forward_layers(d, params, wcache, ids, pos_ids, cu_seqlens, workspace, cls_out, emb_out, T, nseq, max_seqlen, precision,
+                    st));
+  if (T == nseq) return SNX_OK;                                  // every sequence is its CLS row alone: an empty store
+  const bool f32 = precision == SNX_TEACHER_F32;
+  const int H = d->hidden;
+  const Plan s(d, T, f32);
+  char* ws = (char*)workspace;
+  void* y = ws + s.y;
+  if (f32) RC(snx_gemm_f32((const float*)(ws + s.h), H, 1, head_w, H, 1, (float*)y, H, nullptr, 0, T, H, H, 0, st));
+  else RC(snx_gemm_nt_bf16(ws + s.x, head_cache, y, T, H, H, st));
+  return snx_teacher_mv_rows(y, f32, head_b, cu_seqlens, mv_out, T, nseq, H, st);
 }

@@ -4,6 +4,8 @@
     enc = TeacherEncoder.from_pretrained("/models/bge-m3", device="cuda:0", precision="bf16")
     emb = enc.encode(texts, tokenizer, max_length=256)                 # fp32 [n, hidden], unit rows, input order
     emb = enc.encode_tokens(input_ids, attention_mask)                 # the same from a padded batch
+    emb, mv_ptr, mv = enc.encode_multivector(texts, tokenizer)         # + the multi-vector rows (needs colbert_linear.pt)
+    scores = maxsim_pairs(mv, mv_ptr, pair_q, pair_d)                  # late-interaction scores (csrc/maxsim.hip)
 
 ``forward_torch`` restates the same forward in plain torch (fp32, no transformers import): it is what a ``TeacherEncoder``
 on a ``cpu`` device runs, and the comparator of the GPU tests.  Its ``emulate_bf16`` mode rounds at exactly the cast points
@@ -142,6 +144,16 @@ def random_state_dict(config: TeacherConfig, seed: int) -> Dict[str, torch.Tenso
     return out
 
 
+def random_colbert_head(config: TeacherConfig, seed: int) -> Dict[str, torch.Tensor]:
+    """A multi-vector head from a recipe (tests): ``weight`` [H, H] N(0, 0.1) and ``bias`` [H] 0.1 N(0, 1) from a
+    numpy.random.RandomState(seed) of its own, so that ``random_state_dict`` keeps drawing what it always drew."""
+    import numpy as np
+    rs = np.random.RandomState(int(seed))
+    H = config.hidden_size
+    return {"weight": torch.from_numpy((0.1 * rs.standard_normal((H, H))).astype(np.float32)),
+            "bias": torch.from_numpy((0.1 * rs.standard_normal((H,))).astype(np.float32))}
+
+
 def normalize_state_dict(config: TeacherConfig, state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """The encoder's tensors as fp32, keyed without the ``roberta.`` prefix; pooler, LM-head and buffer keys are dropped.
     A missing tensor or a wrong shape raises."""
@@ -182,10 +194,12 @@ def _check_batch(config: TeacherConfig, input_ids, attention_mask) -> Tuple[torc
 
 
 def forward_torch(config: TeacherConfig, params: Dict[str, torch.Tensor], input_ids: torch.Tensor,
-                  attention_mask: torch.Tensor, emulate_bf16: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+                  attention_mask: torch.Tensor, emulate_bf16: bool = False, return_hidden: bool = False):
     """XLMRobertaModel(add_pooling_layer=False) in eval mode on a padded batch, in plain fp32 torch -> (cls fp32 [n, H] =
     the row of every sequence's first token, emb = F.normalize(cls)).  ``params``: ``normalize_state_dict``'s tensors.
-    ``emulate_bf16``: round at the cast points of the GPU's bf16 path (module docstring)."""
+    ``emulate_bf16``: round at the cast points of the GPU's bf16 path (module docstring).  ``return_hidden``: also the
+    last hidden state [n, S, H] as a third value.  The arithmetic runs in the dtype of ``params`` (float64 tensors give
+    a float64 forward)."""
     ids, mask, pos = _check_batch(config, input_ids, attention_mask)
     n, S = ids.shape
     H, heads, eps = config.hidden_size, config.num_attention_heads, config.layer_norm_eps
@@ -224,7 +238,85 @@ def forward_torch(config: TeacherConfig, params: Dict[str, torch.Tensor], input_
         h = ln((y + params[p + "output.dense.bias"]) + h, p + "output.LayerNorm")
     first = mask.argmax(dim=1)
     cls = h[torch.arange(n, device=dev), first]
+    if return_hidden:
+        return cls, F.normalize(cls, p=2, dim=-1), h
     return cls, F.normalize(cls, p=2, dim=-1)
+
+
+def multivector_torch(head: Dict[str, torch.Tensor], hidden: torch.Tensor, attention_mask: torch.Tensor,
+                      emulate_bf16: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The multi-vector head in plain torch on ``forward_torch``'s last hidden state [n, S, H] -> (mv_ptr int64 [n + 1],
+    mv [rows, H]): per sequence the rows behind its first token, normalize(W_c h + b_c), end to end.  ``emulate_bf16``
+    rounds at the cast points of the GPU's bf16 path: the GEMM's operands and output, and the stored row."""
+    def r(t):
+        return t.to(torch.bfloat16).to(t.dtype) if emulate_bf16 else t
+
+    mask = (attention_mask != 0).to(hidden.device)
+    body = mask & (torch.cumsum(mask.to(torch.long), dim=1) > 1)          # every token of a row but its first
+    w, b = head["weight"].to(hidden), head["bias"].to(hidden)
+    y = r(r(hidden[body]) @ r(w).t())
+    mv_ptr = torch.zeros(mask.shape[0] + 1, dtype=torch.long, device=hidden.device)
+    mv_ptr[1:] = torch.cumsum(body.sum(dim=1), 0)
+    return mv_ptr, r(F.normalize(y + b, p=2, dim=-1))
+
+
+def _check_pairs(mv: torch.Tensor, mv_ptr, pair_q, pair_d) -> Tuple[List[int], List[int], List[int]]:
+    """The argument rules of ``maxsim_pairs`` / ``maxsim_pairs_torch`` -> host lists (mv_ptr, pair_q, pair_d)."""
+    if not isinstance(mv, torch.Tensor) or mv.dim() != 2 or mv.dtype not in (torch.bfloat16, torch.float32, torch.float64):
+        raise ValueError("maxsim: mv must be a [rows, D] tensor of bf16 or fp32 rows")
+    D = int(mv.shape[1])
+    if D <= 0 or D % 64 or D > 1024:
+        raise ValueError("maxsim: D must be a multiple of 64, at most 1024")
+    ptr = [int(v) for v in torch.as_tensor(mv_ptr).tolist()]
+    pq, pd = ([int(v) for v in torch.as_tensor(p).reshape(-1).tolist()] for p in (pair_q, pair_d))
+    if len(ptr) < 2 or ptr[0] != 0 or any(b < a for a, b in zip(ptr, ptr[1:])) or ptr[-1] > int(mv.shape[0]):
+        raise ValueError("maxsim: mv_ptr must ascend from 0 and end within the rows of mv")
+    if len(pq) != len(pd):
+        raise ValueError("maxsim: pair_q and pair_d must have one length")
+    nseq = len(ptr) - 1
+    for s in pq + pd:
+        if not 0 <= s < nseq:
+            raise ValueError(f"maxsim: pair index {s} outside [0, {nseq})")
+        if ptr[s + 1] == ptr[s]:
+            raise ValueError(f"maxsim: sequence {s} has no multi-vector row (a text of one token)")
+    return ptr, pq, pd
+
+
+def maxsim_pairs_torch(mv: torch.Tensor, mv_ptr, pair_q, pair_d) -> torch.Tensor:
+    """The definition of ``maxsim_pairs`` restated in float64 torch -> float64 [npairs] on mv's device: per pair the mean
+    over the query's rows of the largest dot product with a row of the document."""
+    ptr, pq, pd = _check_pairs(mv, mv_ptr, pair_q, pair_d)
+    x = mv.to(torch.float64)
+    out = [(x[ptr[a]:ptr[a + 1]] @ x[ptr[b]:ptr[b + 1]].t()).amax(dim=1).sum() / (ptr[a + 1] - ptr[a])
+           for a, b in zip(pq, pd)]
+    return torch.stack(out) if out else torch.zeros(0, dtype=torch.float64, device=mv.device)
+
+
+@torch.no_grad()
+def maxsim_pairs(mv: torch.Tensor, mv_ptr, pair_q, pair_d) -> torch.Tensor:
+    """MaxSim of pairs of sequences of one multi-vector store on the GPU (csrc/maxsim.hip) -> fp32 [npairs] on mv's device.
+    ``mv`` [rows, D] bf16 or fp32 (``encode_multivector``'s store), ``mv_ptr`` [n + 1] the sequences' row ranges,
+    ``pair_q`` / ``pair_d`` sequence indices: score p = mean over the rows i of pair_q[p] of max_j <mv[q][i], mv[d][j]>.
+    A score depends on its two sequences alone: the same bits in any pair list.  ValueError: D not a multiple of 64 or
+    above 1024, an index outside the store, a sequence without rows."""
+    ptr, pq, pd = _check_pairs(mv, mv_ptr, pair_q, pair_d)
+    if mv.device.type != "cuda" or mv.dtype == torch.float64:
+        raise ValueError("maxsim: maxsim_pairs needs a bf16 or fp32 store on a GPU (maxsim_pairs_torch is the CPU form)")
+    from ._lib import call, fn
+    mv = mv.contiguous()
+    nseq, npairs = len(ptr) - 1, len(pq)
+    max_rows = max(b - a for a, b in zip(ptr, ptr[1:]))
+    with torch.cuda.device(mv.device):
+        score = torch.empty(npairs, dtype=torch.float32, device=mv.device)
+        if npairs == 0:
+            return score
+        need = int(fn("snx_maxsim_workspace_bytes")(nseq, npairs, max_rows))
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=mv.device)
+        hptr, hq, hd = (C.c_int64 * (nseq + 1))(*ptr), (C.c_int32 * npairs)(*pq), (C.c_int32 * npairs)(*pd)
+        call("snx_maxsim_pairs", C.c_void_p(mv.data_ptr()), int(mv.dtype == torch.float32), int(mv.shape[0]),
+             int(mv.shape[1]), hptr, nseq, hq, hd, npairs, max_rows, C.c_void_p(score.data_ptr()),
+             C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return score
 
 
 def _read_weights(model_dir: str) -> Dict[str, torch.Tensor]:
@@ -270,7 +362,10 @@ class TeacherEncoder:
     ``cpu``: ``forward_torch`` (with ``emulate_bf16`` for "bf16").  ``state_dict``: XLMRobertaModel's tensors, with or
     without the ``roberta.`` prefix."""
 
-    def __init__(self, config: TeacherConfig, state_dict: Dict[str, torch.Tensor], device="cuda", precision: str = "bf16"):
+    def __init__(self, config: TeacherConfig, state_dict: Dict[str, torch.Tensor], device="cuda", precision: str = "bf16",
+                 colbert_head: Optional[Dict[str, torch.Tensor]] = None):
+        """``colbert_head``: BGE-M3's multi-vector head, ``{"weight": [H, H], "bias": [H]}`` (``colbert_linear.pt``);
+        without it the encoder has the dense output only."""
         if precision not in PRECISIONS:
             raise ValueError(f"teacher: precision must be one of {sorted(PRECISIONS)}")
         config.validate()
@@ -280,6 +375,15 @@ class TeacherEncoder:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.params = {k: v.to(self.device).contiguous() for k, v in normalize_state_dict(config, state_dict).items()}
         self._ws: Optional[torch.Tensor] = None
+        self.head: Optional[Dict[str, torch.Tensor]] = None
+        if colbert_head is not None:
+            H = config.hidden_size
+            w, b = colbert_head.get("weight"), colbert_head.get("bias")
+            if w is None or b is None or tuple(w.shape) != (H, H) or tuple(b.shape) != (H,):
+                raise ValueError(f"teacher: the multi-vector head needs weight [{H}, {H}] and bias [{H}] (a colbert_dim other "
+                                 "than the hidden size is not supported)")
+            self.head = {"weight": w.detach().to(torch.float32).to(self.device).contiguous(),
+                         "bias": b.detach().to(torch.float32).to(self.device).contiguous()}
         if self.device.type == "cuda":
             from ._lib import call, fn
             self._desc = config.desc()
@@ -293,6 +397,16 @@ class TeacherEncoder:
                 self._wcache = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
                 call("snx_teacher_weight_cache_refresh", C.byref(self._desc), self._ptrs,
                      C.c_void_p(self._wcache.data_ptr()), self._stream())
+                if self.head is not None:
+                    nbytes = int(fn("snx_teacher_head_cache_bytes")(C.byref(self._desc)))
+                    self._hcache = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                    call("snx_teacher_head_cache_refresh", C.byref(self._desc), C.c_void_p(self.head["weight"].data_ptr()),
+                         C.c_void_p(self._hcache.data_ptr()), self._stream())
+
+    @property
+    def has_multivector(self) -> bool:
+        """Was a multi-vector head (``colbert_linear.pt``) loaded?"""
+        return self.head is not None
 
     @staticmethod
     def _stream() -> C.c_void_p:
@@ -308,14 +422,17 @@ class TeacherEncoder:
         with open(os.path.join(model_dir, "config.json")) as f:
             config = TeacherConfig.from_hf(json.load(f))
         _check_pooling(model_dir)
-        return cls(config, _read_weights(model_dir), device, precision)
+        head = None
+        if os.path.exists(os.path.join(model_dir, "colbert_linear.pt")):      # BGE-M3's multi-vector head, when present
+            head = torch.load(os.path.join(model_dir, "colbert_linear.pt"), map_location="cpu", weights_only=True)
+        return cls(config, _read_weights(model_dir), device, precision, colbert_head=head)
 
     def to(self, device) -> "TeacherEncoder":
         """An encoder with the same weights on ``device`` (this one when it is there already)."""
         dev = torch.device(device)
         if dev == self.device or (dev.type == self.device.type and dev.index is None):
             return self
-        return TeacherEncoder(self.config, self.params, dev, self.precision)
+        return TeacherEncoder(self.config, self.params, dev, self.precision, colbert_head=self.head)
 
     def _on_my_gpu(self, tokenizer) -> bool:
         """Does ``tokenizer`` return a CSR of ids (``encode_rows``) on this encoder's GPU?"""
@@ -343,10 +460,10 @@ class TeacherEncoder:
                                       cu.to(dev), int(lens.max()), normalize)
 
     def _forward_unpadded(self, ids_u: torch.Tensor, pos_u: torch.Tensor, cu: torch.Tensor, max_len: int,
-                          normalize: bool) -> torch.Tensor:
+                          normalize: bool, multivector: bool = False):
         """The native forward over unpadded token rows, all on the encoder's GPU: ``ids_u`` int64 [T] and ``pos_u`` int32
         [T], sequence after sequence; ``cu`` int32 [n + 1] their offsets; ``max_len`` the longest sequence.  The caller
-        has checked ids and positions."""
+        has checked ids and positions.  ``multivector``: run the head too -> (embeddings, store [T - n, H])."""
         from ._lib import call, fn
         dev = self.device
         n, T = int(cu.numel()) - 1, int(ids_u.numel())
@@ -361,9 +478,79 @@ class TeacherEncoder:
             cls = torch.empty((n, H), dtype=torch.float32, device=dev)
             emb = torch.empty((n, H), dtype=torch.float32, device=dev)
             p = lambda t: C.c_void_p(t.data_ptr())                 # noqa: E731
+            if multivector:
+                mv = torch.empty((max(T - n, 1), H), dtype=torch.float32 if self.precision == "fp32" else torch.bfloat16,
+                                 device=dev)
+                call("snx_teacher_forward_mv", C.byref(self._desc), self._ptrs, p(self._wcache), p(self.head["weight"]),
+                     p(self.head["bias"]), p(self._hcache), p(ids_u), p(pos_u), p(cu), p(self._ws), p(cls), p(emb), p(mv),
+                     T, n, max_len, prec, self._stream())
+                return (emb if normalize else cls), mv[:T - n]
             call("snx_teacher_forward", C.byref(self._desc), self._ptrs, p(self._wcache), p(ids_u), p(pos_u), p(cu),
                  p(self._ws), p(cls), p(emb), T, n, max_len, prec, self._stream())
         return emb if normalize else cls
+
+    @torch.no_grad()
+    def encode_tokens_multivector(self, input_ids: torch.Tensor, attention_mask: torch.Tensor
+                                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """A padded batch [n, S] -> (emb fp32 [n, hidden], exactly ``encode_tokens``' rows; mv_ptr int64 [n + 1]; mv
+        [rows, hidden]) on the encoder's device: per sequence the normalised multi-vector rows of every token behind its
+        first, end to end (bf16 for precision "bf16", fp32 for "fp32").  One forward serves both outputs."""
+        if self.head is None:
+            raise ValueError("teacher: this encoder has no multi-vector head (no colbert_linear.pt in the model directory)")
+        if self.device.type != "cuda":
+            emul = self.precision == "bf16"
+            _, emb, h = forward_torch(self.config, self.params, input_ids, attention_mask, emulate_bf16=emul,
+                                      return_hidden=True)
+            mv_ptr, mv = multivector_torch(self.head, h, attention_mask, emulate_bf16=emul)
+            return emb, mv_ptr, mv.to(torch.bfloat16) if emul else mv
+        ids, mask, pos = _check_batch(self.config, input_ids, attention_mask)
+        keep = mask.bool()
+        lens = mask.sum(dim=1)
+        cu = torch.zeros(int(ids.shape[0]) + 1, dtype=torch.int32, device=lens.device)
+        cu[1:] = torch.cumsum(lens, 0)
+        dev = self.device
+        emb, mv = self._forward_unpadded(ids[keep].to(dev).contiguous(), pos[keep].to(torch.int32).to(dev).contiguous(),
+                                         cu.to(dev), int(lens.max()), True, multivector=True)
+        mv_ptr = (cu.to(torch.long) - torch.arange(cu.numel(), dtype=torch.long, device=cu.device)).to(dev)
+        return emb, mv_ptr, mv
+
+    def encode_multivector(self, texts: Sequence[str], tokenizer: Callable, max_length: int = 512,
+                           batch_tokens: int = DEFAULT_BATCH_TOKENS) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Texts -> (emb fp32 [n, hidden], mv_ptr int64 [n + 1], mv [rows, hidden]) on the encoder's device, sequences in
+        input order: ``encode``'s embeddings and the multi-vector store that ``maxsim_pairs`` reads.  The texts are packed
+        by length as in ``encode``; a store holds 2 * hidden bytes per token in bf16, so it is made per chunk of a
+        corpus and scored at once, never cached."""
+        texts = list(texts)
+        if not texts:
+            raise ValueError("teacher: encode_multivector needs at least one text")
+        if int(batch_tokens) < 1:
+            raise ValueError("teacher: batch_tokens must be positive")
+        if self._on_my_gpu(tokenizer):
+            ptr, flat = tokenizer.encode_rows(texts, int(max_length))
+            ptr, flat = ptr.tolist(), flat.tolist()
+            seqs = [flat[a:b] for a, b in zip(ptr, ptr[1:])]
+        else:
+            seqs = [list(s) for s in tokenizer(texts, truncation=True, max_length=int(max_length), padding=False)["input_ids"]]
+        if any(len(s) == 0 for s in seqs):
+            raise ValueError("teacher: the tokenizer returned an empty sequence")
+        dev = self.device
+        rows = torch.tensor([0] + [len(s) - 1 for s in seqs], dtype=torch.long)
+        mv_ptr = torch.cumsum(rows, 0)
+        emb = torch.empty((len(seqs), self.config.hidden_size), dtype=torch.float32, device=dev)
+        mv = torch.empty((int(mv_ptr[-1]), self.config.hidden_size), device=dev,
+                         dtype=torch.float32 if self.precision == "fp32" else torch.bfloat16)
+        for batch in _length_batches([len(s) for s in seqs], None, batch_tokens):
+            S = max(len(seqs[j]) for j in batch)
+            ids = torch.full((len(batch), S), self.config.pad_token_id, dtype=torch.long)
+            mask = torch.zeros((len(batch), S), dtype=torch.long)
+            for b, j in enumerate(batch):
+                ids[b, :len(seqs[j])] = torch.tensor(seqs[j], dtype=torch.long)
+                mask[b, :len(seqs[j])] = 1
+            e, _, m = self.encode_tokens_multivector(ids, mask)
+            emb[torch.tensor(batch, device=dev)] = e
+            dest = torch.cat([torch.arange(int(mv_ptr[j]), int(mv_ptr[j + 1])) for j in batch]).to(dev)
+            mv[dest] = m                                           # the batch's rows, each sequence to its place
+        return emb, mv_ptr.to(dev), mv
 
     def encode_unpadded(self, ptr: torch.Tensor, ids: torch.Tensor, batch_size: Optional[int] = None,
                         batch_tokens: int = DEFAULT_BATCH_TOKENS, normalize: bool = True) -> torch.Tensor:

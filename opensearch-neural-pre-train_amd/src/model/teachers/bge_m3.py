@@ -10,7 +10,24 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from snx.teacher import DEFAULT_BATCH_TOKENS, TeacherEncoder
+from snx.teacher import DEFAULT_BATCH_TOKENS, TeacherEncoder, maxsim_pairs, maxsim_pairs_torch
+
+SCORE_MODES = ("dense", "colbert", "dense+colbert")
+
+
+def combine_scores(dense, colbert, weights: Tuple[float, float] = (1.0, 1.0)):
+    """(w_dense * dense + w_colbert * colbert) / (w_dense + w_colbert): the weighted mean of the two teacher scores."""
+    w_dense, w_colbert = float(weights[0]), float(weights[1])
+    if w_dense < 0 or w_colbert < 0 or w_dense + w_colbert <= 0:
+        raise ValueError("combine_scores: the weights must be non-negative and not both zero")
+    return (w_dense * dense + w_colbert * colbert) / (w_dense + w_colbert)
+
+
+def maxsim_scores(mv: torch.Tensor, mv_ptr, pair_q, pair_d) -> torch.Tensor:
+    """The native scorer for a store on a GPU; a CPU encoder's store goes through the float64 restatement."""
+    if mv.device.type == "cuda":
+        return maxsim_pairs(mv, mv_ptr, pair_q, pair_d)
+    return maxsim_pairs_torch(mv, mv_ptr, pair_q, pair_d).to(torch.float32)
 
 
 def _load_tokenizer(model_dir: str):
@@ -67,12 +84,47 @@ class BGEM3Teacher(nn.Module):
         return torch.mm(query_embeds, doc_embeds.t())
 
     @torch.no_grad()
-    def get_ranking_scores(self, queries: List[str], documents: List[str], batch_size: int = 32) -> torch.Tensor:
-        """Teacher scores of query-document pairs [num_pairs]."""
+    def get_ranking_scores(self, queries: List[str], documents: List[str], batch_size: int = 32, mode: str = "dense",
+                           weights: Tuple[float, float] = (1.0, 1.0)) -> torch.Tensor:
+        """Teacher scores of query-document pairs [num_pairs].  ``mode``: "dense" (the CLS cosine, the reference's
+        score), "colbert" (MaxSim over the multi-vector rows) or "dense+colbert" (``combine_scores`` with ``weights`` =
+        (w_dense, w_colbert)); the last two need a model directory with ``colbert_linear.pt``."""
         assert len(queries) == len(documents), "Must have same number of queries and docs"
-        query_embeds = self.encode(queries, batch_size=batch_size)
-        doc_embeds = self.encode(documents, batch_size=batch_size)
-        return (query_embeds * doc_embeds).sum(dim=-1)
+        if mode not in SCORE_MODES:
+            raise ValueError(f"get_ranking_scores: mode must be one of {SCORE_MODES}")
+        if mode == "dense":
+            query_embeds = self.encode(queries, batch_size=batch_size)
+            doc_embeds = self.encode(documents, batch_size=batch_size)
+            return (query_embeds * doc_embeds).sum(dim=-1)
+        n = len(queries)
+        pair_q, pair_d = torch.arange(n), torch.arange(n, 2 * n)
+        emb, mv_ptr, mv = self.encode_multivector(list(queries) + list(documents))
+        colbert = maxsim_scores(mv, mv_ptr, pair_q, pair_d)
+        if mode == "colbert":
+            return colbert
+        return combine_scores((emb[:n] * emb[n:]).sum(dim=-1), colbert, weights)
+
+    @torch.no_grad()
+    def encode_multivector(self, texts: List[str]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Texts -> (dense embeddings [n, hidden], mv_ptr [n + 1], multi-vector rows) of one forward
+        (``TeacherEncoder.encode_multivector``)."""
+        return self.model.encode_multivector(texts, self.tokenizer, max_length=self.max_length,
+                                             batch_tokens=self.batch_tokens)
+
+    @torch.no_grad()
+    def compute_multivector_scores(self, queries: List[str], documents_per_query: List[List[str]]) -> List[torch.Tensor]:
+        """MaxSim (late-interaction) scores: per query one fp32 tensor [len(documents_per_query[i])].  Every distinct text
+        is encoded once."""
+        assert len(queries) == len(documents_per_query), "Must have one document list per query"
+        row: Dict[str, int] = {}
+        for t in list(queries) + [d for docs in documents_per_query for d in docs]:
+            row.setdefault(t, len(row))
+        pairs = [(row[q], row[d]) for q, docs in zip(queries, documents_per_query) for d in docs]
+        if not pairs:
+            return [torch.zeros(0, device=self.model.device) for _ in queries]
+        _, mv_ptr, mv = self.encode_multivector(list(row))
+        scores = maxsim_scores(mv, mv_ptr, torch.tensor([p[0] for p in pairs]), torch.tensor([p[1] for p in pairs]))
+        return list(torch.split(scores, [len(docs) for docs in documents_per_query]))
 
     @torch.no_grad()
     def get_soft_labels(self, query: str, positive_doc: str, negative_docs: List[str],

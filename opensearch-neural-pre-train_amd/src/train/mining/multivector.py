@@ -1,0 +1,86 @@
+"""Multi-vector (MaxSim) teacher scores for the records of a training set, straight from the encoder.
+
+``write_teacher_scores`` (dense.py) reads single vectors from a cache on disk.  A multi-vector cannot be cached that way (a
+256-token text is 512 KB in bf16), so here the scorer sits directly behind the forward: per chunk of records the chunk's
+unique texts are encoded once (``encode_mv``: ``BGEM3Teacher.encode_multivector``), the (query, positive) and (query,
+negative) pairs are scored over that store (``scorer``: ``snx.teacher.maxsim_pairs``) and the store is dropped.  The dense
+score of ``mode="dense+colbert"`` is the CLS cosine of the same forward.  The fields written are those of
+``write_teacher_scores`` -- ``teacher_pos_score``, ``teacher_neg_score`` and, for a record with ``negatives[]``,
+``teacher_neg_scores``, each round(float(s), 6) -- so the trainer reads the output unchanged.  A record without a string
+query and positive is written unchanged; a missing negative scores 0.0."""
+from __future__ import annotations
+
+import json
+import os
+from typing import Callable, Dict, List, Sequence, Tuple
+
+from .dense import _r6, _read
+
+
+def _score_chunk(items: List[dict], encode_mv: Callable, scorer: Callable, mode: str, weights: Tuple[float, float]) -> int:
+    """Adds the score fields to the scoreable records of ``items`` in place; returns how many there were."""
+    import torch
+    from src.model.teachers.bge_m3 import combine_scores
+    row: Dict[str, int] = {}
+    pair_q: List[int] = []
+    pair_d: List[int] = []
+
+    def pair(q: int, text):
+        if not isinstance(text, str):
+            return None
+        pair_q.append(q)
+        pair_d.append(row.setdefault(text, len(row)))
+        return len(pair_q) - 1
+
+    plan = []                                                    # per record: None | (pos, neg | None, [negs | None])
+    for item in items:
+        if not isinstance(item, dict) or not isinstance(item.get("query"), str) or not isinstance(item.get("positive"), str):
+            plan.append(None)
+            continue
+        q = row.setdefault(item["query"], len(row))
+        negs = item["negatives"] if isinstance(item.get("negatives"), list) else []
+        plan.append((pair(q, item["positive"]), pair(q, item.get("negative")), [pair(q, n) for n in negs]))
+    if not pair_q:
+        return 0
+    emb, mv_ptr, mv = encode_mv(list(row))
+    pq, pd = torch.tensor(pair_q), torch.tensor(pair_d)
+    scores = scorer(mv, mv_ptr, pq, pd).to(torch.float32)
+    if mode == "dense+colbert":
+        dense = (emb[pq.to(emb.device)] * emb[pd.to(emb.device)]).sum(dim=-1)
+        scores = combine_scores(dense.to(scores.device), scores, weights)
+    scores = scores.cpu().tolist()
+    done = 0
+    for item, pl in zip(items, plan):
+        if pl is None:
+            continue
+        pos, neg, negs = pl
+        item["teacher_pos_score"] = _r6(scores[pos])
+        item["teacher_neg_score"] = _r6(scores[neg]) if neg is not None else 0.0
+        if isinstance(item.get("negatives"), list):
+            item["teacher_neg_scores"] = [_r6(scores[i]) if i is not None else 0.0 for i in negs]
+        done += 1
+    return done
+
+
+def write_multivector_scores(input_files: Sequence[str], output_dir: str, encode_mv: Callable, scorer: Callable,
+                             mode: str = "colbert", weights: Tuple[float, float] = (1.0, 1.0),
+                             chunk_records: int = 256) -> int:
+    """MaxSim teacher scores for every record of ``input_files`` (one output file per shard, same name), ``chunk_records``
+    records per forward-and-score round.  ``encode_mv(texts) -> (emb [n, H], mv_ptr [n + 1], mv [rows, H])``;
+    ``scorer(mv, mv_ptr, pair_q, pair_d) -> [npairs]``.  ``mode``: "colbert", or "dense+colbert" with ``weights`` =
+    (w_dense, w_colbert).  Returns the records scored."""
+    if mode not in ("colbert", "dense+colbert"):
+        raise ValueError("multi-vector scores: mode is 'colbert' or 'dense+colbert'")
+    if int(chunk_records) < 1:
+        raise ValueError("multi-vector scores: chunk_records must be positive")
+    os.makedirs(output_dir, exist_ok=True)
+    total = 0
+    for path in sorted(input_files):
+        items = _read(path)
+        with open(os.path.join(output_dir, os.path.basename(path)), "w", encoding="utf-8") as fout:
+            for at in range(0, len(items), int(chunk_records)):
+                chunk = items[at:at + int(chunk_records)]
+                total += _score_chunk(chunk, encode_mv, scorer, mode, weights)
+                for item in chunk:
+                    fout.write(json.dumps(item, ensure_ascii=False) + "\n")
+    return total
