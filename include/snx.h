@@ -360,6 +360,53 @@ int snx_maxsim_pairs(const void* mv, int32_t mv_f32, int64_t nrows, int32_t D, c
                      const int32_t* pair_q /*[host]*/, const int32_t* pair_d /*[host]*/, int64_t npairs, int32_t max_rows,
                      float* score, void* workspace, size_t ws_bytes, hipStream_t stream);
 
+/* ---- lexical teacher scores (csrc/teacher_lex.hip: head, unique and scorer; csrc/teacher.hip: snx_teacher_forward_m3) --
+ * BGE-M3's sparse output on top of the forward above.  Written from memory of BGE-M3's published code: parity with that
+ * code and with real weights is UNVERIFIED.
+ *   head           w_s [hidden] and b_s (one float): the `sparse_linear` of the model directory (weight [1, hidden], bias [1]).
+ *   token weight   tw[t] = max(0, <h[t], w_s> + b_s) for every token row t of the last hidden state h, CLS included.  h is
+ *                  fp32 in both precisions and is read as fp32: no cast point; the precisions differ through h alone.  One
+ *                  wave per row: a lane's fma chain over its elements in ascending order, then wave_sum, then + b_s.
+ *   lexical weights of sequence s: for each distinct token id v of s, lw[s][v] = max of tw over the occurrences of v in s
+ *                  alone.  An id of `unused_ids` (at most 8; BGE-M3: cls, eos, pad, unk) is dropped, a term is kept only
+ *                  when its weight is > 0, the kept terms are stored in ascending id.  A max is exact: no tolerance.
+ *   score          lex(a, b) = sum over v in ids(a) n ids(b) of lw[a][v] * lw[b][v]: fp32 products, fp32 sum, the order a
+ *                  function of the two term lists alone, so a score has the same bits in every call and every pair list.
+ *                  An empty side or an empty intersection scores 0.0f.
+ *
+ * snx_teacher_token_weights: h [T, H] fp32 (16-byte aligned, H as `hidden` above), w_s [H] -> tw [T] fp32.
+ * snx_lexical_unique: ids [T] int64 and tw [T] of unpadded sequences (cu_seqlens as for snx_teacher_forward) -> per
+ * sequence s the kept terms in the first lex_cnt[s] slots of its own range cu_seqlens[s] .. cu_seqlens[s + 1] - 1 of
+ * lex_id [T] int32 / lex_w [T] fp32, the rest of the range (-1, 0.0f).  One workgroup per sequence sorts 64-bit keys
+ * (id << 32 | weight bits) in LDS sized from max_seqlen; a tw that is not > 0 (a NaN too) counts as 0.  max_seqlen > 8192
+ * or n_unused > 8: SNX_E_SHAPE before any launch; a sequence longer than max_seqlen gets lex_cnt 0.  unused_ids is a HOST
+ * array (it travels as a kernel argument).
+ * snx_lexical_pairs: the contract of snx_maxsim_pairs over a compact CSR: ids [nterms] int32 ascending within a row and
+ * w [nterms] fp32 on the device, lex_ptr [nseq + 1], pair_q, pair_d pageable HOST arrays checked before any launch
+ * (SNX_E_ARG: lex_ptr not ascending from 0 or past nterms, a pair index outside [0, nseq)).  One wave per pair: the lanes
+ * stride over the shorter list (ties: the query's) and binary-search the longer one; a lane adds its products in ascending
+ * order of its items, then wave_sum.  No float atomics, nothing of vocabulary size.
+ * snx_teacher_forward_m3: snx_teacher_forward (same cls_out / emb_out, bit for bit); head_w != NULL: the multi-vector
+ * output of snx_teacher_forward_mv (same mv_out, bit for bit; head_b, head_cache, mv_out required); sparse_w != NULL:
+ * token_weights and lexical_unique into tw_out [T], lex_id [T], lex_w [T], lex_cnt [nseq].  Every argument is checked
+ * before the first launch.  Its arena is the forward's. */
+int snx_teacher_token_weights(const float* h, const float* sparse_w, float sparse_b, float* tw, int32_t T, int32_t H,
+                              hipStream_t stream);
+int snx_lexical_unique(const int64_t* ids, const float* tw, const int32_t* cu_seqlens, const int32_t* unused_ids /*[host]*/,
+                       int32_t n_unused, int32_t* lex_id, float* lex_w, int32_t* lex_cnt, int32_t T, int32_t nseq,
+                       int32_t max_seqlen, hipStream_t stream);
+size_t snx_lexical_pairs_workspace_bytes(int32_t nseq, int64_t npairs);
+int snx_lexical_pairs(const int32_t* ids, const float* w, int64_t nterms, const int64_t* lex_ptr /*[host]*/, int32_t nseq,
+                      const int32_t* pair_q /*[host]*/, const int32_t* pair_d /*[host]*/, int64_t npairs, float* score,
+                      void* workspace, size_t ws_bytes, hipStream_t stream);
+size_t snx_teacher_forward_m3_workspace_bytes(const snx_teacher_desc* d, int32_t T, int32_t nseq, int32_t precision);
+int snx_teacher_forward_m3(const snx_teacher_desc* d, const void* const* params /*[host]*/, const void* wcache,
+                           const float* head_w, const float* head_b, const void* head_cache, const float* sparse_w,
+                           float sparse_b, const int32_t* unused_ids /*[host]*/, int32_t n_unused, const int64_t* ids,
+                           const int32_t* pos_ids, const int32_t* cu_seqlens, void* workspace, float* cls_out,
+                           float* emb_out, void* mv_out, float* tw_out, int32_t* lex_id, float* lex_w, int32_t* lex_cnt,
+                           int32_t T, int32_t nseq, int32_t max_seqlen, int32_t precision, hipStream_t stream);
+
 /* ---- inference post-processing (ref:benchmark/encoders.py:309-345 NeuralSparseEncoderV33._encode_batch) ---- */
 /* Per row of rep [B,V] fp32: entries with rep > 0 and allowed[v] != 0 survive.  k > 0 and more than k survivors:
  * the k largest, weight descending, ties lowest id first (out_sorted[b] = 1); otherwise all survivors in id

@@ -16,9 +16,13 @@
 // row kernel of teacher_mv.hip, which adds the bias, L2-normalises in fp32 and packs every row but a sequence's first into
 // the store that maxsim.hip scores; the GEMM's output is bf16 on the bf16 path and the stored row is rounded to bf16 once.
 // No kernel of this file was added or changed for it: the device code here is what it was.
+//
+// All heads of one forward (snx_teacher_forward_m3): the same layer loop, the same multi-vector tail, and the lexical
+// kernels of teacher_lex.hip (BGE-M3's sparse_linear) over the fp32 residual stream.  Host code only, again.
 #include "common.h"
 #include "rows.h"
 #include "runtime.h"
+#include "teacher_lex.h"
 #include "snx.h"
 
 namespace {
@@ -470,15 +474,16 @@ extern "C" size_t snx_teacher_forward_mv_workspace_bytes(const snx_teacher_desc*
   return snx_teacher_workspace_bytes(d, T, nseq, precision);
 }
 
-extern "C" int snx_teacher_forward_mv(const snx_teacher_desc* d, const void* const* params, const void* wcache,
-                                      const float* head_w, const float* head_b, const void* head_cache, const int64_t* ids,
-                                      const int32_t* pos_ids, const int32_t* cu_seqlens, void* workspace, float* cls_out,
-                                      float* emb_out, void* mv_out, int32_t T, int32_t nseq, int32_t max_seqlen,
-                                      int32_t precision, hipStream_t st) {
-  if (!head_w || !head_b || !head_cache || !mv_out || misaligned(head_w) || misaligned(head_cache) || misaligned(mv_out))
-    return SNX_E_ARG;
-  RC(forward_layers(d, params, wcache, ids, pos_ids, cu_seqlens, workspace, cls_out, emb_out, T, nseq, max_seqlen, precision,
-                    st));
+namespace {
+
+bool mv_args_bad(const float* head_w, const float* head_b, const void* head_cache, const void* mv_out) {
+  return !head_w || !head_b || !head_cache || !mv_out || misaligned(head_w) || misaligned(head_cache) || misaligned(mv_out);
+}
+
+// behind forward_layers: the head GEMM over the last hidden state into the y block, then the row kernel into mv_out
+int mv_head(const snx_teacher_desc* d, const float* head_w, const float* head_b, const void* head_cache,
+            const int32_t* cu_seqlens, void* workspace, void* mv_out, int32_t T, int32_t nseq, int32_t precision,
+            hipStream_t st) {
   if (T == nseq) return SNX_OK;                                  // every sequence is its CLS row alone: an empty store
   const bool f32 = precision == SNX_TEACHER_F32;
   const int H = d->hidden;
@@ -488,4 +493,45 @@ extern "C" int snx_teacher_forward_mv(const snx_teacher_desc* d, const void* con
   if (f32) RC(snx_gemm_f32((const float*)(ws + s.h), H, 1, head_w, H, 1, (float*)y, H, nullptr, 0, T, H, H, 0, st));
   else RC(snx_gemm_nt_bf16(ws + s.x, head_cache, y, T, H, H, st));
   return snx_teacher_mv_rows(y, f32, head_b, cu_seqlens, mv_out, T, nseq, H, st);
+}
+
+}  // namespace
+
+extern "C" int snx_teacher_forward_mv(const snx_teacher_desc* d, const void* const* params, const void* wcache,
+                                      const float* head_w, const float* head_b, const void* head_cache, const int64_t* ids,
+                                      const int32_t* pos_ids, const int32_t* cu_seqlens, void* workspace, float* cls_out,
+                                      float* emb_out, void* mv_out, int32_t T, int32_t nseq, int32_t max_seqlen,
+                                      int32_t precision, hipStream_t st) {
+  if (mv_args_bad(head_w, head_b, head_cache, mv_out)) return SNX_E_ARG;
+  RC(forward_layers(d, params, wcache, ids, pos_ids, cu_seqlens, workspace, cls_out, emb_out, T, nseq, max_seqlen, precision,
+                    st));
+  return mv_head(d, head_w, head_b, head_cache, cu_seqlens, workspace, mv_out, T, nseq, precision, st);
+}
+
+// ---- all of BGE-M3's outputs of one forward: dense, multi-vector (head_w), lexical (sparse_w; teacher_lex.hip) ---------
+extern "C" size_t snx_teacher_forward_m3_workspace_bytes(const snx_teacher_desc* d, int32_t T, int32_t nseq,
+                                                         int32_t precision) {
+  return snx_teacher_workspace_bytes(d, T, nseq, precision);     // the heads read h / x and write y: the forward's arena
+}
+
+extern "C" int snx_teacher_forward_m3(const snx_teacher_desc* d, const void* const* params, const void* wcache,
+                                      const float* head_w, const float* head_b, const void* head_cache,
+                                      const float* sparse_w, float sparse_b, const int32_t* unused_ids, int32_t n_unused,
+                                      const int64_t* ids, const int32_t* pos_ids, const int32_t* cu_seqlens, void* workspace,
+                                      float* cls_out, float* emb_out, void* mv_out, float* tw_out, int32_t* lex_id,
+                                      float* lex_w, int32_t* lex_cnt, int32_t T, int32_t nseq, int32_t max_seqlen,
+                                      int32_t precision, hipStream_t st) {
+  if (head_w && mv_args_bad(head_w, head_b, head_cache, mv_out)) return SNX_E_ARG;
+  if (sparse_w) {                                                // what the lexical kernels would refuse, before any launch
+    if (misaligned(sparse_w) || !tw_out || !lex_id || !lex_w || !lex_cnt || n_unused < 0 || (n_unused > 0 && !unused_ids))
+      return SNX_E_ARG;
+    if (max_seqlen > LEX_MAX_SEQLEN || n_unused > LEX_MAX_UNUSED) return SNX_E_SHAPE;
+  }
+  RC(forward_layers(d, params, wcache, ids, pos_ids, cu_seqlens, workspace, cls_out, emb_out, T, nseq, max_seqlen, precision,
+                    st));
+  if (head_w) RC(mv_head(d, head_w, head_b, head_cache, cu_seqlens, workspace, mv_out, T, nseq, precision, st));
+  if (!sparse_w) return SNX_OK;
+  const float* h = (const float*)((char*)workspace + Plan(d, T, precision == SNX_TEACHER_F32).h);
+  RC(snx_teacher_token_weights(h, sparse_w, sparse_b, tw_out, T, d->hidden, st));
+  return snx_lexical_unique(ids, tw_out, cu_seqlens, unused_ids, n_unused, lex_id, lex_w, lex_cnt, T, nseq, max_seqlen, st);
 }

@@ -79,6 +79,9 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     # and for MaxSim: the 16 accumulator registers, the 16 running row maxima and the prefetched operand slices stay in
     # registers across the document tiles; the finish kernel holds no LDS and one sum, and is not listed
     "maxsim.hip": ("ms_pair_kernel",),
+    # and for the lexical weights: the 64-bit keys live in LDS, a thread's key, its ballot and the unused ids (kernel
+    # arguments) in registers; the head's row kernel and the pair scorer hold no LDS and are not listed
+    "teacher_lex.hip": ("tl_unique_kernel",),
 }
 
 # Per-source compile flags, for the library and for the guard's assembly alike (snx/build.py keys its objects on them).
@@ -91,6 +94,7 @@ _NO_PACKED_F32 = ("-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")
 FILE_FLAGS: Dict[str, Tuple[str, ...]] = {
     "maxsim.hip": _NO_PACKED_F32,
     "teacher_mv.hip": _NO_PACKED_F32,
+    "teacher_lex.hip": _NO_PACKED_F32,
 }
 
 

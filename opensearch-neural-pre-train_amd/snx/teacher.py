@@ -6,6 +6,8 @@
     emb = enc.encode_tokens(input_ids, attention_mask)                 # the same from a padded batch
     emb, mv_ptr, mv = enc.encode_multivector(texts, tokenizer)         # + the multi-vector rows (needs colbert_linear.pt)
     scores = maxsim_pairs(mv, mv_ptr, pair_q, pair_d)                  # late-interaction scores (csrc/maxsim.hip)
+    emb, mv_ptr, mv, lex_ptr, lex_ids, lex_w = enc.encode_m3(texts, tokenizer)   # + the lexical weights (sparse_linear.pt)
+    scores = lexical_pairs(lex_ptr, lex_ids, lex_w, pair_q, pair_d)    # lexical matching scores (csrc/teacher_lex.hip)
 
 ``forward_torch`` restates the same forward in plain torch (fp32, no transformers import): it is what a ``TeacherEncoder``
 on a ``cpu`` device runs, and the comparator of the GPU tests.  Its ``emulate_bf16`` mode rounds at exactly the cast points
@@ -152,6 +154,15 @@ def random_colbert_head(config: TeacherConfig, seed: int) -> Dict[str, torch.Ten
     H = config.hidden_size
     return {"weight": torch.from_numpy((0.1 * rs.standard_normal((H, H))).astype(np.float32)),
             "bias": torch.from_numpy((0.1 * rs.standard_normal((H,))).astype(np.float32))}
+
+
+def random_sparse_head(config: TeacherConfig, seed: int) -> Dict[str, torch.Tensor]:
+    """A sparse head from a recipe (tests): ``weight`` [1, H] N(0, 0.1) and ``bias`` [1] 0.1 N(0, 1) from a
+    numpy.random.RandomState(seed) of its own: on LayerNorm rows about half of the token weights come out positive."""
+    import numpy as np
+    rs = np.random.RandomState(int(seed))
+    return {"weight": torch.from_numpy((0.1 * rs.standard_normal((1, config.hidden_size))).astype(np.float32)),
+            "bias": torch.from_numpy((0.1 * rs.standard_normal((1,))).astype(np.float32))}
 
 
 def normalize_state_dict(config: TeacherConfig, state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -319,6 +330,109 @@ def maxsim_pairs(mv: torch.Tensor, mv_ptr, pair_q, pair_d) -> torch.Tensor:
     return score
 
 
+LEX_MAX_SEQLEN = 8192                  # tokens of one sequence and unused ids that the lexical kernels serve
+LEX_MAX_UNUSED = 8                     # (csrc/teacher_lex.h; include/snx.h "lexical teacher scores")
+
+
+def default_unused_ids(tokenizer) -> List[int]:
+    """The ids BGE-M3 leaves out of its lexical weights: the tokenizer's cls / bos, eos / sep, pad and unk ids."""
+    names = ("cls_token_id", "sep_token_id", "pad_token_id", "unk_token_id", "bos_token_id", "eos_token_id")
+    return sorted({int(i) for i in (getattr(tokenizer, n, None) for n in names) if i is not None})
+
+
+def _check_unused(unused_ids) -> List[int]:
+    ids = [int(v) for v in unused_ids]
+    if len(ids) > LEX_MAX_UNUSED:
+        raise ValueError(f"lexical: at most {LEX_MAX_UNUSED} unused ids, got {len(ids)}")
+    return ids
+
+
+def token_weights_torch(sparse_head: Dict[str, torch.Tensor], hidden: torch.Tensor) -> torch.Tensor:
+    """The sparse head in plain torch on ``forward_torch``'s last hidden state [n, S, H] -> relu(h w_s + b_s) [n, S], in
+    hidden's dtype.  The head has no cast point: there is no bf16 emulation to apply."""
+    w, b = sparse_head["weight"].to(hidden).reshape(-1), sparse_head["bias"].to(hidden).reshape(())
+    return torch.relu(hidden @ w + b)
+
+
+def lexical_weights_torch(input_ids: torch.Tensor, attention_mask: torch.Tensor, token_weights: torch.Tensor,
+                          unused_ids: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The lexical weights restated in plain torch on a padded batch -> the CSR (lex_ptr int64 [n + 1], ids int32, w in
+    token_weights' dtype): per sequence and distinct id the largest token weight among the id's occurrences in that
+    sequence, ids of ``unused_ids`` and weights that are not > 0 dropped, ascending id."""
+    unused = torch.tensor(_check_unused(unused_ids), dtype=torch.long, device=input_ids.device)
+    mask = attention_mask != 0
+    if int(mask.sum(dim=1).max()) > LEX_MAX_SEQLEN:
+        raise ValueError(f"lexical: a sequence has more than {LEX_MAX_SEQLEN} tokens")
+    ptr, ids, ws = [0], [], []
+    for s in range(int(input_ids.shape[0])):
+        uniq, inv = torch.unique(input_ids[s][mask[s]].to(torch.long), return_inverse=True)
+        m = torch.zeros(uniq.numel(), dtype=token_weights.dtype, device=token_weights.device)
+        m = m.scatter_reduce(0, inv.to(m.device), token_weights[s][mask[s]], "amax")
+        ok = (m > 0) & ~torch.isin(uniq, unused).to(m.device)
+        ids.append(uniq.to(m.device)[ok].to(torch.int32))
+        ws.append(m[ok])
+        ptr.append(ptr[-1] + int(ok.sum()))
+    return torch.tensor(ptr, dtype=torch.long, device=token_weights.device), torch.cat(ids), torch.cat(ws)
+
+
+def _check_lex_pairs(lex_ptr, ids: torch.Tensor, w: torch.Tensor, pair_q, pair_d) -> Tuple[List[int], List[int], List[int]]:
+    """The argument rules of ``lexical_pairs`` / ``lexical_pairs_torch`` -> host lists (lex_ptr, pair_q, pair_d)."""
+    if not isinstance(ids, torch.Tensor) or not isinstance(w, torch.Tensor) or ids.dim() != 1 or ids.shape != w.shape or \
+            ids.is_floating_point() or not w.is_floating_point():
+        raise ValueError("lexical: ids (int) and w (float) must be 1-d tensors of one length")
+    ptr = [int(v) for v in torch.as_tensor(lex_ptr).tolist()]
+    pq, pd = ([int(v) for v in torch.as_tensor(p).reshape(-1).tolist()] for p in (pair_q, pair_d))
+    if len(ptr) < 2 or ptr[0] != 0 or any(b < a for a, b in zip(ptr, ptr[1:])) or ptr[-1] > int(ids.numel()):
+        raise ValueError("lexical: lex_ptr must ascend from 0 and end within the terms")
+    if len(pq) != len(pd):
+        raise ValueError("lexical: pair_q and pair_d must have one length")
+    for s in pq + pd:
+        if not 0 <= s < len(ptr) - 1:
+            raise ValueError(f"lexical: pair index {s} outside [0, {len(ptr) - 1})")
+    return ptr, pq, pd
+
+
+def lexical_pairs_torch(lex_ptr, ids: torch.Tensor, w: torch.Tensor, pair_q, pair_d) -> torch.Tensor:
+    """The definition of ``lexical_pairs`` restated in float64 torch -> float64 [npairs] on w's device: per pair the sum
+    over the ids both sequences hold of the product of their weights; 0 when there is none."""
+    ptr, pq, pd = _check_lex_pairs(lex_ptr, ids, w, pair_q, pair_d)
+    x = w.to(torch.float64)
+    out = torch.zeros(len(pq), dtype=torch.float64, device=w.device)
+    for p, (a, b) in enumerate(zip(pq, pd)):
+        ia, ib = ids[ptr[a]:ptr[a + 1]], ids[ptr[b]:ptr[b + 1]]
+        if ia.numel() and ib.numel():
+            at = torch.searchsorted(ib, ia).clamp_(max=ib.numel() - 1)
+            hit = ib[at] == ia
+            out[p] = (x[ptr[a]:ptr[a + 1]][hit] * x[ptr[b]:ptr[b + 1]][at[hit]]).sum()
+    return out
+
+
+@torch.no_grad()
+def lexical_pairs(lex_ptr, ids: torch.Tensor, w: torch.Tensor, pair_q, pair_d) -> torch.Tensor:
+    """Lexical matching scores of pairs of sequences of one CSR of lexical weights on the GPU (csrc/teacher_lex.hip) ->
+    fp32 [npairs] on w's device.  ``lex_ptr`` [n + 1], ``ids`` int32 ascending per sequence and ``w`` fp32: what
+    ``encode_m3`` returns.  A score depends on its two sequences alone: the same bits in any pair list; a sequence
+    without terms scores 0.  ValueError: an index outside the store, a lex_ptr that does not fit the terms."""
+    ptr, pq, pd = _check_lex_pairs(lex_ptr, ids, w, pair_q, pair_d)
+    if w.device.type != "cuda" or w.dtype != torch.float32 or ids.device != w.device:
+        raise ValueError("lexical: lexical_pairs needs int32 ids and fp32 weights on one GPU (lexical_pairs_torch is the "
+                         "CPU form)")
+    from ._lib import call, fn
+    ids, w = ids.to(torch.int32).contiguous(), w.contiguous()
+    nseq, npairs = len(ptr) - 1, len(pq)
+    with torch.cuda.device(w.device):
+        score = torch.empty(npairs, dtype=torch.float32, device=w.device)
+        if npairs == 0:
+            return score
+        need = int(fn("snx_lexical_pairs_workspace_bytes")(nseq, npairs))
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=w.device)
+        hptr, hq, hd = (C.c_int64 * (nseq + 1))(*ptr), (C.c_int32 * npairs)(*pq), (C.c_int32 * npairs)(*pd)
+        call("snx_lexical_pairs", C.c_void_p(ids.data_ptr()), C.c_void_p(w.data_ptr()), int(w.numel()), hptr, nseq, hq, hd,
+             npairs, C.c_void_p(score.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
+             C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return score
+
+
 def _read_weights(model_dir: str) -> Dict[str, torch.Tensor]:
     st = os.path.join(model_dir, "model.safetensors")
     if os.path.exists(st):
@@ -363,9 +477,11 @@ class TeacherEncoder:
     without the ``roberta.`` prefix."""
 
     def __init__(self, config: TeacherConfig, state_dict: Dict[str, torch.Tensor], device="cuda", precision: str = "bf16",
-                 colbert_head: Optional[Dict[str, torch.Tensor]] = None):
+                 colbert_head: Optional[Dict[str, torch.Tensor]] = None,
+                 sparse_head: Optional[Dict[str, torch.Tensor]] = None):
         """``colbert_head``: BGE-M3's multi-vector head, ``{"weight": [H, H], "bias": [H]}`` (``colbert_linear.pt``);
-        without it the encoder has the dense output only."""
+        ``sparse_head``: its lexical head, ``{"weight": [1, H], "bias": [1]}`` (``sparse_linear.pt``); without them the
+        encoder has the dense output only."""
         if precision not in PRECISIONS:
             raise ValueError(f"teacher: precision must be one of {sorted(PRECISIONS)}")
         config.validate()
@@ -384,6 +500,15 @@ class TeacherEncoder:
                                  "than the hidden size is not supported)")
             self.head = {"weight": w.detach().to(torch.float32).to(self.device).contiguous(),
                          "bias": b.detach().to(torch.float32).to(self.device).contiguous()}
+        self.sparse: Optional[Dict[str, torch.Tensor]] = None
+        if sparse_head is not None:
+            H = config.hidden_size
+            w, b = sparse_head.get("weight"), sparse_head.get("bias")
+            if w is None or b is None or tuple(w.shape) != (1, H) or tuple(b.shape) != (1,):
+                raise ValueError(f"teacher: the sparse head needs weight [1, {H}] and bias [1]")
+            self.sparse = {"weight": w.detach().to(torch.float32).to(self.device).contiguous(),
+                           "bias": b.detach().to(torch.float32).to(self.device).contiguous()}
+            self._sparse_b = float(b.detach().to(torch.float32).reshape(()))    # a kernel argument: read once, here
         if self.device.type == "cuda":
             from ._lib import call, fn
             self._desc = config.desc()
@@ -408,6 +533,11 @@ class TeacherEncoder:
         """Was a multi-vector head (``colbert_linear.pt``) loaded?"""
         return self.head is not None
 
+    @property
+    def has_sparse(self) -> bool:
+        """Was a sparse head (``sparse_linear.pt``) loaded?"""
+        return self.sparse is not None
+
     @staticmethod
     def _stream() -> C.c_void_p:
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -425,14 +555,17 @@ class TeacherEncoder:
         head = None
         if os.path.exists(os.path.join(model_dir, "colbert_linear.pt")):      # BGE-M3's multi-vector head, when present
             head = torch.load(os.path.join(model_dir, "colbert_linear.pt"), map_location="cpu", weights_only=True)
-        return cls(config, _read_weights(model_dir), device, precision, colbert_head=head)
+        sparse = None
+        if os.path.exists(os.path.join(model_dir, "sparse_linear.pt")):       # and its lexical head
+            sparse = torch.load(os.path.join(model_dir, "sparse_linear.pt"), map_location="cpu", weights_only=True)
+        return cls(config, _read_weights(model_dir), device, precision, colbert_head=head, sparse_head=sparse)
 
     def to(self, device) -> "TeacherEncoder":
         """An encoder with the same weights on ``device`` (this one when it is there already)."""
         dev = torch.device(device)
         if dev == self.device or (dev.type == self.device.type and dev.index is None):
             return self
-        return TeacherEncoder(self.config, self.params, dev, self.precision, colbert_head=self.head)
+        return TeacherEncoder(self.config, self.params, dev, self.precision, colbert_head=self.head, sparse_head=self.sparse)
 
     def _on_my_gpu(self, tokenizer) -> bool:
         """Does ``tokenizer`` return a CSR of ids (``encode_rows``) on this encoder's GPU?"""
@@ -520,9 +653,25 @@ class TeacherEncoder:
         input order: ``encode``'s embeddings and the multi-vector store that ``maxsim_pairs`` reads.  The texts are packed
         by length as in ``encode``; a store holds 2 * hidden bytes per token in bf16, so it is made per chunk of a
         corpus and scored at once, never cached."""
+        seqs = self._tokenize(texts, tokenizer, max_length, batch_tokens)
+        dev = self.device
+        rows = torch.tensor([0] + [len(s) - 1 for s in seqs], dtype=torch.long)
+        mv_ptr = torch.cumsum(rows, 0)
+        emb = torch.empty((len(seqs), self.config.hidden_size), dtype=torch.float32, device=dev)
+        mv = torch.empty((int(mv_ptr[-1]), self.config.hidden_size), device=dev,
+                         dtype=torch.float32 if self.precision == "fp32" else torch.bfloat16)
+        for batch, ids, mask in self._padded_batches(seqs, batch_tokens):
+            e, _, m = self.encode_tokens_multivector(ids, mask)
+            emb[torch.tensor(batch, device=dev)] = e
+            dest = torch.cat([torch.arange(int(mv_ptr[j]), int(mv_ptr[j + 1])) for j in batch]).to(dev)
+            mv[dest] = m                                           # the batch's rows, each sequence to its place
+        return emb, mv_ptr.to(dev), mv
+
+    def _tokenize(self, texts: Sequence[str], tokenizer: Callable, max_length: int, batch_tokens: int) -> List[List[int]]:
+        """The token ids of ``encode_multivector`` / ``encode_m3``'s texts, as host lists."""
         texts = list(texts)
         if not texts:
-            raise ValueError("teacher: encode_multivector needs at least one text")
+            raise ValueError("teacher: encode_multivector / encode_m3 need at least one text")
         if int(batch_tokens) < 1:
             raise ValueError("teacher: batch_tokens must be positive")
         if self._on_my_gpu(tokenizer):
@@ -533,12 +682,10 @@ class TeacherEncoder:
             seqs = [list(s) for s in tokenizer(texts, truncation=True, max_length=int(max_length), padding=False)["input_ids"]]
         if any(len(s) == 0 for s in seqs):
             raise ValueError("teacher: the tokenizer returned an empty sequence")
-        dev = self.device
-        rows = torch.tensor([0] + [len(s) - 1 for s in seqs], dtype=torch.long)
-        mv_ptr = torch.cumsum(rows, 0)
-        emb = torch.empty((len(seqs), self.config.hidden_size), dtype=torch.float32, device=dev)
-        mv = torch.empty((int(mv_ptr[-1]), self.config.hidden_size), device=dev,
-                         dtype=torch.float32 if self.precision == "fp32" else torch.bfloat16)
+        return seqs
+
+    def _padded_batches(self, seqs: List[List[int]], batch_tokens: int):
+        """``encode``'s length-sorted batches of ``seqs`` as (indices, padded ids, mask)."""
         for batch in _length_batches([len(s) for s in seqs], None, batch_tokens):
             S = max(len(seqs[j]) for j in batch)
             ids = torch.full((len(batch), S), self.config.pad_token_id, dtype=torch.long)
@@ -546,11 +693,112 @@ class TeacherEncoder:
             for b, j in enumerate(batch):
                 ids[b, :len(seqs[j])] = torch.tensor(seqs[j], dtype=torch.long)
                 mask[b, :len(seqs[j])] = 1
-            e, _, m = self.encode_tokens_multivector(ids, mask)
+            yield batch, ids, mask
+
+    @torch.no_grad()
+    def encode_tokens_m3(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, unused_ids: Sequence[int]):
+        """A padded batch [n, S] -> (emb fp32 [n, hidden], exactly ``encode_tokens``' rows; mv_ptr int64 [n + 1]; mv
+        [rows, hidden], exactly ``encode_tokens_multivector``'s store, or None without a multi-vector head; lex_ptr int64
+        [n + 1]; lex_ids int32; lex_w fp32) on the encoder's device: all of BGE-M3's outputs of one forward.  The lexical
+        weights are a CSR: sequence s holds the terms lex_ptr[s] .. lex_ptr[s + 1] - 1, ascending id, every weight > 0,
+        the ids of ``unused_ids`` (at most 8) left out.  A sequence may have at most 8192 tokens."""
+        if self.sparse is None:
+            raise ValueError("teacher: this encoder has no sparse head (no sparse_linear.pt in the model directory)")
+        unused = _check_unused(unused_ids)
+        lens = (attention_mask != 0).sum(dim=1)
+        if int(lens.max()) > LEX_MAX_SEQLEN:
+            raise ValueError(f"lexical: a sequence has more than {LEX_MAX_SEQLEN} tokens")
+        mv_ptr = torch.zeros(int(lens.numel()) + 1, dtype=torch.long)
+        mv_ptr[1:] = torch.cumsum(lens.cpu() - 1, 0)
+        mv_ptr = mv_ptr.to(self.device)
+        if self.device.type != "cuda":
+            emul = self.precision == "bf16"
+            _, emb, h = forward_torch(self.config, self.params, input_ids, attention_mask, emulate_bf16=emul,
+                                      return_hidden=True)
+            mv = None
+            if self.head is not None:
+                mv = multivector_torch(self.head, h, attention_mask, emulate_bf16=emul)[1]
+                mv = mv.to(torch.bfloat16) if emul else mv
+            lex = lexical_weights_torch(input_ids, attention_mask, token_weights_torch(self.sparse, h), unused)
+            return (emb, mv_ptr, mv) + lex
+        ids, mask, pos = _check_batch(self.config, input_ids, attention_mask)
+        keep = mask.bool()
+        cu = torch.zeros(int(ids.shape[0]) + 1, dtype=torch.int32, device=lens.device)
+        cu[1:] = torch.cumsum(lens, 0)
+        dev = self.device
+        emb, mv, lex_id, lex_w, lex_cnt = self._forward_m3_unpadded(
+            ids[keep].to(dev).contiguous(), pos[keep].to(torch.int32).to(dev).contiguous(), cu.to(dev), int(lens.max()), unused)
+        kept = lex_id >= 0                                         # the padded [T] layout -> a CSR, on the device
+        lex_ptr = torch.zeros(int(ids.shape[0]) + 1, dtype=torch.long, device=dev)
+        lex_ptr[1:] = torch.cumsum(lex_cnt.to(torch.long), 0)
+        return emb, mv_ptr, mv, lex_ptr, lex_id[kept], lex_w[kept]
+
+    def _forward_m3_unpadded(self, ids_u: torch.Tensor, pos_u: torch.Tensor, cu: torch.Tensor, max_len: int,
+                             unused: List[int]):
+        """``_forward_unpadded`` with every head the encoder has (snx_teacher_forward_m3) -> (emb, store | None, lex_id [T],
+        lex_w [T], lex_cnt [n]): the lexical weights in the kernel's layout, a sequence's terms at the front of its own
+        token range and (-1, 0) behind them."""
+        from ._lib import call, fn
+        dev = self.device
+        n, T = int(cu.numel()) - 1, int(ids_u.numel())
+        H, prec = self.config.hidden_size, PRECISIONS[self.precision]
+        with torch.cuda.device(dev):
+            need = int(fn("snx_teacher_forward_m3_workspace_bytes")(C.byref(self._desc), T, n, prec))
+            if need <= 0:
+                raise RuntimeError("teacher: snx_teacher_forward_m3_workspace_bytes refused the shape")
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = None                                    # release before growing
+                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            cls = torch.empty((n, H), dtype=torch.float32, device=dev)
+            emb = torch.empty((n, H), dtype=torch.float32, device=dev)
+            tw = torch.empty(T, dtype=torch.float32, device=dev)
+            lex_id = torch.empty(T, dtype=torch.int32, device=dev)
+            lex_w = torch.empty(T, dtype=torch.float32, device=dev)
+            lex_cnt = torch.empty(n, dtype=torch.int32, device=dev)
+            p = lambda t: C.c_void_p(t.data_ptr())                 # noqa: E731
+            mv, head = None, (None, None, None, None)
+            if self.head is not None:
+                mv = torch.empty((max(T - n, 1), H), dtype=torch.float32 if self.precision == "fp32" else torch.bfloat16,
+                                 device=dev)
+                head = (p(self.head["weight"]), p(self.head["bias"]), p(self._hcache), p(mv))
+            call("snx_teacher_forward_m3", C.byref(self._desc), self._ptrs, p(self._wcache), head[0], head[1], head[2],
+                 p(self.sparse["weight"]), self._sparse_b, (C.c_int32 * max(len(unused), 1))(*unused), len(unused), p(ids_u),
+                 p(pos_u), p(cu), p(self._ws), p(cls), p(emb), head[3], p(tw), p(lex_id), p(lex_w), p(lex_cnt), T, n,
+                 max_len, prec, self._stream())
+        return emb, (mv[:T - n] if mv is not None else None), lex_id, lex_w, lex_cnt
+
+    def encode_m3(self, texts: Sequence[str], tokenizer: Callable, max_length: int = 512,
+                  batch_tokens: int = DEFAULT_BATCH_TOKENS, unused_ids: Optional[Sequence[int]] = None):
+        """Texts -> ``encode_tokens_m3``'s six values for the whole list, sequences in input order; batched as
+        ``encode_multivector`` and joined.  ``unused_ids``: default the tokenizer's cls / bos, eos / sep, pad and unk ids."""
+        if self.sparse is None:
+            raise ValueError("teacher: this encoder has no sparse head (no sparse_linear.pt in the model directory)")
+        unused = _check_unused(default_unused_ids(tokenizer) if unused_ids is None else unused_ids)
+        seqs = self._tokenize(texts, tokenizer, max_length, batch_tokens)
+        dev, n = self.device, len(seqs)
+        mv_ptr = torch.cumsum(torch.tensor([0] + [len(s) - 1 for s in seqs], dtype=torch.long), 0)
+        emb = torch.empty((n, self.config.hidden_size), dtype=torch.float32, device=dev)
+        mv = None
+        if self.head is not None:
+            mv = torch.empty((int(mv_ptr[-1]), self.config.hidden_size), device=dev,
+                             dtype=torch.float32 if self.precision == "fp32" else torch.bfloat16)
+        cnt = torch.zeros(n, dtype=torch.long)
+        chunks = []
+        for batch, ids, mask in self._padded_batches(seqs, batch_tokens):
+            e, _, m, lp, li, lw = self.encode_tokens_m3(ids, mask, unused)
             emb[torch.tensor(batch, device=dev)] = e
-            dest = torch.cat([torch.arange(int(mv_ptr[j]), int(mv_ptr[j + 1])) for j in batch]).to(dev)
-            mv[dest] = m                                           # the batch's rows, each sequence to its place
-        return emb, mv_ptr.to(dev), mv
+            if mv is not None:
+                mv[torch.cat([torch.arange(int(mv_ptr[j]), int(mv_ptr[j + 1])) for j in batch]).to(dev)] = m
+            cnt[torch.tensor(batch)] = (lp[1:] - lp[:-1]).cpu()
+            chunks.append((batch, li, lw))
+        lex_ptr = torch.zeros(n + 1, dtype=torch.long)
+        lex_ptr[1:] = torch.cumsum(cnt, 0)
+        lex_ids = torch.empty(int(lex_ptr[-1]), dtype=torch.int32, device=dev)
+        lex_w = torch.empty(int(lex_ptr[-1]), dtype=torch.float32, device=dev)
+        for batch, li, lw in chunks:                               # a chunk's terms, each sequence to its place
+            dest = torch.cat([torch.arange(int(lex_ptr[j]), int(lex_ptr[j + 1])) for j in batch]).to(dev)
+            lex_ids[dest], lex_w[dest] = li, lw.to(torch.float32)
+        return emb, mv_ptr.to(dev), mv, lex_ptr.to(dev), lex_ids, lex_w
 
     def encode_unpadded(self, ptr: torch.Tensor, ids: torch.Tensor, batch_size: Optional[int] = None,
                         batch_tokens: int = DEFAULT_BATCH_TOKENS, normalize: bool = True) -> torch.Tensor:

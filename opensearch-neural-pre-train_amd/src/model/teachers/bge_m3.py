@@ -10,9 +10,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from snx.teacher import DEFAULT_BATCH_TOKENS, TeacherEncoder, maxsim_pairs, maxsim_pairs_torch
+from snx.teacher import (DEFAULT_BATCH_TOKENS, TeacherEncoder, lexical_pairs, lexical_pairs_torch, maxsim_pairs,
+                         maxsim_pairs_torch)
 
-SCORE_MODES = ("dense", "colbert", "dense+colbert")
+SCORE_MODES = ("dense", "colbert", "dense+colbert", "sparse", "dense+sparse", "sparse+colbert", "dense+sparse+colbert")
 
 
 def combine_scores(dense, colbert, weights: Tuple[float, float] = (1.0, 1.0)):
@@ -21,6 +22,38 @@ def combine_scores(dense, colbert, weights: Tuple[float, float] = (1.0, 1.0)):
     if w_dense < 0 or w_colbert < 0 or w_dense + w_colbert <= 0:
         raise ValueError("combine_scores: the weights must be non-negative and not both zero")
     return (w_dense * dense + w_colbert * colbert) / (w_dense + w_colbert)
+
+
+def combine_modes(scores: Dict[str, torch.Tensor], weights: Dict[str, float]):
+    """The weighted mean of the teacher scores present: sum_m weights[m] * scores[m] / sum_m weights[m] over the modes m of
+    ``scores`` ("dense", "sparse", "colbert"); ``combine_scores``' weight rules: non-negative, not all zero."""
+    if not scores or any(m not in weights for m in scores):
+        raise ValueError("combine_modes: every score needs a weight, and there must be one score at least")
+    w = {m: float(weights[m]) for m in scores}
+    if any(v < 0 for v in w.values()) or sum(w.values()) <= 0:
+        raise ValueError("combine_modes: the weights must be non-negative and not all zero")
+    return sum(w[m] * scores[m] for m in scores) / sum(w.values())
+
+
+def mode_weights(weights, pair: bool = False):
+    """``get_ranking_scores``' ``weights`` as ``combine_modes``' dict: (w_dense, w_colbert), (w_dense, w_sparse, w_colbert) or
+    a dict by mode, a missing weight 1.  ``pair``: as ``combine_scores``' (w_dense, w_colbert) instead."""
+    if isinstance(weights, dict):
+        w = {m: float(weights.get(m, 1.0)) for m in ("dense", "sparse", "colbert")}
+    elif len(weights) == 3:
+        w = {"dense": float(weights[0]), "sparse": float(weights[1]), "colbert": float(weights[2])}
+    elif len(weights) == 2:
+        w = {"dense": float(weights[0]), "sparse": 1.0, "colbert": float(weights[1])}
+    else:
+        raise ValueError("weights: (w_dense, w_colbert), (w_dense, w_sparse, w_colbert) or a dict by mode")
+    return (w["dense"], w["colbert"]) if pair else w
+
+
+def lexical_scores(lex_ptr, ids: torch.Tensor, w: torch.Tensor, pair_q, pair_d) -> torch.Tensor:
+    """The native scorer for lexical weights on a GPU; a CPU encoder's go through the float64 restatement."""
+    if w.device.type == "cuda":
+        return lexical_pairs(lex_ptr, ids, w, pair_q, pair_d)
+    return lexical_pairs_torch(lex_ptr, ids, w, pair_q, pair_d).to(torch.float32)
 
 
 def maxsim_scores(mv: torch.Tensor, mv_ptr, pair_q, pair_d) -> torch.Tensor:
@@ -85,10 +118,12 @@ class BGEM3Teacher(nn.Module):
 
     @torch.no_grad()
     def get_ranking_scores(self, queries: List[str], documents: List[str], batch_size: int = 32, mode: str = "dense",
-                           weights: Tuple[float, float] = (1.0, 1.0)) -> torch.Tensor:
+                           weights=(1.0, 1.0)) -> torch.Tensor:
         """Teacher scores of query-document pairs [num_pairs].  ``mode``: "dense" (the CLS cosine, the reference's
-        score), "colbert" (MaxSim over the multi-vector rows) or "dense+colbert" (``combine_scores`` with ``weights`` =
-        (w_dense, w_colbert)); the last two need a model directory with ``colbert_linear.pt``."""
+        score), "colbert" (MaxSim over the multi-vector rows), "sparse" (lexical matching over the lexical weights) or
+        several joined by "+": their weighted mean.  ``weights``: (w_dense, w_colbert), (w_dense, w_sparse, w_colbert) or a
+        dict by mode; a weight that is not given is 1.  The colbert modes need a model directory with
+        ``colbert_linear.pt``, the sparse modes one with ``sparse_linear.pt``."""
         assert len(queries) == len(documents), "Must have same number of queries and docs"
         if mode not in SCORE_MODES:
             raise ValueError(f"get_ranking_scores: mode must be one of {SCORE_MODES}")
@@ -98,11 +133,43 @@ class BGEM3Teacher(nn.Module):
             return (query_embeds * doc_embeds).sum(dim=-1)
         n = len(queries)
         pair_q, pair_d = torch.arange(n), torch.arange(n, 2 * n)
-        emb, mv_ptr, mv = self.encode_multivector(list(queries) + list(documents))
-        colbert = maxsim_scores(mv, mv_ptr, pair_q, pair_d)
-        if mode == "colbert":
-            return colbert
-        return combine_scores((emb[:n] * emb[n:]).sum(dim=-1), colbert, weights)
+        if "sparse" not in mode:
+            emb, mv_ptr, mv = self.encode_multivector(list(queries) + list(documents))
+            colbert = maxsim_scores(mv, mv_ptr, pair_q, pair_d)
+            if mode == "colbert":
+                return colbert
+            return combine_scores((emb[:n] * emb[n:]).sum(dim=-1), colbert, mode_weights(weights, pair=True))
+        if "colbert" in mode and not self.model.has_multivector:
+            raise ValueError("teacher: this encoder has no multi-vector head (no colbert_linear.pt in the model directory)")
+        emb, mv_ptr, mv, lex_ptr, lex_ids, lex_w = self.encode_m3(list(queries) + list(documents))
+        scores = {"sparse": lexical_scores(lex_ptr, lex_ids, lex_w, pair_q, pair_d)}
+        if "dense" in mode:
+            scores["dense"] = (emb[:n] * emb[n:]).sum(dim=-1)
+        if "colbert" in mode:
+            scores["colbert"] = maxsim_scores(mv, mv_ptr, pair_q, pair_d)
+        return combine_modes(scores, mode_weights(weights))
+
+    @torch.no_grad()
+    def encode_m3(self, texts: List[str]):
+        """Texts -> (dense embeddings, mv_ptr, multi-vector rows | None, lex_ptr, lex_ids, lex_w) of one forward
+        (``TeacherEncoder.encode_m3``)."""
+        return self.model.encode_m3(texts, self.tokenizer, max_length=self.max_length, batch_tokens=self.batch_tokens)
+
+    @torch.no_grad()
+    def compute_lexical_scores(self, queries: List[str], documents_per_query: List[List[str]]) -> List[torch.Tensor]:
+        """Lexical matching scores: per query one fp32 tensor [len(documents_per_query[i])].  Every distinct text is
+        encoded once."""
+        assert len(queries) == len(documents_per_query), "Must have one document list per query"
+        row: Dict[str, int] = {}
+        for t in list(queries) + [d for docs in documents_per_query for d in docs]:
+            row.setdefault(t, len(row))
+        pairs = [(row[q], row[d]) for q, docs in zip(queries, documents_per_query) for d in docs]
+        if not pairs:
+            return [torch.zeros(0, device=self.model.device) for _ in queries]
+        _, _, _, lex_ptr, lex_ids, lex_w = self.encode_m3(list(row))
+        scores = lexical_scores(lex_ptr, lex_ids, lex_w, torch.tensor([p[0] for p in pairs]),
+                                torch.tensor([p[1] for p in pairs]))
+        return list(torch.split(scores, [len(docs) for docs in documents_per_query]))
 
     @torch.no_grad()
     def encode_multivector(self, texts: List[str]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

@@ -10,12 +10,14 @@
         --input-pattern "data/v29.0_kd/train_*.jsonl" --output-dir data/v30.0_multi_neg --k 7 --rank-start 10 --rank-end 50 \\
         [--index flat|flat2|ivf|graph --expansion 4 --no-exact --nlist 100 --nprobe 1 --degree 32 --ef 0]
     python -m src.train.cli.teacher_scores score-mv --model-dir /models/bge-m3 --input-pattern "data/v29.0/train_*.jsonl" \\
-        --output-dir data/v29.0_kd_mv [--mode colbert|dense+colbert --dense-weight 1 --colbert-weight 1] [--max-length 256] \\
+        --output-dir data/v29.0_kd_mv [--mode colbert|dense+colbert|sparse|dense+sparse|sparse+colbert|dense+sparse+colbert] \\
+        [--dense-weight 1 --sparse-weight 1 --colbert-weight 1] [--max-length 256] \\
         [--batch-tokens 16384] [--chunk-records 256] [--precision bf16|fp32] [--tokenizer gpu:DIR|unigram:DIR]
 
 ``score-mv`` writes ``score``'s fields from BGE-M3's multi-vector (MaxSim) scores, computed straight behind the forward
 chunk by chunk (src.train.mining.multivector, csrc/maxsim.hip); it needs ``colbert_linear.pt`` in ``--model-dir`` and keeps
-no cache.  ``encode`` is the encoder of ref:scripts/precompute_teacher_scores.py:49-159 (unique texts in first-occurrence order, BGE-M3
+no cache.  A ``--mode`` with ``sparse`` adds BGE-M3's lexical matching score of the same forward (csrc/teacher_lex.hip) and
+needs ``sparse_linear.pt``; ``sparse`` and ``dense+sparse`` need no ``colbert_linear.pt``.  ``encode`` is the encoder of ref:scripts/precompute_teacher_scores.py:49-159 (unique texts in first-occurrence order, BGE-M3
 dense embeddings, L2-normalised) on the native XLM-RoBERTa forward; it writes ``embeddings.npy`` / ``text_index.json``.  A
 sharded run (one process per GPU, ``--num-shards n --shard-index i``) writes ``embeddings.part{i}.npy`` and ``--merge`` joins
 them.  ``score`` is the rest of that script (it reads the cache); ``mine`` is ref:scripts/mine_multi_negatives.py.  Flags
@@ -93,8 +95,10 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     sp.add_argument("--chunk-records", type=int, default=256, help="records per forward-and-score round")
     sp.add_argument("--precision", choices=("bf16", "fp32"), default="bf16")
     sp.add_argument("--tokenizer", type=str, default=None, help="gpu:DIR or unigram:DIR, as for encode")
-    sp.add_argument("--mode", choices=("colbert", "dense+colbert"), default="colbert")
+    sp.add_argument("--mode", choices=("colbert", "dense+colbert", "sparse", "dense+sparse", "sparse+colbert",
+                                       "dense+sparse+colbert"), default="colbert")
     sp.add_argument("--dense-weight", type=float, default=1.0)
+    sp.add_argument("--sparse-weight", type=float, default=1.0)
     sp.add_argument("--colbert-weight", type=float, default=1.0)
     sp.add_argument("--device", type=str, default="cuda:0")
     args = ap.parse_args(argv)
@@ -103,6 +107,9 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             ap.error("need --max-length >= 2, --batch-tokens >= 1, --chunk-records >= 1")
         if args.dense_weight < 0 or args.colbert_weight < 0 or args.dense_weight + args.colbert_weight <= 0:
             ap.error("need non-negative --dense-weight and --colbert-weight, not both zero")
+        used = [getattr(args, f"{m}_weight") for m in args.mode.split("+")]
+        if args.sparse_weight < 0 or sum(used) <= 0:
+            ap.error("need a non-negative --sparse-weight, and a positive weight among the modes of --mode")
         if args.tokenizer is not None and not args.tokenizer.startswith(("gpu:", "unigram:")):
             ap.error("--tokenizer must be gpu:DIR or unigram:DIR")
     if args.command == "encode":
@@ -148,8 +155,9 @@ def encode_main(args: argparse.Namespace, tokenizer=None):
 
 
 def score_mv_main(args: argparse.Namespace, tokenizer=None) -> int:
-    """``score-mv``: MaxSim teacher scores straight from the encoder (src.train.mining.multivector); the records scored."""
-    from src.model.teachers.bge_m3 import maxsim_scores
+    """``score-mv``: MaxSim and lexical teacher scores straight from the encoder (src.train.mining.multivector); the
+    records scored."""
+    from src.model.teachers.bge_m3 import lexical_scores, maxsim_scores
     from src.model.teachers import BGEM3Teacher
     from src.train.mining import copy_val_files, expand_files
     from src.train.mining.multivector import write_multivector_scores
@@ -159,10 +167,15 @@ def score_mv_main(args: argparse.Namespace, tokenizer=None) -> int:
     teacher = BGEM3Teacher(args.model_dir, device=args.device, max_length=args.max_length, normalize_embeddings=True,
                            tokenizer=tokenizer if tokenizer is not None else args.tokenizer, precision=args.precision,
                            batch_tokens=args.batch_tokens)
-    if not teacher.model.has_multivector:
+    sparse = "sparse" in args.mode
+    if "colbert" in args.mode and not teacher.model.has_multivector:
         raise FileNotFoundError(f"{args.model_dir} has no colbert_linear.pt: score-mv needs the multi-vector head")
-    out = write_multivector_scores(files, args.output_dir, teacher.encode_multivector, maxsim_scores, mode=args.mode,
-                                   weights=(args.dense_weight, args.colbert_weight), chunk_records=args.chunk_records)
+    if sparse and not teacher.model.has_sparse:
+        raise FileNotFoundError(f"{args.model_dir} has no sparse_linear.pt: score-mv --mode {args.mode} needs the sparse head")
+    out = write_multivector_scores(files, args.output_dir, teacher.encode_m3 if sparse else teacher.encode_multivector,
+                                   maxsim_scores, mode=args.mode,
+                                   weights=(args.dense_weight, args.sparse_weight, args.colbert_weight),
+                                   chunk_records=args.chunk_records, lex_scorer=lexical_scores)
     logger.info(f"scored {out} record(s) of {len(files)} file(s) into {args.output_dir} ({args.mode})")
     copy_val_files([args.val_pattern], args.output_dir)
     return out

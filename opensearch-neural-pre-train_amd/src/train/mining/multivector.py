@@ -1,10 +1,12 @@
-"""Multi-vector (MaxSim) teacher scores for the records of a training set, straight from the encoder.
+"""Multi-vector (MaxSim) and lexical teacher scores for the records of a training set, straight from the encoder.
 
 ``write_teacher_scores`` (dense.py) reads single vectors from a cache on disk.  A multi-vector cannot be cached that way (a
 256-token text is 512 KB in bf16), so here the scorer sits directly behind the forward: per chunk of records the chunk's
 unique texts are encoded once (``encode_mv``: ``BGEM3Teacher.encode_multivector``), the (query, positive) and (query,
 negative) pairs are scored over that store (``scorer``: ``snx.teacher.maxsim_pairs``) and the store is dropped.  The dense
-score of ``mode="dense+colbert"`` is the CLS cosine of the same forward.  The fields written are those of
+score of ``mode="dense+colbert"`` is the CLS cosine of the same forward.  A mode with "sparse" takes all its scores from one
+forward too: ``encode_mv`` is then ``BGEM3Teacher.encode_m3`` and ``lex_scorer`` (``snx.teacher.lexical_pairs``) scores the
+lexical weights.  The fields written are those of
 ``write_teacher_scores`` -- ``teacher_pos_score``, ``teacher_neg_score`` and, for a record with ``negatives[]``,
 ``teacher_neg_scores``, each round(float(s), 6) -- so the trainer reads the output unchanged.  A record without a string
 query and positive is written unchanged; a missing negative scores 0.0."""
@@ -12,15 +14,18 @@ from __future__ import annotations
 
 import json
 import os
-from typing import Callable, Dict, List, Sequence, Tuple
+from typing import Callable, Dict, List, Optional, Sequence
 
 from .dense import _r6, _read
 
+MV_MODES = ("colbert", "dense+colbert", "sparse", "dense+sparse", "sparse+colbert", "dense+sparse+colbert")
 
-def _score_chunk(items: List[dict], encode_mv: Callable, scorer: Callable, mode: str, weights: Tuple[float, float]) -> int:
+
+def _score_chunk(items: List[dict], encode_mv: Callable, scorer: Callable, mode: str, weights,
+                 lex_scorer: Optional[Callable] = None) -> int:
     """Adds the score fields to the scoreable records of ``items`` in place; returns how many there were."""
     import torch
-    from src.model.teachers.bge_m3 import combine_scores
+    from src.model.teachers.bge_m3 import combine_modes, combine_scores, mode_weights
     row: Dict[str, int] = {}
     pair_q: List[int] = []
     pair_d: List[int] = []
@@ -42,12 +47,24 @@ def _score_chunk(items: List[dict], encode_mv: Callable, scorer: Callable, mode:
         plan.append((pair(q, item["positive"]), pair(q, item.get("negative")), [pair(q, n) for n in negs]))
     if not pair_q:
         return 0
-    emb, mv_ptr, mv = encode_mv(list(row))
     pq, pd = torch.tensor(pair_q), torch.tensor(pair_d)
-    scores = scorer(mv, mv_ptr, pq, pd).to(torch.float32)
-    if mode == "dense+colbert":
-        dense = (emb[pq.to(emb.device)] * emb[pd.to(emb.device)]).sum(dim=-1)
-        scores = combine_scores(dense.to(scores.device), scores, weights)
+
+    def dense_of(emb):
+        return (emb[pq.to(emb.device)] * emb[pd.to(emb.device)]).sum(dim=-1)
+
+    if "sparse" in mode:
+        emb, mv_ptr, mv, lex_ptr, lex_ids, lex_w = encode_mv(list(row))
+        by_mode = {"sparse": lex_scorer(lex_ptr, lex_ids, lex_w, pq, pd).to(torch.float32)}
+        if "dense" in mode:
+            by_mode["dense"] = dense_of(emb).to(by_mode["sparse"].device)
+        if "colbert" in mode:
+            by_mode["colbert"] = scorer(mv, mv_ptr, pq, pd).to(torch.float32).to(by_mode["sparse"].device)
+        scores = combine_modes(by_mode, mode_weights(weights))
+    else:
+        emb, mv_ptr, mv = encode_mv(list(row))
+        scores = scorer(mv, mv_ptr, pq, pd).to(torch.float32)
+        if mode == "dense+colbert":
+            scores = combine_scores(dense_of(emb).to(scores.device), scores, mode_weights(weights, pair=True))
     scores = scores.cpu().tolist()
     done = 0
     for item, pl in zip(items, plan):
@@ -63,14 +80,18 @@ def _score_chunk(items: List[dict], encode_mv: Callable, scorer: Callable, mode:
 
 
 def write_multivector_scores(input_files: Sequence[str], output_dir: str, encode_mv: Callable, scorer: Callable,
-                             mode: str = "colbert", weights: Tuple[float, float] = (1.0, 1.0),
-                             chunk_records: int = 256) -> int:
-    """MaxSim teacher scores for every record of ``input_files`` (one output file per shard, same name), ``chunk_records``
+                             mode: str = "colbert", weights=(1.0, 1.0), chunk_records: int = 256,
+                             lex_scorer: Optional[Callable] = None) -> int:
+    """Teacher scores for every record of ``input_files`` (one output file per shard, same name), ``chunk_records``
     records per forward-and-score round.  ``encode_mv(texts) -> (emb [n, H], mv_ptr [n + 1], mv [rows, H])``;
     ``scorer(mv, mv_ptr, pair_q, pair_d) -> [npairs]``.  ``mode``: "colbert", or "dense+colbert" with ``weights`` =
-    (w_dense, w_colbert).  Returns the records scored."""
-    if mode not in ("colbert", "dense+colbert"):
-        raise ValueError("multi-vector scores: mode is 'colbert' or 'dense+colbert'")
+    (w_dense, w_colbert).  A mode with "sparse" ("sparse", "dense+sparse", "sparse+colbert", "dense+sparse+colbert"):
+    ``encode_mv(texts)`` returns ``encode_m3``'s six values, ``lex_scorer(lex_ptr, ids, w, pair_q, pair_d) -> [npairs]``
+    is required and ``weights`` may be (w_dense, w_sparse, w_colbert) or a dict by mode.  Returns the records scored."""
+    if mode not in MV_MODES:
+        raise ValueError(f"multi-vector scores: mode is one of {MV_MODES}")
+    if "sparse" in mode and lex_scorer is None:
+        raise ValueError("multi-vector scores: a sparse mode needs lex_scorer")
     if int(chunk_records) < 1:
         raise ValueError("multi-vector scores: chunk_records must be positive")
     os.makedirs(output_dir, exist_ok=True)
@@ -80,7 +101,7 @@ def write_multivector_scores(input_files: Sequence[str], output_dir: str, encode
         with open(os.path.join(output_dir, os.path.basename(path)), "w", encoding="utf-8") as fout:
             for at in range(0, len(items), int(chunk_records)):
                 chunk = items[at:at + int(chunk_records)]
-                total += _score_chunk(chunk, encode_mv, scorer, mode, weights)
+                total += _score_chunk(chunk, encode_mv, scorer, mode, weights, lex_scorer)
                 for item in chunk:
                     fout.write(json.dumps(item, ensure_ascii=False) + "\n")
     return total
