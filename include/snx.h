@@ -694,6 +694,36 @@ int snx_dense_search_band(const float* Q, int32_t nq, const float* E, int32_t nd
 int snx_dense_pair_scores(const float* Q, int32_t nq, const float* E, int32_t nd, int32_t D, const int32_t* pair_q,
                           const int32_t* pair_d, int64_t npairs, float* out, hipStream_t stream);
 
+/* ---- multi-vector search (csrc/mv_search.hip): exact MaxSim top-k of every query against every document of a ragged
+ * multi-vector store -- the search that goes with snx_maxsim_pairs, which scores pairs the caller already knows.
+ * Operands: document rows docs [drows, D] with doc_ptr [nd + 1], query rows q [qrows, D] with q_ptr [nq + 1]; both fp32
+ * (mv_f32 != 0) or both bf16, 16-byte aligned, on the device; D % 64 == 0 and D <= 1024, else SNX_E_SHAPE.  doc_ptr and
+ * q_ptr are pageable HOST arrays under the lifetime rule of snx_maxsim_pairs: checked here before the first launch
+ * (SNX_E_ARG: not ascending from 0, past the rows, a query without rows) and copied into the workspace on the stream.
+ * Score (part of the ABI): s(q, d) is bit for bit what snx_maxsim_pairs returns for the two sequences -- the same MFMA
+ * per precision with k ascending, the max over the document's rows, the row maxima added in ascending row order within
+ * each run of 64 query rows counted from the query's first row, the run sums added in ascending order, one division by
+ * Lq.  It does not depend on the other queries or documents of the call, on chunk_docs or on the launch.
+ * Order: snx_dense_search's -- score descending, ties lowest doc id first; every document WITH rows is a candidate
+ * whatever the sign of its score, a document without rows is never returned; unused slots doc -1, score 0.
+ * snx_mv_search: the top k (1 <= k <= 1024) -> out_doc / out_score [nq, k].  snx_mv_search_band: ranks lo .. hi-1
+ * (0 <= lo < hi <= 1024) of the documents not in the query's exclusion row (ex_ptr [nq + 1] / ex_doc on the device, rows
+ * ascending, as for snx_dense_search_band; ex_ptr NULL: none) -> out_doc / out_score [nq, hi - lo], out_found [nq] =
+ * filled slots.  chunk_docs: documents per chunk of the walk (0: default; otherwise 64 .. 8192); it changes no bit.
+ * workspace: snx_mv_search_workspace_bytes(q_ptr, nq, nd, drows, hi, chunk_docs) bytes (0 for arguments the search would
+ * refuse); it holds a row-to-document map, the partial sums of a bounded group of chunks and hi candidates per (query,
+ * chunk) -- nothing of size nq x nd. */
+size_t snx_mv_search_workspace_bytes(const int64_t* q_ptr /*[host]*/, int32_t nq, int32_t nd, int64_t drows, int32_t hi,
+                                     int32_t chunk_docs);
+int snx_mv_search(const void* docs, const void* q, int32_t mv_f32, int32_t D, int64_t drows, const int64_t* doc_ptr /*[host]*/,
+                  int32_t nd, int64_t qrows, const int64_t* q_ptr /*[host]*/, int32_t nq, int32_t k, int32_t chunk_docs,
+                  int32_t* out_doc, float* out_score, void* workspace, size_t ws_bytes, hipStream_t stream);
+int snx_mv_search_band(const void* docs, const void* q, int32_t mv_f32, int32_t D, int64_t drows,
+                       const int64_t* doc_ptr /*[host]*/, int32_t nd, int64_t qrows, const int64_t* q_ptr /*[host]*/,
+                       int32_t nq, const int64_t* ex_ptr, const int32_t* ex_doc, int32_t lo, int32_t hi, int32_t chunk_docs,
+                       int32_t* out_doc, float* out_score, int32_t* out_found, void* workspace, size_t ws_bytes,
+                       hipStream_t stream);
+
 /* ---- two-phase dense retrieval (csrc/dense_two_phase.hip): the result of the exact dense section with most of the work
  * on the bf16 MFMA.  Phase 1 scores bf16 copies of the operands and proposes k1 candidates per query; phase 2 scores the
  * candidates by the exact section's chain on the fp32 operands; a per-query certificate proves, from norms computed once,

@@ -13,7 +13,13 @@
         --output-dir data/v29.0_kd_mv [--mode colbert|dense+colbert|sparse|dense+sparse|sparse+colbert|dense+sparse+colbert] \\
         [--dense-weight 1 --sparse-weight 1 --colbert-weight 1] [--max-length 256] \\
         [--batch-tokens 16384] [--chunk-records 256] [--precision bf16|fp32] [--tokenizer gpu:DIR|unigram:DIR]
+    python -m src.train.cli.teacher_scores mine-mv --model-dir /models/bge-m3 --input-pattern "data/v29.0_kd/train_*.jsonl" \\
+        --output-dir data/v30.0_mv_neg [--k 7 --rank-start 10 --rank-end 50 --max-length 256 --precision bf16]
 
+``mine-mv`` mines hard negatives under the multi-vector teacher (src.train.mining.multivector.mine_multivector_negatives): the
+unique positives of the shards are encoded into an ``snx.retrieval.MultiVectorIndex`` (csrc/mv_search.hip), every query is
+searched exactly under MaxSim, and ranks [--rank-start, --rank-end) of its non-positives become the record's negatives.  It
+prints one JSON line of counts, the store's rows and bytes among them.
 ``score-mv`` writes ``score``'s fields from BGE-M3's multi-vector (MaxSim) scores, computed straight behind the forward
 chunk by chunk (src.train.mining.multivector, csrc/maxsim.hip); it needs ``colbert_linear.pt`` in ``--model-dir`` and keeps
 no cache.  A ``--mode`` with ``sparse`` adds BGE-M3's lexical matching score of the same forward (csrc/teacher_lex.hip) and
@@ -101,7 +107,30 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     sp.add_argument("--sparse-weight", type=float, default=1.0)
     sp.add_argument("--colbert-weight", type=float, default=1.0)
     sp.add_argument("--device", type=str, default="cuda:0")
+    sp = sub.add_parser("mine-mv", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    sp.add_argument("--model-dir", type=str, required=True,
+                    help="local HF directory of the teacher, with colbert_linear.pt (never a model name)")
+    sp.add_argument("--input-pattern", type=str, default="data/v29.0_kd/train_*.jsonl")
+    sp.add_argument("--val-pattern", type=str, default="data/v29.0_kd/val.jsonl")
+    sp.add_argument("--output-dir", type=str, default="data/v30.0_mv_neg")
+    sp.add_argument("--k", type=int, default=7, help="hard negatives per record")
+    sp.add_argument("--rank-start", type=int, default=10)
+    sp.add_argument("--rank-end", type=int, default=50)
+    sp.add_argument("--max-length", type=int, default=256)
+    sp.add_argument("--batch-tokens", type=int, default=16384, help="token rows per forward")
+    sp.add_argument("--chunk-texts", type=int, default=256, help="texts per encoder call")
+    sp.add_argument("--chunk-docs", type=int, default=0)
+    sp.add_argument("--precision", choices=("bf16", "fp32"), default="bf16")
+    sp.add_argument("--tokenizer", type=str, default=None, help="gpu:DIR or unigram:DIR, as for encode")
+    sp.add_argument("--device", type=str, default="cuda:0")
     args = ap.parse_args(argv)
+    if args.command == "mine-mv":
+        if args.k < 1 or not 0 <= args.rank_start < args.rank_end <= 1024:
+            ap.error("need --k >= 1 and 0 <= --rank-start < --rank-end <= 1024")
+        if args.max_length < 2 or args.batch_tokens < 1 or args.chunk_texts < 1:
+            ap.error("need --max-length >= 2, --batch-tokens >= 1, --chunk-texts >= 1")
+        if args.tokenizer is not None and not args.tokenizer.startswith(("gpu:", "unigram:")):
+            ap.error("--tokenizer must be gpu:DIR or unigram:DIR")
     if args.command == "score-mv":
         if args.max_length < 2 or args.batch_tokens < 1 or args.chunk_records < 1:
             ap.error("need --max-length >= 2, --batch-tokens >= 1, --chunk-records >= 1")
@@ -181,6 +210,30 @@ def score_mv_main(args: argparse.Namespace, tokenizer=None) -> int:
     return out
 
 
+def mine_mv_main(args: argparse.Namespace, tokenizer=None) -> dict:
+    """``mine-mv``: hard negatives from the exact MaxSim search (src.train.mining.multivector); the counts, also printed
+    as one JSON line."""
+    from snx.retrieval import MultiVectorIndex
+    from src.model.teachers import BGEM3Teacher
+    from src.train.mining import copy_val_files, expand_files
+    from src.train.mining.multivector import mine_multivector_negatives
+    files = expand_files([args.input_pattern])
+    if not files:
+        raise FileNotFoundError(f"no input files match {args.input_pattern!r}")
+    teacher = BGEM3Teacher(args.model_dir, device=args.device, max_length=args.max_length, normalize_embeddings=True,
+                           tokenizer=tokenizer if tokenizer is not None else args.tokenizer, precision=args.precision,
+                           batch_tokens=args.batch_tokens)
+    if not teacher.model.has_multivector:
+        raise FileNotFoundError(f"{args.model_dir} has no colbert_linear.pt: mine-mv needs the multi-vector head")
+    index = MultiVectorIndex(teacher.model.config.hidden_size, args.device)
+    out = mine_multivector_negatives(files, args.output_dir, teacher.encode_multivector, index, k=args.k,
+                                     rank_start=args.rank_start, rank_end=args.rank_end, chunk_texts=args.chunk_texts,
+                                     chunk_docs=args.chunk_docs)
+    print(json.dumps(out))
+    copy_val_files([args.val_pattern], args.output_dir)
+    return out
+
+
 def main(argv: Optional[List[str]] = None, tokenizer=None):
     args = parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s [%(levelname)s] %(message)s")
@@ -188,6 +241,8 @@ def main(argv: Optional[List[str]] = None, tokenizer=None):
         return encode_main(args, tokenizer)
     if args.command == "score-mv":
         return score_mv_main(args, tokenizer)
+    if args.command == "mine-mv":
+        return mine_mv_main(args, tokenizer)
     import torch
     from snx.retrieval import DenseIndex, GraphIndex, IvfFlatIndex
     from src.train.mining import copy_val_files, expand_files

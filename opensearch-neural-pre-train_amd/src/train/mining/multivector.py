@@ -105,3 +105,86 @@ def write_multivector_scores(input_files: Sequence[str], output_dir: str, encode
                 for item in chunk:
                     fout.write(json.dumps(item, ensure_ascii=False) + "\n")
     return total
+
+
+def mine_multivector_negatives(input_files: Sequence[str], output_dir: str, encode_mv: Callable, index, *, k: int = 7,
+                               rank_start: int = 10, rank_end: int = 50, chunk_texts: int = 256,
+                               chunk_docs: int = 0) -> Dict:
+    """Hard negatives under the late-interaction teacher: per record ``k`` negatives from ranks [rank_start, rank_end) of
+    the MaxSim search of its query over the corpus, the unique positives of the shards, with the query's own positives
+    (all of them, over every record of the query) excluded before ranking.  ``encode_mv(texts) -> (emb, mv_ptr, mv)``
+    (``BGEM3Teacher.encode_multivector``) encodes the corpus ``chunk_texts`` texts at a time into ``index``, an empty
+    ``snx.retrieval.MultiVectorIndex`` or a stand-in with its ``add`` / ``build`` / ``search_band`` / ``pair_scores``, and
+    then the queries.  The records written are ``mine_dense_negatives``': ``negatives[]``, ``teacher_pos_score``,
+    ``teacher_neg_scores`` (the MaxSim values, rounded to 6) and the meta keys; a short band repeats its last negative.  A
+    record without a string query and positive, with a query of one token or with an empty band is written unchanged.
+    Returns the counts: records, queries, docs, store_rows, store_bytes, band_fill, padded, unchanged."""
+    import torch
+    from . import META_KEYS
+    k, rank_start, rank_end, chunk_texts = int(k), int(rank_start), int(rank_end), int(chunk_texts)
+    if k < 1 or not 0 <= rank_start < rank_end <= 1024 or chunk_texts < 1:
+        raise ValueError("multi-vector mining: need k >= 1, 0 <= rank_start < rank_end <= 1024 and chunk_texts >= 1")
+    files = sorted(input_files)
+    shards = [_read(f) for f in files]
+    docs: Dict[str, int] = {}
+    queries: Dict[str, int] = {}
+    positives: List[set] = []
+    for items in shards:
+        for item in items:
+            if isinstance(item, dict) and isinstance(item.get("query"), str) and isinstance(item.get("positive"), str):
+                q = queries.setdefault(item["query"], len(queries))
+                if q == len(positives):
+                    positives.append(set())
+                positives[q].add(docs.setdefault(item["positive"], len(docs)))
+    doc_texts, query_texts = list(docs), list(queries)
+    rows = nbytes = 0
+    for s in range(0, len(doc_texts), chunk_texts):
+        _, ptr, mv = encode_mv(doc_texts[s:s + chunk_texts])
+        index.add(mv, ptr)
+        rows += int(mv.shape[0])
+        nbytes += int(mv.shape[0]) * int(mv.shape[1]) * mv.element_size()
+    index.build()
+    bands: Dict[int, List] = {}                                  # query -> [(doc, score)] in rank order
+    pscore: Dict = {}                                            # (query, positive) -> score
+    fill = 0
+    for s in range(0, len(query_texts), chunk_texts):
+        _, ptr, mv = encode_mv(query_texts[s:s + chunk_texts])
+        ptr = [int(v) for v in torch.as_tensor(ptr).tolist()]
+        kept = [i for i in range(len(ptr) - 1) if ptr[i + 1] > ptr[i]]   # a query of one token has no row: unchanged
+        if not kept or not doc_texts:
+            continue
+        qptr = [ptr[i] for i in kept] + [ptr[-1]]
+        sc, dd, found = index.search_band(mv, qptr, rank_start, rank_end, exclude=[sorted(positives[s + i]) for i in kept],
+                                          chunk_docs=chunk_docs)
+        sc, dd, found = sc.cpu().tolist(), dd.cpu().tolist(), found.cpu().tolist()
+        pairs = [(j, d) for j, i in enumerate(kept) for d in sorted(positives[s + i])]
+        ps = index.pair_scores(mv, qptr, torch.tensor(pairs, dtype=torch.long, device=mv.device)).cpu().tolist()
+        for (j, d), v in zip(pairs, ps):
+            pscore[(s + kept[j], d)] = v
+        for j, i in enumerate(kept):
+            bands[s + i] = [(dd[j][r], sc[j][r]) for r in range(found[j])]
+            fill += found[j]
+    counts = {"full": 0, "padded": 0, "unchanged": 0}
+    os.makedirs(output_dir, exist_ok=True)
+    for path, items in zip(files, shards):
+        with open(os.path.join(output_dir, os.path.basename(path)), "w", encoding="utf-8") as fout:
+            for item in items:
+                q = queries.get(item.get("query")) if isinstance(item, dict) and isinstance(item.get("query"), str) and \
+                    isinstance(item.get("positive"), str) else None
+                picks = bands.get(q, [])[:k]
+                out, st = item, "unchanged"
+                if picks:
+                    st = "full" if len(picks) >= k else "padded"
+                    picks = picks + [picks[-1]] * (k - len(picks))
+                    out = {"query": item["query"], "positive": item["positive"], "negatives": [doc_texts[d] for d, _ in picks],
+                           "teacher_pos_score": _r6(pscore[(q, docs[item["positive"]])]),
+                           "teacher_neg_scores": [_r6(v) for _, v in picks]}
+                    for key in META_KEYS:
+                        if key in item:
+                            out[key] = item[key]
+                counts[st] += 1
+                fout.write(json.dumps(out, ensure_ascii=False) + "\n")
+    nb = len(bands)
+    return {"records": sum(len(x) for x in shards), "queries": len(queries), "docs": len(docs), "store_rows": rows,
+            "store_bytes": nbytes, "band_fill": float(fill / (nb * (rank_end - rank_start))) if nb else 0.0,
+            "padded": counts["padded"], "unchanged": counts["unchanged"]}
