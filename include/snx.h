@@ -724,6 +724,38 @@ int snx_mv_search_band(const void* docs, const void* q, int32_t mv_f32, int32_t 
                        int32_t* out_doc, float* out_score, int32_t* out_found, void* workspace, size_t ws_bytes,
                        hipStream_t stream);
 
+/* ---- multi-vector candidate search (csrc/mv_centroid.hip): a centroid-interaction candidate pass in front of the exact
+ * MaxSim score, after ColBERTv2 / PLAID.  No parity with their centroids or candidate sets is claimed.
+ * Operands: as in the section above, plus centroids [nc, D] in the store's precision (1 <= nc <= 4096, 16-byte aligned, on
+ * the device) and codes [drows] uint16 on the device, 16-byte aligned: the centroid of every document row.
+ * snx_mv_candidates.  S[i, c] = the product of query row i and centroid c on the store's MFMA with k ascending, + 0.0f,
+ * rounded to bf16 (nearest even).  m(i, d) = max over the rows j of d of S[i, codes[j]] (exact).  a(q, d) = the fp32 sum
+ * of m(i, d) over the query's rows i in ascending order, a left fold from +0, divided once by Lq.  Per query the ncand
+ * (1 <= ncand <= 1024) best documents by (a descending, doc ascending) among the documents with rows that are not in the
+ * query's exclusion row (ex_ptr / ex_doc as for snx_mv_search_band) -> cand_doc / cand_score [nq, ncand]; unused slots doc
+ * -1, score 0.  The result is a function of the rows, the centroids, the codes and ncand alone: it does not depend on
+ * chunk_docs (0: default; otherwise 64 .. 8192), on the other queries of the call, on their order or on the launch.
+ * SNX_E_ARG before any search launch: nc or ncand out of range, a code >= nc (found by a kernel over the codes; the call
+ * waits for it on the stream).  workspace: snx_mv_candidates_workspace_bytes(q_ptr, nq, nd, nc, ncand, chunk_docs) bytes
+ * (0 for arguments the call would refuse): the queries' centroid table, the row maxima of a bounded group of chunks and
+ * ncand candidates per (query, chunk) -- nothing of size nq x nd.
+ * snx_mv_rescore.  cand_doc [nq, ncand] on the device (a slot that names no document with rows is skipped).  For every
+ * candidate s(q, d) of the section above, bit for bit, from the document's rows in place in the store; ranks lo .. hi-1
+ * (0 <= lo < hi <= ncand, else SNX_E_ARG) by (s descending, doc ascending) -> out_doc / out_score [nq, hi - lo], unused
+ * slots doc -1, score 0; out_found [nq] = filled slots.  workspace: snx_mv_rescore_workspace_bytes(q_ptr, nq, nd, ncand). */
+size_t snx_mv_candidates_workspace_bytes(const int64_t* q_ptr /*[host]*/, int32_t nq, int32_t nd, int32_t nc, int32_t ncand,
+                                         int32_t chunk_docs);
+int snx_mv_candidates(const uint16_t* codes, int64_t drows, const int64_t* doc_ptr /*[host]*/, int32_t nd,
+                      const void* centroids, int32_t nc, const void* q, int32_t mv_f32, int32_t D, int64_t qrows,
+                      const int64_t* q_ptr /*[host]*/, int32_t nq, const int64_t* ex_ptr, const int32_t* ex_doc,
+                      int32_t ncand, int32_t chunk_docs, int32_t* cand_doc, float* cand_score, void* workspace,
+                      size_t ws_bytes, hipStream_t stream);
+size_t snx_mv_rescore_workspace_bytes(const int64_t* q_ptr /*[host]*/, int32_t nq, int32_t nd, int32_t ncand);
+int snx_mv_rescore(const void* docs, const void* q, int32_t mv_f32, int32_t D, int64_t drows,
+                   const int64_t* doc_ptr /*[host]*/, int32_t nd, int64_t qrows, const int64_t* q_ptr /*[host]*/, int32_t nq,
+                   const int32_t* cand_doc, int32_t ncand, int32_t lo, int32_t hi, int32_t* out_doc, float* out_score,
+                   int32_t* out_found, void* workspace, size_t ws_bytes, hipStream_t stream);
+
 /* ---- two-phase dense retrieval (csrc/dense_two_phase.hip): the result of the exact dense section with most of the work
  * on the bf16 MFMA.  Phase 1 scores bf16 copies of the operands and proposes k1 candidates per query; phase 2 scores the
  * candidates by the exact section's chain on the fp32 operands; a per-query certificate proves, from norms computed once,

@@ -1,0 +1,585 @@
+// Multi-vector candidate search (include/snx.h "multi-vector candidate search"): the centroid-interaction pass of
+// ColBERTv2 / PLAID in front of the exact MaxSim score.  Every document row of the store is replaced by the id of its
+// nearest centroid (a uint16 code); a query scores a document through its own table of query-row x centroid products,
+//
+//   a(q, d) = (1 / Lq) * sum_i max_{j in d} S[i, code[j]],      S[i, c] = bf16(<q_i, centroid_c>),
+//
+// and only the best ncand documents per query go to the exact scorer, which reads them in place from the store.  The
+// candidate pass reads 2 bytes per document row where mv_search.hip reads 2 D.
+//
+// Order keys       A table entry is the bf16 of the product as a 16-bit ORDER KEY: the monotone map of the bf16 bits to a
+//                  signed 16-bit integer (negatives: the low 15 bits flipped).  The max of two entries is then the integer
+//                  max of their keys, and v_pk_max_i16 takes two of them per lane and instruction; the map is its own
+//                  inverse, so the selection decodes the maxima it adds.  The key of -inf stands for "no row".
+// Groups           The query rows of the call lie end to end (mv_search's packing); group g is rows R g .. R g + R - 1 of
+//                  them, whichever queries they belong to.  R = 64 / 32 / 16 for nc <= 1024 / 2048 / 4096, so that a
+//                  group's [nc][R] table is at most 128 KB and stays in LDS for a whole chunk of documents.
+// mvc_table_kernel One workgroup per (64 query rows, 64 centroids): the 64 x 64 tile of S on the store's MFMA with k
+//                  ascending (the operand staging of maxsim.hip), written as keys in the walk's layout [group][nc][R].
+// mvc_walk_kernel  One workgroup (sixteen waves) per (group, chunk of documents), the group the fast grid index.  The
+//                  group's table is copied to LDS once.  R / 8 neighbouring lanes own one document at a time; lane p of
+//                  them owns query rows 8 p .. 8 p + 7 of the group, that is one 128-bit LDS read per code (the lanes of a
+//                  document read one contiguous table row), and keeps their eight running maxima in four registers from the
+//                  document's first code to its last: nothing is carried through memory, whatever the document's length.
+//                  The codes come straight from HBM, 16 aligned bytes (eight codes) per lane and load, the next piece
+//                  requested before the current one is walked; sixteen waves per CU hide the rest of the latency.  (A
+//                  coalesced LDS stage of T codes holds T / Ld documents, so with a document per lane group most groups
+//                  would wait for their tile; the register look-ahead keeps all of them busy.)  When a document ends its
+//                  lanes write the maxima, still as keys, to part[doc][row of the call]: 16 bytes per lane.
+// mvc_select_kernel One workgroup per (query, chunk): a thread adds a document's maxima of the query's rows in ascending
+//                  row order from +0 -- one chain per query, counted from the query's own first row, so that the sum does
+//                  not depend on where the packing put the query -- divides once by Lq, drops documents without rows and
+//                  excluded ones and keeps the chunk's best ncand (dense_key, select_chunk).  mvc_merge_kernel is
+//                  merge_lists over the chunks.
+// mvc_rescore_kernel  ms_pair_kernel's arithmetic, one workgroup per (query, candidate, 64-row run of the query), with
+//                  the query rows read from the query store and the document rows from the index's store through doc_ptr:
+//                  no gather.  It writes the run's sum; mvc_order_kernel (one workgroup per query) adds the runs in
+//                  ascending order, divides by Lq, sorts the candidates by (score descending, doc ascending) and writes
+//                  ranks lo .. hi - 1.  Every bit is snx_maxsim_pairs'.
+// part holds a bounded group of chunks; the host walks the groups on the stream.  Nothing of size nq x nd exists, and
+// there is no float atomic anywhere.
+#include "dense_common.h"
+#include "snx.h"
+
+namespace {
+
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+typedef __attribute__((ext_vector_type(2))) short s16x2;
+
+constexpr int MVC_THREADS = 256;               // table and rescore: four waves, one 32 x 32 accumulator each
+constexpr int MVC_TILE = 64;
+constexpr int MVC_DMAX = 1024;
+constexpr int MVC_NC_MAX = 4096;
+constexpr int MVC_WALK_THREADS = 1024;
+constexpr int MVC_TABLE_BYTES = 128 * 1024;    // a group's table at the largest nc of each R
+constexpr int MVC_CHUNK_MIN = 64, MVC_CHUNK_DEFAULT = 1024, MVC_CHUNK_MAX = 8192;   // docs per chunk (keys in LDS: 32 KB)
+constexpr int MVC_WG_TARGET = 4096;            // workgroups per walk launch that the chunk group aims at
+constexpr size_t MVC_PART_BUDGET = (size_t)128 << 20;   // bytes of maxima per launch, beyond one chunk's
+constexpr uint32_t MVC_NO_ROW = 0x807Fu;       // the key of -inf
+constexpr uint32_t MVC_NO_ROW2 = MVC_NO_ROW | (MVC_NO_ROW << 16);
+
+__host__ __device__ inline int mvc_group_rows(int nc) { return nc <= 1024 ? 64 : (nc <= 2048 ? 32 : 16); }
+
+// fp32 -> the order key of its bf16 (round to nearest even; -0 becomes +0 first), and back: the map is an involution
+__device__ __forceinline__ uint32_t mvc_key(float s) {
+  const uint32_t b = bf16_bits(s + 0.0f);
+  return (b & 0x8000u) ? (b ^ 0x7FFFu) : b;
+}
+__device__ __forceinline__ float mvc_unkey(uint32_t k) { return bits_to_f32((k & 0x8000u) ? (k ^ 0x7FFFu) : k); }
+
+__device__ __forceinline__ uint32_t mvc_max2(uint32_t a, uint32_t b) {       // v_pk_max_i16
+  return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b)));
+}
+
+// The operand staging and the MFMA steps of one precision: MsBf16 / MsF32 of maxsim.hip restated (same slices, same
+// steps, so a score element is the same chain of the same two rows).  fetch: this thread's share of a 64-row K slice
+// (rows t >> 3 and 32 + (t >> 3), 16 bytes each; a row past the count reads as zero); put: registers -> LDS stage; mma:
+// the slice's MFMA steps in ascending k.
+struct MvcBf16 {
+  typedef bf16_t elem;
+  static constexpr int KT = 64, PITCH = 72;
+  struct Stage { uint16_t a[MVC_TILE][PITCH], b[MVC_TILE][PITCH]; };
+  struct Regs { u32x4 v[2]; };
+  __device__ static __forceinline__ void fetch(const elem* __restrict__ P, long row0, int nrows, int D, int k0, int t,
+                                               Regs& r) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int row = (t >> 3) + 32 * i;
+      r.v[i] = row < nrows ? *(const u32x4*)(P + (row0 + row) * D + k0 + (t & 7) * 8) : (u32x4){0u, 0u, 0u, 0u};
+    }
+  }
+  __device__ static __forceinline__ void put(int t, const Regs& r, uint16_t (*S)[PITCH]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) *(u32x4*)&S[(t >> 3) + 32 * i][(t & 7) * 8] = r.v[i];
+  }
+  __device__ static __forceinline__ void mma(const Stage& s, int wm, int wn, int c, int h, f32x16& acc) {
+#pragma unroll
+    for (int u = 0; u < KT / 16; ++u) {
+      const int ko = 16 * u + 8 * h;
+      const bf16x8 a = *(const bf16x8*)&s.a[wm * 32 + c][ko], b = *(const bf16x8*)&s.b[wn * 32 + c][ko];
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+    }
+  }
+};
+
+struct MvcF32 {
+  typedef float elem;
+  static constexpr int KT = 32, PITCH = 68;
+  struct Stage { float a[KT][PITCH], b[KT][PITCH]; };
+  struct Regs { f32x4 v[2]; };
+  __device__ static __forceinline__ void fetch(const elem* __restrict__ P, long row0, int nrows, int D, int k0, int t,
+                                               Regs& r) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int row = (t >> 3) + 32 * i;
+      r.v[i] = row < nrows ? *(const f32x4*)(P + (row0 + row) * D + k0 + (t & 7) * 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+  }
+  __device__ static __forceinline__ void put(int t, const Regs& r, float (*S)[PITCH]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) S[(t & 7) * 4 + u][(t >> 3) + 32 * i] = r.v[i][u];
+  }
+  __device__ static __forceinline__ void mma(const Stage& s, int wm, int wn, int c, int h, f32x16& acc) {
+#pragma unroll
+    for (int u = 0; u < KT / 2; ++u)
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(s.a[2 * u + h][wm * 32 + c], s.b[2 * u + h][wn * 32 + c], acc, 0, 0, 0);
+  }
+};
+
+// One 64 x 64 tile by the whole workgroup: rows a0 .. a0 + na - 1 of A against rows b0 .. b0 + nb - 1 of B over all of D,
+// both operands through the double-buffered K-slice stage, one slice ahead in registers: ms_pair_kernel's loop.  With
+// wave = 2 wm + wn and lane = 32 h + c, acc[r] = <A row a0 + 32 wm + (r & 3) + 8 (r >> 2) + 4 h, B row b0 + 32 wn + c>.
+// The stage must be free on entry; ends on a barrier.
+template <typename P>
+__device__ __forceinline__ void mvc_tile(const typename P::elem* __restrict__ A, long a0, int na,
+                                         const typename P::elem* __restrict__ B, long b0, int nb, int D,
+                                         typename P::Stage* stage, f32x16& acc) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int wm = wave >> 1, wn = wave & 1, c = lane & 31, h = lane >> 5;
+  const int nk = D / P::KT;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  typename P::Regs ra, rb;
+  P::fetch(A, a0, na, D, 0, t, ra);
+  P::fetch(B, b0, nb, D, 0, t, rb);
+  P::put(t, ra, stage[0].a);
+  P::put(t, rb, stage[0].b);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {                           // k ascending, the same steps for every tile
+    const int cur = kt & 1;
+    if (kt + 1 < nk) {
+      P::fetch(A, a0, na, D, (kt + 1) * P::KT, t, ra);
+      P::fetch(B, b0, nb, D, (kt + 1) * P::KT, t, rb);
+    }
+    P::mma(stage[cur], wm, wn, c, h, acc);
+    if (kt + 1 < nk) {
+      P::put(t, ra, stage[cur ^ 1].a);
+      P::put(t, rb, stage[cur ^ 1].b);
+    }
+    __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ codes
+// *bad = 1 when a code of the store's rows is not a centroid id
+__global__ __launch_bounds__(MVC_THREADS) void mvc_check_kernel(const uint16_t* __restrict__ codes, int64_t n, int32_t nc,
+                                                                int32_t* __restrict__ bad) {
+  const int64_t i = (int64_t)blockIdx.x * MVC_THREADS + threadIdx.x;
+  if (i < n && (int32_t)codes[i] >= nc) *bad = 1;
+}
+
+// codes base .. base + 7 (base % 8 == 0, base < drows) as four registers; a code past the store reads as 0
+__device__ __forceinline__ u32x4 mvc_codes8(const uint16_t* __restrict__ codes, long base, long drows) {
+  if (base + 8 <= drows) return *(const u32x4*)(codes + base);
+  u32x4 v = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int u = 0; u < 8; ++u)
+    if (base + u < drows) v[u >> 1] |= (uint32_t)codes[base + u] << (16 * (u & 1));
+  return v;
+}
+
+// ------------------------------------------------------------------------------------------------ table
+// table[(g nc + c) R + i] = key(S[R g + i, c]); a row past the call's query rows holds the key of -inf
+template <typename P>
+__global__ __launch_bounds__(MVC_THREADS) void mvc_table_kernel(const typename P::elem* __restrict__ Q, int64_t qused,
+                                                                int64_t prows, const typename P::elem* __restrict__ Cn,
+                                                                int32_t nc, int32_t D, int32_t R,
+                                                                uint16_t* __restrict__ table) {
+  __shared__ __attribute__((aligned(16))) typename P::Stage stage[2];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int wm = wave >> 1, wn = wave & 1, c = lane & 31, h = lane >> 5;
+  const long q0 = (long)blockIdx.x * MVC_TILE;
+  const int c0 = blockIdx.y * MVC_TILE;
+  const int nq = (int)max(0l, min((long)MVC_TILE, qused - q0));
+  f32x16 acc;
+  mvc_tile<P>(Q, q0, nq, Cn, (long)c0, min(MVC_TILE, nc - c0), D, stage, acc);
+  const int cent = c0 + wn * 32 + c;
+  if (cent >= nc) return;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {                               // acc[4 j .. 4 j + 3]: four consecutive query rows
+    const long row = q0 + wm * 32 + 8 * j + 4 * h;
+    if (row >= prows) continue;                               // prows % 16 == 0: the four rows lie in one group
+    uint32_t k[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) k[i] = row + i < qused ? mvc_key(acc[4 * j + i]) : MVC_NO_ROW;
+    const long g = row / R;
+    const int in = (int)(row - g * R);
+    *(u32x2*)(table + (g * nc + cent) * R + in) = (u32x2){k[0] | (k[1] << 16), k[2] | (k[3] << 16)};
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ walk
+template <int R>
+__global__ __launch_bounds__(MVC_WALK_THREADS) void mvc_walk_kernel(
+    const uint16_t* __restrict__ table, const uint16_t* __restrict__ codes, int64_t drows,
+    const int64_t* __restrict__ doc_ptr, int32_t nd, int32_t nc, int32_t ngroups, int32_t chunk, int32_t c_first,
+    uint16_t* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int LPD = R / 8;                                  // lanes per document: one 16-byte piece of a table row each
+  constexpr int DPW = MVC_WALK_THREADS / LPD;                 // documents the workgroup walks at a time
+  const int t = threadIdx.x;
+  const int g = (int)(blockIdx.x % (unsigned)ngroups), cg = (int)(blockIdx.x / (unsigned)ngroups);
+  const long g0 = (long)c_first * chunk;                      // first doc of the launch's chunk group: part's row 0
+  const long c0 = min((long)nd, g0 + (long)cg * chunk), c1 = min((long)nd, c0 + chunk);
+  u32x4* T = (u32x4*)smem;
+  {                                                           // the group's table, once for the whole chunk
+    const u32x4* src = (const u32x4*)(table + (long)g * nc * R);
+    const int nvec = nc * LPD;
+    for (int i = t; i < nvec; i += MVC_WALK_THREADS) T[i] = src[i];
+  }
+  __syncthreads();
+  const int p = t % LPD, slot = t / LPD;
+  const long prows = (long)ngroups * R;
+  for (long d = c0 + slot; d < c1; d += DPW) {
+    const long a = doc_ptr[d], e = doc_ptr[d + 1];
+    u32x4 m = {MVC_NO_ROW2, MVC_NO_ROW2, MVC_NO_ROW2, MVC_NO_ROW2};
+    if (e > a) {
+      long base = a & ~7l;
+      u32x4 cur = mvc_codes8(codes, base, drows);
+      for (; base < e; base += 8) {
+        u32x4 nxt = {0u, 0u, 0u, 0u};
+        if (base + 8 < e) nxt = mvc_codes8(codes, base + 8, drows);          // in flight while this piece is walked
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const long pos = base + u;
+          if (pos >= a && pos < e) {
+            const int code = min((int)((cur[u >> 1] >> (16 * (u & 1))) & 0xFFFFu), nc - 1);
+            const u32x4 x = T[code * LPD + p];
+#pragma unroll
+            for (int w = 0; w < 4; ++w) m[w] = mvc_max2(m[w], x[w]);
+          }
+        }
+        cur = nxt;
+      }
+    }
+    *(u32x4*)(part + (d - g0) * prows + (long)g * R + p * 8) = m;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ selection
+__global__ __launch_bounds__(SR_THREADS) void mvc_select_kernel(
+    const uint16_t* __restrict__ part, const int64_t* __restrict__ q_ptr, const int64_t* __restrict__ doc_ptr, int32_t nd,
+    int64_t prows, int32_t chunk, int32_t c_first, int32_t nch, const int64_t* __restrict__ ex_ptr,
+    const int32_t* __restrict__ ex_doc, int32_t ncand, unsigned long long* __restrict__ cand, int32_t* __restrict__ ccount) {
+  __shared__ SelectSmem S;
+  __shared__ uint32_t keys[MVC_CHUNK_MAX];
+  const int tid = threadIdx.x, q = blockIdx.x, cg = blockIdx.y;
+  const long c0 = ((long)c_first + cg) * chunk;
+  const int n = (int)max(0l, min((long)chunk, (long)nd - c0));
+  const long qa = q_ptr[q], qe = q_ptr[q + 1];
+  const float lq = (float)(qe - qa);
+  const int64_t e0 = ex_ptr ? ex_ptr[q] : 0, e1 = ex_ptr ? ex_ptr[q + 1] : 0;
+  for (int i = tid; i < n; i += SR_THREADS) {
+    const long d = c0 + i;
+    uint32_t key = 0u;                                        // a document without rows, or an excluded one: no entry
+    bool ok = doc_ptr[d + 1] > doc_ptr[d];
+    if (ok && e1 > e0) {
+      const int64_t p = lower_bound(ex_doc, e0, e1, (int32_t)d);
+      ok = !(p < e1 && ex_doc[p] == (int32_t)d);
+    }
+    if (ok) {
+      const uint16_t* v = part + ((long)cg * chunk + i) * prows;             // prows % 16 == 0: 16-byte pieces
+      float x = 0.f;
+      for (long base = qa & ~7l; base < qe; base += 8) {      // the query's rows, ascending: one chain from +0
+        const u32x4 w = *(const u32x4*)(v + base);
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          if (base + u >= qa && base + u < qe) x += mvc_unkey((w[u >> 1] >> (16 * (u & 1))) & 0xFFFFu);
+      }
+      key = dense_key(x / lq);
+    }
+    keys[i] = key;
+  }
+  __syncthreads();
+  const size_t list = (size_t)q * (size_t)nch + (size_t)(c_first + cg);
+  select_chunk([&](long i) -> uint32_t { return keys[i]; }, (int)c0, n, ncand, S, cand + list * (size_t)ncand,
+               ccount + list);
+}
+
+__global__ __launch_bounds__(SR_THREADS) void mvc_merge_kernel(const unsigned long long* __restrict__ cand,
+                                                               const int32_t* __restrict__ ccount, int32_t nch,
+                                                               int32_t ncand, int32_t* __restrict__ cand_doc,
+                                                               float* __restrict__ cand_score) {
+  __shared__ SelectSmem S;
+  const int q = blockIdx.x;
+  const long base = (long)q * nch;
+  const RankLists lists = {cand + (size_t)base * (size_t)ncand, ccount + base, ncand, ncand};
+  merge_lists<dense_unkey>(lists, nch, S, q, 0, ncand, cand_doc, cand_score, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------ rescore
+// partial[pair qblocks + qb] = the sum, in ascending row order from +0, of the row maxima of the query's run qb against
+// candidate `pair`'s rows; a slot of cand_doc that names no document with rows, and a run past the query, write nothing
+template <typename P>
+__global__ __launch_bounds__(MVC_THREADS) void mvc_rescore_kernel(
+    const typename P::elem* __restrict__ E, const typename P::elem* __restrict__ Q, int32_t D,
+    const int64_t* __restrict__ doc_ptr, int32_t nd, const int64_t* __restrict__ q_ptr,
+    const int32_t* __restrict__ cand_doc, int32_t ncand, int32_t qblocks, float* __restrict__ partial) {
+  __shared__ __attribute__((aligned(16))) typename P::Stage stage[2];
+  __shared__ float rmax[2][MVC_TILE];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int wm = wave >> 1, wn = wave & 1, c = lane & 31, h = lane >> 5;
+  const long pair = blockIdx.x;
+  const int qb = blockIdx.y, q = (int)(pair / ncand);
+  const int32_t d = cand_doc[pair];
+  if ((uint32_t)d >= (uint32_t)nd) return;
+  const long d0 = doc_ptr[d], Ld = doc_ptr[d + 1] - d0;
+  const long q0 = q_ptr[q] + (long)qb * MVC_TILE;
+  const int nq = (int)min((long)MVC_TILE, q_ptr[q + 1] - q0);  // query rows of this run
+  if (Ld <= 0 || nq <= 0) return;
+  float m[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) m[r] = -INFINITY;
+  for (long n0 = 0; n0 < Ld; n0 += MVC_TILE) {
+    const int nv = (int)min((long)MVC_TILE, Ld - n0);          // doc rows of this tile
+    f32x16 acc;
+    mvc_tile<P>(Q, q0, nq, E, d0 + n0, nv, D, stage, acc);
+    const bool ok = wn * 32 + c < nv;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) m[r] = fmaxf(m[r], ok ? acc[r] : -INFINITY);
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) m[r] = fmaxf(m[r], __shfl_xor(m[r], o, 64));
+    if (c == 0) rmax[wn][wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h] = m[r];
+  }
+  __syncthreads();
+  if (t == 0) {
+    float s = 0.f;
+    for (int i = 0; i < nq; ++i) s += fmaxf(rmax[0][i], rmax[1][i]);        // ascending rows
+    partial[pair * qblocks + qb] = s;
+  }
+}
+
+__global__ __launch_bounds__(SR_THREADS) void mvc_order_kernel(
+    const float* __restrict__ partial, const int32_t* __restrict__ cand_doc, const int64_t* __restrict__ q_ptr,
+    const int64_t* __restrict__ doc_ptr, int32_t nd, int32_t ncand, int32_t qblocks, int32_t lo, int32_t hi,
+    int32_t* __restrict__ out_doc, float* __restrict__ out_score, int32_t* __restrict__ out_found) {
+  __shared__ unsigned long long sbuf[SR_KMAX];               // rank keys: descending = the ABI's order
+  __shared__ int total;
+  const int tid = threadIdx.x, q = blockIdx.x;
+  const int Lq = (int)(q_ptr[q + 1] - q_ptr[q]);
+  const int nb = (Lq + MVC_TILE - 1) / MVC_TILE;
+  const int P = pow2_at_least(ncand);
+  int local = 0;
+  for (int j = tid; j < P; j += SR_THREADS) {
+    unsigned long long key = 0ull;
+    const int32_t d = j < ncand ? cand_doc[(long)q * ncand + j] : -1;
+    if ((uint32_t)d < (uint32_t)nd && doc_ptr[d + 1] > doc_ptr[d]) {
+      const float* v = partial + ((long)q * ncand + j) * qblocks;
+      float s = v[0];
+      for (int b = 1; b < nb; ++b) s += v[b];                 // ascending runs
+      key = rank_key(dense_key(s / (float)Lq), (uint32_t)d);
+      ++local;
+    }
+    sbuf[j] = key;
+  }
+  const int nsel = min(block_sum(local, total), hi);          // found counts the ranks below hi, as the exact search's
+  bitonic_desc<SR_THREADS, int>(sbuf, P);
+  write_ranks<dense_unkey>(sbuf, nsel, q, lo, hi, out_doc, out_score, out_found);
+}
+
+// ------------------------------------------------------------------------------------------------ host
+// ptr [n + 1] ascends from 0 and ends within `rows`; need_rows: every sequence has at least one
+inline bool mvc_ptr_ok(const int64_t* ptr, int32_t n, int64_t rows, bool need_rows) {
+  if (!ptr || ptr[0] != 0) return false;
+  for (int32_t s = 0; s < n; ++s)
+    if (ptr[s + 1] < ptr[s] + (need_rows ? 1 : 0)) return false;
+  return ptr[n] <= rows;
+}
+
+inline int mvc_upload(char* ws, size_t off, const void* src, size_t bytes, hipStream_t st) {
+  const hipError_t e = hipMemcpyAsync(ws + off, src, bytes, hipMemcpyHostToDevice, st);
+  return e == hipSuccess ? SNX_OK : (int)e;
+}
+
+inline bool mvc_bad_cand(int32_t nq, int32_t nd, int32_t nc, int32_t ncand, int32_t chunk_docs) {
+  return nq < 0 || nd < 0 || nc < 1 || nc > MVC_NC_MAX || ncand < 1 || ncand > SR_KMAX ||
+         (chunk_docs != 0 && (chunk_docs < MVC_CHUNK_MIN || chunk_docs > MVC_CHUNK_MAX));
+}
+
+// the candidate pass's workspace: device copies of the pointers, the check's flag, the table, the maxima of one chunk
+// group, the candidate lists
+struct MvcPlan {
+  size_t dptr, qptr, flag, table, part, cand, ccount, total;
+  int chunk, nch, group, ngroups, R;
+  int64_t prows;
+  bool ok;
+  MvcPlan(const int64_t* q_ptr, int32_t nq, int32_t nd, int32_t nc, int32_t ncand, int32_t chunk_docs) {
+    chunk = chunk_docs > 0 ? chunk_docs : MVC_CHUNK_DEFAULT;
+    nch = sr_nch(nd, chunk);
+    R = mvc_group_rows(nc);
+    const int64_t qused = q_ptr[nq];
+    ok = qused <= 0x7FFFFFFFL - MVC_TILE && (int64_t)nq * nch <= 0x7FFFFFFFL;
+    ngroups = ok ? (int)((qused + R - 1) / R) : 1;
+    prows = (int64_t)ngroups * R;
+    const size_t per_chunk = (size_t)chunk * (size_t)prows * 2;
+    long g = (MVC_WG_TARGET + (long)ngroups - 1) / ngroups;
+    if ((size_t)g * per_chunk > MVC_PART_BUDGET) g = (long)(MVC_PART_BUDGET / (per_chunk ? per_chunk : 1));
+    group = (int)(g < 1 ? 1 : (g > nch ? nch : (g > 65535 ? 65535 : g)));
+    ok = ok && (long)ngroups * group <= 0x7FFFFFFFL;
+    Arena a;
+    dptr = a.take(((size_t)nd + 1) * 8);
+    qptr = a.take(((size_t)nq + 1) * 8);
+    flag = a.take(4);
+    table = a.take((size_t)prows * (size_t)nc * 2);
+    part = a.take((size_t)group * per_chunk);
+    cand = a.take((size_t)nq * (size_t)nch * (size_t)ncand * 8);
+    ccount = a.take((size_t)nq * (size_t)nch * 4);
+    total = a.off;
+  }
+};
+
+LdsOptIn g_mvc_lds[3];
+
+template <int R>
+int mvc_walk(int which, dim3 grid, hipStream_t st, const uint16_t* table, const uint16_t* codes, int64_t drows,
+             const int64_t* dptr, int32_t nd, int32_t nc, int ngroups, int chunk, int c, uint16_t* part) {
+  if (const int rc = g_mvc_lds[which].ensure((const void*)mvc_walk_kernel<R>, MVC_TABLE_BYTES)) return rc;
+  hipLaunchKernelGGL(mvc_walk_kernel<R>, grid, dim3(MVC_WALK_THREADS), (size_t)nc * R * 2, st, table, codes, drows, dptr, nd,
+                     nc, ngroups, chunk, c, part);
+  SNX_CHECK_LAUNCH();
+  return SNX_OK;
+}
+
+// the rescore's workspace: device copies of the pointers and one partial sum per (query, candidate, run)
+struct MvcRescorePlan {
+  size_t dptr, qptr, partial, total;
+  int qblocks;
+  bool ok;
+  MvcRescorePlan(const int64_t* q_ptr, int32_t nq, int32_t nd, int32_t ncand) {
+    int64_t longest = 1;
+    for (int32_t q = 0; q < nq; ++q) longest = q_ptr[q + 1] - q_ptr[q] > longest ? q_ptr[q + 1] - q_ptr[q] : longest;
+    const int64_t qb = (longest + MVC_TILE - 1) / MVC_TILE;
+    ok = qb <= 65535 && (int64_t)nq * ncand <= 0x7FFFFFFFL;
+    qblocks = ok ? (int)qb : 1;
+    Arena a;
+    dptr = a.take(((size_t)nd + 1) * 8);
+    qptr = a.take(((size_t)nq + 1) * 8);
+    partial = a.take((size_t)nq * (size_t)ncand * (size_t)qblocks * 4);
+    total = a.off;
+  }
+};
+
+}  // namespace
+
+extern "C" size_t snx_mv_candidates_workspace_bytes(const int64_t* q_ptr, int32_t nq, int32_t nd, int32_t nc, int32_t ncand,
+                                                    int32_t chunk_docs) {
+  if (nq <= 0 || mvc_bad_cand(nq, nd, nc, ncand, chunk_docs) || !mvc_ptr_ok(q_ptr, nq, 0x7FFFFFFFFFFFFFFFL, true)) return 0;
+  const MvcPlan plan(q_ptr, nq, nd, nc, ncand, chunk_docs);
+  return plan.ok ? plan.total : 0;
+}
+
+extern "C" int snx_mv_candidates(const uint16_t* codes, int64_t drows, const int64_t* doc_ptr, int32_t nd,
+                                 const void* centroids, int32_t nc, const void* q, int32_t mv_f32, int32_t D, int64_t qrows,
+                                 const int64_t* q_ptr, int32_t nq, const int64_t* ex_ptr, const int32_t* ex_doc,
+                                 int32_t ncand, int32_t chunk_docs, int32_t* cand_doc, float* cand_score, void* workspace,
+                                 size_t ws_bytes, hipStream_t st) {
+  if (D <= 0 || (D % 64) != 0 || D > MVC_DMAX || qrows < 0 || drows < 0) return SNX_E_SHAPE;
+  if (mvc_bad_cand(nq, nd, nc, ncand, chunk_docs)) return SNX_E_ARG;
+  if (nq == 0) return SNX_OK;
+  if (!q || !centroids || !cand_doc || !cand_score || !workspace || (ex_ptr && !ex_doc) || ((uintptr_t)q & 15) != 0 ||
+      ((uintptr_t)centroids & 15) != 0 || ((uintptr_t)codes & 15) != 0 || ((uintptr_t)workspace & 15) != 0)
+    return SNX_E_ARG;
+  // the two pointer arrays are pageable host memory (snx.h): everything a kernel will trust is checked here, before any
+  // launch; hipMemcpyAsync below has staged them when it returns
+  if (!mvc_ptr_ok(doc_ptr, nd, drows, false) || !mvc_ptr_ok(q_ptr, nq, qrows, true)) return SNX_E_ARG;
+  const int64_t dused = doc_ptr[nd], qused = q_ptr[nq];
+  if (dused > 0 && !codes) return SNX_E_ARG;
+  const MvcPlan plan(q_ptr, nq, nd, nc, ncand, chunk_docs);
+  if (!plan.ok) return SNX_E_SHAPE;
+  if (ws_bytes < plan.total) return SNX_E_ARG;
+  char* ws = (char*)workspace;
+  if (dused > 0) {                                            // the codes are a device array: a kernel looks, the host waits
+    int32_t* flag = (int32_t*)(ws + plan.flag);
+    int32_t bad = 0;
+    hipError_t e = hipMemsetAsync(flag, 0, 4, st);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(mvc_check_kernel, dim3((unsigned)((dused + MVC_THREADS - 1) / MVC_THREADS)), dim3(MVC_THREADS), 0, st,
+                       codes, dused, nc, flag);
+    SNX_CHECK_LAUNCH();
+    e = hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return (int)e;
+    if (bad) return SNX_E_ARG;
+  }
+  RC(mvc_upload(ws, plan.dptr, doc_ptr, ((size_t)nd + 1) * 8, st));
+  RC(mvc_upload(ws, plan.qptr, q_ptr, ((size_t)nq + 1) * 8, st));
+  const int64_t* dptr = (const int64_t*)(ws + plan.dptr);
+  const int64_t* qptr = (const int64_t*)(ws + plan.qptr);
+  uint16_t *table = (uint16_t*)(ws + plan.table), *part = (uint16_t*)(ws + plan.part);
+  unsigned long long* cand = (unsigned long long*)(ws + plan.cand);
+  int32_t* ccount = (int32_t*)(ws + plan.ccount);
+  const int R = plan.R;
+  if (dused > 0) {
+    const dim3 grid((unsigned)((plan.prows + MVC_TILE - 1) / MVC_TILE), (unsigned)((nc + MVC_TILE - 1) / MVC_TILE));
+    if (mv_f32)
+      hipLaunchKernelGGL(mvc_table_kernel<MvcF32>, grid, dim3(MVC_THREADS), 0, st, (const float*)q, qused, plan.prows,
+                         (const float*)centroids, nc, D, R, table);
+    else
+      hipLaunchKernelGGL(mvc_table_kernel<MvcBf16>, grid, dim3(MVC_THREADS), 0, st, (const bf16_t*)q, qused, plan.prows,
+                         (const bf16_t*)centroids, nc, D, R, table);
+    SNX_CHECK_LAUNCH();
+  }
+  for (int c = 0; c < plan.nch; c += plan.group) {            // one chunk group after the other: part is reused in order
+    const int g = plan.nch - c < plan.group ? plan.nch - c : plan.group;
+    if (dused > 0) {
+      const dim3 grid((unsigned)((long)plan.ngroups * g));    // group fast, chunk slow
+      if (R == 64) RC(mvc_walk<64>(0, grid, st, table, codes, drows, dptr, nd, nc, plan.ngroups, plan.chunk, c, part));
+      else if (R == 32) RC(mvc_walk<32>(1, grid, st, table, codes, drows, dptr, nd, nc, plan.ngroups, plan.chunk, c, part));
+      else RC(mvc_walk<16>(2, grid, st, table, codes, drows, dptr, nd, nc, plan.ngroups, plan.chunk, c, part));
+    }
+    hipLaunchKernelGGL(mvc_select_kernel, dim3(nq, g), dim3(SR_THREADS), 0, st, (const uint16_t*)part, qptr, dptr, nd,
+                       plan.prows, plan.chunk, c, plan.nch, ex_ptr, ex_doc, ncand, cand, ccount);
+    SNX_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(mvc_merge_kernel, dim3(nq), dim3(SR_THREADS), 0, st, (const unsigned long long*)cand,
+                     (const int32_t*)ccount, plan.nch, ncand, cand_doc, cand_score);
+  SNX_CHECK_LAUNCH();
+  return SNX_OK;
+}
+
+extern "C" size_t snx_mv_rescore_workspace_bytes(const int64_t* q_ptr, int32_t nq, int32_t nd, int32_t ncand) {
+  if (nq <= 0 || nd < 0 || ncand < 1 || ncand > SR_KMAX || !mvc_ptr_ok(q_ptr, nq, 0x7FFFFFFFFFFFFFFFL, true)) return 0;
+  const MvcRescorePlan plan(q_ptr, nq, nd, ncand);
+  return plan.ok ? plan.total : 0;
+}
+
+extern "C" int snx_mv_rescore(const void* docs, const void* q, int32_t mv_f32, int32_t D, int64_t drows,
+                              const int64_t* doc_ptr, int32_t nd, int64_t qrows, const int64_t* q_ptr, int32_t nq,
+                              const int32_t* cand_doc, int32_t ncand, int32_t lo, int32_t hi, int32_t* out_doc,
+                              float* out_score, int32_t* out_found, void* workspace, size_t ws_bytes, hipStream_t st) {
+  if (D <= 0 || (D % 64) != 0 || D > MVC_DMAX || qrows < 0 || drows < 0 || nq < 0 || nd < 0) return SNX_E_SHAPE;
+  if (ncand < 1 || ncand > SR_KMAX || lo < 0 || hi <= lo || hi > ncand) return SNX_E_ARG;
+  if (nq == 0) return SNX_OK;
+  if (!q || !cand_doc || !out_doc || !out_score || !out_found || !workspace || ((uintptr_t)q & 15) != 0 ||
+      ((uintptr_t)docs & 15) != 0 || ((uintptr_t)workspace & 15) != 0)
+    return SNX_E_ARG;
+  if (!mvc_ptr_ok(doc_ptr, nd, drows, false) || !mvc_ptr_ok(q_ptr, nq, qrows, true)) return SNX_E_ARG;
+  if (doc_ptr[nd] > 0 && !docs) return SNX_E_ARG;
+  const MvcRescorePlan plan(q_ptr, nq, nd, ncand);
+  if (!plan.ok) return SNX_E_SHAPE;
+  if (ws_bytes < plan.total) return SNX_E_ARG;
+  char* ws = (char*)workspace;
+  RC(mvc_upload(ws, plan.dptr, doc_ptr, ((size_t)nd + 1) * 8, st));
+  RC(mvc_upload(ws, plan.qptr, q_ptr, ((size_t)nq + 1) * 8, st));
+  const int64_t* dptr = (const int64_t*)(ws + plan.dptr);
+  const int64_t* qptr = (const int64_t*)(ws + plan.qptr);
+  float* partial = (float*)(ws + plan.partial);
+  const dim3 grid((unsigned)((long)nq * ncand), (unsigned)plan.qblocks);
+  if (mv_f32)
+    hipLaunchKernelGGL(mvc_rescore_kernel<MvcF32>, grid, dim3(MVC_THREADS), 0, st, (const float*)docs, (const float*)q, D,
+                       dptr, nd, qptr, cand_doc, ncand, plan.qblocks, partial);
+  else
+    hipLaunchKernelGGL(mvc_rescore_kernel<MvcBf16>, grid, dim3(MVC_THREADS), 0, st, (const bf16_t*)docs, (const bf16_t*)q, D,
+                       dptr, nd, qptr, cand_doc, ncand, plan.qblocks, partial);
+  SNX_CHECK_LAUNCH();
+  hipLaunchKernelGGL(mvc_order_kernel, dim3(nq), dim3(SR_THREADS), 0, st, (const float*)partial, cand_doc, qptr, dptr, nd,
+                     ncand, plan.qblocks, lo, hi, out_doc, out_score, out_found);
+  SNX_CHECK_LAUNCH();
+  return SNX_OK;
+}

@@ -79,6 +79,10 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     # and for MaxSim: the 16 accumulator registers, the 16 running row maxima and the prefetched operand slices stay in
     # registers across the document tiles; the finish kernel holds no LDS and one sum, and is not listed
     "maxsim.hip": ("ms_pair_kernel",),
+    # and for the candidate pass: the walk's four packed maxima and its two code pieces, the table and rescore tiles'
+    # accumulators and prefetched slices, and the selection's keys stay in registers and LDS
+    "mv_centroid.hip": ("mvc_table_kernel", "mvc_walk_kernel", "mvc_select_kernel", "mvc_merge_kernel",
+                        "mvc_rescore_kernel", "mvc_order_kernel"),
     # and for the lexical weights: the 64-bit keys live in LDS, a thread's key, its ballot and the unused ids (kernel
     # arguments) in registers; the head's row kernel and the pair scorer hold no LDS and are not listed
     "teacher_lex.hip": ("tl_unique_kernel",),
@@ -95,6 +99,7 @@ FILE_FLAGS: Dict[str, Tuple[str, ...]] = {
     "maxsim.hip": _NO_PACKED_F32,
     "teacher_mv.hip": _NO_PACKED_F32,
     "teacher_lex.hip": _NO_PACKED_F32,
+    "mv_centroid.hip": _NO_PACKED_F32,
 }
 
 

@@ -1,4 +1,5 @@
-"""Exact MaxSim search over a ragged multi-vector store (csrc/mv_search.hip, include/snx.h "multi-vector search")."""
+"""MaxSim search over a ragged multi-vector store: exact (csrc/mv_search.hip, include/snx.h "multi-vector search") and
+through a centroid-interaction candidate pass (csrc/mv_centroid.hip, "multi-vector candidate search")."""
 import ctypes as C
 from typing import List, Optional, Tuple
 
@@ -12,6 +13,8 @@ from ._common import (K_MAX, at, cat_or_empty, check_pairs, check_query_slice, c
 
 MV_DIM_MAX = 1024
 MV_CHUNK_MIN, MV_CHUNK_MAX = 64, 8192  # docs per chunk of the walk
+MV_CENTROIDS_MAX = 4096                # a query group's centroid table has to fit LDS
+_MV_ASSIGN_ROWS = 1 << 18              # store rows cast to fp32 per slice of the code assignment
 _MV_ROWS_PER_LAUNCH = 1 << 15          # query rows of one launch: 512 query blocks
 
 
@@ -37,6 +40,20 @@ class MultiVectorIndex:
         scores, docs, found = index.search_band(qmv, q_ptr, lo, hi, exclude=None, chunk_docs=0, query_slice=0)
         s = index.pair_scores(qmv, q_ptr, pairs)
 
+    and the same searches through a candidate pass over centroid codes (2 bytes per document row, not 2 D):
+
+        index.train_centroids(ncentroids, niter=10, seed=0, sample_rows=0)      # after build(); or
+        index.set_centroids(c)                                                  # fp32 [nc, dim], unit rows
+        a, docs = index.candidates(qmv, q_ptr, ncand, exclude=None, chunk_docs=0, query_slice=0)
+        scores, docs = index.search_two_phase(qmv, q_ptr, k, ncand, chunk_docs=0, query_slice=0)
+        scores, docs, found = index.search_band_two_phase(qmv, q_ptr, lo, hi, ncand, exclude=None, ...)
+
+    ``index.codes`` (uint16 [num_rows]) is every row's best centroid under ``DenseIndex``'s order, ``index.centroids`` the
+    centroids in the store's dtype.  a(q, d) = mean over the query's rows of the best bf16-rounded product of the row
+    with a centroid of the document; the ``ncand`` best documents by (a descending, doc ascending) are scored exactly, in
+    place, and ranked.  With ``ncand`` at least the number of documents with rows the result is the exact search's, bit
+    for bit; below it the result is approximate, and every returned score is still s(q, d).  ``add`` invalidates both.
+
     s(q, d) is bit for bit ``maxsim_pairs``' score of the two sequences; the order is ``DenseIndex``'s (score descending,
     ties lowest doc id first, every document with rows a candidate whatever the sign of its score; unused slots 0 / -1).
     Results do not depend on ``chunk_docs``, ``query_slice`` or the order of the queries.  A sequence without rows (a
@@ -52,6 +69,8 @@ class MultiVectorIndex:
         self._ptr: List[int] = [0]
         self.rows: Optional[torch.Tensor] = None
         self._hptr = None
+        self.centroids: Optional[torch.Tensor] = None         # [nc, dim] in the store's dtype, as the table kernel reads them
+        self.codes: Optional[torch.Tensor] = None             # uint16 [num_rows]: the best centroid of every row
 
     @property
     def num_docs(self) -> int:
@@ -84,6 +103,7 @@ class MultiVectorIndex:
         self._parts.append(mv[:ptr[-1]])
         self._ptr += [self._ptr[-1] + v for v in ptr[1:]]
         self.rows = None                                      # a new batch invalidates a built index
+        self.centroids = self.codes = None                    # and its codes
 
     def build(self) -> "MultiVectorIndex":
         if len(self._parts) != 1:
@@ -181,3 +201,124 @@ class MultiVectorIndex:
             store = torch.cat([qmv[:ptr[-1]], self.rows[torch.cat(take).to(dev)]])
             out[torch.tensor(ok, device=dev)] = maxsim_pairs(store, sptr, [pq[i] for i in ok], [local[pd[i]] for i in ok])
         return out
+
+    # -------------------------------------------------------------------------------------------- candidate search
+    def _quantizer(self, who: str, nc: int, niter: int = 0, seed: int = 0):
+        """The dense helpers of ``IvfFlatIndex`` (k-means step, nearest centroid) over this index's dim and device."""
+        from .ivf import IvfFlatIndex
+        if not self.built:
+            raise RuntimeError(f"MultiVectorIndex.{who}: call build() first")
+        if self.num_rows == 0:
+            raise ValueError(f"MultiVectorIndex.{who}: the index has no rows")
+        if self.device.type != "cuda":
+            raise ValueError(f"MultiVectorIndex.{who}: the code assignment needs the index on a GPU")
+        return IvfFlatIndex(self.dim, nc, self.device, niter=niter, seed=seed)
+
+    def _assign(self, quantizer, c: torch.Tensor) -> None:
+        """``centroids`` = ``c`` in the store's dtype; ``codes`` = every row's best of those (ties: the lowest)."""
+        self.centroids = c.to(self.dtype).contiguous()
+        seen = self.centroids.float()
+        codes = torch.empty(self.num_rows, dtype=torch.int32, device=self.device)
+        for s in range(0, self.num_rows, _MV_ASSIGN_ROWS):
+            codes[s:s + _MV_ASSIGN_ROWS] = quantizer._best(self.rows[s:s + _MV_ASSIGN_ROWS].float(), seen, 1)[1].reshape(-1)
+        self.codes = codes.to(torch.uint16)
+
+    def train_centroids(self, ncentroids: int, niter: int = 10, seed: int = 0, sample_rows: int = 0) -> "MultiVectorIndex":
+        """Spherical k-means over the store's rows as fp32 (``sample_rows`` > 0: over that many evenly spaced rows), by
+        ``IvfFlatIndex``'s procedure and seed rule; then the codes.  ``ncentroids`` is clamped to the rows trained on."""
+        if isinstance(ncentroids, bool) or not isinstance(ncentroids, (int, np.integer)) or \
+                not 1 <= int(ncentroids) <= MV_CENTROIDS_MAX:
+            raise ValueError(f"MultiVectorIndex.train_centroids: ncentroids must be an int in [1, {MV_CENTROIDS_MAX}]")
+        if int(sample_rows) < 0:
+            raise ValueError("MultiVectorIndex.train_centroids: sample_rows must be >= 0 (0: every row)")
+        n = self.num_rows if self.built else 0
+        m = min(int(sample_rows), n) if int(sample_rows) > 0 else n
+        nc = min(int(ncentroids), max(m, 1))
+        quantizer = self._quantizer("train_centroids", nc, niter, seed)
+        x = self.rows if m == n else self.rows[(torch.arange(m, device=self.device) * n) // m]
+        self._assign(quantizer, quantizer._kmeans(x.float(), nc))
+        return self
+
+    def set_centroids(self, c: torch.Tensor) -> "MultiVectorIndex":
+        """``c`` fp32 [nc, dim] with unit rows, 1 <= nc <= 4096, on the index's device: the centroids, without training."""
+        if not isinstance(c, torch.Tensor) or c.dtype != torch.float32 or c.dim() != 2 or c.shape[1] != self.dim or \
+                not 1 <= c.shape[0] <= MV_CENTROIDS_MAX:
+            raise ValueError(f"MultiVectorIndex.set_centroids: c must be fp32 [nc, {self.dim}], 1 <= nc <= {MV_CENTROIDS_MAX}")
+        if c.device != self.device:
+            raise ValueError(f"MultiVectorIndex.set_centroids: c must be on {self.device}")
+        if not bool(torch.isfinite(c).all()):
+            raise ValueError("MultiVectorIndex.set_centroids: c must be finite")
+        self._assign(self._quantizer("set_centroids", int(c.shape[0])), c)
+        return self
+
+    def _two_phase(self, who: str, ncand, hi: int) -> int:
+        if isinstance(ncand, bool) or not isinstance(ncand, (int, np.integer)) or not 1 <= int(ncand) <= K_MAX:
+            raise ValueError(f"MultiVectorIndex.{who}: ncand must be an int in [1, {K_MAX}]")
+        if hi > int(ncand):
+            raise ValueError(f"MultiVectorIndex.{who}: ranks up to {hi} need ncand >= {hi}")
+        if self.built and self.codes is None:
+            raise RuntimeError(f"MultiVectorIndex.{who}: call train_centroids() or set_centroids() first")
+        return int(ncand)
+
+    def _launches(self, qmv, ptr, query_slice):
+        """Per launch: (first query, queries, their rows, their host pointer array)."""
+        for s, m in self._slices(ptr, query_slice):
+            yield s, m, qmv[ptr[s]:ptr[s + m]], (C.c_int64 * (m + 1))(*[v - ptr[s] for v in ptr[s:s + m + 1]])
+
+    def _candidates(self, qmv, ptr, ex_ptr, ex_doc, ncand: int, chunk_docs: int, query_slice: int):
+        nq, nd, dev, nc = len(ptr) - 1, self.num_docs, self.device, int(self.centroids.shape[0])
+        approx, docs, _, _ = search_outputs(nq, ncand, dev, False)
+        with torch.cuda.device(dev):
+            for s, m, rows, hq in self._launches(qmv, ptr, query_slice):
+                ws, ws_bytes = workspace("snx_mv_candidates_workspace_bytes", dev, hq, m, nd, nc, ncand, chunk_docs)
+                call("snx_mv_candidates", _p(self.codes), self.num_rows, self._hptr, nd, _p(self.centroids), nc, _p(rows),
+                     int(self.dtype == torch.float32), self.dim, int(rows.shape[0]), hq, m, _p(at(ex_ptr, s)), _p(ex_doc),
+                     ncand, chunk_docs, _p(docs[s:]), _p(approx[s:]), _p(ws), ws_bytes, _stream())
+        return approx, docs
+
+    def _rescore(self, qmv, ptr, cand: torch.Tensor, lo: int, hi: int, query_slice: int):
+        nq, nd, dev, ncand = len(ptr) - 1, self.num_docs, self.device, int(cand.shape[1])
+        scores, docs, _, _ = search_outputs(nq, hi - lo, dev, False)
+        found = torch.empty(nq, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            for s, m, rows, hq in self._launches(qmv, ptr, query_slice):
+                ws, ws_bytes = workspace("snx_mv_rescore_workspace_bytes", dev, hq, m, nd, ncand)
+                call("snx_mv_rescore", _p(self.rows), _p(rows), int(self.dtype == torch.float32), self.dim, self.num_rows,
+                     self._hptr, nd, int(rows.shape[0]), hq, m, _p(cand[s:]), ncand, lo, hi, _p(docs[s:]), _p(scores[s:]),
+                     _p(found[s:]), _p(ws), ws_bytes, _stream())
+        return scores, docs, found
+
+    def candidates(self, qmv: torch.Tensor, q_ptr, ncand: int, exclude=None, chunk_docs: int = 0, query_slice: int = 0
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The ``ncand`` best documents of each query under the centroid score a(q, d) (the class docstring) among the
+        documents with rows that are not in ``exclude[q]`` -> (a [nq, ncand] fp32, docs [nq, ncand] int32); unused slots
+        0 / -1."""
+        ncand = self._two_phase("candidates", ncand, 0)
+        qmv, ptr, chunk_docs = self._queries("candidates", qmv, q_ptr, chunk_docs, query_slice)
+        ex_ptr, ex_doc = exclusion_or_null(exclude, len(ptr) - 1, self.num_docs, self.device)
+        return self._candidates(qmv, ptr, ex_ptr, ex_doc, ncand, chunk_docs, query_slice)
+
+    def search_two_phase(self, qmv: torch.Tensor, q_ptr, k: int, ncand: int, chunk_docs: int = 0, query_slice: int = 0
+                         ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``search`` over the ``ncand`` >= ``k`` candidates of ``candidates``, scored exactly."""
+        k = int(k)
+        if not 1 <= k <= K_MAX:
+            raise ValueError(f"MultiVectorIndex.search_two_phase: k must be in [1, {K_MAX}]")
+        ncand = self._two_phase("search_two_phase", ncand, k)
+        qmv, ptr, chunk_docs = self._queries("search_two_phase", qmv, q_ptr, chunk_docs, query_slice)
+        _, cand = self._candidates(qmv, ptr, None, None, ncand, chunk_docs, query_slice)
+        return self._rescore(qmv, ptr, cand, 0, k, query_slice)[:2]
+
+    def search_band_two_phase(self, qmv: torch.Tensor, q_ptr, lo: int, hi: int, ncand: int, exclude=None,
+                              chunk_docs: int = 0, query_slice: int = 0
+                              ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``search_band`` over the ``ncand`` >= ``hi`` candidates of ``candidates`` (``exclude`` applies there), scored
+        exactly."""
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo < hi <= K_MAX:
+            raise ValueError(f"MultiVectorIndex.search_band_two_phase: need 0 <= lo < hi <= {K_MAX}")
+        ncand = self._two_phase("search_band_two_phase", ncand, hi)
+        qmv, ptr, chunk_docs = self._queries("search_band_two_phase", qmv, q_ptr, chunk_docs, query_slice)
+        ex_ptr, ex_doc = exclusion_or_null(exclude, len(ptr) - 1, self.num_docs, self.device)
+        _, cand = self._candidates(qmv, ptr, ex_ptr, ex_doc, ncand, chunk_docs, query_slice)
+        return self._rescore(qmv, ptr, cand, lo, hi, query_slice)

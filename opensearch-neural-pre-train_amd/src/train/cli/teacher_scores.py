@@ -14,7 +14,8 @@
         [--dense-weight 1 --sparse-weight 1 --colbert-weight 1] [--max-length 256] \\
         [--batch-tokens 16384] [--chunk-records 256] [--precision bf16|fp32] [--tokenizer gpu:DIR|unigram:DIR]
     python -m src.train.cli.teacher_scores mine-mv --model-dir /models/bge-m3 --input-pattern "data/v29.0_kd/train_*.jsonl" \\
-        --output-dir data/v30.0_mv_neg [--k 7 --rank-start 10 --rank-end 50 --max-length 256 --precision bf16]
+        --output-dir data/v30.0_mv_neg [--k 7 --rank-start 10 --rank-end 50 --max-length 256 --precision bf16] \\
+        [--index exact|centroid --ncentroids 1024 --ncand 0]
 
 ``mine-mv`` mines hard negatives under the multi-vector teacher (src.train.mining.multivector.mine_multivector_negatives): the
 unique positives of the shards are encoded into an ``snx.retrieval.MultiVectorIndex`` (csrc/mv_search.hip), every query is
@@ -120,6 +121,11 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     sp.add_argument("--batch-tokens", type=int, default=16384, help="token rows per forward")
     sp.add_argument("--chunk-texts", type=int, default=256, help="texts per encoder call")
     sp.add_argument("--chunk-docs", type=int, default=0)
+    sp.add_argument("--index", choices=("exact", "centroid"), default="exact",
+                    help="centroid: candidates from the centroid-interaction pass (csrc/mv_centroid.hip), scored exactly")
+    sp.add_argument("--ncentroids", type=int, default=1024, help="--index centroid: centroids trained over the store's rows")
+    sp.add_argument("--ncand", type=int, default=0,
+                    help="--index centroid: candidates per query (0: max(4 * rank_end, 128), capped at 1024)")
     sp.add_argument("--precision", choices=("bf16", "fp32"), default="bf16")
     sp.add_argument("--tokenizer", type=str, default=None, help="gpu:DIR or unigram:DIR, as for encode")
     sp.add_argument("--device", type=str, default="cuda:0")
@@ -127,6 +133,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     if args.command == "mine-mv":
         if args.k < 1 or not 0 <= args.rank_start < args.rank_end <= 1024:
             ap.error("need --k >= 1 and 0 <= --rank-start < --rank-end <= 1024")
+        if not 1 <= args.ncentroids <= 4096 or not (args.ncand == 0 or args.rank_end <= args.ncand <= 1024):
+            ap.error("need 1 <= --ncentroids <= 4096 and --ncand 0 or --rank-end <= --ncand <= 1024")
         if args.max_length < 2 or args.batch_tokens < 1 or args.chunk_texts < 1:
             ap.error("need --max-length >= 2, --batch-tokens >= 1, --chunk-texts >= 1")
         if args.tokenizer is not None and not args.tokenizer.startswith(("gpu:", "unigram:")):
@@ -228,7 +236,8 @@ def mine_mv_main(args: argparse.Namespace, tokenizer=None) -> dict:
     index = MultiVectorIndex(teacher.model.config.hidden_size, args.device)
     out = mine_multivector_negatives(files, args.output_dir, teacher.encode_multivector, index, k=args.k,
                                      rank_start=args.rank_start, rank_end=args.rank_end, chunk_texts=args.chunk_texts,
-                                     chunk_docs=args.chunk_docs)
+                                     chunk_docs=args.chunk_docs, index_type=args.index, ncentroids=args.ncentroids,
+                                     ncand=args.ncand)
     print(json.dumps(out))
     copy_val_files([args.val_pattern], args.output_dir)
     return out

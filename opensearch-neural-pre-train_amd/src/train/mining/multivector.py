@@ -107,9 +107,15 @@ def write_multivector_scores(input_files: Sequence[str], output_dir: str, encode
     return total
 
 
+def default_ncand(rank_end: int) -> int:
+    """Candidates per query of the centroid pass when the caller names none: four times the band's end, at least 128."""
+    return min(max(4 * int(rank_end), 128), 1024)
+
+
 def mine_multivector_negatives(input_files: Sequence[str], output_dir: str, encode_mv: Callable, index, *, k: int = 7,
                                rank_start: int = 10, rank_end: int = 50, chunk_texts: int = 256,
-                               chunk_docs: int = 0) -> Dict:
+                               chunk_docs: int = 0, index_type: str = "exact", ncentroids: int = 1024,
+                               ncand: int = 0) -> Dict:
     """Hard negatives under the late-interaction teacher: per record ``k`` negatives from ranks [rank_start, rank_end) of
     the MaxSim search of its query over the corpus, the unique positives of the shards, with the query's own positives
     (all of them, over every record of the query) excluded before ranking.  ``encode_mv(texts) -> (emb, mv_ptr, mv)``
@@ -118,12 +124,19 @@ def mine_multivector_negatives(input_files: Sequence[str], output_dir: str, enco
     then the queries.  The records written are ``mine_dense_negatives``': ``negatives[]``, ``teacher_pos_score``,
     ``teacher_neg_scores`` (the MaxSim values, rounded to 6) and the meta keys; a short band repeats its last negative.  A
     record without a string query and positive, with a query of one token or with an empty band is written unchanged.
-    Returns the counts: records, queries, docs, store_rows, store_bytes, band_fill, padded, unchanged."""
+    ``index_type="centroid"``: the band comes from ``index.search_band_two_phase`` over ``ncand`` candidates of the
+    centroid-interaction pass (0: ``default_ncand(rank_end)``), after ``index.train_centroids(ncentroids)``; the negatives
+    are then approximate, their scores and the positives' still exact.  Returns the counts: records, queries, docs, store_rows, store_bytes, band_fill, padded, unchanged."""
     import torch
     from . import META_KEYS
     k, rank_start, rank_end, chunk_texts = int(k), int(rank_start), int(rank_end), int(chunk_texts)
     if k < 1 or not 0 <= rank_start < rank_end <= 1024 or chunk_texts < 1:
         raise ValueError("multi-vector mining: need k >= 1, 0 <= rank_start < rank_end <= 1024 and chunk_texts >= 1")
+    if index_type not in ("exact", "centroid"):
+        raise ValueError('multi-vector mining: index_type is "exact" or "centroid"')
+    ncand = int(ncand) or default_ncand(rank_end)
+    if index_type == "centroid" and not rank_end <= ncand <= 1024:
+        raise ValueError("multi-vector mining: need rank_end <= ncand <= 1024")
     files = sorted(input_files)
     shards = [_read(f) for f in files]
     docs: Dict[str, int] = {}
@@ -144,6 +157,8 @@ def mine_multivector_negatives(input_files: Sequence[str], output_dir: str, enco
         rows += int(mv.shape[0])
         nbytes += int(mv.shape[0]) * int(mv.shape[1]) * mv.element_size()
     index.build()
+    if index_type == "centroid" and doc_texts:
+        index.train_centroids(int(ncentroids))
     bands: Dict[int, List] = {}                                  # query -> [(doc, score)] in rank order
     pscore: Dict = {}                                            # (query, positive) -> score
     fill = 0
@@ -154,8 +169,12 @@ def mine_multivector_negatives(input_files: Sequence[str], output_dir: str, enco
         if not kept or not doc_texts:
             continue
         qptr = [ptr[i] for i in kept] + [ptr[-1]]
-        sc, dd, found = index.search_band(mv, qptr, rank_start, rank_end, exclude=[sorted(positives[s + i]) for i in kept],
-                                          chunk_docs=chunk_docs)
+        exclude = [sorted(positives[s + i]) for i in kept]
+        if index_type == "centroid":
+            sc, dd, found = index.search_band_two_phase(mv, qptr, rank_start, rank_end, ncand, exclude=exclude,
+                                                        chunk_docs=chunk_docs)
+        else:
+            sc, dd, found = index.search_band(mv, qptr, rank_start, rank_end, exclude=exclude, chunk_docs=chunk_docs)
         sc, dd, found = sc.cpu().tolist(), dd.cpu().tolist(), found.cpu().tolist()
         pairs = [(j, d) for j, i in enumerate(kept) for d in sorted(positives[s + i])]
         ps = index.pair_scores(mv, qptr, torch.tensor(pairs, dtype=torch.long, device=mv.device)).cpu().tolist()
