@@ -756,6 +756,43 @@ int snx_mv_rescore(const void* docs, const void* q, int32_t mv_f32, int32_t D, i
                    const int32_t* cand_doc, int32_t ncand, int32_t lo, int32_t hi, int32_t* out_doc, float* out_score,
                    int32_t* out_found, void* workspace, size_t ws_bytes, hipStream_t stream);
 
+/* ---- multi-vector residual store (csrc/mv_centroid.hip, the mvr_ kernels): ColBERTv2's residual compression of a bf16
+ * store, and the rescore of the section above computed from the packed form.  A row is its centroid code plus nbits (1, 2
+ * or 4) bits per dimension; no parity with ColBERTv2's index files is claimed.
+ * Codec.  cutoffs: fp32 [2^nbits - 1], strictly ascending, on the device.  weights: [2^nbits] bf16 bit patterns (uint16)
+ * on the device.  For row j and dimension k, r = fl32(fp32(row[j, k]) - fp32(centroid[codes[j]][k])), one IEEE
+ * subtraction, and bucket(j, k) = #{m : cutoffs[m] < r} (a NaN residual: bucket 0).  Packing order: a row is D nbits / 8
+ * bytes, and dimension k of it is the nbits bits at bit k nbits of those bytes read as one little-endian number (bit b
+ * is bit b % 8 of byte b / 8).  So the 16 dimensions 16 u .. 16 u + 15 are ONE aligned word of 16 nbits bits (2, 4 or 8
+ * bytes), word u of the row: a scorer thread's share of a 64-wide K slice.  The row that the packed form holds is
+ * fl32(fp32(centroid[codes[j]][k]) + fp32(weights[bucket(j, k)])); the scorer never forms it.
+ * snx_mv_residual_encode: rows [n, D] bf16 with their codes [n] -> bits [n, D nbits / 8]; rows, centroids and bits
+ * 16-byte aligned.  It reads a slice of rows and writes that slice's bytes, so a store is packed slice by slice.
+ * snx_mv_rescore_residual.  snx_mv_rescore's operands with codes [drows], bits [drows, D nbits / 8], centroids [nc, D]
+ * bf16 and weights in place of docs; mv_f32 must be 0 (SNX_E_ARG: the packed store is bf16).  Score (part of the ABI):
+ *   t(i, j) = fl32(S32[i, codes[j]] + R(i, j)),
+ * S32[i, c] the fp32 product of query row i and centroid c on the bf16 MFMA with k ascending (snx_mv_candidates' chain,
+ * before its rounding to bf16), R(i, j) the same chain of query row i against the bf16 row weights[bucket(j, k)];
+ * m(i, d) = max over the rows j of d of t(i, j); the maxima are added in ascending row order within each run of 64 query
+ * rows counted from the query's own first row, the run sums added in ascending order, one division by Lq -- as
+ * snx_maxsim_pairs adds.  The score is a function of the query, the document's codes and bits, the centroids and the
+ * weights alone: not of the other queries, their order, or the launch.  A code >= nc is read as nc - 1.
+ * Ranks lo .. hi-1 -> out_doc / out_score / out_found as snx_mv_rescore.  raw_score [nq, ncand] (NULL: not written): the
+ * score of every candidate slot in cand_doc's order, bit-equal to the ranked value, 0 for a skipped slot.
+ * SNX_E_SHAPE / SNX_E_ARG before any launch: D, nbits not 1 / 2 / 4, nc outside 1 .. 4096, ncand, lo, hi, a null or
+ * misaligned pointer, bad pointer arrays.  workspace: snx_mv_rescore_residual_workspace_bytes(q_ptr, nq, nd, nc, ncand):
+ * the partial sums and at most 128 MB of fp32 table blocks [nc][64], one per (query, run); the host walks groups of them. */
+int snx_mv_residual_encode(const void* rows, int64_t n, const uint16_t* codes, const void* centroids, int32_t nc, int32_t D,
+                           int32_t nbits, const float* cutoffs, void* bits, hipStream_t stream);
+size_t snx_mv_rescore_residual_workspace_bytes(const int64_t* q_ptr /*[host]*/, int32_t nq, int32_t nd, int32_t nc,
+                                               int32_t ncand);
+int snx_mv_rescore_residual(const uint16_t* codes, const void* bits, const void* centroids, const uint16_t* weights,
+                            int32_t nc, int32_t nbits, const void* q, int32_t mv_f32, int32_t D, int64_t drows,
+                            const int64_t* doc_ptr /*[host]*/, int32_t nd, int64_t qrows, const int64_t* q_ptr /*[host]*/,
+                            int32_t nq, const int32_t* cand_doc, int32_t ncand, int32_t lo, int32_t hi, int32_t* out_doc,
+                            float* out_score, int32_t* out_found, float* raw_score, void* workspace, size_t ws_bytes,
+                            hipStream_t stream);
+
 /* ---- two-phase dense retrieval (csrc/dense_two_phase.hip): the result of the exact dense section with most of the work
  * on the bf16 MFMA.  Phase 1 scores bf16 copies of the operands and proposes k1 candidates per query; phase 2 scores the
  * candidates by the exact section's chain on the fp32 operands; a per-query certificate proves, from norms computed once,

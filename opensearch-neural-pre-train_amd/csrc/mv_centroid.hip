@@ -38,6 +38,9 @@
 //                  ranks lo .. hi - 1.  Every bit is snx_maxsim_pairs'.
 // part holds a bounded group of chunks; the host walks the groups on the stream.  Nothing of size nq x nd exists, and
 // there is no float atomic anywhere.
+// The residual-compressed store and its scorer (mvr_* kernels, "multi-vector residual store") follow the rescore below.
+#include <vector>
+
 #include "dense_common.h"
 #include "snx.h"
 
@@ -465,6 +468,256 @@ struct MvcRescorePlan {
   }
 };
 
+// ------------------------------------------------------------------------------------------------ residual store
+// include/snx.h "multi-vector residual store": a bf16 row is kept as its centroid code plus nbits bits per dimension that
+// name a bucket of row - centroid, and a candidate is scored from that form.  The product splits,
+//   <q_i, centroid[code_j] + w_j> -> fl32(S32[i, code_j] + R(i, j)),
+// S32 the fp32 table of query row x centroid products and R the MFMA chain of the query row against the row of bf16
+// bucket weights, so that a document row costs D nbits / 8 bytes of bits and 256 bytes of table, never 2 D.
+// mvr_encode_kernel  One thread per 32-bit word of the packed store: 32 / nbits dimensions of a row, the residual by one
+//                    fp32 subtraction, the bucket by counting cutoffs below it.  Dimension k of a row sits at bit k nbits
+//                    of the row's D nbits / 8 bytes, little-endian.
+// mvr_table_kernel   mvc_table_kernel's tile, written as fp32: one block [nc][64] per (query, 64-row run), so that a block
+//                    does not depend on where the call's packing put the query.  A bounded group of blocks exists at a
+//                    time (MVR_TABLE_BUDGET); the host walks the groups on the stream.
+// mvr_score_kernel   mvc_rescore_kernel's grid and MFMA loop.  The query run goes through MvcBf16's K-slice stage as
+//                    there.  The document operand never exists in memory: thread t owns row t >> 2 of the 64-row tile and
+//                    dimensions 16 (t & 3) .. + 15 of every 64-wide K slice, which with the order above is ONE aligned
+//                    word of 16 nbits bits (2, 4 or 8 bytes), loaded one slice ahead with the row clamped into the
+//                    document -- no branch around a load.  Eight lookups in an LDS table of 2^(2 nbits) weight PAIRS
+//                    (two bf16 per entry, at most 1 KB) turn the word into the 32 bytes the thread writes into the stage
+//                    in MvcBf16's layout.  The lane's code and its four 16-byte table pieces (accumulator rows
+//                    (r & 3) + 8 (r >> 2) + 4 h: four runs of four consecutive query rows) are requested before the K loop
+//                    and added after it; columns past the document's end become -inf; maxima and sums as
+//                    mvc_rescore_kernel.  mvc_order_kernel ranks; mvr_raw_kernel writes the scores in candidate order.
+constexpr size_t MVR_TABLE_BUDGET = (size_t)128 << 20;     // bytes of fp32 table blocks per launch group
+
+__device__ __forceinline__ float mvr_bf16_f32(uint16_t b) { return bits_to_f32((uint32_t)b); }
+
+template <int NB>
+__global__ __launch_bounds__(MVC_THREADS) void mvr_encode_kernel(
+    const uint16_t* __restrict__ rows, const uint16_t* __restrict__ codes, int64_t n, const uint16_t* __restrict__ Cn,
+    int32_t nc, int32_t D, const float* __restrict__ cutoffs, uint32_t* __restrict__ out) {
+  constexpr int DPW = 32 / NB, NCUT = (1 << NB) - 1;         // dimensions per word: 32, 16 or 8 (a multiple of 8)
+  const int wpr = D / DPW;
+  const int64_t idx = (int64_t)blockIdx.x * MVC_THREADS + threadIdx.x;
+  if (idx >= n * wpr) return;
+  const int64_t row = idx / wpr;
+  const int k0 = (int)(idx - row * wpr) * DPW;
+  const int code = min((int)codes[row], nc - 1);
+  float cut[NCUT];
+#pragma unroll
+  for (int m = 0; m < NCUT; ++m) cut[m] = cutoffs[m];
+  uint32_t word = 0u;
+#pragma unroll
+  for (int v = 0; v < DPW / 8; ++v) {
+    const u32x4 x = *(const u32x4*)(rows + row * D + k0 + 8 * v);
+    const u32x4 c = *(const u32x4*)(Cn + (long)code * D + k0 + 8 * v);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const uint32_t sh = 16 * (u & 1);
+      const float r = mvr_bf16_f32((uint16_t)(x[u >> 1] >> sh)) - mvr_bf16_f32((uint16_t)(c[u >> 1] >> sh));
+      uint32_t bucket = 0u;
+#pragma unroll
+      for (int m = 0; m < NCUT; ++m) bucket += cut[m] < r ? 1u : 0u;
+      word |= bucket << (NB * (8 * v + u));
+    }
+  }
+  out[idx] = word;
+}
+
+// the query whose runs hold block `blk`: blk_ptr [nq + 1] ascends from 0, blk_ptr[q + 1] - blk_ptr[q] >= 1
+__device__ __forceinline__ int mvr_query_of(const int64_t* __restrict__ blk_ptr, int32_t nq, int64_t blk) {
+  int lo = 0, hi = nq;                                       // the last q with blk_ptr[q] <= blk
+  while (hi - lo > 1) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (blk_ptr[mid] <= blk) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// table[((blk - b0) nc + c) 64 + i] = S32[row i of the run, c]; a row past the query's end holds the product of a zero row
+__global__ __launch_bounds__(MVC_THREADS) void mvr_table_kernel(
+    const bf16_t* __restrict__ Q, const int64_t* __restrict__ q_ptr, const int64_t* __restrict__ blk_ptr, int32_t nq,
+    int64_t b0, const bf16_t* __restrict__ Cn, int32_t nc, int32_t D, float* __restrict__ table) {
+  __shared__ __attribute__((aligned(16))) MvcBf16::Stage stage[2];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int wm = wave >> 1, wn = wave & 1, c = lane & 31, h = lane >> 5;
+  const int64_t blk = b0 + blockIdx.x;
+  const int q = mvr_query_of(blk_ptr, nq, blk);
+  const long q0 = q_ptr[q] + (blk - blk_ptr[q]) * MVC_TILE;
+  const int nr = (int)max(0l, min((long)MVC_TILE, q_ptr[q + 1] - q0));
+  const int c0 = blockIdx.y * MVC_TILE;
+  f32x16 acc;
+  mvc_tile<MvcBf16>(Q, q0, nr, Cn, (long)c0, min(MVC_TILE, nc - c0), D, stage, acc);
+  const int cent = c0 + wn * 32 + c;
+  if (cent >= nc) return;
+  float* dst = table + ((long)blockIdx.x * nc + cent) * MVC_TILE + wm * 32 + 4 * h;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) *(f32x4*)(dst + 8 * j) = (f32x4){acc[4 * j], acc[4 * j + 1], acc[4 * j + 2], acc[4 * j + 3]};
+}
+
+template <int NB> struct MvrWord;
+template <> struct MvrWord<1> { typedef uint16_t type; };
+template <> struct MvrWord<2> { typedef uint32_t type; };
+template <> struct MvrWord<4> { typedef unsigned long long type; };
+
+// a thread's word of a K slice -> its 16 bf16 weights in the stage: row t >> 2, columns 16 (t & 3) .. + 15
+template <int NB>
+__device__ __forceinline__ void mvr_expand(typename MvrWord<NB>::type w, const uint32_t* lut, int t,
+                                           uint16_t (*S)[MvcBf16::PITCH]) {
+  uint32_t o[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) o[i] = lut[(uint32_t)(w >> (2 * NB * i)) & ((1u << (2 * NB)) - 1u)];
+  // All eight lookups land before the first store.  hipcc would overlap the first store with the last four lookups under
+  // counted waits that are right only because LDS stores hold slots of the same counter; the build's scan of LDS reads
+  // (snx/asmcheck.py) counts reads alone, and the overlap is worth nothing next to the MFMA loop.
+  __builtin_amdgcn_s_waitcnt(0xC07F);                         // lgkmcnt(0)
+  u32x4* dst = (u32x4*)&S[t >> 2][(t & 3) * 16];
+  dst[0] = (u32x4){o[0], o[1], o[2], o[3]};
+  dst[1] = (u32x4){o[4], o[5], o[6], o[7]};
+}
+
+// partial[pair qblocks + qb] as mvc_rescore_kernel's, from the packed store; the launch covers queries q_first .. and the
+// table blocks b0 .. b1 - 1, a run outside them is another launch's
+template <int NB>
+__global__ __launch_bounds__(MVC_THREADS) void mvr_score_kernel(
+    const uint16_t* __restrict__ codes, const unsigned char* __restrict__ bits, const uint16_t* __restrict__ weights,
+    const float* __restrict__ table, int32_t nc, const bf16_t* __restrict__ Q, int32_t D,
+    const int64_t* __restrict__ doc_ptr, int32_t nd, const int64_t* __restrict__ q_ptr,
+    const int64_t* __restrict__ blk_ptr, int64_t b0, int64_t b1, int32_t q_first, const int32_t* __restrict__ cand_doc,
+    int32_t ncand, int32_t qblocks, float* __restrict__ partial) {
+  typedef typename MvrWord<NB>::type W;
+  typedef MvcBf16 P;
+  __shared__ __attribute__((aligned(16))) P::Stage stage[2];
+  __shared__ float rmax[2][MVC_TILE];
+  __shared__ uint32_t lut[1 << (2 * NB)];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int wm = wave >> 1, wn = wave & 1, c = lane & 31, h = lane >> 5;
+  const long pair = (long)q_first * ncand + blockIdx.x;
+  const int qb = blockIdx.y, q = (int)(pair / ncand);
+  const int32_t d = cand_doc[pair];
+  if ((uint32_t)d >= (uint32_t)nd) return;
+  const long d0 = doc_ptr[d], Ld = doc_ptr[d + 1] - d0;
+  const long q0 = q_ptr[q] + (long)qb * MVC_TILE;
+  const int nq = (int)min((long)MVC_TILE, q_ptr[q + 1] - q0);  // query rows of this run
+  if (Ld <= 0 || nq <= 0) return;
+  const int64_t blk = blk_ptr[q] + qb;
+  if (blk < b0 || blk >= b1) return;
+  if (t < (1 << (2 * NB)))                                    // entry e: the weights of buckets e & mask (low half) and e >> NB
+    lut[t] = (uint32_t)weights[t & ((1 << NB) - 1)] | ((uint32_t)weights[t >> NB] << 16);
+  __syncthreads();
+  const float* tab = table + (blk - b0) * (long)nc * MVC_TILE + wm * 32 + 4 * h;
+  const int nk = D / P::KT, wpr = D / 16;                     // words of a row
+  float m[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) m[r] = -INFINITY;
+  for (long n0 = 0; n0 < Ld; n0 += MVC_TILE) {
+    const int nv = (int)min((long)MVC_TILE, Ld - n0);          // doc rows of this tile
+    const W* wsrc = (const W*)bits + (d0 + n0 + min(t >> 2, nv - 1)) * wpr + (t & 3);
+    const int code = min((int)codes[d0 + n0 + min(wn * 32 + c, nv - 1)], nc - 1);
+    f32x4 s[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[j] = *(const f32x4*)(tab + (long)code * MVC_TILE + 8 * j);
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    P::Regs ra;
+    P::fetch(Q, q0, nq, D, 0, t, ra);
+    W w = wsrc[0];
+    P::put(t, ra, stage[0].a);
+    mvr_expand<NB>(w, lut, t, stage[0].b);
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {                         // mvc_tile's loop: k ascending
+      const int cur = kt & 1;
+      if (kt + 1 < nk) {
+        P::fetch(Q, q0, nq, D, (kt + 1) * P::KT, t, ra);
+        w = wsrc[4 * (kt + 1)];
+      }
+      P::mma(stage[cur], wm, wn, c, h, acc);
+      if (kt + 1 < nk) {
+        P::put(t, ra, stage[cur ^ 1].a);
+        mvr_expand<NB>(w, lut, t, stage[cur ^ 1].b);
+      }
+      __syncthreads();
+    }
+    const bool ok = wn * 32 + c < nv;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) m[r] = fmaxf(m[r], ok ? s[r >> 2][r & 3] + acc[r] : -INFINITY);
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) m[r] = fmaxf(m[r], __shfl_xor(m[r], o, 64));
+    if (c == 0) rmax[wn][wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h] = m[r];
+  }
+  __syncthreads();
+  if (t == 0) {
+    float sum = 0.f;
+    for (int i = 0; i < nq; ++i) sum += fmaxf(rmax[0][i], rmax[1][i]);      // ascending rows
+    partial[pair * qblocks + qb] = sum;
+  }
+}
+
+// raw[q ncand + j] = the score mvc_order_kernel ranks for candidate slot j, 0 for a slot it skips
+__global__ __launch_bounds__(MVC_THREADS) void mvr_raw_kernel(
+    const float* __restrict__ partial, const int32_t* __restrict__ cand_doc, const int64_t* __restrict__ q_ptr,
+    const int64_t* __restrict__ doc_ptr, int32_t nd, int64_t npairs, int32_t ncand, int32_t qblocks,
+    float* __restrict__ raw) {
+  const int64_t i = (int64_t)blockIdx.x * MVC_THREADS + threadIdx.x;
+  if (i >= npairs) return;
+  const int q = (int)(i / ncand);
+  const int32_t d = cand_doc[i];
+  float out = 0.f;
+  if ((uint32_t)d < (uint32_t)nd && doc_ptr[d + 1] > doc_ptr[d]) {
+    const int Lq = (int)(q_ptr[q + 1] - q_ptr[q]);
+    const int nb = (Lq + MVC_TILE - 1) / MVC_TILE;
+    const float* v = partial + i * qblocks;
+    float s = v[0];
+    for (int b = 1; b < nb; ++b) s += v[b];                   // ascending runs
+    out = s / (float)Lq;
+  }
+  raw[i] = out;
+}
+
+inline bool mvr_bad_nbits(int32_t nbits) { return nbits != 1 && nbits != 2 && nbits != 4; }
+
+// the residual rescore's workspace: MvcRescorePlan's arrays, the first table block of every query, one group of blocks
+struct MvrPlan {
+  size_t dptr, qptr, bptr, partial, table, total;
+  int qblocks;
+  int64_t nblocks, group;
+  bool ok;
+  MvrPlan(const int64_t* q_ptr, int32_t nq, int32_t nd, int32_t nc, int32_t ncand) {
+    const MvcRescorePlan base(q_ptr, nq, nd, ncand);
+    ok = base.ok;
+    qblocks = base.qblocks;
+    nblocks = 0;
+    for (int32_t q = 0; q < nq; ++q) nblocks += (q_ptr[q + 1] - q_ptr[q] + MVC_TILE - 1) / MVC_TILE;
+    const size_t block = (size_t)nc * MVC_TILE * 4;
+    const int64_t cap = (int64_t)(MVR_TABLE_BUDGET / block);  // >= 128 blocks at nc = 4096
+    group = nblocks < cap ? nblocks : cap;
+    Arena a;
+    dptr = a.take(((size_t)nd + 1) * 8);
+    qptr = a.take(((size_t)nq + 1) * 8);
+    bptr = a.take(((size_t)nq + 1) * 8);
+    partial = a.take((size_t)nq * (size_t)ncand * (size_t)qblocks * 4);
+    table = a.take((size_t)group * block);
+    total = a.off;
+  }
+};
+
+template <int NB>
+int mvr_launch_score(dim3 grid, hipStream_t st, const uint16_t* codes, const void* bits, const uint16_t* weights,
+                     const float* table, int32_t nc, const bf16_t* q, int32_t D, const int64_t* dptr, int32_t nd,
+                     const int64_t* qptr, const int64_t* bptr, int64_t b0, int64_t b1, int32_t q_first,
+                     const int32_t* cand_doc, int32_t ncand, int32_t qblocks, float* partial) {
+  hipLaunchKernelGGL(mvr_score_kernel<NB>, grid, dim3(MVC_THREADS), 0, st, codes, (const unsigned char*)bits, weights, table,
+                     nc, q, D, dptr, nd, qptr, bptr, b0, b1, q_first, cand_doc, ncand, qblocks, partial);
+  SNX_CHECK_LAUNCH();
+  return SNX_OK;
+}
+
 }  // namespace
 
 extern "C" size_t snx_mv_candidates_workspace_bytes(const int64_t* q_ptr, int32_t nq, int32_t nd, int32_t nc, int32_t ncand,
@@ -581,5 +834,100 @@ extern "C" int snx_mv_rescore(const void* docs, const void* q, int32_t mv_f32, i
   hipLaunchKernelGGL(mvc_order_kernel, dim3(nq), dim3(SR_THREADS), 0, st, (const float*)partial, cand_doc, qptr, dptr, nd,
                      ncand, plan.qblocks, lo, hi, out_doc, out_score, out_found);
   SNX_CHECK_LAUNCH();
+  return SNX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ residual store: host
+extern "C" int snx_mv_residual_encode(const void* rows, int64_t n, const uint16_t* codes, const void* centroids, int32_t nc,
+                                      int32_t D, int32_t nbits, const float* cutoffs, void* bits, hipStream_t st) {
+  if (D <= 0 || (D % 64) != 0 || D > MVC_DMAX || n < 0 || n > 0x7FFFFFFFFFFFFFFFL / D) return SNX_E_SHAPE;
+  if (mvr_bad_nbits(nbits) || nc < 1 || nc > MVC_NC_MAX) return SNX_E_ARG;
+  if (n == 0) return SNX_OK;
+  if (!rows || !codes || !centroids || !cutoffs || !bits || ((uintptr_t)rows & 15) != 0 || ((uintptr_t)centroids & 15) != 0 ||
+      ((uintptr_t)bits & 15) != 0)
+    return SNX_E_ARG;
+  const int64_t words = n * (D * nbits / 32), blocks = (words + MVC_THREADS - 1) / MVC_THREADS;
+  if (blocks > 0x7FFFFFFFL) return SNX_E_SHAPE;
+  const dim3 grid((unsigned)blocks);
+  const uint16_t *r = (const uint16_t*)rows, *c = (const uint16_t*)centroids;
+  if (nbits == 1)
+    hipLaunchKernelGGL(mvr_encode_kernel<1>, grid, dim3(MVC_THREADS), 0, st, r, codes, n, c, nc, D, cutoffs, (uint32_t*)bits);
+  else if (nbits == 2)
+    hipLaunchKernelGGL(mvr_encode_kernel<2>, grid, dim3(MVC_THREADS), 0, st, r, codes, n, c, nc, D, cutoffs, (uint32_t*)bits);
+  else
+    hipLaunchKernelGGL(mvr_encode_kernel<4>, grid, dim3(MVC_THREADS), 0, st, r, codes, n, c, nc, D, cutoffs, (uint32_t*)bits);
+  SNX_CHECK_LAUNCH();
+  return SNX_OK;
+}
+
+extern "C" size_t snx_mv_rescore_residual_workspace_bytes(const int64_t* q_ptr, int32_t nq, int32_t nd, int32_t nc,
+                                                          int32_t ncand) {
+  if (nq <= 0 || nd < 0 || nc < 1 || nc > MVC_NC_MAX || ncand < 1 || ncand > SR_KMAX ||
+      !mvc_ptr_ok(q_ptr, nq, 0x7FFFFFFFFFFFFFFFL, true))
+    return 0;
+  const MvrPlan plan(q_ptr, nq, nd, nc, ncand);
+  return plan.ok ? plan.total : 0;
+}
+
+extern "C" int snx_mv_rescore_residual(const uint16_t* codes, const void* bits, const void* centroids, const uint16_t* weights,
+                                       int32_t nc, int32_t nbits, const void* q, int32_t mv_f32, int32_t D, int64_t drows,
+                                       const int64_t* doc_ptr, int32_t nd, int64_t qrows, const int64_t* q_ptr, int32_t nq,
+                                       const int32_t* cand_doc, int32_t ncand, int32_t lo, int32_t hi, int32_t* out_doc,
+                                       float* out_score, int32_t* out_found, float* raw_score, void* workspace,
+                                       size_t ws_bytes, hipStream_t st) {
+  if (D <= 0 || (D % 64) != 0 || D > MVC_DMAX || qrows < 0 || drows < 0 || nq < 0 || nd < 0) return SNX_E_SHAPE;
+  if (mv_f32 || mvr_bad_nbits(nbits) || nc < 1 || nc > MVC_NC_MAX || ncand < 1 || ncand > SR_KMAX || lo < 0 || hi <= lo ||
+      hi > ncand)
+    return SNX_E_ARG;
+  if (nq == 0) return SNX_OK;
+  if (!q || !centroids || !weights || !cand_doc || !out_doc || !out_score || !out_found || !workspace ||
+      ((uintptr_t)q & 15) != 0 || ((uintptr_t)centroids & 15) != 0 || ((uintptr_t)bits & 15) != 0 ||
+      ((uintptr_t)workspace & 15) != 0)
+    return SNX_E_ARG;
+  if (!mvc_ptr_ok(doc_ptr, nd, drows, false) || !mvc_ptr_ok(q_ptr, nq, qrows, true)) return SNX_E_ARG;
+  if (doc_ptr[nd] > 0 && (!codes || !bits)) return SNX_E_ARG;
+  const MvrPlan plan(q_ptr, nq, nd, nc, ncand);
+  if (!plan.ok) return SNX_E_SHAPE;
+  if (ws_bytes < plan.total) return SNX_E_ARG;
+  char* ws = (char*)workspace;
+  std::vector<int64_t> blk((size_t)nq + 1, 0);                // the first table block of every query
+  for (int32_t i = 0; i < nq; ++i) blk[i + 1] = blk[i] + (q_ptr[i + 1] - q_ptr[i] + MVC_TILE - 1) / MVC_TILE;
+  RC(mvc_upload(ws, plan.dptr, doc_ptr, ((size_t)nd + 1) * 8, st));
+  RC(mvc_upload(ws, plan.qptr, q_ptr, ((size_t)nq + 1) * 8, st));
+  RC(mvc_upload(ws, plan.bptr, blk.data(), ((size_t)nq + 1) * 8, st));   // pageable: staged when the call returns
+  const int64_t* dptr = (const int64_t*)(ws + plan.dptr);
+  const int64_t* qptr = (const int64_t*)(ws + plan.qptr);
+  const int64_t* bptr = (const int64_t*)(ws + plan.bptr);
+  float *partial = (float*)(ws + plan.partial), *table = (float*)(ws + plan.table);
+  const bf16_t* Q = (const bf16_t*)q;
+  int32_t qa = 0;                                             // the query that holds block b0
+  for (int64_t b0 = 0; b0 < plan.nblocks; b0 += plan.group) {  // one group of table blocks after the other, in order
+    const int64_t b1 = b0 + plan.group < plan.nblocks ? b0 + plan.group : plan.nblocks;
+    while (blk[qa + 1] <= b0) ++qa;
+    int32_t qe = qa;                                          // the query that holds block b1 - 1
+    while (blk[qe + 1] < b1) ++qe;
+    hipLaunchKernelGGL(mvr_table_kernel, dim3((unsigned)(b1 - b0), (unsigned)((nc + MVC_TILE - 1) / MVC_TILE)),
+                       dim3(MVC_THREADS), 0, st, Q, qptr, bptr, nq, b0, (const bf16_t*)centroids, nc, D, table);
+    SNX_CHECK_LAUNCH();
+    const dim3 grid((unsigned)((long)(qe - qa + 1) * ncand), (unsigned)plan.qblocks);
+    if (nbits == 1)
+      RC(mvr_launch_score<1>(grid, st, codes, bits, weights, table, nc, Q, D, dptr, nd, qptr, bptr, b0, b1, qa, cand_doc,
+                             ncand, plan.qblocks, partial));
+    else if (nbits == 2)
+      RC(mvr_launch_score<2>(grid, st, codes, bits, weights, table, nc, Q, D, dptr, nd, qptr, bptr, b0, b1, qa, cand_doc,
+                             ncand, plan.qblocks, partial));
+    else
+      RC(mvr_launch_score<4>(grid, st, codes, bits, weights, table, nc, Q, D, dptr, nd, qptr, bptr, b0, b1, qa, cand_doc,
+                             ncand, plan.qblocks, partial));
+  }
+  hipLaunchKernelGGL(mvc_order_kernel, dim3(nq), dim3(SR_THREADS), 0, st, (const float*)partial, cand_doc, qptr, dptr, nd,
+                     ncand, plan.qblocks, lo, hi, out_doc, out_score, out_found);
+  SNX_CHECK_LAUNCH();
+  if (raw_score) {
+    const int64_t npairs = (int64_t)nq * ncand;
+    hipLaunchKernelGGL(mvr_raw_kernel, dim3((unsigned)((npairs + MVC_THREADS - 1) / MVC_THREADS)), dim3(MVC_THREADS), 0, st,
+                       (const float*)partial, cand_doc, qptr, dptr, nd, npairs, ncand, plan.qblocks, raw_score);
+    SNX_CHECK_LAUNCH();
+  }
   return SNX_OK;
 }

@@ -82,7 +82,11 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     # and for the candidate pass: the walk's four packed maxima and its two code pieces, the table and rescore tiles'
     # accumulators and prefetched slices, and the selection's keys stay in registers and LDS
     "mv_centroid.hip": ("mvc_table_kernel", "mvc_walk_kernel", "mvc_select_kernel", "mvc_merge_kernel",
-                        "mvc_rescore_kernel", "mvc_order_kernel"),
+                        "mvc_rescore_kernel", "mvc_order_kernel",
+                        # the residual store: the score tile's accumulators, running maxima, the prefetched query slice,
+                        # the packed word and the sixteen table entries of a lane stay in registers; the encode and raw
+                        # kernels hold no LDS and are not listed
+                        "mvr_table_kernel", "mvr_score_kernel"),
     # and for the lexical weights: the 64-bit keys live in LDS, a thread's key, its ballot and the unused ids (kernel
     # arguments) in registers; the head's row kernel and the pair scorer hold no LDS and are not listed
     "teacher_lex.hip": ("tl_unique_kernel",),

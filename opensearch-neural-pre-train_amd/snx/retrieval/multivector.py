@@ -1,5 +1,6 @@
 """MaxSim search over a ragged multi-vector store: exact (csrc/mv_search.hip, include/snx.h "multi-vector search") and
-through a centroid-interaction candidate pass (csrc/mv_centroid.hip, "multi-vector candidate search")."""
+through a centroid-interaction candidate pass (csrc/mv_centroid.hip, "multi-vector candidate search"), over bf16 rows or
+over a residual-compressed store ("multi-vector residual store")."""
 import ctypes as C
 from typing import List, Optional, Tuple
 
@@ -16,6 +17,8 @@ MV_CHUNK_MIN, MV_CHUNK_MAX = 64, 8192  # docs per chunk of the walk
 MV_CENTROIDS_MAX = 4096                # a query group's centroid table has to fit LDS
 _MV_ASSIGN_ROWS = 1 << 18              # store rows cast to fp32 per slice of the code assignment
 _MV_ROWS_PER_LAUNCH = 1 << 15          # query rows of one launch: 512 query blocks
+MV_NBITS = (1, 2, 4)                   # bits per dimension of a residual-compressed store
+_MV_QUANTILE_MAX = 1 << 24             # elements torch.quantile takes
 
 
 def _ptr_list(ptr, rows: int, who: str, name: str) -> List[int]:
@@ -54,6 +57,18 @@ class MultiVectorIndex:
     place, and ranked.  With ``ncand`` at least the number of documents with rows the result is the exact search's, bit
     for bit; below it the result is approximate, and every returned score is still s(q, d).  ``add`` invalidates both.
 
+    A bf16 index can drop its rows for ColBERTv2's residual form, ``codes`` plus ``nbits`` bits per dimension:
+
+        index.compress(nbits, cutoffs=None, weights=None, sample_rows=1 << 14, keep_rows=False)   # after the centroids
+        rows = index.decompress(row_ids)       # fp32 [n, dim]: centroid[code] + weights[bucket], what the packed form holds
+
+    ``index.residuals`` (uint8 [num_rows, dim * nbits / 8]) holds, for dimension k of a row, the bucket
+    #{m : cutoffs[m] < fp32(row[k]) - fp32(centroid[k])} at bit k * nbits of the row's bytes (little-endian).  The
+    two-phase searches and ``pair_scores`` then score from the packed form (include/snx.h: the query-centroid product and
+    the query-weight product, each an MFMA chain, added once): s(q, d) is the MaxSim of the query with the decompressed
+    rows up to fp32 rounding, no longer ``maxsim_pairs``' bits.  ``candidates`` is unchanged.  Without ``keep_rows`` the
+    bf16 rows are released, and ``search``, ``search_band``, ``train_centroids`` and ``set_centroids`` raise.
+
     s(q, d) is bit for bit ``maxsim_pairs``' score of the two sequences; the order is ``DenseIndex``'s (score descending,
     ties lowest doc id first, every document with rows a candidate whatever the sign of its score; unused slots 0 / -1).
     Results do not depend on ``chunk_docs``, ``query_slice`` or the order of the queries.  A sequence without rows (a
@@ -71,6 +86,14 @@ class MultiVectorIndex:
         self._hptr = None
         self.centroids: Optional[torch.Tensor] = None         # [nc, dim] in the store's dtype, as the table kernel reads them
         self.codes: Optional[torch.Tensor] = None             # uint16 [num_rows]: the best centroid of every row
+        self._uncompress()
+
+    def _uncompress(self) -> None:
+        self.nbits = 0                                        # 0: not compressed
+        self.residuals: Optional[torch.Tensor] = None         # uint8 [num_rows, dim * nbits / 8]
+        self.cutoffs: Optional[torch.Tensor] = None           # fp32 [2^nbits - 1], strictly ascending
+        self.weights: Optional[torch.Tensor] = None           # fp32 [2^nbits]: the bf16 weights, widened
+        self.weights_bf16: Optional[torch.Tensor] = None
 
     @property
     def num_docs(self) -> int:
@@ -82,7 +105,12 @@ class MultiVectorIndex:
 
     @property
     def built(self) -> bool:
-        return self.rows is not None
+        return self.rows is not None or self.residuals is not None
+
+    def _need_rows(self, who: str) -> None:
+        if self.rows is None and self.residuals is not None:
+            raise RuntimeError(f"MultiVectorIndex.{who}: the bf16 rows were released by compress(); it needs "
+                               "compress(..., keep_rows=True)")
 
     def _store(self, mv, ptr, who: str, name: str) -> Tuple[torch.Tensor, List[int]]:
         if not isinstance(mv, torch.Tensor) or mv.dim() != 2 or mv.dtype not in (torch.bfloat16, torch.float32):
@@ -96,6 +124,7 @@ class MultiVectorIndex:
         return mv.contiguous(), _ptr_list(ptr, int(mv.shape[0]), f"MultiVectorIndex.{who}", f"{name}_ptr")
 
     def add(self, mv: torch.Tensor, mv_ptr) -> None:
+        self._need_rows("add")                                # the earlier rows are gone: the store cannot be rebuilt
         mv, ptr = self._store(mv, mv_ptr, "add", "mv")
         if self.num_docs + len(ptr) - 1 >= 2 ** 31:
             raise ValueError("MultiVectorIndex: doc ids are int32")
@@ -104,6 +133,7 @@ class MultiVectorIndex:
         self._ptr += [self._ptr[-1] + v for v in ptr[1:]]
         self.rows = None                                      # a new batch invalidates a built index
         self.centroids = self.codes = None                    # and its codes
+        self._uncompress()                                    # and their residuals
 
     def build(self) -> "MultiVectorIndex":
         if len(self._parts) != 1:
@@ -166,6 +196,7 @@ class MultiVectorIndex:
         k = int(k)
         if not 1 <= k <= K_MAX:
             raise ValueError(f"MultiVectorIndex.search: k must be in [1, {K_MAX}]")
+        self._need_rows("search")
         qmv, ptr, chunk_docs = self._queries("search", qmv, q_ptr, chunk_docs, query_slice)
         return self._run(qmv, ptr, None, None, 0, k, chunk_docs, query_slice, False)[:2]
 
@@ -176,6 +207,7 @@ class MultiVectorIndex:
         lo, hi = int(lo), int(hi)
         if not 0 <= lo < hi <= K_MAX:
             raise ValueError(f"MultiVectorIndex.search_band: need 0 <= lo < hi <= {K_MAX}")
+        self._need_rows("search_band")
         qmv, ptr, chunk_docs = self._queries("search_band", qmv, q_ptr, chunk_docs, query_slice)
         ex_ptr, ex_doc = exclusion_or_null(exclude, len(ptr) - 1, self.num_docs, self.device)
         return self._run(qmv, ptr, ex_ptr, ex_doc, lo, hi, chunk_docs, query_slice, True)
@@ -189,6 +221,8 @@ class MultiVectorIndex:
         nq, dev = len(ptr) - 1, self.device
         pq, pd = check_pairs(pairs, nq, self.num_docs, dev, "MultiVectorIndex.pair_scores")
         pq, pd = pq.tolist(), pd.tolist()
+        if self.residuals is not None:
+            return self._pair_scores_residual(qmv, ptr, pq, pd)
         ok = [i for i, d in enumerate(pd) if self._ptr[d + 1] > self._ptr[d]]     # a document without rows scores 0.0
         named = sorted({pd[i] for i in ok})
         local = {d: nq + i for i, d in enumerate(named)}
@@ -206,6 +240,7 @@ class MultiVectorIndex:
     def _quantizer(self, who: str, nc: int, niter: int = 0, seed: int = 0):
         """The dense helpers of ``IvfFlatIndex`` (k-means step, nearest centroid) over this index's dim and device."""
         from .ivf import IvfFlatIndex
+        self._need_rows(who)
         if not self.built:
             raise RuntimeError(f"MultiVectorIndex.{who}: call build() first")
         if self.num_rows == 0:
@@ -222,6 +257,7 @@ class MultiVectorIndex:
         for s in range(0, self.num_rows, _MV_ASSIGN_ROWS):
             codes[s:s + _MV_ASSIGN_ROWS] = quantizer._best(self.rows[s:s + _MV_ASSIGN_ROWS].float(), seen, 1)[1].reshape(-1)
         self.codes = codes.to(torch.uint16)
+        self._uncompress()                                    # residuals of other codes
 
     def train_centroids(self, ncentroids: int, niter: int = 10, seed: int = 0, sample_rows: int = 0) -> "MultiVectorIndex":
         """Spherical k-means over the store's rows as fp32 (``sample_rows`` > 0: over that many evenly spaced rows), by
@@ -280,6 +316,9 @@ class MultiVectorIndex:
         nq, nd, dev, ncand = len(ptr) - 1, self.num_docs, self.device, int(cand.shape[1])
         scores, docs, _, _ = search_outputs(nq, hi - lo, dev, False)
         found = torch.empty(nq, dtype=torch.int32, device=dev)
+        if self.residuals is not None:
+            self._rescore_residual(qmv, ptr, cand, lo, hi, query_slice, docs, scores, found, None)
+            return scores, docs, found
         with torch.cuda.device(dev):
             for s, m, rows, hq in self._launches(qmv, ptr, query_slice):
                 ws, ws_bytes = workspace("snx_mv_rescore_workspace_bytes", dev, hq, m, nd, ncand)
@@ -322,3 +361,109 @@ class MultiVectorIndex:
         ex_ptr, ex_doc = exclusion_or_null(exclude, len(ptr) - 1, self.num_docs, self.device)
         _, cand = self._candidates(qmv, ptr, ex_ptr, ex_doc, ncand, chunk_docs, query_slice)
         return self._rescore(qmv, ptr, cand, lo, hi, query_slice)
+
+    # -------------------------------------------------------------------------------------------- residual store
+    def compress(self, nbits: int, cutoffs=None, weights=None, sample_rows: int = 1 << 14, keep_rows: bool = False
+                 ) -> "MultiVectorIndex":
+        """Packs the bf16 rows into ``residuals`` (the class docstring) by csrc's ``mvr_encode_kernel``, a slice of rows at
+        a time.  ``cutoffs`` [2^nbits - 1] strictly ascending and ``weights`` [2^nbits] (rounded to bf16); without them,
+        ColBERTv2's quantiles of the residuals of ``sample_rows`` evenly spaced rows (at most 2^24 / dim: what
+        ``torch.quantile`` takes): cutoffs at m / 2^nbits, weights at (m + 0.5) / 2^nbits.  ``keep_rows=False`` releases
+        the bf16 rows."""
+        who = "MultiVectorIndex.compress"
+        if isinstance(nbits, bool) or not isinstance(nbits, (int, np.integer)) or int(nbits) not in MV_NBITS:
+            raise ValueError(f"{who}: nbits must be 1, 2 or 4")
+        nbits = int(nbits)
+        if self.dtype == torch.float32:
+            raise ValueError(f"{who}: an fp32 index is kept for exactness; only a bf16 index is compressed")
+        self._need_rows("compress")
+        if not self.built:
+            raise RuntimeError(f"{who}: call build() first")
+        if self.codes is None:
+            raise RuntimeError(f"{who}: call train_centroids() or set_centroids() first")
+        if (cutoffs is None) != (weights is None):
+            raise ValueError(f"{who}: give both cutoffs and weights, or neither")
+        if isinstance(sample_rows, bool) or int(sample_rows) < 1:
+            raise ValueError(f"{who}: sample_rows must be positive")
+        if cutoffs is not None:
+            cutoffs = torch.as_tensor(cutoffs, dtype=torch.float32).reshape(-1)
+            weights = torch.as_tensor(weights, dtype=torch.float32).reshape(-1)
+            if cutoffs.numel() != (1 << nbits) - 1 or weights.numel() != 1 << nbits:
+                raise ValueError(f"{who}: nbits = {nbits} takes {(1 << nbits) - 1} cutoffs and {1 << nbits} weights")
+            if not bool(torch.isfinite(cutoffs).all()) or not bool(torch.isfinite(weights).all()) or \
+                    not bool((cutoffs[1:] > cutoffs[:-1]).all()):
+                raise ValueError(f"{who}: cutoffs must be finite and strictly ascending, weights finite")
+        if self.device.type != "cuda":
+            raise ValueError(f"{who}: the codec needs the index on a GPU")
+        n, dev = self.num_rows, self.device
+        if cutoffs is None:
+            m = min(int(sample_rows), _MV_QUANTILE_MAX // self.dim, n)
+            pick = (torch.arange(m, device=dev) * n) // m
+            res = (self.rows[pick].float() - self.centroids[self._codes_of(pick)].float()).reshape(-1)
+            steps = torch.arange(1 << nbits, device=dev, dtype=torch.float32) / (1 << nbits)
+            cutoffs, weights = torch.quantile(res, steps[1:]), torch.quantile(res, steps + 0.5 / (1 << nbits))
+            if not bool((cutoffs[1:] > cutoffs[:-1]).all()):
+                raise ValueError(f"{who}: the residuals' quantiles do not ascend strictly; give cutoffs and weights")
+        self.cutoffs = cutoffs.to(dev).contiguous()
+        self.weights_bf16 = weights.to(dev).to(torch.bfloat16).contiguous()
+        self.weights = self.weights_bf16.float()
+        packed = torch.empty((n, self.dim * nbits // 8), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            for s in range(0, n, _MV_ASSIGN_ROWS):
+                rows = self.rows[s:s + _MV_ASSIGN_ROWS]
+                call("snx_mv_residual_encode", _p(rows), int(rows.shape[0]), _p(self.codes[s:]), _p(self.centroids),
+                     int(self.centroids.shape[0]), self.dim, nbits, _p(self.cutoffs), _p(packed[s:]), _stream())
+        self.residuals, self.nbits = packed, nbits
+        if not keep_rows:
+            self.rows, self._parts = None, []
+        return self
+
+    def _codes_of(self, row_ids: torch.Tensor) -> torch.Tensor:
+        return self.codes.view(torch.int16)[row_ids].long() & 0xFFFF
+
+    def decompress(self, row_ids) -> torch.Tensor:
+        """fp32 [n, dim] = fp32(centroid[code]) + weights[bucket] for the rows named: what the packed form holds."""
+        if self.residuals is None:
+            raise RuntimeError("MultiVectorIndex.decompress: call compress() first")
+        ids = torch.as_tensor(row_ids, device=self.device).long().reshape(-1)
+        if ids.numel() and not bool(((ids >= 0) & (ids < self.num_rows)).all()):
+            raise ValueError(f"MultiVectorIndex.decompress: row ids must lie in [0, {self.num_rows})")
+        shifts = torch.arange(0, 8, self.nbits, device=self.device, dtype=torch.int32)
+        buckets = (self.residuals[ids].to(torch.int32)[:, :, None] >> shifts) & ((1 << self.nbits) - 1)
+        return self.centroids[self._codes_of(ids)].float() + self.weights[buckets.reshape(ids.numel(), self.dim).long()]
+
+    def _rescore_residual(self, qmv, ptr, cand, lo, hi, query_slice, docs, scores, found, raw) -> None:
+        nd, dev, ncand, nc = self.num_docs, self.device, int(cand.shape[1]), int(self.centroids.shape[0])
+        with torch.cuda.device(dev):
+            for s, m, rows, hq in self._launches(qmv, ptr, query_slice):
+                ws, ws_bytes = workspace("snx_mv_rescore_residual_workspace_bytes", dev, hq, m, nd, nc, ncand)
+                call("snx_mv_rescore_residual", _p(self.codes), _p(self.residuals), _p(self.centroids),
+                     _p(self.weights_bf16), nc, self.nbits, _p(rows), 0, self.dim, self.num_rows, self._hptr, nd,
+                     int(rows.shape[0]), hq, m, _p(cand[s:]), ncand, lo, hi, _p(docs[s:]), _p(scores[s:]), _p(found[s:]),
+                     _p(at(raw, s)), _p(ws), ws_bytes, _stream())
+
+    def _pair_scores_residual(self, qmv, ptr, pq: List[int], pd: List[int]) -> torch.Tensor:
+        """The pairs grouped per query into candidate rows of at most ``K_MAX`` slots; the scores are ``raw_score``'s, so
+        they are the bits the searches rank.  A document without rows scores 0.0, as on the uncompressed index."""
+        nq, dev = len(ptr) - 1, self.device
+        out = torch.zeros(len(pd), dtype=torch.float32, device=dev)
+        slot, todo = [0] * nq, list(range(len(pd)))
+        while todo:                                           # one pass per K_MAX pairs of the busiest query
+            width = min(K_MAX, max(sum(1 for i in todo if pq[i] == q) for q in {pq[i] for i in todo}))
+            cand = torch.full((nq, width), -1, dtype=torch.int32)
+            used, where, rest = [0] * nq, [], []
+            for i in todo:
+                if used[pq[i]] < width:
+                    cand[pq[i], used[pq[i]]] = pd[i]
+                    where.append((i, pq[i] * width + used[pq[i]]))
+                    used[pq[i]] += 1
+                else:
+                    rest.append(i)
+            cand = cand.to(dev)
+            scores, docs, _, _ = search_outputs(nq, 1, dev, False)
+            found = torch.empty(nq, dtype=torch.int32, device=dev)
+            raw = torch.empty((nq, width), dtype=torch.float32, device=dev)
+            self._rescore_residual(qmv, ptr, cand, 0, 1, 0, docs, scores, found, raw)
+            out[torch.tensor([i for i, _ in where], device=dev)] = raw.reshape(-1)[torch.tensor([j for _, j in where], device=dev)]
+            todo = rest
+        return out
