@@ -793,6 +793,41 @@ int snx_mv_rescore_residual(const uint16_t* codes, const void* bits, const void*
                             float* out_score, int32_t* out_found, float* raw_score, void* workspace, size_t ws_bytes,
                             hipStream_t stream);
 
+/* ---- multi-vector probed candidates (csrc/mv_centroid.hip, the mvp_ kernels): centroid inverted lists in front of the
+ * candidate pass, after ColBERTv2 / PLAID.  There is no centroid-score threshold (PLAID's t_cs).
+ * Definition.  S[i, c] is the table entry of snx_mv_candidates: the bf16 order key of query row i times centroid c.
+ *   top(i) = the min(nprobe, nc) centroids of row i by (key descending, centroid id ascending);
+ *   L[c]   = the ascending list of the distinct documents that own at least one row with code c;
+ *   P(q)   = the union of L[c] over the rows i of q and c in top(i), minus the query's exclusion row;
+ *   result = the best ncand documents of P(q) by (a descending, doc ascending), a(q, d) exactly snx_mv_candidates' value:
+ *            the max over ALL rows of d, one left fold from +0 over the query's own rows, one division.
+ * Hence nprobe >= nc gives snx_mv_candidates' output bit for bit, and any nprobe gives snx_mv_candidates' output with the
+ * complement of P(q) added to the exclusion.  The result does not depend on chunk_docs, on the other queries of the call,
+ * on their order, or on the order in which a document was marked.
+ * snx_mv_lists_build: codes and doc_ptr -> list_ptr [nc + 1] int64 and list_docs int32 on the device (room for
+ * doc_ptr[nd] entries; list_ptr[nc] are used), L[c] = list_docs[list_ptr[c] .. list_ptr[c + 1]).  A code >= nc is read as
+ * nc - 1.  The lists are a pure function of the inputs.  workspace: snx_mv_lists_workspace_bytes(nd, nc) bytes.
+ * snx_mv_candidates_probed: snx_mv_candidates' operands and outputs, plus list_ptr [nc + 1] on the HOST, list_docs
+ * [list_len] on the device and nprobe.  chunk_docs (0: 1,024; otherwise 64 .. 8192, read as at most 1,024) is the number
+ * of probed documents a walk workgroup takes.  SNX_E_ARG before any launch: nprobe outside 1 .. 64; list_ptr not
+ * ascending from 0 or not ending at list_len; what snx_mv_candidates refuses.  An id of list_docs outside [0, nd) is
+ * skipped.  The call waits on the stream for the code check and, per slice of queries, for the size of the largest P(q).
+ * workspace: snx_mv_candidates_probed_workspace_bytes(q_ptr, nq, nd, nc, ncand, chunk_docs, nprobe) bytes (0 for arguments
+ * the call would refuse): the table, nprobe centroids per query row, one bit per (query, document) of a bounded slice of
+ * queries, the row maxima of a bounded group of blocks and ncand candidates per (query, block) -- the bitmap is the only
+ * per-(query, document) state. */
+size_t snx_mv_lists_workspace_bytes(int32_t nd, int32_t nc);
+int snx_mv_lists_build(const uint16_t* codes, int64_t drows, const int64_t* doc_ptr /*[host]*/, int32_t nd, int32_t nc,
+                       int64_t* list_ptr, int32_t* list_docs, void* workspace, size_t ws_bytes, hipStream_t stream);
+size_t snx_mv_candidates_probed_workspace_bytes(const int64_t* q_ptr /*[host]*/, int32_t nq, int32_t nd, int32_t nc,
+                                                int32_t ncand, int32_t chunk_docs, int32_t nprobe);
+int snx_mv_candidates_probed(const uint16_t* codes, int64_t drows, const int64_t* doc_ptr /*[host]*/, int32_t nd,
+                             const void* centroids, int32_t nc, const void* q, int32_t mv_f32, int32_t D, int64_t qrows,
+                             const int64_t* q_ptr /*[host]*/, int32_t nq, const int64_t* ex_ptr, const int32_t* ex_doc,
+                             int32_t ncand, int32_t chunk_docs, const int64_t* list_ptr /*[host]*/,
+                             const int32_t* list_docs, int64_t list_len, int32_t nprobe, int32_t* cand_doc,
+                             float* cand_score, void* workspace, size_t ws_bytes, hipStream_t stream);
+
 /* ---- two-phase dense retrieval (csrc/dense_two_phase.hip): the result of the exact dense section with most of the work
  * on the bf16 MFMA.  Phase 1 scores bf16 copies of the operands and proposes k1 candidates per query; phase 2 scores the
  * candidates by the exact section's chain on the fp32 operands; a per-query certificate proves, from norms computed once,

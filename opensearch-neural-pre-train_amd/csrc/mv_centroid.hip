@@ -38,7 +38,9 @@
 //                  ranks lo .. hi - 1.  Every bit is snx_maxsim_pairs'.
 // part holds a bounded group of chunks; the host walks the groups on the stream.  Nothing of size nq x nd exists, and
 // there is no float atomic anywhere.
-// The residual-compressed store and its scorer (mvr_* kernels, "multi-vector residual store") follow the rescore below.
+// The residual-compressed store and its scorer (mvr_* kernels, "multi-vector residual store") follow the rescore below,
+// and behind them the centroid inverted lists and the walk over a query's probed documents (mvp_* kernels, "multi-vector
+// probed candidates").
 #include <vector>
 
 #include "dense_common.h"
@@ -718,6 +720,452 @@ int mvr_launch_score(dim3 grid, hipStream_t st, const uint16_t* codes, const voi
   return SNX_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ probed candidates
+// include/snx.h "multi-vector probed candidates": centroid inverted lists in front of the walk (ColBERTv2 / PLAID).  A
+// query row looks only at the documents that own a row in one of its nprobe best centroids; a(q, d) of those documents is
+// the value above, so the pass costs an unprobed document one bit of a bitmap, not Ld LDS gathers.
+// mvp_list_*        The lists.  mvp_list_doc_kernel: one wave per document sets the bits of its codes in an LDS bitmap of
+//                   nc bits and, per distinct code, counts (first pass) or takes a place (second pass) in the segment of
+//                   (centroid, chunk of 4,096 documents).  mvp_list_scan_kernel turns the counts into segment starts in
+//                   (centroid, chunk) order; mvp_list_sort_kernel orders every segment in LDS.  The integer atomics decide
+//                   only the place inside a segment, which the sort then fixes: the lists are a function of the codes.
+// mvp_probe_kernel  One workgroup per table group, the group's [nc][R] table copied to LDS in 16-byte pieces; a wave per
+//                   query row keeps 64 packed (key, ~centroid) values per lane and takes nprobe wave maxima.
+// mvp_mark_kernel   One workgroup per (query row, probe slot) walks L[c] and sets the document's bit in the query's row of
+//                   the bitmap (atomicOr: idempotent); mvp_unmark_kernel clears the bits of exclude[q].
+// mvp_count_kernel  One workgroup per query: pre[q][s] = the set bits in front of the 1,024-id word range s, and the
+//                   largest |P(q)| of the launch, which the host reads to size the walk.
+// mvp_walk_kernel   One workgroup per (query, table group the query overlaps, block of up to 1,024 PROBED documents).  It
+//                   finds its block through pre, scans the block's words into an ascending list of doc ids in LDS, copies
+//                   the 8-row pieces of the group's table that hold the query's rows ([nc][pieces]) and walks the list
+//                   with `pieces` lanes per document: mvc_walk_kernel's look-ahead of eight codes and packed maxima.  The
+//                   maxima go to part[slot][the query's own pieces].
+// mvp_select_kernel mvc_select_kernel's fold over a block's slots, radix_select + ordered_take with the slot's doc id.
+// Blocks of a query follow each other in doc order, so mvc_merge_kernel (merge_lists) finishes the query.
+constexpr int MVP_NPROBE_MAX = 64;
+constexpr int MVP_THREADS = 256;
+constexpr int MVP_PROBE_THREADS = 512;         // eight waves: a lane keeps 64 keys in registers
+constexpr int MVP_SEG_WORDS = 32;              // bitmap words per prefix entry: 1,024 doc ids
+constexpr int MVP_BLOCK_MAX = 1024;            // probed documents of a walk workgroup
+constexpr int MVP_LIST_CHUNK = 4096;           // documents per segment of a list while it is built (ids in LDS: 16 KB)
+constexpr size_t MVP_BITS_BUDGET = (size_t)128 << 20;   // bytes of bitmap per slice of queries
+constexpr size_t MVP_PART_BUDGET = (size_t)128 << 20;   // bytes of maxima per walk launch
+
+// the distinct codes of document 4 blockIdx.x + wave as bits; FILL: list_docs[cur[code, chunk]++] = doc, else ++cur[..]
+template <bool FILL>
+__global__ __launch_bounds__(MVP_THREADS) void mvp_list_doc_kernel(const uint16_t* __restrict__ codes,
+                                                                   const int64_t* __restrict__ doc_ptr, int32_t nd, int32_t nc,
+                                                                   int32_t nchunks, unsigned long long* __restrict__ cur,
+                                                                   int32_t* __restrict__ list_docs) {
+  __shared__ uint32_t bm[MVP_THREADS / 64][MVC_NC_MAX / 32];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long d = (long)blockIdx.x * (MVP_THREADS / 64) + wave;
+  for (int w = lane; w < MVC_NC_MAX / 32; w += 64) bm[wave][w] = 0u;
+  __syncthreads();
+  if (d < nd) {
+    const long e = doc_ptr[d + 1];
+    for (long j = doc_ptr[d] + lane; j < e; j += 64) {
+      const int c = min((int)codes[j], nc - 1);
+      atomicOr(&bm[wave][c >> 5], 1u << (c & 31));
+    }
+  }
+  __syncthreads();
+  if (d >= nd) return;
+  const long chunk = d / MVP_LIST_CHUNK;
+  for (int w = lane; w < MVC_NC_MAX / 32; w += 64) {
+    uint32_t x = bm[wave][w];
+    while (x) {
+      const int c = w * 32 + __ffs((int)x) - 1;
+      x &= x - 1u;
+      const unsigned long long at = atomicAdd(cur + (long)c * nchunks + chunk, 1ull);
+      if (FILL) list_docs[at] = (int32_t)d;
+    }
+  }
+}
+
+// seg[i] (counts, flat over (centroid, chunk)) -> the sum of the counts in front of i, also into cur; list_ptr [nc + 1]
+__global__ __launch_bounds__(MVC_WALK_THREADS) void mvp_list_scan_kernel(unsigned long long* __restrict__ seg,
+                                                                         unsigned long long* __restrict__ cur, int64_t n,
+                                                                         int32_t nc, int32_t nchunks,
+                                                                         int64_t* __restrict__ list_ptr) {
+  __shared__ unsigned long long wsum[MVC_WALK_THREADS / 64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const long per = (n + MVC_WALK_THREADS - 1) / MVC_WALK_THREADS;
+  const long i0 = min((long)n, t * per), i1 = min((long)n, i0 + per);
+  unsigned long long run = 0ull;
+  for (long i = i0; i < i1; ++i) run += seg[i];
+  unsigned long long incl = run;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long y = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += y;
+  }
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  unsigned long long off = 0ull, all = 0ull;
+#pragma unroll
+  for (int w = 0; w < MVC_WALK_THREADS / 64; ++w) {
+    const unsigned long long x = wsum[w];
+    off += w < wave ? x : 0ull;
+    all += x;
+  }
+  if (t == 0) list_ptr[nc] = (int64_t)all;
+  run = off + incl - run;
+  for (long i = i0; i < i1; ++i) {
+    const unsigned long long x = seg[i];
+    seg[i] = run;
+    cur[i] = run;
+    if (i % nchunks == 0) list_ptr[i / nchunks] = (int64_t)run;
+    run += x;
+  }
+}
+
+// segment blockIdx.x of list_docs (at most MVP_LIST_CHUNK ids, all different) into ascending order
+__global__ __launch_bounds__(MVP_THREADS) void mvp_list_sort_kernel(const unsigned long long* __restrict__ seg, int64_t n,
+                                                                    const int64_t* __restrict__ list_ptr, int32_t nc,
+                                                                    int32_t* __restrict__ list_docs) {
+  __shared__ uint32_t s[MVP_LIST_CHUNK];
+  const int t = threadIdx.x;
+  const long i = blockIdx.x;
+  const long a = (long)seg[i], e = i + 1 < n ? (long)seg[i + 1] : (long)list_ptr[nc];
+  const int m = (int)min((long)MVP_LIST_CHUNK, e - a);
+  if (m < 2) return;
+  const int P = pow2_at_least(m);
+  for (int j = t; j < P; j += MVP_THREADS) s[j] = j < m ? (uint32_t)list_docs[a + j] : 0xFFFFFFFFu;
+  __syncthreads();
+  for (int size = 2; size <= P; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int k = t; k < (P >> 1); k += MVP_THREADS) {
+        const int lo = 2 * k - (k & (stride - 1)), hi = lo + stride;
+        const bool asc = (lo & size) == 0;
+        const uint32_t x = s[lo], y = s[hi];
+        if ((x > y) == asc) { s[lo] = y; s[hi] = x; }
+      }
+      __syncthreads();
+    }
+  for (int j = t; j < m; j += MVP_THREADS) list_docs[a + j] = (int32_t)s[j];
+}
+
+// probe[row np + r] = the r-th best centroid of query row `row` by (key descending, centroid ascending), r < np <= nc
+__global__ __launch_bounds__(MVP_PROBE_THREADS) void mvp_probe_kernel(const uint16_t* __restrict__ table, int64_t qused,
+                                                                     int32_t nc, int32_t R, int32_t np,
+                                                                     int32_t* __restrict__ probe) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const long g = blockIdx.x;
+  {
+    u32x4* T = (u32x4*)smem;
+    const u32x4* src = (const u32x4*)(table + g * nc * R);
+    const int nvec = nc * (R / 8);
+    for (int i = t; i < nvec; i += MVP_PROBE_THREADS) T[i] = src[i];
+  }
+  __syncthreads();
+  const uint16_t* T16 = (const uint16_t*)smem;
+  for (int in = wave; in < R; in += MVP_PROBE_THREADS / 64) {
+    const long row = g * R + in;
+    if (row >= qused) break;
+    uint32_t v[64];                                           // (key as unsigned) << 16 | ~centroid; 0: no centroid
+#pragma unroll
+    for (int k = 0; k < 64; ++k) {
+      const int c = 64 * k + lane;
+      v[k] = c < nc ? ((((uint32_t)T16[c * R + in] ^ 0x8000u) << 16) | (0xFFFFu - (uint32_t)c)) : 0u;
+    }
+    for (int r = 0; r < np; ++r) {
+      uint32_t best = 0u;
+#pragma unroll
+      for (int k = 0; k < 64; ++k) best = max(best, v[k]);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, o, 64));
+      if (lane == 0) probe[row * np + r] = (int32_t)(0xFFFFu - (best & 0xFFFFu));
+#pragma unroll
+      for (int k = 0; k < 64; ++k) v[k] = v[k] == best ? 0u : v[k];
+    }
+  }
+}
+
+// the bit of every document of L[probe[row, slot]] in the bitmap row of the query that owns `row`
+__global__ __launch_bounds__(MVP_THREADS) void mvp_mark_kernel(const int32_t* __restrict__ probe, int32_t np,
+                                                               const int64_t* __restrict__ q_ptr, int32_t q0, int32_t nqs,
+                                                               const int64_t* __restrict__ list_ptr,
+                                                               const int32_t* __restrict__ list_docs, int32_t nd, int64_t wp,
+                                                               uint32_t* __restrict__ bits) {
+  const long row = q_ptr[q0] + blockIdx.x;
+  int lo = q0, hi = q0 + nqs;                                 // the last query with q_ptr[q] <= row
+  while (hi - lo > 1) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (q_ptr[mid] <= row) lo = mid; else hi = mid;
+  }
+  const int c = probe[row * np + blockIdx.y];
+  uint32_t* b = bits + (long)(lo - q0) * wp;
+  const long e = list_ptr[c + 1];
+  for (long i = list_ptr[c] + threadIdx.x; i < e; i += MVP_THREADS) {
+    const int32_t d = list_docs[i];
+    if ((uint32_t)d >= (uint32_t)nd) continue;
+    const uint32_t m = 1u << (d & 31);
+    // most rows of a query probe the same lists: look before the atomic (a stale look only repeats an idempotent or)
+    if (!(__hip_atomic_load(b + (d >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & m)) atomicOr(b + (d >> 5), m);
+  }
+}
+
+__global__ __launch_bounds__(MVP_THREADS) void mvp_unmark_kernel(const int64_t* __restrict__ ex_ptr,
+                                                                 const int32_t* __restrict__ ex_doc, int32_t nd, int64_t wp,
+                                                                 uint32_t* __restrict__ bits) {
+  const long q = blockIdx.x;
+  const int64_t e = ex_ptr[q + 1];
+  for (int64_t i = ex_ptr[q] + threadIdx.x; i < e; i += MVP_THREADS) {
+    const int32_t d = ex_doc[i];
+    if ((uint32_t)d < (uint32_t)nd) atomicAnd(bits + q * wp + (d >> 5), ~(1u << (d & 31)));
+  }
+}
+
+// the sum of c over the threads in front of this one, by a workgroup of MVC_WALK_THREADS; tot = the sum over all of them
+__device__ __forceinline__ int mvp_block_scan(int c, int* wsum, int& tot) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = c;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += y;
+  }
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  int off = 0;
+  tot = 0;
+#pragma unroll
+  for (int w = 0; w < MVC_WALK_THREADS / 64; ++w) {
+    const int x = wsum[w];
+    off += w < wave ? x : 0;
+    tot += x;
+  }
+  __syncthreads();
+  return off + incl - c;
+}
+
+// pre[q (nseg + 1) + s] = the set bits of query q's bitmap row in front of word MVP_SEG_WORDS s; [nseg]: all of them
+__global__ __launch_bounds__(MVC_WALK_THREADS) void mvp_count_kernel(const uint32_t* __restrict__ bits, int64_t wp,
+                                                                     int32_t nseg, int32_t* __restrict__ pre,
+                                                                     int32_t* __restrict__ maxtot) {
+  __shared__ int wsum[MVC_WALK_THREADS / 64];
+  const int t = threadIdx.x;
+  const u32x4* src = (const u32x4*)(bits + (long)blockIdx.x * wp);
+  int32_t* out = pre + (long)blockIdx.x * (nseg + 1);
+  int base = 0;
+  for (int s0 = 0; s0 < nseg; s0 += MVC_WALK_THREADS) {
+    const int s = s0 + t;
+    int c = 0;
+    if (s < nseg) {
+#pragma unroll
+      for (int u = 0; u < MVP_SEG_WORDS / 4; ++u) {
+        const u32x4 x = src[(long)s * (MVP_SEG_WORDS / 4) + u];
+        c += __popc(x[0]) + __popc(x[1]) + __popc(x[2]) + __popc(x[3]);
+      }
+    }
+    int tot;
+    const int off = mvp_block_scan(c, wsum, tot);
+    if (s < nseg) out[s] = base + off;
+    base += tot;
+  }
+  if (t == 0) {
+    out[nseg] = base;
+    atomicMax(maxtot, base);
+  }
+}
+
+// part[((q bg + bl) blk + i) pitch + 8 (piece - q's first piece) ..] = the maxima of the i-th probed document of block
+// b_first + bl of query q0 + q against the eight query rows of the piece; slotdoc[.. + i] = the document
+__global__ __launch_bounds__(MVC_WALK_THREADS) void mvp_walk_kernel(
+    const uint16_t* __restrict__ table, const uint16_t* __restrict__ codes, int64_t drows,
+    const int64_t* __restrict__ doc_ptr, int32_t nc, int32_t R, const int64_t* __restrict__ q_ptr, int32_t q0,
+    const uint32_t* __restrict__ bits, int64_t wp, const int32_t* __restrict__ pre, int32_t nseg, int32_t blk,
+    int32_t b_first, int32_t bg, int32_t pitch, uint16_t* __restrict__ part, int32_t* __restrict__ slotdoc) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ int32_t doclist[MVP_BLOCK_MAX];
+  __shared__ int wsum[MVC_WALK_THREADS / 64];
+  const int t = threadIdx.x;
+  const int bl = blockIdx.x, q = blockIdx.z;
+  const long qa = q_ptr[q0 + q], qe = q_ptr[q0 + q + 1];
+  const long g = qa / R + blockIdx.y;
+  if (g * R >= qe) return;                                    // the query does not reach this group
+  const int32_t* pq = pre + (long)q * (nseg + 1);
+  const long first = ((long)b_first + bl) * blk;
+  if (first >= pq[nseg]) return;                              // no probed document left for this block
+  const int n = (int)min((long)blk, pq[nseg] - first);
+  int s0 = 0;                                                 // the last word range with pre <= first
+  for (int hi = nseg; hi - s0 > 1;) {
+    const int mid = s0 + ((hi - s0) >> 1);
+    if (pq[mid] <= first) s0 = mid; else hi = mid;
+  }
+  const uint32_t* b = bits + (long)q * wp;
+  long base = pq[s0];
+  for (long w0 = (long)s0 * MVP_SEG_WORDS; w0 < wp && base < first + n; w0 += MVC_WALK_THREADS) {
+    const long w = w0 + t;
+    uint32_t x = w < wp ? b[w] : 0u;
+    int tot;
+    long ord = base + mvp_block_scan(__popc(x), wsum, tot);
+    while (x) {
+      const int bit = __ffs((int)x) - 1;
+      x &= x - 1u;
+      if (ord >= first && ord < first + n) doclist[ord - first] = (int32_t)(w * 32 + bit);
+      ++ord;
+    }
+    base += tot;
+  }
+  // the 8-row pieces of the group that hold rows of the query: local pieces pl0 .. pl0 + np - 1
+  const int LPD = R / 8;
+  const long gp = g * LPD, qp = qa >> 3;
+  const int pl0 = (int)max(0l, qp - gp), np = (int)min((long)LPD - 1, ((qe - 1) >> 3) - gp) - pl0 + 1;
+  u32x4* T = (u32x4*)smem;
+  {
+    const u32x4* src = (const u32x4*)(table + g * nc * R) + pl0;
+    const int nvec = nc * np;
+    for (int i = t; i < nvec; i += MVC_WALK_THREADS) {
+      const int c = i / np;
+      T[i] = src[c * LPD + (i - c * np)];
+    }
+  }
+  __syncthreads();
+  const int slot = t / np, p = t - slot * np, DPW = MVC_WALK_THREADS / np;
+  if (slot >= DPW) return;
+  const long out0 = ((long)q * bg + bl) * blk;
+  for (int i = slot; i < n; i += DPW) {
+    const int32_t d = doclist[i];
+    const long a = doc_ptr[d], e = doc_ptr[d + 1];
+    u32x4 m = {MVC_NO_ROW2, MVC_NO_ROW2, MVC_NO_ROW2, MVC_NO_ROW2};
+    if (e > a) {
+      long cb = a & ~7l;
+      u32x4 cur = mvc_codes8(codes, cb, drows);
+      for (; cb < e; cb += 8) {
+        u32x4 nxt = {0u, 0u, 0u, 0u};
+        if (cb + 8 < e) nxt = mvc_codes8(codes, cb + 8, drows);              // in flight while this piece is walked
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const long pos = cb + u;
+          if (pos >= a && pos < e) {
+            const int code = min((int)((cur[u >> 1] >> (16 * (u & 1))) & 0xFFFFu), nc - 1);
+            const u32x4 x = T[code * np + p];
+#pragma unroll
+            for (int w = 0; w < 4; ++w) m[w] = mvc_max2(m[w], x[w]);
+          }
+        }
+        cur = nxt;
+      }
+    }
+    *(u32x4*)(part + (out0 + i) * pitch + (gp + pl0 + p - qp) * 8) = m;
+    if (blockIdx.y == 0 && p == 0) slotdoc[out0 + i] = d;
+  }
+}
+
+__global__ __launch_bounds__(SR_THREADS) void mvp_select_kernel(
+    const uint16_t* __restrict__ part, const int32_t* __restrict__ slotdoc, const int64_t* __restrict__ q_ptr, int32_t q0,
+    const int32_t* __restrict__ pre, int32_t nseg, int32_t blk, int32_t b_first, int32_t bg, int32_t pitch, int32_t nlist,
+    int32_t ncand, unsigned long long* __restrict__ cand, int32_t* __restrict__ ccount) {
+  __shared__ SelectSmem S;
+  __shared__ uint32_t keys[MVP_BLOCK_MAX];
+  const int tid = threadIdx.x, q = blockIdx.x, bl = blockIdx.y;
+  const long b = (long)b_first + bl;
+  if (b >= nlist) return;
+  const int n = (int)max(0l, min((long)blk, (long)pre[(long)q * (nseg + 1) + nseg] - b * blk));
+  const long qa = q_ptr[q0 + q], qe = q_ptr[q0 + q + 1], q8 = qa & ~7l;
+  const float lq = (float)(qe - qa);
+  const long out0 = ((long)q * bg + bl) * blk;
+  for (int i = tid; i < n; i += SR_THREADS) {
+    const uint16_t* v = part + (out0 + i) * pitch;
+    float x = 0.f;
+    for (long base = q8; base < qe; base += 8) {              // the query's rows, ascending: one chain from +0
+      const u32x4 w = *(const u32x4*)(v + (base - q8));
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (base + u >= qa && base + u < qe) x += mvc_unkey((w[u >> 1] >> (16 * (u & 1))) & 0xFFFFu);
+    }
+    keys[i] = dense_key(x / lq);
+  }
+  __syncthreads();
+  const size_t list = (size_t)q * (size_t)nlist + (size_t)b;
+  unsigned long long* out = cand + list * (size_t)ncand;
+  const int32_t* sd = slotdoc + out0;
+  auto key = [&](long i) -> uint32_t { return keys[i]; };
+  uint32_t thr;
+  int need_eq, nsel;
+  radix_select(key, n, ncand, S, thr, need_eq, nsel);          // select_chunk's body with the slot's document as the id
+  ordered_take(key, n, thr, need_eq, S, [&](long i, int pos) { out[pos] = rank_key(keys[i], (uint32_t)sd[i]); });
+  if (tid == 0) ccount[list] = nsel;
+}
+
+struct MvpListPlan {
+  size_t dptr, seg, cur, total;
+  int nchunks;
+  int64_t n;
+  bool ok;
+  MvpListPlan(int32_t nd, int32_t nc) {
+    nchunks = sr_nch(nd, MVP_LIST_CHUNK);
+    n = (int64_t)nc * nchunks;
+    ok = n <= 0x7FFFFFFFL;
+    Arena a;
+    dptr = a.take(((size_t)nd + 1) * 8);
+    seg = a.take((size_t)n * 8);
+    cur = a.take((size_t)n * 8);
+    total = a.off;
+  }
+};
+
+inline bool mvp_bad_probe(int32_t nprobe) { return nprobe < 1 || nprobe > MVP_NPROBE_MAX; }
+
+// the probed pass's workspace.  A slice of qs queries holds a bitmap row, a prefix row and candidate lists each; a walk
+// launch covers bg blocks of every query of the slice.
+struct MvpPlan {
+  size_t dptr, qptr, lptr, flag, table, probe, bits, pre, part, slotdoc, cand, ccount, total;
+  int R, ngroups, np, blk, nseg, nblk, maxg, maxnp, pitch, qs, bg;
+  int64_t prows, wp;
+  bool ok;
+  MvpPlan(const int64_t* q_ptr, int32_t nq, int32_t nd, int32_t nc, int32_t ncand, int32_t chunk_docs, int32_t nprobe) {
+    R = mvc_group_rows(nc);
+    const int64_t qused = q_ptr[nq];
+    ok = qused <= 0x7FFFFFFFL - MVC_TILE && nq <= 65535;
+    ngroups = ok ? (int)((qused + R - 1) / R) : 1;
+    prows = (int64_t)ngroups * R;
+    np = nprobe < nc ? nprobe : nc;
+    blk = chunk_docs > 0 && chunk_docs < MVP_BLOCK_MAX ? chunk_docs : MVP_BLOCK_MAX;
+    nseg = sr_nch(nd, MVP_SEG_WORDS * 32);
+    wp = (int64_t)nseg * MVP_SEG_WORDS;
+    nblk = sr_nch(nd, blk);
+    maxg = maxnp = pitch = 1;
+    const int LPD = R / 8;
+    for (int32_t q = 0; ok && q < nq; ++q) {                  // groups and 8-row pieces a query reaches
+      const int64_t a = q_ptr[q], e = q_ptr[q + 1] - 1;
+      const int g = (int)(e / R - a / R + 1), pieces = (int)((e >> 3) - (a >> 3) + 1);
+      maxg = g > maxg ? g : maxg;
+      pitch = pieces > pitch ? pieces : pitch;
+      const int in = pieces < LPD ? pieces : LPD;             // at most a group's pieces, at most the query's
+      maxnp = in > maxnp ? in : maxnp;
+    }
+    pitch *= 8;
+    const size_t block = (size_t)blk * pitch * 2;
+    size_t s = MVP_BITS_BUDGET / ((size_t)wp * 4), s2 = MVP_PART_BUDGET / block;
+    s = s < s2 ? s : s2;
+    qs = (int)(s < 1 ? 1 : (s > (size_t)nq ? (size_t)nq : s));
+    size_t g = MVP_PART_BUDGET / ((size_t)qs * block);
+    bg = (int)(g < 1 ? 1 : (g > (size_t)nblk ? (size_t)nblk : g));
+    bg = bg > 65535 ? 65535 : bg;
+    ok = ok && (int64_t)qs * nblk <= 0x7FFFFFFFL && maxg <= 65535;
+    Arena a;
+    dptr = a.take(((size_t)nd + 1) * 8);
+    qptr = a.take(((size_t)nq + 1) * 8);
+    lptr = a.take(((size_t)nc + 1) * 8);
+    flag = a.take(8);
+    table = a.take((size_t)prows * (size_t)nc * 2);
+    probe = a.take((size_t)prows * (size_t)np * 4);
+    bits = a.take((size_t)qs * (size_t)wp * 4);
+    pre = a.take((size_t)qs * ((size_t)nseg + 1) * 4);
+    part = a.take((size_t)qs * (size_t)bg * block);
+    slotdoc = a.take((size_t)qs * (size_t)bg * (size_t)blk * 4);
+    cand = a.take((size_t)qs * (size_t)nblk * (size_t)ncand * 8);
+    ccount = a.take((size_t)qs * (size_t)nblk * 4);
+    total = a.off;
+  }
+};
+
+LdsOptIn g_mvp_lds[2];
+
 }  // namespace
 
 extern "C" size_t snx_mv_candidates_workspace_bytes(const int64_t* q_ptr, int32_t nq, int32_t nd, int32_t nc, int32_t ncand,
@@ -927,6 +1375,165 @@ extern "C" int snx_mv_rescore_residual(const uint16_t* codes, const void* bits, 
     const int64_t npairs = (int64_t)nq * ncand;
     hipLaunchKernelGGL(mvr_raw_kernel, dim3((unsigned)((npairs + MVC_THREADS - 1) / MVC_THREADS)), dim3(MVC_THREADS), 0, st,
                        (const float*)partial, cand_doc, qptr, dptr, nd, npairs, ncand, plan.qblocks, raw_score);
+    SNX_CHECK_LAUNCH();
+  }
+  return SNX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ probed candidates: host
+extern "C" size_t snx_mv_lists_workspace_bytes(int32_t nd, int32_t nc) {
+  if (nd < 0 || nc < 1 || nc > MVC_NC_MAX) return 0;
+  const MvpListPlan plan(nd, nc);
+  return plan.ok ? plan.total : 0;
+}
+
+extern "C" int snx_mv_lists_build(const uint16_t* codes, int64_t drows, const int64_t* doc_ptr, int32_t nd, int32_t nc,
+                                  int64_t* list_ptr, int32_t* list_docs, void* workspace, size_t ws_bytes, hipStream_t st) {
+  if (drows < 0 || nd < 0) return SNX_E_SHAPE;
+  if (nc < 1 || nc > MVC_NC_MAX || !list_ptr || !workspace || ((uintptr_t)workspace & 15) != 0) return SNX_E_ARG;
+  if (!mvc_ptr_ok(doc_ptr, nd, drows, false)) return SNX_E_ARG;
+  const int64_t dused = doc_ptr[nd];
+  if (dused > 0 && (!codes || !list_docs)) return SNX_E_ARG;
+  const MvpListPlan plan(nd, nc);
+  if (!plan.ok) return SNX_E_SHAPE;
+  if (ws_bytes < plan.total) return SNX_E_ARG;
+  char* ws = (char*)workspace;
+  RC(mvc_upload(ws, plan.dptr, doc_ptr, ((size_t)nd + 1) * 8, st));
+  const int64_t* dptr = (const int64_t*)(ws + plan.dptr);
+  unsigned long long *seg = (unsigned long long*)(ws + plan.seg), *cur = (unsigned long long*)(ws + plan.cur);
+  const hipError_t e = hipMemsetAsync(seg, 0, (size_t)plan.n * 8, st);
+  if (e != hipSuccess) return (int)e;
+  const dim3 docs((unsigned)((nd + (long)MVP_THREADS / 64 - 1) / (MVP_THREADS / 64)));
+  if (dused > 0) {
+    hipLaunchKernelGGL(mvp_list_doc_kernel<false>, docs, dim3(MVP_THREADS), 0, st, codes, dptr, nd, nc, plan.nchunks, seg,
+                       list_docs);
+    SNX_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(mvp_list_scan_kernel, dim3(1), dim3(MVC_WALK_THREADS), 0, st, seg, cur, plan.n, nc, plan.nchunks,
+                     list_ptr);
+  SNX_CHECK_LAUNCH();
+  if (dused > 0) {
+    hipLaunchKernelGGL(mvp_list_doc_kernel<true>, docs, dim3(MVP_THREADS), 0, st, codes, dptr, nd, nc, plan.nchunks, cur,
+                       list_docs);
+    SNX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mvp_list_sort_kernel, dim3((unsigned)plan.n), dim3(MVP_THREADS), 0, st,
+                       (const unsigned long long*)seg, plan.n, (const int64_t*)list_ptr, nc, list_docs);
+    SNX_CHECK_LAUNCH();
+  }
+  return SNX_OK;
+}
+
+extern "C" size_t snx_mv_candidates_probed_workspace_bytes(const int64_t* q_ptr, int32_t nq, int32_t nd, int32_t nc,
+                                                           int32_t ncand, int32_t chunk_docs, int32_t nprobe) {
+  if (nq <= 0 || mvc_bad_cand(nq, nd, nc, ncand, chunk_docs) || mvp_bad_probe(nprobe) ||
+      !mvc_ptr_ok(q_ptr, nq, 0x7FFFFFFFFFFFFFFFL, true))
+    return 0;
+  const MvpPlan plan(q_ptr, nq, nd, nc, ncand, chunk_docs, nprobe);
+  return plan.ok ? plan.total : 0;
+}
+
+extern "C" int snx_mv_candidates_probed(const uint16_t* codes, int64_t drows, const int64_t* doc_ptr, int32_t nd,
+                                        const void* centroids, int32_t nc, const void* q, int32_t mv_f32, int32_t D,
+                                        int64_t qrows, const int64_t* q_ptr, int32_t nq, const int64_t* ex_ptr,
+                                        const int32_t* ex_doc, int32_t ncand, int32_t chunk_docs, const int64_t* list_ptr,
+                                        const int32_t* list_docs, int64_t list_len, int32_t nprobe, int32_t* cand_doc,
+                                        float* cand_score, void* workspace, size_t ws_bytes, hipStream_t st) {
+  if (D <= 0 || (D % 64) != 0 || D > MVC_DMAX || qrows < 0 || drows < 0) return SNX_E_SHAPE;
+  if (mvc_bad_cand(nq, nd, nc, ncand, chunk_docs) || mvp_bad_probe(nprobe)) return SNX_E_ARG;
+  if (nq == 0) return SNX_OK;
+  if (!q || !centroids || !cand_doc || !cand_score || !workspace || (ex_ptr && !ex_doc) || ((uintptr_t)q & 15) != 0 ||
+      ((uintptr_t)centroids & 15) != 0 || ((uintptr_t)codes & 15) != 0 || ((uintptr_t)workspace & 15) != 0)
+    return SNX_E_ARG;
+  if (!mvc_ptr_ok(doc_ptr, nd, drows, false) || !mvc_ptr_ok(q_ptr, nq, qrows, true)) return SNX_E_ARG;
+  // the lists: a host pointer array as doc_ptr, ending at the length of list_docs; a kernel bounds every id it reads
+  if (list_len < 0 || !mvc_ptr_ok(list_ptr, nc, list_len, false) || list_ptr[nc] != list_len || (list_len > 0 && !list_docs))
+    return SNX_E_ARG;
+  const int64_t dused = doc_ptr[nd], qused = q_ptr[nq];
+  if (dused > 0 && !codes) return SNX_E_ARG;
+  const MvpPlan plan(q_ptr, nq, nd, nc, ncand, chunk_docs, nprobe);
+  if (!plan.ok) return SNX_E_SHAPE;
+  if (ws_bytes < plan.total) return SNX_E_ARG;
+  char* ws = (char*)workspace;
+  int32_t* flag = (int32_t*)(ws + plan.flag);                 // [0]: a bad code, [1]: the largest |P(q)| of a slice
+  if (dused > 0) {
+    int32_t bad = 0;
+    hipError_t e = hipMemsetAsync(flag, 0, 4, st);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(mvc_check_kernel, dim3((unsigned)((dused + MVC_THREADS - 1) / MVC_THREADS)), dim3(MVC_THREADS), 0, st,
+                       codes, dused, nc, flag);
+    SNX_CHECK_LAUNCH();
+    e = hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return (int)e;
+    if (bad) return SNX_E_ARG;
+  }
+  RC(mvc_upload(ws, plan.dptr, doc_ptr, ((size_t)nd + 1) * 8, st));
+  RC(mvc_upload(ws, plan.qptr, q_ptr, ((size_t)nq + 1) * 8, st));
+  RC(mvc_upload(ws, plan.lptr, list_ptr, ((size_t)nc + 1) * 8, st));
+  const int64_t* dptr = (const int64_t*)(ws + plan.dptr);
+  const int64_t* qptr = (const int64_t*)(ws + plan.qptr);
+  const int64_t* lptr = (const int64_t*)(ws + plan.lptr);
+  uint16_t *table = (uint16_t*)(ws + plan.table), *part = (uint16_t*)(ws + plan.part);
+  int32_t *probe = (int32_t*)(ws + plan.probe), *pre = (int32_t*)(ws + plan.pre), *slotdoc = (int32_t*)(ws + plan.slotdoc);
+  uint32_t* bits = (uint32_t*)(ws + plan.bits);
+  unsigned long long* cand = (unsigned long long*)(ws + plan.cand);
+  int32_t* ccount = (int32_t*)(ws + plan.ccount);
+  const int R = plan.R;
+  const bool live = dused > 0 && list_len > 0;                // otherwise no document can be probed
+  if (live) {
+    const dim3 grid((unsigned)((plan.prows + MVC_TILE - 1) / MVC_TILE), (unsigned)((nc + MVC_TILE - 1) / MVC_TILE));
+    if (mv_f32)
+      hipLaunchKernelGGL(mvc_table_kernel<MvcF32>, grid, dim3(MVC_THREADS), 0, st, (const float*)q, qused, plan.prows,
+                         (const float*)centroids, nc, D, R, table);
+    else
+      hipLaunchKernelGGL(mvc_table_kernel<MvcBf16>, grid, dim3(MVC_THREADS), 0, st, (const bf16_t*)q, qused, plan.prows,
+                         (const bf16_t*)centroids, nc, D, R, table);
+    SNX_CHECK_LAUNCH();
+    RC(g_mvp_lds[0].ensure((const void*)mvp_probe_kernel, MVC_TABLE_BYTES));
+    hipLaunchKernelGGL(mvp_probe_kernel, dim3((unsigned)plan.ngroups), dim3(MVP_PROBE_THREADS), (size_t)nc * R * 2, st,
+                       (const uint16_t*)table, qused, nc, R, plan.np, probe);
+    SNX_CHECK_LAUNCH();
+    RC(g_mvp_lds[1].ensure((const void*)mvp_walk_kernel, MVC_TABLE_BYTES));
+  }
+  for (int32_t q0 = 0; q0 < nq; q0 += plan.qs) {              // one slice of queries after the other: the bitmap is reused
+    const int32_t nqs = nq - q0 < plan.qs ? nq - q0 : plan.qs;
+    hipError_t e = hipMemsetAsync(bits, 0, (size_t)nqs * (size_t)plan.wp * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(flag + 1, 0, 4, st);
+    if (e != hipSuccess) return (int)e;
+    if (live) {
+      hipLaunchKernelGGL(mvp_mark_kernel, dim3((unsigned)(q_ptr[q0 + nqs] - q_ptr[q0]), (unsigned)plan.np), dim3(MVP_THREADS),
+                         0, st, (const int32_t*)probe, plan.np, qptr, q0, nqs, lptr, list_docs, nd, plan.wp, bits);
+      SNX_CHECK_LAUNCH();
+      if (ex_ptr) {
+        hipLaunchKernelGGL(mvp_unmark_kernel, dim3((unsigned)nqs), dim3(MVP_THREADS), 0, st, ex_ptr + q0, ex_doc, nd, plan.wp,
+                           bits);
+        SNX_CHECK_LAUNCH();
+      }
+    }
+    hipLaunchKernelGGL(mvp_count_kernel, dim3((unsigned)nqs), dim3(MVC_WALK_THREADS), 0, st, (const uint32_t*)bits, plan.wp,
+                       plan.nseg, pre, flag + 1);
+    SNX_CHECK_LAUNCH();
+    int32_t most = 0;                                         // the walk's grid follows the probed documents, not nd
+    e = hipMemcpyAsync(&most, flag + 1, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return (int)e;
+    const int nlist = most > 0 ? (int)((most + (long)plan.blk - 1) / plan.blk) : 1;
+    for (int b0 = 0; b0 < nlist; b0 += plan.bg) {             // part is reused in order
+      const int nb = nlist - b0 < plan.bg ? nlist - b0 : plan.bg;
+      if (most > 0) {
+        hipLaunchKernelGGL(mvp_walk_kernel, dim3((unsigned)nb, (unsigned)plan.maxg, (unsigned)nqs), dim3(MVC_WALK_THREADS),
+                           (size_t)nc * plan.maxnp * 16, st, (const uint16_t*)table, codes, drows, dptr, nc, R, qptr, q0,
+                           (const uint32_t*)bits, plan.wp, (const int32_t*)pre, plan.nseg, plan.blk, b0, plan.bg, plan.pitch,
+                           part, slotdoc);
+        SNX_CHECK_LAUNCH();
+      }
+      hipLaunchKernelGGL(mvp_select_kernel, dim3((unsigned)nqs, (unsigned)nb), dim3(SR_THREADS), 0, st, (const uint16_t*)part,
+                         (const int32_t*)slotdoc, qptr, q0, (const int32_t*)pre, plan.nseg, plan.blk, b0, plan.bg, plan.pitch,
+                         nlist, ncand, cand, ccount);
+      SNX_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(mvc_merge_kernel, dim3((unsigned)nqs), dim3(SR_THREADS), 0, st, (const unsigned long long*)cand,
+                       (const int32_t*)ccount, nlist, ncand, cand_doc + (size_t)q0 * ncand, cand_score + (size_t)q0 * ncand);
     SNX_CHECK_LAUNCH();
   }
   return SNX_OK;

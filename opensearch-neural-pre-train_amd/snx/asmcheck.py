@@ -86,7 +86,12 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
                         # the residual store: the score tile's accumulators, running maxima, the prefetched query slice,
                         # the packed word and the sixteen table entries of a lane stay in registers; the encode and raw
                         # kernels hold no LDS and are not listed
-                        "mvr_table_kernel", "mvr_score_kernel"),
+                        "mvr_table_kernel", "mvr_score_kernel",
+                        # the probed pass: the probe's 64 packed keys of a lane, the walk's maxima and code pieces, and
+                        # the scans' running sums stay in registers; the mark and unmark kernels hold no LDS and are not
+                        # listed
+                        "mvp_list_doc_kernel", "mvp_list_scan_kernel", "mvp_list_sort_kernel", "mvp_probe_kernel",
+                        "mvp_count_kernel", "mvp_walk_kernel", "mvp_select_kernel"),
     # and for the lexical weights: the 64-bit keys live in LDS, a thread's key, its ballot and the unused ids (kernel
     # arguments) in registers; the head's row kernel and the pair scorer hold no LDS and are not listed
     "teacher_lex.hip": ("tl_unique_kernel",),

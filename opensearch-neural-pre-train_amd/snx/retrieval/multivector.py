@@ -18,6 +18,7 @@ MV_CENTROIDS_MAX = 4096                # a query group's centroid table has to f
 _MV_ASSIGN_ROWS = 1 << 18              # store rows cast to fp32 per slice of the code assignment
 _MV_ROWS_PER_LAUNCH = 1 << 15          # query rows of one launch: 512 query blocks
 MV_NBITS = (1, 2, 4)                   # bits per dimension of a residual-compressed store
+MV_NPROBE_MAX = 64                     # centroids a query row probes
 _MV_QUANTILE_MAX = 1 << 24             # elements torch.quantile takes
 
 
@@ -50,6 +51,12 @@ class MultiVectorIndex:
         a, docs = index.candidates(qmv, q_ptr, ncand, exclude=None, chunk_docs=0, query_slice=0)
         scores, docs = index.search_two_phase(qmv, q_ptr, k, ncand, chunk_docs=0, query_slice=0)
         scores, docs, found = index.search_band_two_phase(qmv, q_ptr, lo, hi, ncand, exclude=None, ...)
+
+    The three take ``nprobe`` (0: every document is walked; 1 .. 64: the probed pass, include/snx.h "multi-vector probed
+    candidates").  A query row then looks only at the documents that own a row in one of its ``nprobe`` best centroids
+    (key descending, centroid id ascending); the candidates are the best ``ncand`` of the union over the query's rows,
+    under the same a(q, d).  ``index.list_ptr`` (int64 [nc + 1]) / ``index.list_docs`` (int32) are the centroids' inverted
+    lists, ascending doc ids, built by the first probed call; ``nprobe`` >= nc gives the unprobed result bit for bit.
 
     ``index.codes`` (uint16 [num_rows]) is every row's best centroid under ``DenseIndex``'s order, ``index.centroids`` the
     centroids in the store's dtype.  a(q, d) = mean over the query's rows of the best bf16-rounded product of the row
@@ -86,7 +93,13 @@ class MultiVectorIndex:
         self._hptr = None
         self.centroids: Optional[torch.Tensor] = None         # [nc, dim] in the store's dtype, as the table kernel reads them
         self.codes: Optional[torch.Tensor] = None             # uint16 [num_rows]: the best centroid of every row
+        self._unlist()
         self._uncompress()
+
+    def _unlist(self) -> None:
+        self.list_ptr: Optional[torch.Tensor] = None          # int64 [nc + 1]: the inverted lists of the codes,
+        self.list_docs: Optional[torch.Tensor] = None         # int32 [list_ptr[nc]]: ascending doc ids per centroid
+        self._hlist = None
 
     def _uncompress(self) -> None:
         self.nbits = 0                                        # 0: not compressed
@@ -133,6 +146,7 @@ class MultiVectorIndex:
         self._ptr += [self._ptr[-1] + v for v in ptr[1:]]
         self.rows = None                                      # a new batch invalidates a built index
         self.centroids = self.codes = None                    # and its codes
+        self._unlist()                                        # and their lists
         self._uncompress()                                    # and their residuals
 
     def build(self) -> "MultiVectorIndex":
@@ -257,6 +271,7 @@ class MultiVectorIndex:
         for s in range(0, self.num_rows, _MV_ASSIGN_ROWS):
             codes[s:s + _MV_ASSIGN_ROWS] = quantizer._best(self.rows[s:s + _MV_ASSIGN_ROWS].float(), seen, 1)[1].reshape(-1)
         self.codes = codes.to(torch.uint16)
+        self._unlist()                                        # lists of other codes
         self._uncompress()                                    # residuals of other codes
 
     def train_centroids(self, ncentroids: int, niter: int = 10, seed: int = 0, sample_rows: int = 0) -> "MultiVectorIndex":
@@ -287,7 +302,9 @@ class MultiVectorIndex:
         self._assign(self._quantizer("set_centroids", int(c.shape[0])), c)
         return self
 
-    def _two_phase(self, who: str, ncand, hi: int) -> int:
+    def _two_phase(self, who: str, ncand, hi: int, nprobe=0) -> int:
+        if isinstance(nprobe, bool) or not isinstance(nprobe, (int, np.integer)) or not 0 <= int(nprobe) <= MV_NPROBE_MAX:
+            raise ValueError(f"MultiVectorIndex.{who}: nprobe must be an int in [0, {MV_NPROBE_MAX}] (0: no probing)")
         if isinstance(ncand, bool) or not isinstance(ncand, (int, np.integer)) or not 1 <= int(ncand) <= K_MAX:
             raise ValueError(f"MultiVectorIndex.{who}: ncand must be an int in [1, {K_MAX}]")
         if hi > int(ncand):
@@ -301,11 +318,36 @@ class MultiVectorIndex:
         for s, m in self._slices(ptr, query_slice):
             yield s, m, qmv[ptr[s]:ptr[s + m]], (C.c_int64 * (m + 1))(*[v - ptr[s] for v in ptr[s:s + m + 1]])
 
-    def _candidates(self, qmv, ptr, ex_ptr, ex_doc, ncand: int, chunk_docs: int, query_slice: int):
+    def _lists(self) -> None:
+        """``list_ptr`` / ``list_docs`` from the codes (csrc's ``mvp_list_*`` kernels), once per code assignment."""
+        if self.list_ptr is not None:
+            return
+        nd, dev, nc = self.num_docs, self.device, int(self.centroids.shape[0])
+        list_ptr = torch.empty(nc + 1, dtype=torch.int64, device=dev)
+        docs = torch.empty(max(self.num_rows, 1), dtype=torch.int32, device=dev)     # a row adds at most one entry
+        with torch.cuda.device(dev):
+            ws, ws_bytes = workspace("snx_mv_lists_workspace_bytes", dev, nd, nc)
+            call("snx_mv_lists_build", _p(self.codes), self.num_rows, self._hptr, nd, nc, _p(list_ptr), _p(docs), _p(ws),
+                 ws_bytes, _stream())
+        host = list_ptr.tolist()
+        self.list_ptr, self.list_docs = list_ptr, docs[:host[-1]].clone()
+        self._hlist = (C.c_int64 * (nc + 1))(*host)
+
+    def _candidates(self, qmv, ptr, ex_ptr, ex_doc, ncand: int, chunk_docs: int, query_slice: int, nprobe: int = 0):
         nq, nd, dev, nc = len(ptr) - 1, self.num_docs, self.device, int(self.centroids.shape[0])
         approx, docs, _, _ = search_outputs(nq, ncand, dev, False)
+        if nprobe:
+            self._lists()
         with torch.cuda.device(dev):
             for s, m, rows, hq in self._launches(qmv, ptr, query_slice):
+                if nprobe:
+                    ws, ws_bytes = workspace("snx_mv_candidates_probed_workspace_bytes", dev, hq, m, nd, nc, ncand,
+                                             chunk_docs, nprobe)
+                    call("snx_mv_candidates_probed", _p(self.codes), self.num_rows, self._hptr, nd, _p(self.centroids), nc,
+                         _p(rows), int(self.dtype == torch.float32), self.dim, int(rows.shape[0]), hq, m, _p(at(ex_ptr, s)),
+                         _p(ex_doc), ncand, chunk_docs, self._hlist, _p(self.list_docs), int(self.list_docs.numel()), nprobe,
+                         _p(docs[s:]), _p(approx[s:]), _p(ws), ws_bytes, _stream())
+                    continue
                 ws, ws_bytes = workspace("snx_mv_candidates_workspace_bytes", dev, hq, m, nd, nc, ncand, chunk_docs)
                 call("snx_mv_candidates", _p(self.codes), self.num_rows, self._hptr, nd, _p(self.centroids), nc, _p(rows),
                      int(self.dtype == torch.float32), self.dim, int(rows.shape[0]), hq, m, _p(at(ex_ptr, s)), _p(ex_doc),
@@ -327,39 +369,39 @@ class MultiVectorIndex:
                      _p(found[s:]), _p(ws), ws_bytes, _stream())
         return scores, docs, found
 
-    def candidates(self, qmv: torch.Tensor, q_ptr, ncand: int, exclude=None, chunk_docs: int = 0, query_slice: int = 0
-                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    def candidates(self, qmv: torch.Tensor, q_ptr, ncand: int, exclude=None, chunk_docs: int = 0, query_slice: int = 0,
+                   nprobe: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
         """The ``ncand`` best documents of each query under the centroid score a(q, d) (the class docstring) among the
         documents with rows that are not in ``exclude[q]`` -> (a [nq, ncand] fp32, docs [nq, ncand] int32); unused slots
-        0 / -1."""
-        ncand = self._two_phase("candidates", ncand, 0)
+        0 / -1.  ``nprobe`` > 0: among the probed documents only."""
+        ncand = self._two_phase("candidates", ncand, 0, nprobe)
         qmv, ptr, chunk_docs = self._queries("candidates", qmv, q_ptr, chunk_docs, query_slice)
         ex_ptr, ex_doc = exclusion_or_null(exclude, len(ptr) - 1, self.num_docs, self.device)
-        return self._candidates(qmv, ptr, ex_ptr, ex_doc, ncand, chunk_docs, query_slice)
+        return self._candidates(qmv, ptr, ex_ptr, ex_doc, ncand, chunk_docs, query_slice, int(nprobe))
 
-    def search_two_phase(self, qmv: torch.Tensor, q_ptr, k: int, ncand: int, chunk_docs: int = 0, query_slice: int = 0
-                         ) -> Tuple[torch.Tensor, torch.Tensor]:
+    def search_two_phase(self, qmv: torch.Tensor, q_ptr, k: int, ncand: int, chunk_docs: int = 0, query_slice: int = 0,
+                         nprobe: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
         """``search`` over the ``ncand`` >= ``k`` candidates of ``candidates``, scored exactly."""
         k = int(k)
         if not 1 <= k <= K_MAX:
             raise ValueError(f"MultiVectorIndex.search_two_phase: k must be in [1, {K_MAX}]")
-        ncand = self._two_phase("search_two_phase", ncand, k)
+        ncand = self._two_phase("search_two_phase", ncand, k, nprobe)
         qmv, ptr, chunk_docs = self._queries("search_two_phase", qmv, q_ptr, chunk_docs, query_slice)
-        _, cand = self._candidates(qmv, ptr, None, None, ncand, chunk_docs, query_slice)
+        _, cand = self._candidates(qmv, ptr, None, None, ncand, chunk_docs, query_slice, int(nprobe))
         return self._rescore(qmv, ptr, cand, 0, k, query_slice)[:2]
 
     def search_band_two_phase(self, qmv: torch.Tensor, q_ptr, lo: int, hi: int, ncand: int, exclude=None,
-                              chunk_docs: int = 0, query_slice: int = 0
+                              chunk_docs: int = 0, query_slice: int = 0, nprobe: int = 0
                               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """``search_band`` over the ``ncand`` >= ``hi`` candidates of ``candidates`` (``exclude`` applies there), scored
         exactly."""
         lo, hi = int(lo), int(hi)
         if not 0 <= lo < hi <= K_MAX:
             raise ValueError(f"MultiVectorIndex.search_band_two_phase: need 0 <= lo < hi <= {K_MAX}")
-        ncand = self._two_phase("search_band_two_phase", ncand, hi)
+        ncand = self._two_phase("search_band_two_phase", ncand, hi, nprobe)
         qmv, ptr, chunk_docs = self._queries("search_band_two_phase", qmv, q_ptr, chunk_docs, query_slice)
         ex_ptr, ex_doc = exclusion_or_null(exclude, len(ptr) - 1, self.num_docs, self.device)
-        _, cand = self._candidates(qmv, ptr, ex_ptr, ex_doc, ncand, chunk_docs, query_slice)
+        _, cand = self._candidates(qmv, ptr, ex_ptr, ex_doc, ncand, chunk_docs, query_slice, int(nprobe))
         return self._rescore(qmv, ptr, cand, lo, hi, query_slice)
 
     # -------------------------------------------------------------------------------------------- residual store

@@ -15,7 +15,7 @@
         [--batch-tokens 16384] [--chunk-records 256] [--precision bf16|fp32] [--tokenizer gpu:DIR|unigram:DIR]
     python -m src.train.cli.teacher_scores mine-mv --model-dir /models/bge-m3 --input-pattern "data/v29.0_kd/train_*.jsonl" \\
         --output-dir data/v30.0_mv_neg [--k 7 --rank-start 10 --rank-end 50 --max-length 256 --precision bf16] \\
-        [--index exact|centroid --ncentroids 1024 --ncand 0 --nbits 0]
+        [--index exact|centroid --ncentroids 1024 --ncand 0 --nbits 0 --nprobe 0]
 
 ``mine-mv`` mines hard negatives under the multi-vector teacher (src.train.mining.multivector.mine_multivector_negatives): the
 unique positives of the shards are encoded into an ``snx.retrieval.MultiVectorIndex`` (csrc/mv_search.hip), every query is
@@ -129,6 +129,9 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     sp.add_argument("--nbits", type=int, choices=(0, 1, 2, 4), default=0,
                     help="--index centroid, bf16: residual-compress the store to this many bits per dimension and score "
                          "from the packed form (0: keep the bf16 rows)")
+    sp.add_argument("--nprobe", type=int, default=0,
+                    help="--index centroid: centroid lists a query row probes for candidates, 1 .. 64 (0: every document "
+                         "is walked)")
     sp.add_argument("--precision", choices=("bf16", "fp32"), default="bf16")
     sp.add_argument("--tokenizer", type=str, default=None, help="gpu:DIR or unigram:DIR, as for encode")
     sp.add_argument("--device", type=str, default="cuda:0")
@@ -136,6 +139,8 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     if args.command == "mine-mv":
         if args.nbits and (args.index != "centroid" or args.precision != "bf16"):
             ap.error("--nbits needs --index centroid and --precision bf16")
+        if not 0 <= args.nprobe <= 64 or (args.nprobe and args.index != "centroid"):
+            ap.error("need --nprobe 0, or 1 .. 64 with --index centroid")
         if args.k < 1 or not 0 <= args.rank_start < args.rank_end <= 1024:
             ap.error("need --k >= 1 and 0 <= --rank-start < --rank-end <= 1024")
         if not 1 <= args.ncentroids <= 4096 or not (args.ncand == 0 or args.rank_end <= args.ncand <= 1024):
@@ -242,7 +247,7 @@ def mine_mv_main(args: argparse.Namespace, tokenizer=None) -> dict:
     out = mine_multivector_negatives(files, args.output_dir, teacher.encode_multivector, index, k=args.k,
                                      rank_start=args.rank_start, rank_end=args.rank_end, chunk_texts=args.chunk_texts,
                                      chunk_docs=args.chunk_docs, index_type=args.index, ncentroids=args.ncentroids,
-                                     ncand=args.ncand, nbits=args.nbits)
+                                     ncand=args.ncand, nbits=args.nbits, nprobe=args.nprobe)
     print(json.dumps(out))
     copy_val_files([args.val_pattern], args.output_dir)
     return out

@@ -115,7 +115,7 @@ def default_ncand(rank_end: int) -> int:
 def mine_multivector_negatives(input_files: Sequence[str], output_dir: str, encode_mv: Callable, index, *, k: int = 7,
                                rank_start: int = 10, rank_end: int = 50, chunk_texts: int = 256,
                                chunk_docs: int = 0, index_type: str = "exact", ncentroids: int = 1024,
-                               ncand: int = 0, nbits: int = 0) -> Dict:
+                               ncand: int = 0, nbits: int = 0, nprobe: int = 0) -> Dict:
     """Hard negatives under the late-interaction teacher: per record ``k`` negatives from ranks [rank_start, rank_end) of
     the MaxSim search of its query over the corpus, the unique positives of the shards, with the query's own positives
     (all of them, over every record of the query) excluded before ranking.  ``encode_mv(texts) -> (emb, mv_ptr, mv)``
@@ -128,7 +128,9 @@ def mine_multivector_negatives(input_files: Sequence[str], output_dir: str, enco
     centroid-interaction pass (0: ``default_ncand(rank_end)``), after ``index.train_centroids(ncentroids)``; the negatives
     are then approximate, their scores and the positives' still exact.  ``nbits`` 1, 2 or 4 (centroid only; 0: uncompressed):
     the store is then residual-compressed (``index.compress(nbits)``), the bf16 rows are released and every score, the
-    positives' included, is the packed form's.  Returns the counts: records, queries, docs, store_rows, store_bytes, band_fill, padded, unchanged."""
+    positives' included, is the packed form's.  ``nprobe`` 1 .. 64 (centroid only; 0: every document is walked): the
+    candidates come from the documents in the ``nprobe`` best centroid lists of each query row
+    (``search_band_two_phase(..., nprobe=nprobe)``).  Returns the counts: records, queries, docs, store_rows, store_bytes, band_fill, padded, unchanged."""
     import torch
     from . import META_KEYS
     k, rank_start, rank_end, chunk_texts = int(k), int(rank_start), int(rank_end), int(chunk_texts)
@@ -141,6 +143,10 @@ def mine_multivector_negatives(input_files: Sequence[str], output_dir: str, enco
         raise ValueError("multi-vector mining: need rank_end <= ncand <= 1024")
     if int(nbits) not in (0, 1, 2, 4) or (int(nbits) and index_type != "centroid"):
         raise ValueError('multi-vector mining: nbits is 0, or 1, 2 or 4 with index_type="centroid"')
+    if isinstance(nprobe, bool) or not isinstance(nprobe, int) or not 0 <= nprobe <= 64 or \
+            (nprobe and index_type != "centroid"):
+        raise ValueError('multi-vector mining: nprobe is 0, or 1 .. 64 with index_type="centroid"')
+    probed = {"nprobe": nprobe} if nprobe else {}
     files = sorted(input_files)
     shards = [_read(f) for f in files]
     docs: Dict[str, int] = {}
@@ -178,7 +184,7 @@ def mine_multivector_negatives(input_files: Sequence[str], output_dir: str, enco
         exclude = [sorted(positives[s + i]) for i in kept]
         if index_type == "centroid":
             sc, dd, found = index.search_band_two_phase(mv, qptr, rank_start, rank_end, ncand, exclude=exclude,
-                                                        chunk_docs=chunk_docs)
+                                                        chunk_docs=chunk_docs, **probed)
         else:
             sc, dd, found = index.search_band(mv, qptr, rank_start, rank_end, exclude=exclude, chunk_docs=chunk_docs)
         sc, dd, found = sc.cpu().tolist(), dd.cpu().tolist(), found.cpu().tolist()
