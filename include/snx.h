@@ -828,6 +828,39 @@ int snx_mv_candidates_probed(const uint16_t* codes, int64_t drows, const int64_t
                              const int32_t* list_docs, int64_t list_len, int32_t nprobe, int32_t* cand_doc,
                              float* cand_score, void* workspace, size_t ws_bytes, hipStream_t stream);
 
+/* ---- multi-vector fixed-dimensional encodings (csrc/mv_fde.hip): MUVERA's data-oblivious map of a ragged set of bf16 rows
+ * to one fp32 vector; <query FDE, document FDE> approximates the Chamfer / MaxSim sum, so that every dense index serves as
+ * a candidate generator in front of snx_mv_rescore.  MUVERA's final count-sketch projection is not part of it, and no
+ * parity with another implementation's random operands is claimed.
+ * Parameters (SNX_E_SHAPE otherwise): D % 64 == 0, D <= 1024; k_sim in 0 .. 6, B = 2^k_sim buckets; reps in 1 .. 32; d_proj
+ * 16, 32 or 64; fde_dim = reps B d_proj <= 4096.  Operands, bf16 on the device, 16-byte aligned: planes [reps, k_sim, D]
+ * (may be NULL when k_sim == 0) and proj [reps, d_proj, D].
+ * Definition.  For a row x and repetition r: c_r(x) = sum_j 2^j [<planes[r, j], x> > 0] and y_r(x) = proj[r] x, every dot
+ * product the bf16 products accumulated in fp32 on v_mfma_f32_32x32x16_bf16, k-steps of 16 in ascending order.
+ *   query FDE, block (r, b):     the fp32 sum of y_r(x) over the sequence's rows with c_r(x) == b, a left fold in ascending
+ *                                row order from +0, multiplied once by scale = fp32(1 / sqrt(d_proj)); an empty block is 0;
+ *   document FDE, block (r, b):  the same sum divided by the count (one fp32 division), then multiplied by scale; an empty
+ *                                block is scale * y_r(x*), x* the sequence's row with the smallest popcount(b xor c_r(x)),
+ *                                ties to the lowest row.
+ * A sequence without rows encodes to zeros.  Block (r, b) sits at offset (r B + b) d_proj of the sequence's fde_dim floats.
+ * An FDE is a pure function of its own sequence's rows and the operands: the same bits in every call, whatever else the
+ * call holds and however it is sliced.  There is no atomic on a float.
+ * snx_mv_fde_pack: planes and proj -> packed, snx_mv_fde_packed_bytes(D, k_sim, reps, d_proj) bytes (0 for parameters
+ * the calls refuse): one operand in the order the MFMA reads it, the sign columns of a repetition next to its projection
+ * columns.  Once per encoder.
+ * snx_mv_fde_encode: rows [nrows, D] bf16 with mv_ptr [nseq + 1] (a pageable HOST array under the lifetime rule of
+ * snx_maxsim_pairs; nseq <= 2^24) -> out [nseq, fde_dim] fp32, 16-byte aligned; is_query != 0: the query form.
+ * SNX_E_SHAPE / SNX_E_ARG before any launch: the parameters, a null or misaligned pointer, mv_ptr not ascending from 0 or
+ * past nrows, a workspace smaller than snx_mv_fde_workspace_bytes(mv_ptr, nseq) (0 for arguments the call would refuse):
+ * the device copy of mv_ptr and the first sequence of every workgroup's unit. */
+size_t snx_mv_fde_packed_bytes(int32_t D, int32_t k_sim, int32_t reps, int32_t d_proj);
+int snx_mv_fde_pack(const void* planes, const void* proj, int32_t D, int32_t k_sim, int32_t reps, int32_t d_proj,
+                    void* packed, hipStream_t stream);
+size_t snx_mv_fde_workspace_bytes(const int64_t* mv_ptr /*[host]*/, int32_t nseq);
+int snx_mv_fde_encode(const void* rows, int64_t nrows, const int64_t* mv_ptr /*[host]*/, int32_t nseq, const void* packed,
+                      int32_t D, int32_t k_sim, int32_t reps, int32_t d_proj, int32_t is_query, float* out, void* workspace,
+                      size_t ws_bytes, hipStream_t stream);
+
 /* ---- two-phase dense retrieval (csrc/dense_two_phase.hip): the result of the exact dense section with most of the work
  * on the bf16 MFMA.  Phase 1 scores bf16 copies of the operands and proposes k1 candidates per query; phase 2 scores the
  * candidates by the exact section's chain on the fp32 operands; a per-query certificate proves, from norms computed once,

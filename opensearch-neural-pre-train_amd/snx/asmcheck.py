@@ -95,6 +95,9 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
     # and for the lexical weights: the 64-bit keys live in LDS, a thread's key, its ballot and the unused ids (kernel
     # arguments) in registers; the head's row kernel and the pair scorer hold no LDS and are not listed
     "teacher_lex.hip": ("tl_unique_kernel",),
+    # and for the FDE encoder: the two accumulator tiles, the packed operand of the current and the next K slice and the
+    # prefetched rows stay in registers, the bucket sums in LDS; the pack and empty-sequence kernels hold no LDS
+    "mv_fde.hip": ("mvf_encode_kernel",),
 }
 
 # Per-source compile flags, for the library and for the guard's assembly alike (snx/build.py keys its objects on them).
@@ -109,6 +112,7 @@ FILE_FLAGS: Dict[str, Tuple[str, ...]] = {
     "teacher_mv.hip": _NO_PACKED_F32,
     "teacher_lex.hip": _NO_PACKED_F32,
     "mv_centroid.hip": _NO_PACKED_F32,
+    "mv_fde.hip": _NO_PACKED_F32,
 }
 
 

@@ -29,14 +29,17 @@ same dense embeddings, with ``DenseIndex``'s scores and order inside the probed 
 graph walked by a best-first beam, again with ``DenseIndex``'s scores and order (csrc/graph.hip, include/snx.h "graph
 dense retrieval").  ``MultiVectorIndex`` is the exact MaxSim search over the ragged multi-vector rows of
 ``snx.teacher``'s ``encode_multivector``, with ``maxsim_pairs``' scores bit for bit and ``DenseIndex``'s order
-(csrc/mv_search.hip, include/snx.h "multi-vector search")."""
+(csrc/mv_search.hip, include/snx.h "multi-vector search").  ``FdeEncoder`` maps such a ragged sequence to one fp32 vector,
+MUVERA's fixed-dimensional encoding, so that a dense index proposes the candidates of ``MultiVectorIndex``'s two-phase
+searches (csrc/mv_fde.hip, include/snx.h "multi-vector fixed-dimensional encodings")."""
 from ._common import K_MAX, exclusion_csr
 from .dense import DENSE_CHUNK_MIN, DENSE_DIM_MAX, DenseIndex, bf16_rows
 from .graph import GRAPH_DEGREE_MAX, GRAPH_EF_MAX, GRAPH_KNN_MAX, GRAPH_WIDTH_MAX, GraphIndex, entry_sample
 from .hybrid import (FUSE_L_MAX, FUSE_METHODS, FUSE_TOP_K_MAX, Bm25Index, bm25_idf, fuse_ranked, term_counts,
                      term_counts_max_len)
 from .ivf import IVF_NLIST_MAX, IVF_SPLIT_MIN, IvfFlatIndex
-from .multivector import MV_CHUNK_MAX, MV_CHUNK_MIN, MV_DIM_MAX, MultiVectorIndex
+from .multivector import (MV_CHUNK_MAX, MV_CHUNK_MIN, MV_DIM_MAX, MV_FDE_DPROJ, MV_FDE_KSIM_MAX, MV_FDE_REPS_MAX, FdeEncoder,
+                          MultiVectorIndex)
 from .qrels import (BOOTSTRAP_M_MAX, BOOTSTRAP_SEGMENT, CUTOFFS_MAX, RANKED_R_MAX, bootstrap_indices, bootstrap_means,
                     discount_table, ranked_relevance, relevance_csr)
 from .seismic import SEISMIC_Q_MAX, SeismicIndex

@@ -7,10 +7,11 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from .._lib import call
+from .._lib import call, fn
 from ..ops import _p, _stream
-from ._common import (K_MAX, at, cat_or_empty, check_pairs, check_query_slice, cuda_device, exclusion_or_null, search_outputs,
-                      workspace)
+from .dense import DENSE_DIM_MAX, DenseIndex
+from ._common import (K_MAX, at, cat_or_empty, check_pairs, check_query_slice, cuda_device, exclusion_csr, exclusion_or_null,
+                      offsets, search_outputs, workspace)
 
 MV_DIM_MAX = 1024
 MV_CHUNK_MIN, MV_CHUNK_MAX = 64, 8192  # docs per chunk of the walk
@@ -20,6 +21,11 @@ _MV_ROWS_PER_LAUNCH = 1 << 15          # query rows of one launch: 512 query blo
 MV_NBITS = (1, 2, 4)                   # bits per dimension of a residual-compressed store
 MV_NPROBE_MAX = 64                     # centroids a query row probes
 _MV_QUANTILE_MAX = 1 << 24             # elements torch.quantile takes
+MV_FDE_KSIM_MAX = 6                    # 2^k_sim buckets per repetition of a fixed-dimensional encoding
+MV_FDE_REPS_MAX = 32
+MV_FDE_DPROJ = (16, 32, 64)
+_MV_FDE_ROWS = 1 << 18                 # store rows of one encode call
+_MV_FDE_SEQS = 1 << 16                 # and its sequences
 
 
 def _ptr_list(ptr, rows: int, who: str, name: str) -> List[int]:
@@ -31,6 +37,98 @@ def _ptr_list(ptr, rows: int, who: str, name: str) -> List[int]:
     if p[0] != 0 or any(b < a for a, b in zip(p, p[1:])) or p[-1] > rows:
         raise ValueError(f"{who}: {name} must ascend from 0 and end within the rows")
     return p
+
+
+class FdeEncoder:
+    """MUVERA's fixed-dimensional encoding of ragged bf16 multi-vector rows on the GPU (csrc/mv_fde.hip, include/snx.h
+    "multi-vector fixed-dimensional encodings"): one fp32 vector of ``fde_dim = reps * 2^k_sim * d_proj`` per sequence, such
+    that <query FDE, document FDE> approximates the MaxSim sum.  Data-oblivious: nothing is trained.
+
+        enc = FdeEncoder(dim, k_sim, reps, d_proj, device, seed=0, planes=None, proj=None)
+        fde = enc.encode_documents(mv, mv_ptr)         # fp32 [n, fde_dim]
+        qfde = enc.encode_queries(qmv, q_ptr)
+
+    ``dim`` a multiple of 64, at most 1024; ``k_sim`` 0 .. 6; ``reps`` 1 .. 32; ``d_proj`` 16, 32 or 64; ``fde_dim`` at most
+    ``DENSE_DIM_MAX``.  ``planes`` [reps, k_sim, dim] and ``proj`` [reps, d_proj, dim] are bf16 (given, or rounded to it).
+    Without them, exactly
+
+        planes = torch.randn(reps, k_sim, dim, generator=torch.Generator().manual_seed(seed)).to(torch.bfloat16)
+        proj = (2 * torch.randint(0, 2, (reps, d_proj, dim), generator=torch.Generator().manual_seed(seed + 1)) - 1)
+               .to(torch.bfloat16)
+
+    both drawn on the CPU.  The encoding itself is the header's: bit-reproducible, a pure function of the sequence's own
+    rows.  Only bf16 rows are encoded; fp32 rows raise."""
+
+    def __init__(self, dim: int, k_sim: int, reps: int, d_proj: int, device, seed: int = 0, planes=None, proj=None):
+        for name, v in (("dim", dim), ("k_sim", k_sim), ("reps", reps), ("d_proj", d_proj), ("seed", seed)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"FdeEncoder: {name} must be an int")
+        if not 1 <= dim <= MV_DIM_MAX or dim % 64:
+            raise ValueError(f"FdeEncoder: dim must be a multiple of 64, at most {MV_DIM_MAX}")
+        if not 0 <= k_sim <= MV_FDE_KSIM_MAX or not 1 <= reps <= MV_FDE_REPS_MAX or d_proj not in MV_FDE_DPROJ:
+            raise ValueError(f"FdeEncoder: need k_sim in [0, {MV_FDE_KSIM_MAX}], reps in [1, {MV_FDE_REPS_MAX}] and d_proj "
+                             f"in {MV_FDE_DPROJ}")
+        self.dim, self.k_sim, self.reps, self.d_proj = int(dim), int(k_sim), int(reps), int(d_proj)
+        self.fde_dim = self.reps * (1 << self.k_sim) * self.d_proj
+        if self.fde_dim > DENSE_DIM_MAX:
+            raise ValueError(f"FdeEncoder: fde_dim = reps * 2^k_sim * d_proj = {self.fde_dim} exceeds {DENSE_DIM_MAX}")
+        self.device = torch.device(device) if torch.device(device).type != "cuda" else cuda_device(device)
+        if (planes is None) != (proj is None):
+            raise ValueError("FdeEncoder: give both planes and proj, or neither")
+        if planes is None:
+            planes = torch.randn(self.reps, self.k_sim, self.dim, generator=torch.Generator().manual_seed(int(seed)))
+            proj = 2 * torch.randint(0, 2, (self.reps, self.d_proj, self.dim),
+                                     generator=torch.Generator().manual_seed(int(seed) + 1)) - 1
+        for name, x, mid in (("planes", planes, self.k_sim), ("proj", proj, self.d_proj)):
+            if not isinstance(x, torch.Tensor) or tuple(x.shape) != (self.reps, mid, self.dim) or \
+                    not bool(torch.isfinite(x.float()).all()):
+                raise ValueError(f"FdeEncoder: {name} must be a finite tensor [{self.reps}, {mid}, {self.dim}]")
+        self.planes = planes.to(torch.bfloat16).to(self.device).contiguous()
+        self.proj = proj.to(torch.bfloat16).to(self.device).contiguous()
+        self._packed: Optional[torch.Tensor] = None               # the MFMA operand, packed by the first encode
+
+    def _geometry(self):
+        return self.dim, self.k_sim, self.reps, self.d_proj
+
+    def _encode(self, who: str, mv, ptr, is_query: int) -> torch.Tensor:
+        if not isinstance(mv, torch.Tensor) or mv.dim() != 2 or mv.shape[1] != self.dim:
+            raise ValueError(f"FdeEncoder.{who}: the rows must be a [rows, {self.dim}] tensor")
+        if mv.dtype != torch.bfloat16:
+            raise ValueError(f"FdeEncoder.{who}: only bf16 rows are encoded, got {mv.dtype}")
+        if mv.device != self.device:
+            raise ValueError(f"FdeEncoder.{who}: the rows must be on {self.device}")
+        ptr = _ptr_list(ptr, int(mv.shape[0]), f"FdeEncoder.{who}", "ptr")
+        if self.device.type != "cuda":
+            raise ValueError(f"FdeEncoder.{who}: the encoder needs a GPU")
+        mv, n, dev = mv.contiguous(), len(ptr) - 1, self.device
+        out = torch.empty((n, self.fde_dim), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            if self._packed is None:
+                packed = torch.empty(int(fn("snx_mv_fde_packed_bytes")(*self._geometry())), dtype=torch.uint8, device=dev)
+                call("snx_mv_fde_pack", _p(self.planes if self.k_sim else None), _p(self.proj), *self._geometry(),
+                     _p(packed), _stream())
+                self._packed = packed
+            s = 0
+            while s < n:                                          # slices of whole sequences
+                e = s + 1
+                while e < n and e - s < _MV_FDE_SEQS and ptr[e + 1] - ptr[s] <= _MV_FDE_ROWS:
+                    e += 1
+                rows = mv[ptr[s]:ptr[e]]
+                hp = (C.c_int64 * (e - s + 1))(*[v - ptr[s] for v in ptr[s:e + 1]])
+                ws, ws_bytes = workspace("snx_mv_fde_workspace_bytes", dev, hp, e - s)
+                call("snx_mv_fde_encode", _p(rows), int(rows.shape[0]), hp, e - s, _p(self._packed), *self._geometry(),
+                     is_query, _p(out[s:]), _p(ws), ws_bytes, _stream())
+                s = e
+        return out
+
+    def encode_documents(self, mv: torch.Tensor, mv_ptr) -> torch.Tensor:
+        """``mv`` bf16 [rows, dim] with ``mv_ptr`` [n + 1] -> the document FDEs, fp32 [n, fde_dim]: bucket means, an empty
+        block filled from the nearest code.  A sequence without rows encodes to zeros."""
+        return self._encode("encode_documents", mv, mv_ptr, 0)
+
+    def encode_queries(self, qmv: torch.Tensor, q_ptr) -> torch.Tensor:
+        """The query FDEs: bucket sums, an empty block 0."""
+        return self._encode("encode_queries", qmv, q_ptr, 1)
 
 
 class MultiVectorIndex:
@@ -64,6 +162,15 @@ class MultiVectorIndex:
     place, and ranked.  With ``ncand`` at least the number of documents with rows the result is the exact search's, bit
     for bit; below it the result is approximate, and every returned score is still s(q, d).  ``add`` invalidates both.
 
+    Or the candidates come from fixed-dimensional encodings (``FdeEncoder``), with no centroids at all:
+
+        index.set_fde(FdeEncoder(dim, k_sim, reps, d_proj, device))             # after build(); bf16 stores
+        scores, docs = index.search_two_phase(qmv, q_ptr, k, ncand, fde=True)   # also candidates, search_band_two_phase
+
+    ``index.fde`` (fp32 [num_docs, fde_dim]) holds the documents' FDEs; the candidates are the best ``ncand`` documents with
+    rows, outside ``exclude``, by <query FDE, document FDE> under ``DenseIndex``'s chain and order, and the rescore is the
+    same exact one.  ``fde=True`` with ``nprobe`` > 0 raises.  ``add`` invalidates the FDEs.
+
     A bf16 index can drop its rows for ColBERTv2's residual form, ``codes`` plus ``nbits`` bits per dimension:
 
         index.compress(nbits, cutoffs=None, weights=None, sample_rows=1 << 14, keep_rows=False)   # after the centroids
@@ -95,6 +202,13 @@ class MultiVectorIndex:
         self.codes: Optional[torch.Tensor] = None             # uint16 [num_rows]: the best centroid of every row
         self._unlist()
         self._uncompress()
+        self._unfde()
+
+    def _unfde(self) -> None:
+        self.fde: Optional[torch.Tensor] = None               # fp32 [num_docs, fde_dim]: the documents' FDEs (set_fde)
+        self._fde_encoder: Optional[FdeEncoder] = None
+        self._fde_index: Optional[DenseIndex] = None          # the dense index over them
+        self._fde_rowless: Optional[torch.Tensor] = None      # int64: the documents without rows, ascending
 
     def _unlist(self) -> None:
         self.list_ptr: Optional[torch.Tensor] = None          # int64 [nc + 1]: the inverted lists of the codes,
@@ -148,6 +262,7 @@ class MultiVectorIndex:
         self.centroids = self.codes = None                    # and its codes
         self._unlist()                                        # and their lists
         self._uncompress()                                    # and their residuals
+        self._unfde()                                         # and the FDEs
 
     def build(self) -> "MultiVectorIndex":
         if len(self._parts) != 1:
@@ -302,14 +417,19 @@ class MultiVectorIndex:
         self._assign(self._quantizer("set_centroids", int(c.shape[0])), c)
         return self
 
-    def _two_phase(self, who: str, ncand, hi: int, nprobe=0) -> int:
+    def _two_phase(self, who: str, ncand, hi: int, nprobe=0, fde: bool = False) -> int:
+        if fde and nprobe:
+            raise ValueError(f"MultiVectorIndex.{who}: fde=True takes its candidates from the dense index over the FDEs; "
+                             "nprobe must be 0")
         if isinstance(nprobe, bool) or not isinstance(nprobe, (int, np.integer)) or not 0 <= int(nprobe) <= MV_NPROBE_MAX:
             raise ValueError(f"MultiVectorIndex.{who}: nprobe must be an int in [0, {MV_NPROBE_MAX}] (0: no probing)")
         if isinstance(ncand, bool) or not isinstance(ncand, (int, np.integer)) or not 1 <= int(ncand) <= K_MAX:
             raise ValueError(f"MultiVectorIndex.{who}: ncand must be an int in [1, {K_MAX}]")
         if hi > int(ncand):
             raise ValueError(f"MultiVectorIndex.{who}: ranks up to {hi} need ncand >= {hi}")
-        if self.built and self.codes is None:
+        if fde and self._fde_index is None:
+            raise RuntimeError(f"MultiVectorIndex.{who}: call set_fde() first")
+        if not fde and self.built and self.codes is None:
             raise RuntimeError(f"MultiVectorIndex.{who}: call train_centroids() or set_centroids() first")
         return int(ncand)
 
@@ -370,39 +490,91 @@ class MultiVectorIndex:
         return scores, docs, found
 
     def candidates(self, qmv: torch.Tensor, q_ptr, ncand: int, exclude=None, chunk_docs: int = 0, query_slice: int = 0,
-                   nprobe: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+                   nprobe: int = 0, fde: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """The ``ncand`` best documents of each query under the centroid score a(q, d) (the class docstring) among the
         documents with rows that are not in ``exclude[q]`` -> (a [nq, ncand] fp32, docs [nq, ncand] int32); unused slots
-        0 / -1.  ``nprobe`` > 0: among the probed documents only."""
-        ncand = self._two_phase("candidates", ncand, 0, nprobe)
+        0 / -1.  ``nprobe`` > 0: among the probed documents only.  ``fde=True`` (after ``set_fde``): the score is the inner
+        product of the query's FDE with the document's instead, under ``DenseIndex.search_band``'s chain and order;
+        ``chunk_docs`` is then unused."""
+        ncand = self._two_phase("candidates", ncand, 0, nprobe, fde)
         qmv, ptr, chunk_docs = self._queries("candidates", qmv, q_ptr, chunk_docs, query_slice)
+        if fde:
+            return self._fde_candidates(qmv, ptr, exclude, ncand, query_slice)
         ex_ptr, ex_doc = exclusion_or_null(exclude, len(ptr) - 1, self.num_docs, self.device)
         return self._candidates(qmv, ptr, ex_ptr, ex_doc, ncand, chunk_docs, query_slice, int(nprobe))
 
     def search_two_phase(self, qmv: torch.Tensor, q_ptr, k: int, ncand: int, chunk_docs: int = 0, query_slice: int = 0,
-                         nprobe: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+                         nprobe: int = 0, fde: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """``search`` over the ``ncand`` >= ``k`` candidates of ``candidates``, scored exactly."""
         k = int(k)
         if not 1 <= k <= K_MAX:
             raise ValueError(f"MultiVectorIndex.search_two_phase: k must be in [1, {K_MAX}]")
-        ncand = self._two_phase("search_two_phase", ncand, k, nprobe)
+        ncand = self._two_phase("search_two_phase", ncand, k, nprobe, fde)
         qmv, ptr, chunk_docs = self._queries("search_two_phase", qmv, q_ptr, chunk_docs, query_slice)
-        _, cand = self._candidates(qmv, ptr, None, None, ncand, chunk_docs, query_slice, int(nprobe))
+        if fde:
+            _, cand = self._fde_candidates(qmv, ptr, None, ncand, query_slice)
+        else:
+            _, cand = self._candidates(qmv, ptr, None, None, ncand, chunk_docs, query_slice, int(nprobe))
         return self._rescore(qmv, ptr, cand, 0, k, query_slice)[:2]
 
     def search_band_two_phase(self, qmv: torch.Tensor, q_ptr, lo: int, hi: int, ncand: int, exclude=None,
-                              chunk_docs: int = 0, query_slice: int = 0, nprobe: int = 0
+                              chunk_docs: int = 0, query_slice: int = 0, nprobe: int = 0, fde: bool = False
                               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """``search_band`` over the ``ncand`` >= ``hi`` candidates of ``candidates`` (``exclude`` applies there), scored
         exactly."""
         lo, hi = int(lo), int(hi)
         if not 0 <= lo < hi <= K_MAX:
             raise ValueError(f"MultiVectorIndex.search_band_two_phase: need 0 <= lo < hi <= {K_MAX}")
-        ncand = self._two_phase("search_band_two_phase", ncand, hi, nprobe)
+        ncand = self._two_phase("search_band_two_phase", ncand, hi, nprobe, fde)
         qmv, ptr, chunk_docs = self._queries("search_band_two_phase", qmv, q_ptr, chunk_docs, query_slice)
+        if fde:
+            _, cand = self._fde_candidates(qmv, ptr, exclude, ncand, query_slice)
+            return self._rescore(qmv, ptr, cand, lo, hi, query_slice)
         ex_ptr, ex_doc = exclusion_or_null(exclude, len(ptr) - 1, self.num_docs, self.device)
         _, cand = self._candidates(qmv, ptr, ex_ptr, ex_doc, ncand, chunk_docs, query_slice, int(nprobe))
         return self._rescore(qmv, ptr, cand, lo, hi, query_slice)
+
+    # -------------------------------------------------------------------------------------------- fixed-dimensional encodings
+    def set_fde(self, encoder: FdeEncoder, slice_docs: int = 1 << 14) -> "MultiVectorIndex":
+        """After ``build()``: ``index.fde`` = ``encoder.encode_documents`` of the store, ``slice_docs`` documents at a time,
+        and a ``DenseIndex`` over it; ``fde=True`` then draws the candidates of the two-phase searches from that index.  No
+        centroids are needed.  bf16 stores only; ``add`` invalidates it."""
+        who = "MultiVectorIndex.set_fde"
+        if not isinstance(encoder, FdeEncoder) or encoder.dim != self.dim or encoder.device != self.device:
+            raise ValueError(f"{who}: encoder must be an FdeEncoder of dim {self.dim} on {self.device}")
+        if self.dtype == torch.float32:
+            raise ValueError(f"{who}: an fp32 index is kept for exactness; only a bf16 index is encoded")
+        if isinstance(slice_docs, bool) or int(slice_docs) < 1:
+            raise ValueError(f"{who}: slice_docs must be positive")
+        self._need_rows("set_fde")
+        if not self.built:
+            raise RuntimeError(f"{who}: call build() first")
+        nd, ptr = self.num_docs, self._ptr
+        fde = torch.empty((nd, encoder.fde_dim), dtype=torch.float32, device=self.device)
+        for s in range(0, nd, int(slice_docs)):
+            e = min(nd, s + int(slice_docs))
+            fde[s:e] = encoder.encode_documents(self.rows[ptr[s]:ptr[e]], [v - ptr[s] for v in ptr[s:e + 1]])
+        lens = torch.tensor(ptr).diff()
+        self.fde, self._fde_encoder = fde, encoder
+        self._fde_rowless = torch.nonzero(lens == 0).flatten()
+        self._fde_index = DenseIndex(encoder.fde_dim, self.device)
+        self._fde_index.add(fde)
+        self._fde_index.build()
+        return self
+
+    def _fde_candidates(self, qmv, ptr, exclude, ncand: int, query_slice: int):
+        """The best ``ncand`` admissible documents by <query FDE, document FDE>: ``DenseIndex.search_band`` with the
+        documents without rows (their FDE is zero, their score 0) added to every exclusion row."""
+        nq, nd = len(ptr) - 1, self.num_docs
+        if self._fde_rowless.numel():
+            ex_ptr, ex_doc = exclusion_csr(exclude if exclude is not None else [[]] * nq, nq, nd, "cpu")
+            row = torch.repeat_interleave(torch.arange(nq), ex_ptr.diff())
+            key = torch.unique(torch.cat([row * nd + ex_doc.long(),
+                                          (torch.arange(nq)[:, None] * nd + self._fde_rowless[None, :]).reshape(-1)]))
+            exclude = (offsets(torch.bincount(key // nd, minlength=nq)), (key % nd).to(torch.int32))
+        qfde = self._fde_encoder.encode_queries(qmv[:ptr[-1]], ptr)
+        scores, docs, _ = self._fde_index.search_band(qfde, 0, ncand, exclude=exclude, query_slice=query_slice)
+        return scores, docs
 
     # -------------------------------------------------------------------------------------------- residual store
     def compress(self, nbits: int, cutoffs=None, weights=None, sample_rows: int = 1 << 14, keep_rows: bool = False

@@ -15,7 +15,7 @@
         [--batch-tokens 16384] [--chunk-records 256] [--precision bf16|fp32] [--tokenizer gpu:DIR|unigram:DIR]
     python -m src.train.cli.teacher_scores mine-mv --model-dir /models/bge-m3 --input-pattern "data/v29.0_kd/train_*.jsonl" \\
         --output-dir data/v30.0_mv_neg [--k 7 --rank-start 10 --rank-end 50 --max-length 256 --precision bf16] \\
-        [--index exact|centroid --ncentroids 1024 --ncand 0 --nbits 0 --nprobe 0]
+        [--index exact|centroid|fde --ncentroids 1024 --ncand 0 --nbits 0 --nprobe 0 --k-sim 4 --reps 16 --d-proj 16]
 
 ``mine-mv`` mines hard negatives under the multi-vector teacher (src.train.mining.multivector.mine_multivector_negatives): the
 unique positives of the shards are encoded into an ``snx.retrieval.MultiVectorIndex`` (csrc/mv_search.hip), every query is
@@ -121,8 +121,12 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     sp.add_argument("--batch-tokens", type=int, default=16384, help="token rows per forward")
     sp.add_argument("--chunk-texts", type=int, default=256, help="texts per encoder call")
     sp.add_argument("--chunk-docs", type=int, default=0)
-    sp.add_argument("--index", choices=("exact", "centroid"), default="exact",
-                    help="centroid: candidates from the centroid-interaction pass (csrc/mv_centroid.hip), scored exactly")
+    sp.add_argument("--index", choices=("exact", "centroid", "fde"), default="exact",
+                    help="centroid: candidates from the centroid-interaction pass (csrc/mv_centroid.hip), scored exactly; "
+                         "fde: from a dense search over fixed-dimensional encodings (csrc/mv_fde.hip), no centroids")
+    sp.add_argument("--k-sim", type=int, default=4, help="--index fde: sign bits per repetition, 0 .. 6")
+    sp.add_argument("--reps", type=int, default=16, help="--index fde: repetitions, 1 .. 32")
+    sp.add_argument("--d-proj", type=int, choices=(16, 32, 64), default=16, help="--index fde: projected width")
     sp.add_argument("--ncentroids", type=int, default=1024, help="--index centroid: centroids trained over the store's rows")
     sp.add_argument("--ncand", type=int, default=0,
                     help="--index centroid: candidates per query (0: max(4 * rank_end, 128), capped at 1024)")
@@ -141,6 +145,10 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
             ap.error("--nbits needs --index centroid and --precision bf16")
         if not 0 <= args.nprobe <= 64 or (args.nprobe and args.index != "centroid"):
             ap.error("need --nprobe 0, or 1 .. 64 with --index centroid")
+        if args.index == "fde" and (not 0 <= args.k_sim <= 6 or not 1 <= args.reps <= 32 or
+                                    args.reps * (1 << args.k_sim) * args.d_proj > 4096 or args.precision != "bf16"):
+            ap.error("--index fde needs --precision bf16, 0 <= --k-sim <= 6, 1 <= --reps <= 32 and "
+                     "reps * 2^k_sim * d_proj <= 4096")
         if args.k < 1 or not 0 <= args.rank_start < args.rank_end <= 1024:
             ap.error("need --k >= 1 and 0 <= --rank-start < --rank-end <= 1024")
         if not 1 <= args.ncentroids <= 4096 or not (args.ncand == 0 or args.rank_end <= args.ncand <= 1024):
@@ -247,7 +255,8 @@ def mine_mv_main(args: argparse.Namespace, tokenizer=None) -> dict:
     out = mine_multivector_negatives(files, args.output_dir, teacher.encode_multivector, index, k=args.k,
                                      rank_start=args.rank_start, rank_end=args.rank_end, chunk_texts=args.chunk_texts,
                                      chunk_docs=args.chunk_docs, index_type=args.index, ncentroids=args.ncentroids,
-                                     ncand=args.ncand, nbits=args.nbits, nprobe=args.nprobe)
+                                     ncand=args.ncand, nbits=args.nbits, nprobe=args.nprobe,
+                                     k_sim=args.k_sim, reps=args.reps, d_proj=args.d_proj)
     print(json.dumps(out))
     copy_val_files([args.val_pattern], args.output_dir)
     return out

@@ -115,7 +115,8 @@ def default_ncand(rank_end: int) -> int:
 def mine_multivector_negatives(input_files: Sequence[str], output_dir: str, encode_mv: Callable, index, *, k: int = 7,
                                rank_start: int = 10, rank_end: int = 50, chunk_texts: int = 256,
                                chunk_docs: int = 0, index_type: str = "exact", ncentroids: int = 1024,
-                               ncand: int = 0, nbits: int = 0, nprobe: int = 0) -> Dict:
+                               ncand: int = 0, nbits: int = 0, nprobe: int = 0, k_sim: int = 4, reps: int = 16,
+                               d_proj: int = 16, fde_seed: int = 0) -> Dict:
     """Hard negatives under the late-interaction teacher: per record ``k`` negatives from ranks [rank_start, rank_end) of
     the MaxSim search of its query over the corpus, the unique positives of the shards, with the query's own positives
     (all of them, over every record of the query) excluded before ranking.  ``encode_mv(texts) -> (emb, mv_ptr, mv)``
@@ -130,23 +131,25 @@ def mine_multivector_negatives(input_files: Sequence[str], output_dir: str, enco
     the store is then residual-compressed (``index.compress(nbits)``), the bf16 rows are released and every score, the
     positives' included, is the packed form's.  ``nprobe`` 1 .. 64 (centroid only; 0: every document is walked): the
     candidates come from the documents in the ``nprobe`` best centroid lists of each query row
-    (``search_band_two_phase(..., nprobe=nprobe)``).  Returns the counts: records, queries, docs, store_rows, store_bytes, band_fill, padded, unchanged."""
+    (``search_band_two_phase(..., nprobe=nprobe)``).  ``index_type="fde"``: no centroids; the candidates come from a dense
+    search over MUVERA fixed-dimensional encodings (``index.set_fde(FdeEncoder(dim, k_sim, reps, d_proj, device, fde_seed))``,
+    then ``search_band_two_phase(..., fde=True)``), the scores exact as for "centroid".  Returns the counts: records, queries, docs, store_rows, store_bytes, band_fill, padded, unchanged."""
     import torch
     from . import META_KEYS
     k, rank_start, rank_end, chunk_texts = int(k), int(rank_start), int(rank_end), int(chunk_texts)
     if k < 1 or not 0 <= rank_start < rank_end <= 1024 or chunk_texts < 1:
         raise ValueError("multi-vector mining: need k >= 1, 0 <= rank_start < rank_end <= 1024 and chunk_texts >= 1")
-    if index_type not in ("exact", "centroid"):
-        raise ValueError('multi-vector mining: index_type is "exact" or "centroid"')
+    if index_type not in ("exact", "centroid", "fde"):
+        raise ValueError('multi-vector mining: index_type is "exact", "centroid" or "fde"')
     ncand = int(ncand) or default_ncand(rank_end)
-    if index_type == "centroid" and not rank_end <= ncand <= 1024:
+    if index_type != "exact" and not rank_end <= ncand <= 1024:
         raise ValueError("multi-vector mining: need rank_end <= ncand <= 1024")
     if int(nbits) not in (0, 1, 2, 4) or (int(nbits) and index_type != "centroid"):
         raise ValueError('multi-vector mining: nbits is 0, or 1, 2 or 4 with index_type="centroid"')
     if isinstance(nprobe, bool) or not isinstance(nprobe, int) or not 0 <= nprobe <= 64 or \
             (nprobe and index_type != "centroid"):
         raise ValueError('multi-vector mining: nprobe is 0, or 1 .. 64 with index_type="centroid"')
-    probed = {"nprobe": nprobe} if nprobe else {}
+    probed = {"nprobe": nprobe} if nprobe else ({"fde": True} if index_type == "fde" else {})
     files = sorted(input_files)
     shards = [_read(f) for f in files]
     docs: Dict[str, int] = {}
@@ -171,6 +174,9 @@ def mine_multivector_negatives(input_files: Sequence[str], output_dir: str, enco
         index.train_centroids(int(ncentroids))
         if int(nbits):
             index.compress(int(nbits))
+    if index_type == "fde" and doc_texts:
+        from snx.retrieval import FdeEncoder
+        index.set_fde(FdeEncoder(index.dim, int(k_sim), int(reps), int(d_proj), index.device, seed=int(fde_seed)))
     bands: Dict[int, List] = {}                                  # query -> [(doc, score)] in rank order
     pscore: Dict = {}                                            # (query, positive) -> score
     fill = 0
@@ -182,7 +188,7 @@ def mine_multivector_negatives(input_files: Sequence[str], output_dir: str, enco
             continue
         qptr = [ptr[i] for i in kept] + [ptr[-1]]
         exclude = [sorted(positives[s + i]) for i in kept]
-        if index_type == "centroid":
+        if index_type != "exact":
             sc, dd, found = index.search_band_two_phase(mv, qptr, rank_start, rank_end, ncand, exclude=exclude,
                                                         chunk_docs=chunk_docs, **probed)
         else:
