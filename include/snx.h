@@ -828,6 +828,54 @@ int snx_mv_candidates_probed(const uint16_t* codes, int64_t drows, const int64_t
                              const int32_t* list_docs, int64_t list_len, int32_t nprobe, int32_t* cand_doc,
                              float* cand_score, void* workspace, size_t ws_bytes, hipStream_t stream);
 
+/* ---- multi-vector token retrieval (csrc/mv_centroid.hip, the mvt_ kernels): token retrieval with imputed missing
+ * similarity (XTR; WARP's shape over a residual store) on the store of "multi-vector residual store", with the terms of
+ * "multi-vector probed candidates".  There is no candidate list and no second pass: the cost follows the probed rows.  The
+ * store is bf16 only, compressed with nbits in 1 / 2 / 4; no parity with another engine's results is claimed.
+ * Definition.
+ *   top(i)   = the min(nprobe, nc) centroids of query row i by (bf16 key descending, centroid id ascending): the probed
+ *              pass's top(i);
+ *   c*(i)    = the next centroid in that order; it exists only when nprobe < nc;
+ *   t(i, j)  = fl32(S32[i, codes[j]] + R(i, j)): snx_mv_rescore_residual's row score, the same two MFMA chains with k
+ *              ascending, S32 added once at the end;
+ *   m'(i, d) = the max of t(i, j) over the rows j of d with codes[j] in top(i); when d has no such row,
+ *              m'(i, d) = miss(i) = S32[i, c*(i)], the fp32 product before any rounding to bf16;
+ *   x(q, d)  = the m'(i, d) added as snx_maxsim_pairs adds: ascending row order within each run of 64 query rows counted
+ *              from the query's own first row, the run sums added in ascending order, one division by Lq;
+ *   P(q)     = the documents that own a row with code in top(i) for some row i of q, minus the query's exclusion row (the
+ *              probed pass's P(q)); a document outside it is never returned;
+ *   result   = ranks lo .. hi-1 of P(q) by (x descending, doc ascending) -> out_doc / out_score [nq, hi - lo]; unused
+ *              slots doc -1, score 0; out_found [nq] = the filled slots.
+ * Hence (1) with nprobe >= nc every row is probed, nothing is imputed, x(q, d) is snx_mv_rescore_residual's score bit for
+ * bit and the result is that call's over all documents with rows; (2) the result is a function of the query, the store,
+ * the centroids, the weights and nprobe alone: not of the other queries of the call, their order, or the launch.
+ * The maximum over the probed rows is taken with integer atomics on the monotone order key of the fp32 value (no float
+ * atomic): for finite values it is the bits fmaxf over the same values gives; the key of -0 lies below the key of +0, so a
+ * tie of the two gives +0 -- which no output bit can show, since every m' is added to a sum that starts at +0.
+ * Operands.  codes, bits, centroids, weights, q, doc_ptr, q_ptr, ex_ptr / ex_doc as snx_mv_rescore_residual and
+ * snx_mv_search_band; mv_f32 must be 0.  row_list_ptr [nc + 1] int64 on the HOST and row_list int32 [doc_ptr[nd]] on the
+ * device: every row id grouped by its code, ascending within a centroid; row_doc int32 [drows] on the device: the
+ * document of every row.  A list entry outside the store, one whose code (read as at most nc - 1) is not its list's
+ * centroid, and a row_doc outside [0, nd) are skipped.  drows < 2^31.
+ * SNX_E_SHAPE / SNX_E_ARG before any launch: D not a multiple of 64 or past 1024, nbits not 1 / 2 / 4, mv_f32 != 0, nc
+ * outside 1 .. 4096, nprobe outside 1 .. 64, lo / hi outside 0 <= lo < hi <= 1024, a null or misaligned pointer, doc_ptr /
+ * q_ptr / row_list_ptr not ascending from 0 or not ending within drows / within qrows / at doc_ptr[nd], a query without
+ * rows.  The call waits on the stream once per slice of queries, for the largest |P(q)| and the size of the score grid.
+ * workspace: snx_mv_token_search_workspace_bytes(q_ptr, nq, nd, drows, nc, nprobe, hi) bytes (0 for arguments the search
+ * would refuse): at most 128 MB of fp32 table (it is dropped after the probe), nprobe + 1 centroids and products per query
+ * row, per query of a bounded slice one bit and one prefix bit-count word per 32 documents, the centroid-major work list,
+ * and one fp32 key per (query of the slice, document of P(q), query row) under a budget of 256 MB or one query's worth
+ * -- nothing of size nq x nd x Lq. */
+size_t snx_mv_token_search_workspace_bytes(const int64_t* q_ptr /*[host]*/, int32_t nq, int32_t nd, int64_t drows, int32_t nc,
+                                           int32_t nprobe, int32_t hi);
+int snx_mv_token_search(const uint16_t* codes, const void* bits, const void* centroids, const uint16_t* weights, int32_t nc,
+                        int32_t nbits, const void* q, int32_t mv_f32, int32_t D, int64_t drows,
+                        const int64_t* doc_ptr /*[host]*/, int32_t nd, const int64_t* row_list_ptr /*[host]*/,
+                        const int32_t* row_list, const int32_t* row_doc, int64_t qrows, const int64_t* q_ptr /*[host]*/,
+                        int32_t nq, const int64_t* ex_ptr, const int32_t* ex_doc, int32_t nprobe, int32_t lo, int32_t hi,
+                        int32_t* out_doc, float* out_score, int32_t* out_found, void* workspace, size_t ws_bytes,
+                        hipStream_t stream);
+
 /* ---- multi-vector fixed-dimensional encodings (csrc/mv_fde.hip): MUVERA's data-oblivious map of a ragged set of bf16 rows
  * to one fp32 vector; <query FDE, document FDE> approximates the Chamfer / MaxSim sum, so that every dense index serves as
  * a candidate generator in front of snx_mv_rescore.  MUVERA's final count-sketch projection is not part of it, and no

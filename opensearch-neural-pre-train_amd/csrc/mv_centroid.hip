@@ -1538,3 +1538,620 @@ extern "C" int snx_mv_candidates_probed(const uint16_t* codes, int64_t drows, co
   }
   return SNX_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ token retrieval
+// include/snx.h "multi-vector token retrieval" (XTR's imputed similarity over the residual store, WARP's shape): a query
+// row scores only the document rows that sit in its nprobe best centroids, a document that shows it no such row gets the
+// row's next-best centroid product instead, and there is no candidate list and no second pass.  The cost follows the
+// probed ROWS.  The work is joined BY CENTROID: the packed rows of a centroid are expanded once for all the query rows of
+// the slice that probe it, and the score is an MFMA tile.
+// mvt_table_kernel  mvc_tile over (64 query rows, 64 centroids), written as fp32 [row][nc]: S32, for a bounded group of
+//                   query rows at a time.
+// mvt_probe_kernel  One wave per query row: 64 packed (bf16 key, ~centroid) values per lane from the fp32 row, nprobe + 1
+//                   wave maxima: top(i) and c*(i), each with its fp32 product.  The table is not needed after it.
+// mvt_mark_kernel   One workgroup per (query row, probe slot) walks the centroid's ROW list and sets the bit of each
+//                   row's document in the query's bitmap row (atomicOr: idempotent); mvp_unmark_kernel clears exclude[q].
+// mvt_count_kernel  One workgroup per query: the set bits in front of every bitmap WORD (a document's rank inside P(q) is
+//                   that plus one popcount), |P(q)|, and the largest of the slice for the host.
+// mvt_join_*        count / scan / fill over rows x nprobe entries: per centroid the query rows that probe it, with their
+//                   S32.  The scan also lays out the score grid: tiles(c) = ceil(entries / 64) * ceil(rows / 256).  The
+//                   integer atomics decide only the place of an entry inside its centroid; every value it leads to goes
+//                   through an integer max, so the place reaches no output bit.
+// mvt_score_kernel  One workgroup per (centroid, 64 entries, 256 list rows), found by a binary search of the tile prefix.
+//                   The A operand is GATHERED: the entries' query rows, through MvcBf16's stage, one K slice ahead.  The
+//                   B operand is expanded from the packed words of the list's rows (mvr_expand, the LDS table of weight
+//                   pairs), the next word in flight during the MFMA steps.  k ascending, S32 added once at the end: t(i, j)
+//                   is mvr_score_kernel's value.  Rows of one document are adjacent in a list, so a segmented max over the
+//                   32 columns of a wave half (five shuffle steps keyed by the column's document) leaves one value per
+//                   (query row, document run) in the run's last lane, and only that lane issues the atomicMax -- on the
+//                   order key of the fp32 value, into cell [query][rank of d in P(q)][row of the query].
+// mvt_finish_kernel One thread per (query, document): a probed document's cells become m'(i, d) (an untouched cell: miss(i)),
+//                   folded in snx_maxsim_pairs' order, divided once; key and doc go to the rank's slot.
+// mvt_select_kernel One workgroup per query: radix_select / ordered_take over the slots (they are in doc order), sorted,
+//                   ranks lo .. hi-1 written.
+// Nothing of size nq x nd x Lq exists: the cells cover P(q) of a slice of queries under a fixed budget, and the host
+// shrinks the slice when the largest P(q) asks for it.
+namespace {
+
+constexpr int MVT_THREADS = 256;
+constexpr int MVT_STRETCH = 256;               // list rows of a score workgroup: four 64-row tiles
+constexpr size_t MVT_TABLE_BUDGET = (size_t)128 << 20;   // bytes of fp32 table per probe launch
+constexpr size_t MVT_BITS_BUDGET = (size_t)128 << 20;    // bytes of bitmap and word prefix per slice of queries
+constexpr size_t MVT_CELL_BUDGET = (size_t)256 << 20;    // bytes of cells per slice, beyond one query's
+constexpr int64_t MVT_ENTRIES = (int64_t)1 << 24;        // (query row, probe) entries of a slice, beyond one query's
+
+// the last query of q0 .. q0 + nqs - 1 with q_ptr[q] <= row
+__device__ __forceinline__ int mvt_query_of(const int64_t* __restrict__ q_ptr, int q0, int nqs, long row) {
+  int lo = q0, hi = q0 + nqs;
+  while (hi - lo > 1) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (q_ptr[mid] <= row) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// table[(row - r0) nc + c] = S32[row, c] for the query rows r0 .. r1 - 1
+__global__ __launch_bounds__(MVC_THREADS) void mvt_table_kernel(const bf16_t* __restrict__ Q, int64_t r0, int64_t r1,
+                                                                const bf16_t* __restrict__ Cn, int32_t nc, int32_t D,
+                                                                float* __restrict__ table) {
+  __shared__ __attribute__((aligned(16))) MvcBf16::Stage stage[2];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int wm = wave >> 1, wn = wave & 1, c = lane & 31, h = lane >> 5;
+  const long a0 = r0 + (long)blockIdx.x * MVC_TILE;
+  const int na = (int)max(0l, min((long)MVC_TILE, r1 - a0));
+  const int c0 = blockIdx.y * MVC_TILE;
+  f32x16 acc;
+  mvc_tile<MvcBf16>(Q, a0, na, Cn, (long)c0, min(MVC_TILE, nc - c0), D, stage, acc);
+  const int cent = c0 + wn * 32 + c;
+  if (cent >= nc) return;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int ti = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+    if (ti < na) table[(a0 - r0 + ti) * nc + cent] = acc[r];
+  }
+}
+
+// pc[row np1 + r] = the r-th centroid of `row` by (bf16 key of S32 descending, centroid ascending), r < min(np1, nc), and
+// ps[..] its S32; slot np1 - 1 is c*(i), and holds -1 / 0 when every centroid is probed
+__global__ __launch_bounds__(MVT_THREADS) void mvt_probe_kernel(const float* __restrict__ table, int64_t r0, int64_t r1,
+                                                                int32_t nc, int32_t np1, int32_t* __restrict__ pc,
+                                                                float* __restrict__ ps) {
+  const int lane = threadIdx.x & 63;
+  const long row = r0 + (long)blockIdx.x * (MVT_THREADS / 64) + (threadIdx.x >> 6);
+  if (row >= r1) return;
+  const float* T = table + (row - r0) * nc;
+  uint32_t v[64];                                             // (key as unsigned) << 16 | ~centroid; 0: no centroid
+#pragma unroll
+  for (int k = 0; k < 64; ++k) {
+    const int c = 64 * k + lane;
+    v[k] = c < nc ? (((mvc_key(T[c]) ^ 0x8000u) << 16) | (0xFFFFu - (uint32_t)c)) : 0u;
+  }
+  const int take = min(np1, nc);
+  for (int r = 0; r < take; ++r) {
+    uint32_t best = 0u;
+#pragma unroll
+    for (int k = 0; k < 64; ++k) best = max(best, v[k]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, o, 64));
+    if (lane == 0) {
+      const int c = (int)(0xFFFFu - (best & 0xFFFFu));
+      pc[row * np1 + r] = c;
+      ps[row * np1 + r] = T[c];
+    }
+#pragma unroll
+    for (int k = 0; k < 64; ++k) v[k] = v[k] == best ? 0u : v[k];
+  }
+  if (take < np1 && lane == 0) {
+    pc[row * np1 + np1 - 1] = -1;
+    ps[row * np1 + np1 - 1] = 0.f;
+  }
+}
+
+// the document of list row j when the row is one of centroid c's: a row id outside the store, a code that is not c and a
+// document outside [0, nd) give -1
+__device__ __forceinline__ int32_t mvt_row_doc(int32_t j, int c, const uint16_t* __restrict__ codes, int64_t drows,
+                                               int32_t nc, const int32_t* __restrict__ row_doc, int32_t nd) {
+  if (j < 0 || (int64_t)j >= drows || min((int)codes[j], nc - 1) != c) return -1;
+  const int32_t d = row_doc[j];
+  return (uint32_t)d < (uint32_t)nd ? d : -1;
+}
+
+// the bit of the document of every row of centroid pc[row, slot]'s list, in the bitmap row of the query that owns `row`
+__global__ __launch_bounds__(MVT_THREADS) void mvt_mark_kernel(
+    const int32_t* __restrict__ pc, int32_t np1, const int64_t* __restrict__ q_ptr, int32_t q0, int32_t nqs,
+    const int64_t* __restrict__ rlp, const int32_t* __restrict__ row_list, const int32_t* __restrict__ row_doc,
+    const uint16_t* __restrict__ codes, int64_t drows, int32_t nc, int32_t nd, int64_t wp, uint32_t* __restrict__ bits) {
+  const long row = q_ptr[q0] + blockIdx.x;
+  const int q = mvt_query_of(q_ptr, q0, nqs, row);
+  const int c = pc[row * np1 + blockIdx.y];
+  uint32_t* b = bits + (long)(q - q0) * wp;
+  const long e = rlp[c + 1];
+  for (long i = rlp[c] + threadIdx.x; i < e; i += MVT_THREADS) {
+    const int32_t d = mvt_row_doc(row_list[i], c, codes, drows, nc, row_doc, nd);
+    if (d < 0) continue;
+    const uint32_t m = 1u << (d & 31);
+    // rows of a document are neighbours and rows of a query share lists: look before the atomic (a stale look only
+    // repeats an idempotent or)
+    if (!(__hip_atomic_load(b + (d >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & m)) atomicOr(b + (d >> 5), m);
+  }
+}
+
+// prew[q wp + w] = the set bits of query q's bitmap row in front of word w; tot[q] = all of them; *maxtot their maximum
+__global__ __launch_bounds__(MVC_WALK_THREADS) void mvt_count_kernel(const uint32_t* __restrict__ bits, int64_t wp,
+                                                                     int32_t* __restrict__ prew, int32_t* __restrict__ tot,
+                                                                     int32_t* __restrict__ maxtot) {
+  __shared__ int wsum[MVC_WALK_THREADS / 64];
+  const int t = threadIdx.x;
+  const uint32_t* b = bits + (long)blockIdx.x * wp;
+  int32_t* out = prew + (long)blockIdx.x * wp;
+  int base = 0;
+  for (long w0 = 0; w0 < wp; w0 += MVC_WALK_THREADS) {
+    const long w = w0 + t;
+    int all;
+    const int off = mvp_block_scan(w < wp ? __popc(b[w]) : 0, wsum, all);
+    if (w < wp) out[w] = base + off;
+    base += all;
+  }
+  if (t == 0) {
+    tot[blockIdx.x] = base;
+    atomicMax(maxtot, base);
+  }
+}
+
+// entry i = (query row r0 + i / np, probe slot i % np): ++cnt[its centroid]
+__global__ __launch_bounds__(MVT_THREADS) void mvt_join_count_kernel(const int32_t* __restrict__ pc, int32_t np, int32_t np1,
+                                                                     int64_t r0, int64_t n, int32_t* __restrict__ cnt) {
+  const int64_t i = (int64_t)blockIdx.x * MVT_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const int64_t row = r0 + i / np;
+  atomicAdd(cnt + pc[row * np1 + (int)(i - (i / np) * np)], 1);
+}
+
+// cnt -> wl_ptr [nc + 1] (entry starts) and cur (a copy the fill counts up); tile_ptr [nc + 1]: the score workgroups in
+// front of centroid c, ceil(cnt[c] / 64) * ceil(list rows of c / MVT_STRETCH) each
+__global__ __launch_bounds__(MVC_WALK_THREADS) void mvt_join_scan_kernel(const int32_t* __restrict__ cnt,
+                                                                         const int64_t* __restrict__ rlp, int32_t nc,
+                                                                         int32_t* __restrict__ wl_ptr, int32_t* __restrict__ cur,
+                                                                         int64_t* __restrict__ tile_ptr) {
+  __shared__ unsigned long long wsum[2][MVC_WALK_THREADS / 64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int per = (nc + MVC_WALK_THREADS - 1) / MVC_WALK_THREADS;              // at most four centroids a thread
+  const int c0 = min(nc, t * per), c1 = min(nc, c0 + per);
+  unsigned long long x[2] = {0ull, 0ull};                     // entries, tiles
+  for (int c = c0; c < c1; ++c) {
+    const long n = cnt[c], len = rlp[c + 1] - rlp[c];
+    x[0] += (unsigned long long)n;
+    x[1] += (unsigned long long)(((n + MVC_TILE - 1) / MVC_TILE) * ((len + MVT_STRETCH - 1) / MVT_STRETCH));
+  }
+  unsigned long long incl[2] = {x[0], x[1]};
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1)
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const unsigned long long y = __shfl_up(incl[u], o, 64);
+      if (lane >= o) incl[u] += y;
+    }
+  if (lane == 63) { wsum[0][wave] = incl[0]; wsum[1][wave] = incl[1]; }
+  __syncthreads();
+  unsigned long long run[2], all[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    unsigned long long off = 0ull;
+    all[u] = 0ull;
+#pragma unroll
+    for (int w = 0; w < MVC_WALK_THREADS / 64; ++w) {
+      const unsigned long long y = wsum[u][w];
+      off += w < wave ? y : 0ull;
+      all[u] += y;
+    }
+    run[u] = off + incl[u] - x[u];
+  }
+  for (int c = c0; c < c1; ++c) {
+    const long n = cnt[c], len = rlp[c + 1] - rlp[c];
+    wl_ptr[c] = (int32_t)run[0];
+    cur[c] = (int32_t)run[0];
+    tile_ptr[c] = (int64_t)run[1];
+    run[0] += (unsigned long long)n;
+    run[1] += (unsigned long long)(((n + MVC_TILE - 1) / MVC_TILE) * ((len + MVT_STRETCH - 1) / MVT_STRETCH));
+  }
+  if (t == 0) {
+    wl_ptr[nc] = (int32_t)all[0];
+    tile_ptr[nc] = (int64_t)all[1];
+  }
+}
+
+// entry i takes a place in its centroid's stretch of the work list: the query row and its S32 with that centroid
+__global__ __launch_bounds__(MVT_THREADS) void mvt_join_fill_kernel(const int32_t* __restrict__ pc,
+                                                                    const float* __restrict__ ps, int32_t np, int32_t np1,
+                                                                    int64_t r0, int64_t n, int32_t* __restrict__ cur,
+                                                                    int32_t* __restrict__ wl_row, float* __restrict__ wl_s) {
+  const int64_t i = (int64_t)blockIdx.x * MVT_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const int64_t row = r0 + i / np, at = row * np1 + (i - (i / np) * np);
+  const int pos = atomicAdd(cur + pc[at], 1);
+  wl_row[pos] = (int32_t)row;
+  wl_s[pos] = ps[at];
+}
+
+// cells[((q - q0) stride + rank of d in P(q)) pitch + i - q_ptr[q]] = max(.., key(t(i, j))) over the list rows j of the
+// workgroup's stretch that belong to d, for the 64 entries (query rows i) of its tile
+template <int NB>
+__global__ __launch_bounds__(MVC_THREADS) void mvt_score_kernel(
+    const uint16_t* __restrict__ codes, const unsigned char* __restrict__ bits, const uint16_t* __restrict__ weights,
+    int32_t nc, const bf16_t* __restrict__ Q, int32_t D, int64_t drows, const int64_t* __restrict__ rlp,
+    const int32_t* __restrict__ row_list, const int32_t* __restrict__ row_doc, int32_t nd,
+    const int64_t* __restrict__ q_ptr, int32_t q0, int32_t nqs, const int32_t* __restrict__ wl_ptr,
+    const int32_t* __restrict__ wl_row, const float* __restrict__ wl_s, const int64_t* __restrict__ tile_ptr,
+    const uint32_t* __restrict__ pbits, const int32_t* __restrict__ prew, int64_t wp, int64_t stride, int32_t pitch,
+    uint32_t* __restrict__ cells) {
+  typedef typename MvrWord<NB>::type W;
+  typedef MvcBf16 P;
+  __shared__ __attribute__((aligned(16))) P::Stage stage[2];
+  __shared__ uint32_t lut[1 << (2 * NB)];
+  __shared__ int32_t qrow[MVC_TILE], qq[MVC_TILE], qi[MVC_TILE];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int wm = wave >> 1, wn = wave & 1, c = lane & 31, h = lane >> 5;
+  const int64_t tile = blockIdx.x;
+  int cen = 0;                                                // the last centroid with tile_ptr <= tile: it owns the tile
+  for (int hi = nc; hi - cen > 1;) {
+    const int mid = cen + ((hi - cen) >> 1);
+    if (tile_ptr[mid] <= tile) cen = mid; else hi = mid;
+  }
+  const long la = rlp[cen], len = rlp[cen + 1] - la;
+  const long nst = (len + MVT_STRETCH - 1) / MVT_STRETCH, local = tile - tile_ptr[cen];
+  if (nst <= 0 || local < 0) return;
+  const long qt = local / nst, st = local - qt * nst;
+  const long e0 = wl_ptr[cen] + qt * MVC_TILE;
+  const int ne = (int)min((long)MVC_TILE, wl_ptr[cen + 1] - e0);
+  const long a = la + st * MVT_STRETCH;
+  const int nrow = (int)min((long)MVT_STRETCH, len - st * MVT_STRETCH);
+  if (ne <= 0 || nrow <= 0) return;
+  if (t < (1 << (2 * NB)))                                    // mvr_score_kernel's table of weight pairs
+    lut[t] = (uint32_t)weights[t & ((1 << NB) - 1)] | ((uint32_t)weights[t >> NB] << 16);
+  if (t < MVC_TILE) {
+    int32_t row = -1, ql = 0, in = 0;
+    if (t < ne) {
+      row = wl_row[e0 + t];
+      const int q = mvt_query_of(q_ptr, q0, nqs, row);
+      ql = q - q0;
+      in = (int)(row - q_ptr[q]);
+    }
+    qrow[t] = row; qq[t] = ql; qi[t] = in;
+  }
+  __syncthreads();
+  const int ar[2] = {qrow[t >> 3], qrow[(t >> 3) + 32]};       // the gathered A rows of this thread's two 16-byte pieces
+  auto fetch = [&](int k0, P::Regs& r) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      r.v[i] = ar[i] >= 0 ? *(const u32x4*)(Q + (long)ar[i] * D + k0 + (t & 7) * 8) : (u32x4){0u, 0u, 0u, 0u};
+  };
+  const int nk = D / P::KT, wpr = D / 16;                     // words of a row
+  const int col = wn * 32 + c;
+  float s32[16];                                              // S32 of this lane's sixteen entries with the centroid
+#pragma unroll
+  for (int r = 0; r < 16; ++r) s32[r] = wl_s[e0 + min(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, ne - 1)];
+  for (int n0 = 0; n0 < nrow; n0 += MVC_TILE) {
+    const int nv = min(MVC_TILE, nrow - n0);                  // list rows of this tile
+    int32_t br = row_list[a + n0 + min(t >> 2, nv - 1)];       // the row this thread expands; an id outside the store
+    br = (br >= 0 && (int64_t)br < drows) ? br : 0;            // reads row 0, and its column is dropped below
+    const W* wsrc = (const W*)bits + (long)br * wpr + (t & 3);
+    // the document of this lane's column, -1 for a column past the stretch or a row that is not the centroid's
+    const int32_t dcol = col < nv ? mvt_row_doc(row_list[a + n0 + col], cen, codes, drows, nc, row_doc, nd) : -1;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    P::Regs ra;
+    fetch(0, ra);
+    W w = wsrc[0];
+    P::put(t, ra, stage[0].a);
+    mvr_expand<NB>(w, lut, t, stage[0].b);
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {                         // k ascending, mvr_score_kernel's steps
+      const int cur = kt & 1;
+      if (kt + 1 < nk) {
+        fetch((kt + 1) * P::KT, ra);
+        w = wsrc[4 * (kt + 1)];
+      }
+      P::mma(stage[cur], wm, wn, c, h, acc);
+      if (kt + 1 < nk) {
+        P::put(t, ra, stage[cur ^ 1].a);
+        mvr_expand<NB>(w, lut, t, stage[cur ^ 1].b);
+      }
+      __syncthreads();
+    }
+    // the run of columns with this lane's document: same[k] = the column 2^k to the left belongs to it too
+    bool same[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      const int od = __shfl_up(dcol, 1 << k, 32);
+      same[k] = c >= (1 << k) && od == dcol;
+    }
+    const int nx = __shfl_down(dcol, 1, 32);
+    const bool last = dcol >= 0 && (c == 31 || nx != dcol);   // the run's last lane holds the run's maximum
+    float v[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      v[r] = s32[r] + acc[r];                                 // S32 once, at the end
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        const float ov = __shfl_up(v[r], 1 << k, 32);
+        v[r] = same[k] ? fmaxf(v[r], ov) : v[r];
+      }
+    }
+    // The shuffles end here, before the LDS reads of the cells' indices: hipcc would interleave the two under counted
+    // waits that are right only because a shuffle holds a slot of the same counter; the build's scan of LDS reads
+    // (snx/asmcheck.py) counts reads alone.
+    __builtin_amdgcn_s_waitcnt(0xC07F);                       // lgkmcnt(0)
+    __builtin_amdgcn_sched_barrier(0);
+    int seen = -1, rank = -1;                                 // the query whose rank of dcol is known
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int ti = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+      if (last && ti < ne) {
+        const int ql = qq[ti];
+        if (ql != seen) {
+          const long at = (long)ql * wp + (dcol >> 5);
+          const uint32_t word = pbits[at], bit = 1u << (dcol & 31);
+          rank = (word & bit) ? prew[at] + __popc(word & (bit - 1u)) : -1;    // an excluded document has no rank
+          seen = ql;
+        }
+        if (rank >= 0) atomicMax(cells + ((long)ql * stride + rank) * pitch + qi[ti], dense_key(v[r]));
+      }
+    }
+  }
+}
+
+// a probed document's cells -> x(q, d): fkey / fdoc[(q - q0) stride + rank] = its order key and the document
+__global__ __launch_bounds__(MVT_THREADS) void mvt_finish_kernel(
+    const uint32_t* __restrict__ cells, const uint32_t* __restrict__ pbits, const int32_t* __restrict__ prew, int64_t wp,
+    int32_t nd, int64_t stride, int32_t pitch, const int64_t* __restrict__ q_ptr, int32_t q0, const float* __restrict__ ps,
+    int32_t np1, int32_t has_miss, uint32_t* __restrict__ fkey, int32_t* __restrict__ fdoc) {
+  const long d = (long)blockIdx.x * MVT_THREADS + threadIdx.x;
+  const int ql = blockIdx.y;
+  if (d >= nd) return;
+  const long at = (long)ql * wp + (d >> 5);
+  const uint32_t word = pbits[at], bit = 1u << (d & 31);
+  if (!(word & bit)) return;
+  const long slot = (long)ql * stride + prew[at] + __popc(word & (bit - 1u));
+  const uint32_t* v = cells + slot * pitch;
+  const long qa = q_ptr[q0 + ql];
+  const int Lq = (int)(q_ptr[q0 + ql + 1] - qa);
+  const float* miss = ps + qa * np1 + (np1 - 1);              // S32[i, c*(i)], np1 apart
+  float total = 0.f;
+  for (int b0 = 0; b0 < Lq; b0 += MVC_TILE) {                  // runs of 64 rows from the query's first: ascending rows
+    const int b1 = min(Lq, b0 + MVC_TILE);
+    float s = 0.f;
+    for (int i = b0; i < b1; ++i) {
+      const uint32_t key = v[i];
+      s += key ? dense_unkey(key) : (has_miss ? miss[(long)i * np1] : 0.f);
+    }
+    total = b0 == 0 ? s : total + s;                          // ascending runs
+  }
+  fkey[slot] = dense_key(total / (float)Lq);
+  fdoc[slot] = (int32_t)d;
+}
+
+// the slots of a query as merge_lists reads a list: in doc order, so ordered_take's tie rule is the ABI's
+struct MvtSlots {
+  const uint32_t* key;
+  const int32_t* doc;
+  __device__ __forceinline__ unsigned long long at(long f) const { return rank_key(key[f], (uint32_t)doc[f]); }
+  __device__ __forceinline__ uint32_t operator()(long f) const { return key[f]; }
+};
+
+__global__ __launch_bounds__(SR_THREADS) void mvt_select_kernel(const uint32_t* __restrict__ fkey,
+                                                                const int32_t* __restrict__ fdoc,
+                                                                const int32_t* __restrict__ tot, int64_t stride, int32_t lo,
+                                                                int32_t hi, int32_t* __restrict__ out_doc,
+                                                                float* __restrict__ out_score, int32_t* __restrict__ out_found) {
+  __shared__ SelectSmem S;
+  __shared__ unsigned long long sbuf[SR_KMAX];               // rank keys: descending = the ABI's order
+  const int tid = threadIdx.x, q = blockIdx.x;
+  const MvtSlots slots = {fkey + (long)q * stride, fdoc + (long)q * stride};
+  const long n = tot[q];
+  uint32_t thr;
+  int need_eq, nsel;
+  radix_select(slots, n, hi, S, thr, need_eq, nsel);          // merge_lists' body over one list of |P(q)| entries
+  const int P = pow2_at_least(nsel);
+  for (int i = tid; i < P; i += SR_THREADS) sbuf[i] = 0ull;
+  __syncthreads();
+  ordered_take(slots, n, thr, need_eq, S, [&](long f, int pos) { sbuf[pos] = slots.at(f); });
+  bitonic_desc<SR_THREADS, int>(sbuf, P);
+  write_ranks<dense_unkey>(sbuf, nsel, q, lo, hi, out_doc, out_score, out_found);
+}
+
+inline bool mvt_bad(int32_t nq, int32_t nd, int32_t nc, int32_t nprobe, int32_t lo, int32_t hi) {
+  return nq < 0 || nd < 0 || nc < 1 || nc > MVC_NC_MAX || mvp_bad_probe(nprobe) || lo < 0 || hi <= lo || hi > SR_KMAX;
+}
+
+// the token search's workspace.  A slice of at most qs queries holds a bitmap row and a word-prefix row each; its cells,
+// keys and docs share `slots` (query, probed document) places of `pitch` query rows, its work list `entries` places.
+struct MvtPlan {
+  size_t qptr, lptr, flag, table, pc, ps, bits, prew, tot, cnt, wlptr, cur, tileptr, wlrow, wls, cells, fkey, fdoc, total;
+  int np, np1, pitch, qs;
+  int64_t wp, trows, entries, slots;
+  bool ok;
+  MvtPlan(const int64_t* q_ptr, int32_t nq, int32_t nd, int32_t nc, int32_t nprobe) {
+    const int64_t qused = q_ptr[nq];
+    int64_t longest = 1;
+    for (int32_t q = 0; q < nq; ++q) longest = q_ptr[q + 1] - q_ptr[q] > longest ? q_ptr[q + 1] - q_ptr[q] : longest;
+    np = nprobe < nc ? nprobe : nc;
+    np1 = np + 1;
+    ok = qused <= 0x7FFFFFFFL - MVC_TILE && longest * np <= 0x3FFFFFFFL && longest <= 0x00FFFFFFL;
+    pitch = ok ? (int)((longest + 3) & ~3l) : 4;
+    wp = (((int64_t)nd + 31) / 32 + 3) & ~3l;
+    wp = wp < 4 ? 4 : wp;
+    const int64_t tr = (int64_t)(MVT_TABLE_BUDGET / ((size_t)nc * 4)) & ~(int64_t)(MVC_TILE - 1);   // >= 8,192 rows
+    trows = qused < tr ? ((qused + MVC_TILE - 1) & ~(int64_t)(MVC_TILE - 1)) : tr;
+    trows = trows < MVC_TILE ? MVC_TILE : trows;
+    size_t s = MVT_BITS_BUDGET / ((size_t)wp * 8);
+    qs = (int)(s < 1 ? 1 : (s > (size_t)nq ? (size_t)nq : s));
+    qs = qs > 65535 ? 65535 : qs;                             // a grid's y
+    const int64_t e_all = qused * np, e_one = longest * np;
+    entries = e_all < MVT_ENTRIES ? e_all : (e_one > MVT_ENTRIES ? e_one : MVT_ENTRIES);
+    entries = entries < 1 ? 1 : entries;
+    const int64_t budget = (int64_t)(MVT_CELL_BUDGET / ((size_t)pitch * 4));
+    const int64_t s_all = (int64_t)nq * nd;                   // every document probed by every query
+    slots = s_all < budget ? s_all : (nd > budget ? nd : budget);
+    slots = slots < 1 ? 1 : slots;
+    Arena a;
+    qptr = a.take(((size_t)nq + 1) * 8);
+    lptr = a.take(((size_t)nc + 1) * 8);
+    flag = a.take(16);
+    table = a.take((size_t)trows * (size_t)nc * 4);
+    pc = a.take((size_t)qused * (size_t)np1 * 4);
+    ps = a.take((size_t)qused * (size_t)np1 * 4);
+    bits = a.take((size_t)qs * (size_t)wp * 4);
+    prew = a.take((size_t)qs * (size_t)wp * 4);
+    tot = a.take((size_t)qs * 4);
+    cnt = a.take((size_t)nc * 4);
+    wlptr = a.take(((size_t)nc + 1) * 4);
+    cur = a.take((size_t)nc * 4);
+    tileptr = a.take(((size_t)nc + 1) * 8);
+    wlrow = a.take((size_t)entries * 4);
+    wls = a.take((size_t)entries * 4);
+    cells = a.take((size_t)slots * (size_t)pitch * 4);
+    fkey = a.take((size_t)slots * 4);
+    fdoc = a.take((size_t)slots * 4);
+    total = a.off;
+  }
+};
+
+template <int NB>
+int mvt_launch_score(unsigned grid, hipStream_t st, const uint16_t* codes, const void* bits, const uint16_t* weights,
+                     int32_t nc, const bf16_t* q, int32_t D, int64_t drows, const int64_t* lptr, const int32_t* row_list,
+                     const int32_t* row_doc, int32_t nd, const int64_t* qptr, int32_t q0, int32_t nqs, const int32_t* wlptr,
+                     const int32_t* wlrow, const float* wls, const int64_t* tileptr, const uint32_t* pbits,
+                     const int32_t* prew, int64_t wp, int64_t stride, int32_t pitch, uint32_t* cells) {
+  hipLaunchKernelGGL(mvt_score_kernel<NB>, dim3(grid), dim3(MVC_THREADS), 0, st, codes, (const unsigned char*)bits, weights, nc,
+                     q, D, drows, lptr, row_list, row_doc, nd, qptr, q0, nqs, wlptr, wlrow, wls, tileptr, pbits, prew, wp,
+                     stride, pitch, cells);
+  SNX_CHECK_LAUNCH();
+  return SNX_OK;
+}
+
+}  // namespace
+
+extern "C" size_t snx_mv_token_search_workspace_bytes(const int64_t* q_ptr, int32_t nq, int32_t nd, int64_t drows, int32_t nc,
+                                                      int32_t nprobe, int32_t hi) {
+  if (nq <= 0 || drows < 0 || mvt_bad(nq, nd, nc, nprobe, 0, hi) || !mvc_ptr_ok(q_ptr, nq, 0x7FFFFFFFFFFFFFFFL, true)) return 0;
+  const MvtPlan plan(q_ptr, nq, nd, nc, nprobe);
+  return plan.ok ? plan.total : 0;
+}
+
+extern "C" int snx_mv_token_search(const uint16_t* codes, const void* bits, const void* centroids, const uint16_t* weights,
+                                   int32_t nc, int32_t nbits, const void* q, int32_t mv_f32, int32_t D, int64_t drows,
+                                   const int64_t* doc_ptr, int32_t nd, const int64_t* row_list_ptr, const int32_t* row_list,
+                                   const int32_t* row_doc, int64_t qrows, const int64_t* q_ptr, int32_t nq,
+                                   const int64_t* ex_ptr, const int32_t* ex_doc, int32_t nprobe, int32_t lo, int32_t hi,
+                                   int32_t* out_doc, float* out_score, int32_t* out_found, void* workspace, size_t ws_bytes,
+                                   hipStream_t st) {
+  if (D <= 0 || (D % 64) != 0 || D > MVC_DMAX || qrows < 0 || drows < 0 || drows > 0x7FFFFFFFL) return SNX_E_SHAPE;
+  if (mv_f32 || mvr_bad_nbits(nbits) || mvt_bad(nq, nd, nc, nprobe, lo, hi)) return SNX_E_ARG;
+  if (nq == 0) return SNX_OK;
+  if (!q || !centroids || !weights || !out_doc || !out_score || !out_found || !workspace || (ex_ptr && !ex_doc) ||
+      ((uintptr_t)q & 15) != 0 || ((uintptr_t)centroids & 15) != 0 || ((uintptr_t)bits & 15) != 0 ||
+      ((uintptr_t)workspace & 15) != 0)
+    return SNX_E_ARG;
+  // the three pointer arrays are pageable host memory: everything a kernel will trust is checked here, before any launch
+  if (!mvc_ptr_ok(doc_ptr, nd, drows, false) || !mvc_ptr_ok(q_ptr, nq, qrows, true)) return SNX_E_ARG;
+  const int64_t dused = doc_ptr[nd];
+  if (!mvc_ptr_ok(row_list_ptr, nc, dused, false) || row_list_ptr[nc] != dused) return SNX_E_ARG;
+  if (dused > 0 && (!codes || !bits || !row_list || !row_doc)) return SNX_E_ARG;
+  const MvtPlan plan(q_ptr, nq, nd, nc, nprobe);
+  if (!plan.ok) return SNX_E_SHAPE;
+  if (ws_bytes < plan.total) return SNX_E_ARG;
+  char* ws = (char*)workspace;
+  RC(mvc_upload(ws, plan.qptr, q_ptr, ((size_t)nq + 1) * 8, st));
+  RC(mvc_upload(ws, plan.lptr, row_list_ptr, ((size_t)nc + 1) * 8, st));
+  const int64_t* qptr = (const int64_t*)(ws + plan.qptr);
+  const int64_t* lptr = (const int64_t*)(ws + plan.lptr);
+  int32_t* flag = (int32_t*)(ws + plan.flag);                 // [0]: the largest |P(q)| of a slice; [2..3]: its score tiles
+  float *table = (float*)(ws + plan.table), *ps = (float*)(ws + plan.ps), *wls = (float*)(ws + plan.wls);
+  int32_t *pc = (int32_t*)(ws + plan.pc), *prew = (int32_t*)(ws + plan.prew), *tot = (int32_t*)(ws + plan.tot);
+  int32_t *cnt = (int32_t*)(ws + plan.cnt), *wlptr = (int32_t*)(ws + plan.wlptr), *cur = (int32_t*)(ws + plan.cur);
+  int32_t *wlrow = (int32_t*)(ws + plan.wlrow), *fdoc = (int32_t*)(ws + plan.fdoc);
+  int64_t* tileptr = (int64_t*)(ws + plan.tileptr);
+  uint32_t *pbits = (uint32_t*)(ws + plan.bits), *cells = (uint32_t*)(ws + plan.cells), *fkey = (uint32_t*)(ws + plan.fkey);
+  const bf16_t* Q = (const bf16_t*)q;
+  const int64_t qused = q_ptr[nq];
+  const int np = plan.np, np1 = plan.np1;
+  for (int64_t r0 = 0; r0 < qused; r0 += plan.trows) {        // top(i), c*(i) and their S32 for every query row of the call
+    const int64_t r1 = r0 + plan.trows < qused ? r0 + plan.trows : qused;
+    hipLaunchKernelGGL(mvt_table_kernel, dim3((unsigned)((r1 - r0 + MVC_TILE - 1) / MVC_TILE), (unsigned)((nc + MVC_TILE - 1) / MVC_TILE)),
+                       dim3(MVC_THREADS), 0, st, Q, r0, r1, (const bf16_t*)centroids, nc, D, table);
+    SNX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mvt_probe_kernel, dim3((unsigned)((r1 - r0 + MVT_THREADS / 64 - 1) / (MVT_THREADS / 64))),
+                       dim3(MVT_THREADS), 0, st, (const float*)table, r0, r1, nc, np1, pc, ps);
+    SNX_CHECK_LAUNCH();
+  }
+  int32_t cap = plan.qs;
+  for (int32_t q0 = 0; q0 < nq;) {                            // one slice of queries after the other
+    int32_t nqs = nq - q0 < cap ? nq - q0 : cap;
+    while (nqs > 1 && (q_ptr[q0 + nqs] - q_ptr[q0]) * np > plan.entries) --nqs;
+    const int64_t r0 = q_ptr[q0], rows = q_ptr[q0 + nqs] - r0, entries = rows * np;
+    hipError_t e = hipMemsetAsync(pbits, 0, (size_t)nqs * (size_t)plan.wp * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(flag, 0, 16, st);
+    if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, (size_t)nc * 4, st);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(mvt_mark_kernel, dim3((unsigned)rows, (unsigned)np), dim3(MVT_THREADS), 0, st, (const int32_t*)pc, np1,
+                       qptr, q0, nqs, lptr, row_list, row_doc, codes, drows, nc, nd, plan.wp, pbits);
+    SNX_CHECK_LAUNCH();
+    if (ex_ptr) {
+      hipLaunchKernelGGL(mvp_unmark_kernel, dim3((unsigned)nqs), dim3(MVP_THREADS), 0, st, ex_ptr + q0, ex_doc, nd, plan.wp,
+                         pbits);
+      SNX_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(mvt_count_kernel, dim3((unsigned)nqs), dim3(MVC_WALK_THREADS), 0, st, (const uint32_t*)pbits, plan.wp,
+                       prew, tot, flag);
+    SNX_CHECK_LAUNCH();
+    const dim3 egrid((unsigned)((entries + MVT_THREADS - 1) / MVT_THREADS));
+    hipLaunchKernelGGL(mvt_join_count_kernel, egrid, dim3(MVT_THREADS), 0, st, (const int32_t*)pc, np, np1, r0, entries, cnt);
+    SNX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mvt_join_scan_kernel, dim3(1), dim3(MVC_WALK_THREADS), 0, st, (const int32_t*)cnt, lptr, nc, wlptr, cur,
+                       tileptr);
+    SNX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mvt_join_fill_kernel, egrid, dim3(MVT_THREADS), 0, st, (const int32_t*)pc, (const float*)ps, np, np1, r0,
+                       entries, cur, wlrow, wls);
+    SNX_CHECK_LAUNCH();
+    int32_t most = 0;                                         // the cells follow the probed documents, not nd
+    int64_t tiles = 0;
+    e = hipMemcpyAsync(&most, flag, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&tiles, tileptr + nc, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return (int)e;
+    if (nqs > 1 && (int64_t)nqs * most > plan.slots) {        // the slice's cells do not fit: a smaller slice, from here on
+      cap = (int32_t)(plan.slots / most);
+      cap = cap < 1 ? 1 : cap;
+      continue;
+    }
+    if (tiles > 0x7FFFFFFFL) return SNX_E_SHAPE;
+    const int64_t stride = most > 0 ? most : 1;
+    if (most > 0) {
+      e = hipMemsetAsync(cells, 0, (size_t)nqs * (size_t)stride * (size_t)plan.pitch * 4, st);
+      if (e != hipSuccess) return (int)e;
+      if (tiles > 0) {
+        if (nbits == 1)
+          RC(mvt_launch_score<1>((unsigned)tiles, st, codes, bits, weights, nc, Q, D, drows, lptr, row_list, row_doc, nd, qptr,
+                                 q0, nqs, wlptr, wlrow, wls, tileptr, pbits, prew, plan.wp, stride, plan.pitch, cells));
+        else if (nbits == 2)
+          RC(mvt_launch_score<2>((unsigned)tiles, st, codes, bits, weights, nc, Q, D, drows, lptr, row_list, row_doc, nd, qptr,
+                                 q0, nqs, wlptr, wlrow, wls, tileptr, pbits, prew, plan.wp, stride, plan.pitch, cells));
+        else
+          RC(mvt_launch_score<4>((unsigned)tiles, st, codes, bits, weights, nc, Q, D, drows, lptr, row_list, row_doc, nd, qptr,
+                                 q0, nqs, wlptr, wlrow, wls, tileptr, pbits, prew, plan.wp, stride, plan.pitch, cells));
+      }
+      hipLaunchKernelGGL(mvt_finish_kernel, dim3((unsigned)((nd + MVT_THREADS - 1) / MVT_THREADS), (unsigned)nqs),
+                         dim3(MVT_THREADS), 0, st, (const uint32_t*)cells, (const uint32_t*)pbits, (const int32_t*)prew,
+                         plan.wp, nd, stride, plan.pitch, qptr, q0, (const float*)ps, np1, (int32_t)(np < nc), fkey, fdoc);
+      SNX_CHECK_LAUNCH();
+    }
+    const size_t w = (size_t)(hi - lo);
+    hipLaunchKernelGGL(mvt_select_kernel, dim3((unsigned)nqs), dim3(SR_THREADS), 0, st, (const uint32_t*)fkey,
+                       (const int32_t*)fdoc, (const int32_t*)tot, stride, lo, hi, out_doc + (size_t)q0 * w,
+                       out_score + (size_t)q0 * w, out_found + q0);
+    SNX_CHECK_LAUNCH();
+    q0 += nqs;
+  }
+  return SNX_OK;
+}

@@ -91,7 +91,12 @@ GUARDED: Dict[str, Tuple[str, ...]] = {
                         # the scans' running sums stay in registers; the mark and unmark kernels hold no LDS and are not
                         # listed
                         "mvp_list_doc_kernel", "mvp_list_scan_kernel", "mvp_list_sort_kernel", "mvp_probe_kernel",
-                        "mvp_count_kernel", "mvp_walk_kernel", "mvp_select_kernel"),
+                        "mvp_count_kernel", "mvp_walk_kernel", "mvp_select_kernel",
+                        # token retrieval: the score tile's accumulators, gathered row ids, prefetched slice and packed
+                        # word, and the scans' sums stay in registers; the probe (64 packed keys of a lane, wave maxima by
+                        # shuffles), mark, join count / fill and finish kernels hold no LDS and are not listed
+                        "mvt_table_kernel", "mvt_count_kernel", "mvt_join_scan_kernel", "mvt_score_kernel",
+                        "mvt_select_kernel"),
     # and for the lexical weights: the 64-bit keys live in LDS, a thread's key, its ballot and the unused ids (kernel
     # arguments) in registers; the head's row kernel and the pair scorer hold no LDS and are not listed
     "teacher_lex.hip": ("tl_unique_kernel",),

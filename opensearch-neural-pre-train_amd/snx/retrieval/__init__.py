@@ -31,7 +31,10 @@ dense retrieval").  ``MultiVectorIndex`` is the exact MaxSim search over the rag
 ``snx.teacher``'s ``encode_multivector``, with ``maxsim_pairs``' scores bit for bit and ``DenseIndex``'s order
 (csrc/mv_search.hip, include/snx.h "multi-vector search").  ``FdeEncoder`` maps such a ragged sequence to one fp32 vector,
 MUVERA's fixed-dimensional encoding, so that a dense index proposes the candidates of ``MultiVectorIndex``'s two-phase
-searches (csrc/mv_fde.hip, include/snx.h "multi-vector fixed-dimensional encodings")."""
+searches (csrc/mv_fde.hip, include/snx.h "multi-vector fixed-dimensional encodings").  On a compressed index
+``MultiVectorIndex.search_tokens`` / ``search_band_tokens`` are token retrieval with imputed missing similarity: a query
+row scores only the packed rows in its ``nprobe`` best centroids, with no candidate list and no second pass (the mvt_
+kernels of csrc/mv_centroid.hip, include/snx.h "multi-vector token retrieval")."""
 from ._common import K_MAX, exclusion_csr
 from .dense import DENSE_CHUNK_MIN, DENSE_DIM_MAX, DenseIndex, bf16_rows
 from .graph import GRAPH_DEGREE_MAX, GRAPH_EF_MAX, GRAPH_KNN_MAX, GRAPH_WIDTH_MAX, GraphIndex, entry_sample

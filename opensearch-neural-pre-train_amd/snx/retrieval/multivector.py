@@ -183,6 +183,18 @@ class MultiVectorIndex:
     rows up to fp32 rounding, no longer ``maxsim_pairs``' bits.  ``candidates`` is unchanged.  Without ``keep_rows`` the
     bf16 rows are released, and ``search``, ``search_band``, ``train_centroids`` and ``set_centroids`` raise.
 
+    A compressed index also answers by token retrieval (include/snx.h "multi-vector token retrieval"; XTR's imputed
+    similarity), with no candidate list and no second pass:
+
+        scores, docs = index.search_tokens(qmv, q_ptr, k, nprobe, query_slice=0)
+        scores, docs, found = index.search_band_tokens(qmv, q_ptr, lo, hi, nprobe, exclude=None, query_slice=0)
+
+    A query row scores only the packed rows whose code is one of its ``nprobe`` (1 .. 64) best centroids; per query row a
+    document counts with the best of those scores, or, when it shows the row none, with the row's product with its next
+    centroid; the mean over the query's rows ranks the documents that were probed at all.  ``nprobe`` >= nc gives
+    ``search_two_phase`` over every document, bit for bit.  ``index.row_list_ptr`` (int64 [nc + 1]) / ``index.row_list``
+    (int32 [num_rows]) are the row ids grouped by code, built by the first call after ``compress``.
+
     s(q, d) is bit for bit ``maxsim_pairs``' score of the two sequences; the order is ``DenseIndex``'s (score descending,
     ties lowest doc id first, every document with rows a candidate whatever the sign of its score; unused slots 0 / -1).
     Results do not depend on ``chunk_docs``, ``query_slice`` or the order of the queries.  A sequence without rows (a
@@ -221,6 +233,13 @@ class MultiVectorIndex:
         self.cutoffs: Optional[torch.Tensor] = None           # fp32 [2^nbits - 1], strictly ascending
         self.weights: Optional[torch.Tensor] = None           # fp32 [2^nbits]: the bf16 weights, widened
         self.weights_bf16: Optional[torch.Tensor] = None
+        self._unrows()
+
+    def _unrows(self) -> None:
+        self.row_list_ptr: Optional[torch.Tensor] = None      # int64 [nc + 1]: the rows grouped by code (search_tokens),
+        self.row_list: Optional[torch.Tensor] = None          # int32 [num_rows]: ascending row ids per centroid
+        self._row_doc: Optional[torch.Tensor] = None          # int32 [num_rows]: the document of every row
+        self._hrows = None
 
     @property
     def num_docs(self) -> int:
@@ -628,6 +647,7 @@ class MultiVectorIndex:
                 call("snx_mv_residual_encode", _p(rows), int(rows.shape[0]), _p(self.codes[s:]), _p(self.centroids),
                      int(self.centroids.shape[0]), self.dim, nbits, _p(self.cutoffs), _p(packed[s:]), _stream())
         self.residuals, self.nbits = packed, nbits
+        self._unrows()                                        # the row lists are built once per compression
         if not keep_rows:
             self.rows, self._parts = None, []
         return self
@@ -655,6 +675,65 @@ class MultiVectorIndex:
                      _p(self.weights_bf16), nc, self.nbits, _p(rows), 0, self.dim, self.num_rows, self._hptr, nd,
                      int(rows.shape[0]), hq, m, _p(cand[s:]), ncand, lo, hi, _p(docs[s:]), _p(scores[s:]), _p(found[s:]),
                      _p(at(raw, s)), _p(ws), ws_bytes, _stream())
+
+    # -------------------------------------------------------------------------------------------- token retrieval
+    def _row_lists(self) -> None:
+        """``row_list_ptr`` / ``row_list`` (every row id grouped by its code, ascending within a centroid) and the
+        row-to-document map, once per compression: a stable device sort, plumbing in front of the ``mvt_`` kernels."""
+        if self.row_list_ptr is not None:
+            return
+        nc, dev = int(self.centroids.shape[0]), self.device
+        codes = self._codes_of(torch.arange(self.num_rows, device=dev))
+        ptr = torch.zeros(nc + 1, dtype=torch.int64, device=dev)
+        ptr[1:] = torch.bincount(codes, minlength=nc).cumsum(0)
+        lens = torch.tensor(self._ptr, dtype=torch.int64).diff().to(dev)
+        self.row_list = torch.sort(codes, stable=True).indices.to(torch.int32).contiguous()
+        self._row_doc = torch.repeat_interleave(torch.arange(self.num_docs, dtype=torch.int32, device=dev), lens).contiguous()
+        self._hrows = (C.c_int64 * (nc + 1))(*ptr.tolist())
+        self.row_list_ptr = ptr
+
+    def _tokens(self, who: str, qmv, q_ptr, lo: int, hi: int, nprobe, exclude, query_slice):
+        if isinstance(nprobe, bool) or not isinstance(nprobe, (int, np.integer)) or not 1 <= int(nprobe) <= MV_NPROBE_MAX:
+            raise ValueError(f"MultiVectorIndex.{who}: nprobe must be an int in [1, {MV_NPROBE_MAX}]")
+        if self.dtype == torch.float32:
+            raise ValueError(f"MultiVectorIndex.{who}: token retrieval reads the compressed store; an fp32 index has none")
+        if self.built and self.residuals is None:
+            raise RuntimeError(f"MultiVectorIndex.{who}: call compress() first; token retrieval scores the packed rows")
+        qmv, ptr, _ = self._queries(who, qmv, q_ptr, 0, query_slice)
+        nq, nd, dev, nc = len(ptr) - 1, self.num_docs, self.device, int(self.centroids.shape[0])
+        ex_ptr, ex_doc = exclusion_or_null(exclude, nq, nd, dev)
+        self._row_lists()
+        scores, docs, _, _ = search_outputs(nq, hi - lo, dev, False)
+        found = torch.empty(nq, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            for s, m, rows, hq in self._launches(qmv, ptr, query_slice):
+                ws, ws_bytes = workspace("snx_mv_token_search_workspace_bytes", dev, hq, m, nd, self.num_rows, nc,
+                                         int(nprobe), hi)
+                call("snx_mv_token_search", _p(self.codes), _p(self.residuals), _p(self.centroids), _p(self.weights_bf16),
+                     nc, self.nbits, _p(rows), 0, self.dim, self.num_rows, self._hptr, nd, self._hrows, _p(self.row_list),
+                     _p(self._row_doc), int(rows.shape[0]), hq, m, _p(at(ex_ptr, s)), _p(ex_doc), int(nprobe), lo, hi,
+                     _p(docs[s:]), _p(scores[s:]), _p(found[s:]), _p(ws), ws_bytes, _stream())
+        return scores, docs, found
+
+    def search_tokens(self, qmv: torch.Tensor, q_ptr, k: int, nprobe: int, query_slice: int = 0
+                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Token retrieval over the compressed store (include/snx.h "multi-vector token retrieval") -> (scores [nq, k]
+        fp32, docs [nq, k] int32): the top k of the documents that own a row in one of the ``nprobe`` best centroids of
+        some query row, by x(q, d) -- per query row the best packed-form score among those rows, or the row's next-best
+        centroid product when the document shows it none.  No candidate list, no second pass."""
+        k = int(k)
+        if not 1 <= k <= K_MAX:
+            raise ValueError(f"MultiVectorIndex.search_tokens: k must be in [1, {K_MAX}]")
+        return self._tokens("search_tokens", qmv, q_ptr, 0, k, nprobe, None, query_slice)[:2]
+
+    def search_band_tokens(self, qmv: torch.Tensor, q_ptr, lo: int, hi: int, nprobe: int, exclude=None,
+                           query_slice: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Ranks ``lo .. hi-1`` of ``search_tokens``' order among the probed documents outside ``exclude[q]`` -> (scores,
+        docs, found [nq] int32)."""
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo < hi <= K_MAX:
+            raise ValueError(f"MultiVectorIndex.search_band_tokens: need 0 <= lo < hi <= {K_MAX}")
+        return self._tokens("search_band_tokens", qmv, q_ptr, lo, hi, nprobe, exclude, query_slice)
 
     def _pair_scores_residual(self, qmv, ptr, pq: List[int], pd: List[int]) -> torch.Tensor:
         """The pairs grouped per query into candidate rows of at most ``K_MAX`` slots; the scores are ``raw_score``'s, so

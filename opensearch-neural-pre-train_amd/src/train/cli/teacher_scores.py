@@ -121,9 +121,10 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     sp.add_argument("--batch-tokens", type=int, default=16384, help="token rows per forward")
     sp.add_argument("--chunk-texts", type=int, default=256, help="texts per encoder call")
     sp.add_argument("--chunk-docs", type=int, default=0)
-    sp.add_argument("--index", choices=("exact", "centroid", "fde"), default="exact",
+    sp.add_argument("--index", choices=("exact", "centroid", "fde", "token"), default="exact",
                     help="centroid: candidates from the centroid-interaction pass (csrc/mv_centroid.hip), scored exactly; "
-                         "fde: from a dense search over fixed-dimensional encodings (csrc/mv_fde.hip), no centroids")
+                         "fde: from a dense search over fixed-dimensional encodings (csrc/mv_fde.hip), no centroids; "
+                         "token: token retrieval over the compressed store (needs --nbits and --nprobe, takes no --ncand)")
     sp.add_argument("--k-sim", type=int, default=4, help="--index fde: sign bits per repetition, 0 .. 6")
     sp.add_argument("--reps", type=int, default=16, help="--index fde: repetitions, 1 .. 32")
     sp.add_argument("--d-proj", type=int, choices=(16, 32, 64), default=16, help="--index fde: projected width")
@@ -141,10 +142,12 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
     sp.add_argument("--device", type=str, default="cuda:0")
     args = ap.parse_args(argv)
     if args.command == "mine-mv":
-        if args.nbits and (args.index != "centroid" or args.precision != "bf16"):
-            ap.error("--nbits needs --index centroid and --precision bf16")
-        if not 0 <= args.nprobe <= 64 or (args.nprobe and args.index != "centroid"):
-            ap.error("need --nprobe 0, or 1 .. 64 with --index centroid")
+        if args.nbits and (args.index not in ("centroid", "token") or args.precision != "bf16"):
+            ap.error("--nbits needs --index centroid or token and --precision bf16")
+        if not 0 <= args.nprobe <= 64 or (args.nprobe and args.index not in ("centroid", "token")):
+            ap.error("need --nprobe 0, or 1 .. 64 with --index centroid or token")
+        if args.index == "token" and (not args.nbits or not args.nprobe or args.ncand):
+            ap.error("--index token needs --nbits 1, 2 or 4 and --nprobe 1 .. 64, and takes no --ncand")
         if args.index == "fde" and (not 0 <= args.k_sim <= 6 or not 1 <= args.reps <= 32 or
                                     args.reps * (1 << args.k_sim) * args.d_proj > 4096 or args.precision != "bf16"):
             ap.error("--index fde needs --precision bf16, 0 <= --k-sim <= 6, 1 <= --reps <= 32 and "

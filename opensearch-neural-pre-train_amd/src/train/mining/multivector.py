@@ -133,22 +133,28 @@ def mine_multivector_negatives(input_files: Sequence[str], output_dir: str, enco
     candidates come from the documents in the ``nprobe`` best centroid lists of each query row
     (``search_band_two_phase(..., nprobe=nprobe)``).  ``index_type="fde"``: no centroids; the candidates come from a dense
     search over MUVERA fixed-dimensional encodings (``index.set_fde(FdeEncoder(dim, k_sim, reps, d_proj, device, fde_seed))``,
-    then ``search_band_two_phase(..., fde=True)``), the scores exact as for "centroid".  Returns the counts: records, queries, docs, store_rows, store_bytes, band_fill, padded, unchanged."""
+    then ``search_band_two_phase(..., fde=True)``), the scores exact as for "centroid".  ``index_type="token"``: token
+    retrieval over the compressed store (``index.search_band_tokens(..., nprobe)`` after ``train_centroids`` and
+    ``compress(nbits)``); it needs ``nbits`` 1, 2 or 4 and ``nprobe`` 1 .. 64 and takes no ``ncand``; the negatives' scores
+    are then token retrieval's x(q, d) (include/snx.h), the positives' the packed form's.  Returns the counts: records, queries, docs, store_rows, store_bytes, band_fill, padded, unchanged."""
     import torch
     from . import META_KEYS
     k, rank_start, rank_end, chunk_texts = int(k), int(rank_start), int(rank_end), int(chunk_texts)
     if k < 1 or not 0 <= rank_start < rank_end <= 1024 or chunk_texts < 1:
         raise ValueError("multi-vector mining: need k >= 1, 0 <= rank_start < rank_end <= 1024 and chunk_texts >= 1")
-    if index_type not in ("exact", "centroid", "fde"):
-        raise ValueError('multi-vector mining: index_type is "exact", "centroid" or "fde"')
+    if index_type not in ("exact", "centroid", "fde", "token"):
+        raise ValueError('multi-vector mining: index_type is "exact", "centroid", "fde" or "token"')
+    token = index_type == "token"
+    if token and int(ncand):
+        raise ValueError('multi-vector mining: index_type="token" has no candidate list; ncand must be 0')
     ncand = int(ncand) or default_ncand(rank_end)
-    if index_type != "exact" and not rank_end <= ncand <= 1024:
+    if index_type != "exact" and not token and not rank_end <= ncand <= 1024:
         raise ValueError("multi-vector mining: need rank_end <= ncand <= 1024")
-    if int(nbits) not in (0, 1, 2, 4) or (int(nbits) and index_type != "centroid"):
-        raise ValueError('multi-vector mining: nbits is 0, or 1, 2 or 4 with index_type="centroid"')
+    if int(nbits) not in (0, 1, 2, 4) or (int(nbits) and index_type not in ("centroid", "token")) or (token and not int(nbits)):
+        raise ValueError('multi-vector mining: nbits is 0, or 1, 2 or 4 with index_type="centroid"; "token" needs 1, 2 or 4')
     if isinstance(nprobe, bool) or not isinstance(nprobe, int) or not 0 <= nprobe <= 64 or \
-            (nprobe and index_type != "centroid"):
-        raise ValueError('multi-vector mining: nprobe is 0, or 1 .. 64 with index_type="centroid"')
+            (nprobe and index_type not in ("centroid", "token")) or (token and not nprobe):
+        raise ValueError('multi-vector mining: nprobe is 0, or 1 .. 64 with index_type="centroid"; "token" needs 1 .. 64')
     probed = {"nprobe": nprobe} if nprobe else ({"fde": True} if index_type == "fde" else {})
     files = sorted(input_files)
     shards = [_read(f) for f in files]
@@ -170,7 +176,7 @@ def mine_multivector_negatives(input_files: Sequence[str], output_dir: str, enco
         rows += int(mv.shape[0])
         nbytes += int(mv.shape[0]) * int(mv.shape[1]) * mv.element_size()
     index.build()
-    if index_type == "centroid" and doc_texts:
+    if index_type in ("centroid", "token") and doc_texts:
         index.train_centroids(int(ncentroids))
         if int(nbits):
             index.compress(int(nbits))
@@ -188,7 +194,9 @@ def mine_multivector_negatives(input_files: Sequence[str], output_dir: str, enco
             continue
         qptr = [ptr[i] for i in kept] + [ptr[-1]]
         exclude = [sorted(positives[s + i]) for i in kept]
-        if index_type != "exact":
+        if token:
+            sc, dd, found = index.search_band_tokens(mv, qptr, rank_start, rank_end, nprobe, exclude=exclude)
+        elif index_type != "exact":
             sc, dd, found = index.search_band_two_phase(mv, qptr, rank_start, rank_end, ncand, exclude=exclude,
                                                         chunk_docs=chunk_docs, **probed)
         else:
